@@ -5,13 +5,18 @@ One "step" = one fluid_step(): sort + P2G, flags/index, the pressure do..while (
 matrix-free PCG, velocity update, error), FLIP gather + advect, on the synthetic
 water_cube_drop scene, particles and fields resident in HBM.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel of the timed region (the
 fused PCG search-update + 7-point apply, FLUID_PROF_PCG_SQ), measured live with hipEvent pairs on
-the solver's stream; `cpu_baseline` is the oracle (CPU restatement, 1 thread) timed on one step
-from the same state.
+the solver's stream.  A plain run sets up, warms up, times the K steps and prints the line; the
+legs that take runs of their own (`cpu_baseline` = the oracle timed on the same state, the 128^3
+config, the stencil micro-benchmark, the x0 = 0 iteration count, the 500-step long run, the
+snow-MPM legs, `parity_at_size`) run only with --full.
+
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy
+(float64; a fixed, seeded sample of the particles and of the pressure cells, < 64 MB in all).
 """
 import argparse
 import json
@@ -55,7 +60,58 @@ def parse():
                          "auto = the library's own choice (replicates the pressure block below 384^3)")
     ap.add_argument("--force-dist", action="store_true", help="run the decomposed code path even with one rank (overhead check)")
     ap.add_argument("--sample-every", type=int, default=32, help="bracket every k-th PCG launch (and every k/8-th P2G / sort / G2P / solve) with a hipEvent pair; each record stalls the stream ~5-10 us")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline (CPU baselines, 128^3 config, stencil micro-benchmark, x0 = 0 iterations, "
+                         "long run, snow-MPM, parity at size); the --no-* options above switch single legs off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (particle and pressure samples, step stats) as DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
+    return a
+
+
+DUMP_SEED = 20240901            # fixed: the same cells and particles are sampled in every run
+DUMP_PARTICLES = 500_000        # 2 x 12 MB of float64 (x, y, z)
+DUMP_CELLS = 2_000_000          # 16 MB of float64 pressure
+
+
+def _sample(total, k):
+    """Sorted indices of a fixed, seeded sample of k out of `total` (all of them when total <= k)."""
+    if total <= k:
+        return np.arange(total)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(total, size=k, replace=False))
+
+
+def dump_outputs(out_dir, sim, last, dist, world, rank, n_global):
+    """What the timed path computed in its last step, as a caller of it receives it: particle positions and velocities (a fixed
+    sample when there are more than DUMP_PARTICLES), the pressure field at a fixed sample of cells (one GPU), and the step's stats.
+    Every rank takes part (the decomposed path gathers the sampled particles by global id); rank 0 writes."""
+    keys = ("dt_in", "dt_out", "error", "max_speed", "relres", "num_active", "outer_passes", "cg_iters", "cg_iters_last")
+    arrays = {"step_stats": np.array([float(last[k]) for k in keys], dtype=np.float64)}
+    if dist is None:
+        pos, vel = sim.download_particles()
+        sel = _sample(len(pos), DUMP_PARTICLES)
+        arrays["positions"], arrays["velocities"] = pos[sel], vel[sel]
+        del pos, vel
+        pres = sim.field(entry.load_package().FIELD.PRESSURE).reshape(-1)
+        arrays["pressure_sample"] = np.ascontiguousarray(pres[_sample(pres.size, DUMP_CELLS)], dtype=np.float64)
+        del pres
+    else:
+        # particles by global id (= index in the uploaded array); the pressure lives in per-rank windows and is not dumped here
+        pos, vel, ids = sim.download_local()
+        keep = np.isin(ids, _sample(n_global, DUMP_PARTICLES))
+        parts = [None] * world
+        dist.all_gather_object(parts, (ids[keep].astype(np.int64), pos[keep], vel[keep]))
+        if rank == 0:
+            gid = np.concatenate([p[0] for p in parts])
+            order = np.argsort(gid, kind="stable")
+            arrays["positions"] = np.concatenate([p[1] for p in parts])[order]
+            arrays["velocities"] = np.concatenate([p[2] for p in parts])[order]
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        for name, arr in arrays.items():
+            np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
 
 
 def usable_cores():
@@ -240,9 +296,9 @@ def main():
         st0 = sim.step()
         if transport is not None:
             solve_mode = "replicated" if st0["paths"] & 8 else "decomposed"    # FLUID_PATH_DIST_*: what FLUID_DIST_AUTO picked
-    # state at the start of the timed region, for the CPU leg
+    # state at the start of the timed region, for the CPU leg (--full)
     cpu_state = None
-    if rank == 0 and not a.no_cpu and world == 1 and not a.force_dist:
+    if a.full and rank == 0 and not a.no_cpu and world == 1 and not a.force_dist:
         p, v = sim.download_particles()
         cpu_state = (p, v, sim.dt)
 
@@ -271,6 +327,8 @@ def main():
         t = torch.tensor([elapsed], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, sim, stats[-1], dist, world, rank, len(pos0))
 
     # N > 1: the same steps with the OTHER form of the multi-GPU pressure block, timed the same way, reported beside the
     # headline as `alt_mode` (no multi-GPU box is available to the builder: this is how both forms get measured)
@@ -452,7 +510,7 @@ def main():
                       "g2p_avg": per(g2p), "sort_avg": per(srt)},
     }
 
-    # Everything below adds keys beside the headline; a failure there is recorded, the line is printed regardless.
+    # --full: everything below adds keys beside the headline; a failure there is recorded, the line is printed regardless.
     def aux_legs():
         if not a.no_micro and world == 1 and n == 256 and ppc == 8 and a.flip_blend >= 1:
             # BASELINE.json configs[1] taken literally (128^3, 8 particles/cell, FLIP blend 0.95), same metric, for reference
@@ -644,10 +702,11 @@ def main():
                                      "vel_rel_l2": float(np.linalg.norm(vg - vo) / max(np.linalg.norm(vo), 1e-300)),
                                      "indices_equal": bool(np.array_equal(sim2.field(fs.FIELD.INDICES), orc.field(4)))}
             sim2.close()
-    try:
-        aux_legs()
-    except Exception as e:  # noqa: BLE001
-        out["aux_error"] = f"{type(e).__name__}: {e}"[:400]
+    if a.full:
+        try:
+            aux_legs()
+        except Exception as e:  # noqa: BLE001
+            out["aux_error"] = f"{type(e).__name__}: {e}"[:400]
     if "value_long_run" in out:   # keep it next to `value` at the top of the line
         out = {k: out[k] for k in (["metric", "value", "value_long_run"] + [k for k in out if k not in ("metric", "value", "value_long_run")])}
     print(json.dumps(out))

@@ -8,8 +8,8 @@ O=gpurun_out/fin
 mkdir -p $O
 PART=${1:-all}
 if [ $PART = all ] || [ $PART = 1 ]; then
-timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --no-cpu --no-long-run --no-mpm > $O/trace.log 2>&1
+timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --full --no-cpu --no-long-run --no-mpm > $O/trace.log 2>&1
 python tools/step_breakdown.py "$(ls -t $O/trace/*/*_kernel_trace.csv | head -n 1)" 12 > $O/step_breakdown.txt
 cp "$(ls -t $O/trace/*/*_kernel_stats.csv | head -n 1)" $O/kernel_stats.csv
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -- python3 bench.py --steps 3 --warmup 1 --no-cpu --no-micro --no-long-run --no-mpm > $O/fetch.log 2>&1
@@ -18,7 +18,7 @@ python tools/pmc_summary.py "$(ls -t $O/fetch/*/*_counter_collection.csv | head 
 timeout -k 10 300 python bench.py --force-dist --no-cpu --no-micro --no-long-run --no-mpm > $O/bench_force_dist.json 2> /dev/null
 fi
 if [ $PART = all ] || [ $PART = 2 ]; then
-timeout -k 10 300 python bench.py --n 128 --no-long-run --no-mpm > $O/bench128.json 2> /dev/null
+timeout -k 10 300 python bench.py --full --n 128 --no-long-run --no-mpm > $O/bench128.json 2> /dev/null
 timeout -k 10 300 python bench.py --n 512 --ppc 4 --steps 5 --warmup 2 --no-cpu --no-micro --no-long-run --no-mpm > $O/bench512.json 2> /dev/null
 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/splash -- python3 tools/long_run.py 256 200 > $O/splash.log 2>&1
 python tools/step_breakdown.py "$(ls -t $O/splash/*/*_kernel_trace.csv | head -n 1)" 195 > $O/step_breakdown_splash.txt
