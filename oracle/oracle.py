@@ -237,7 +237,9 @@ class Oracle:
         return arr
 
     def system(self):
-        """(rows, cols, vals, b, b2, p) of the last pass in index space."""
+        """(rows, cols, vals, b, b2, p) of the last pass in index space.  b is re-read from DIVER (setA2, fluid.cc:535): after a
+        whole pressure_pass() that is already the divergence after the update (= b2), so take the system of a solve from
+        rhs_div(); build_matrix(); solve() followed by system()."""
         na = _lib.oracle_num_active(self._h)
         nnz = _lib.oracle_get_triplets(self._h, None, None, None)
         rows = np.empty(nnz, np.int32)
