@@ -41,6 +41,12 @@ class StepStats(C.Structure):
                 "box_lo": list(self.box_lo), "box_hi": list(self.box_hi), "paths": self.paths}
 
 
+class Source(C.Structure):
+    """fluid_source_t: a persistent particle source (include/fluid_hip.h, "particle sources and sinks")."""
+    _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("per_cell", C.c_int32), ("mode", C.c_int32),
+                ("every", C.c_int32), ("vel_mode", C.c_int32), ("vel", C.c_double * 3), ("seed", C.c_uint64)]
+
+
 class MpmParams(C.Structure):
     """mpm_params_t (include/mpm_hip.h); defaults = the literals of mpm.cc."""
     _fields_ = [("B", C.c_int32), ("W", C.c_int32), ("device", C.c_int32), ("cg_max_iters", C.c_int32),
@@ -105,6 +111,10 @@ SYMBOLS = [
     ("fluid_extrapolate", C.c_int, [_P, C.POINTER(C.c_int32)]),
     ("fluid_resample", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int64)]),
     ("fluid_get_droplets", C.c_int, [_P, C.POINTER(C.c_int32), _P, C.c_int32]),
+    ("fluid_add_particles", C.c_int, [_P, C.c_int64, _P, _P]),
+    ("fluid_set_source", C.c_int, [_P, C.c_int32, C.POINTER(Source)]),
+    ("fluid_set_sink", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("fluid_get_source_stats", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("fluid_stencil_apply_hbm", C.c_int, [_P, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
     ("fluid_profile_enable", C.c_int, [_P, C.c_int]),
     ("fluid_profile_read", C.c_int, [_P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -281,6 +281,17 @@ void launch_extrap_init(hipStream_t st, Grid g, const uint8_t* solid, const floa
 void launch_extrap_layer(hipStream_t st, Grid g, int pass, int* layer, double* u, double* v, double* w, int* n_new);
 void launch_resample(hipStream_t st, Grid g, long n, Particles p, const int* cell_start, int per_cell, int xlim, double far_, int* n_parked);
 
+// particle sources and sinks (kernels_sources.hip)
+struct SinkSet { int n; Box box[8]; };
+void launch_src_count(hipStream_t st, Grid g, long n, Particles p, Box box, int* hist);
+void launch_src_plan(hipStream_t st, Grid g, Box box, uint64_t h0, int per_cell, bool fill, const uint8_t* solid, const int* hist, int* cnt);
+void launch_src_emit(hipStream_t st, Grid g, Box box, uint64_t h0, int per_cell, bool fill, const uint8_t* solid, const int* hist, const int* off,
+                     Particles p, uint32_t pid0, const double vel[3]);
+void launch_src_append(hipStream_t st, long n, const double* pos, const double* vel, Particles p, uint32_t pid0);
+void launch_interp_from_grid(hipStream_t st, Grid g, long n, Particles p, const double* u, const double* v, const double* w);
+void launch_sink_mark(hipStream_t st, Grid g, long n, Particles p, const SinkSet& sk, int* keep_dev, int* keep_pid, int* removed);
+void launch_sink_compact(hipStream_t st, long n, Particles a, Particles b, const int* keep_dev, const int* dev_off, const int* pid_new);
+
 void launch_spline_eval(hipStream_t st, int which, long n, const double* x, double* w);
 void launch_dot(hipStream_t st, long n, const double* a, const double* b, double* part, int nb, double* out);
 

@@ -170,6 +170,7 @@ int fluid_destroy(fluid_sim_t* s)
     if (s->ds) dist_destroy(s);
     prof_resolve(s);
     free_particles(s);
+    sources_free(s);
     void* ptrs[] = {s->solid, s->flags, s->container, s->rhs, s->diver, s->diver2, s->u, s->v, s->w, s->ub, s->vb, s->wb, s->dcx, s->dcy,
                     s->dcz, s->pressure, s->p_guess, s->p_guess2, s->p_q, s->indices, s->scan_sums, s->ipart, s->R, s->S[0], s->Q, s->X, s->mg_slab, s->mg_part, s->cntL, s->part_bb, s->part_rr,
                     s->part_rz[0], s->part_rz[1], s->part_pq, s->part_err, s->ps, s->cell_count, s->cell_start, s->ss,
@@ -335,6 +336,7 @@ int fluid_upload_particles(fluid_sim_t* s, int64_t n, const double* pos, const d
     s->sorted = s->have_p2g = s->have_flags = false;
     s->have_guess = false;  // a new particle set: the first solve starts from 0
     s->sort_hint = false;
+    s->vel_ok = false;
     return FLUID_OK;
 }
 
@@ -1207,6 +1209,7 @@ static int phase_flip_advect(fluid_sim* s)
     s->stats.dt_out = s->dt;
     s->sorted = false;
     s->have_p2g = false;  // particles moved: fields are stale for a new gather
+    s->vel_ok = true;     // u, v, w: this step's velocities after the update, until the next P2G (fluid_add_particles)
     return FLUID_OK;
 }
 
@@ -1331,6 +1334,8 @@ int fluid_step(fluid_sim_t* s, fluid_step_stats_t* stats)
         if (s->prm.max_outer_passes > 0 && s->stats.outer_passes >= s->prm.max_outer_passes) break;
     } while (error > s->prm.outer_tol);             // :1484 (NaN ends the loop, inf continues)
     if ((rc = phase_flip_advect(s))) return rc;     // :1490
+    if ((rc = sources_apply(s))) return rc;         // :1495-1497 (the reference's emitter, commented out there): sinks, sources
+    s->n_steps++;
     if (stats) *stats = s->stats;
     return FLUID_OK;
 }

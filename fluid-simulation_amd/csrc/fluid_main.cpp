@@ -9,6 +9,12 @@
 // Initial particles: with the defaults (N = 121, 10 per voxel) exactly the reference's — fill(CoordBBox(-20, 20)) scattered by
 // UniformPointScatter with std::mt19937(FLUID_SEED) (fluid_scene_uniform_scatter: 689210 points); any other N / PPC takes the
 // scaled synthetic cube (fluid_scene_water_cube_drop).
+//   FLUID_SOURCE_EVERY (0 = off) — the reference's own emitter, commented out there: at the end of step i with i % K == 0 the
+// points of UniformPointScatter with std::mt19937(i+1) at 10 per voxel over fluidGrid (fluid.cc:1374-1375, 1495) are appended
+// with their velocities interpolated from the grid (pos.interpFromGrid(vels, 60, containerGrid), fluid.cc:1497), i.e.
+// fluid_scene_uniform_scatter(flo, fhi, 10, i+1, hi) + fluid_add_particles(..., NULL); the reference's `if (i%5 == 0)` gate
+// (fluid.cc:1379) is K here.  The box is the one of the initial scene (-20..20 at N = 121, scaled with N like the cube); the
+// particle count is printed after every step.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -39,6 +45,7 @@ int main(int, char**)
     const char* outenv = getenv("FLUID_OUT");
     const std::string outdir = outenv ? outenv : "simulation";
     const bool raw_f32 = env_long("FLUID_RAW", 0) != 0;
+    const long src_every = env_long("FLUID_SOURCE_EVERY", 0);
 
     fluid_sim_t* sim = nullptr;
     if (fluid_create(&prm, &sim) != FLUID_OK) {
@@ -47,6 +54,11 @@ int main(int, char**)
     }
     const bool ref_scene = prm.n == 121 && ppc == 10;   // fluid.cc:1176,1347-1350
     const int32_t flo[3] = {-20, -20, -20}, fhi[3] = {20, 20, 20};
+    // fluidGrid of the emitter: the initial cube's box (fluid_scene_water_cube_drop: side round(N 41 / 121), -20..20 at N = 121)
+    const int m_src = (int)((double)prm.n * 41.0 / 121.0 + 0.5), c0_src = -(m_src / 2);
+    const int32_t slo[3] = {c0_src, c0_src, c0_src}, shi[3] = {c0_src + m_src - 1, c0_src + m_src - 1, c0_src + m_src - 1};
+    const int32_t bound_src = -(prm.n / 2) + prm.n - 1;   // 60 at N = 121 (PointList::add's |p| < boundary - 2)
+    std::vector<double> src_pos;
     const int64_t np = ref_scene ? fluid_scene_uniform_scatter(flo, fhi, 10.f, (uint32_t)seed, 60, nullptr)
                                  : fluid_scene_water_cube_drop(prm.n, ppc, seed, nullptr);
     std::vector<double> pos((size_t)3 * np);
@@ -81,6 +93,15 @@ int main(int, char**)
             std::cerr << "fluid_step: " << fluid_last_error() << std::endl;
             return 1;
         }
+        if (src_every > 0 && i % src_every == 0) {   // fluid.cc:1374-1375, 1379, 1495, 1497
+            const int64_t ns = fluid_scene_uniform_scatter(slo, shi, 10.f, (uint32_t)(i + 1), bound_src, nullptr);
+            src_pos.resize((size_t)3 * (ns > 0 ? ns : 0));
+            if (ns < 0 || fluid_scene_uniform_scatter(slo, shi, 10.f, (uint32_t)(i + 1), bound_src, src_pos.data()) != ns ||
+                fluid_add_particles(sim, ns, src_pos.data(), nullptr) != FLUID_OK) {
+                std::cerr << "fluid_add_particles: " << fluid_last_error() << std::endl;
+                return 1;
+            }
+        }
         std::cout << "After" << std::endl;
         dt = st.dt_out;
         std::cout << "DT " << dt << std::endl;
@@ -88,6 +109,7 @@ int main(int, char**)
         std::cout << "Iteration:\t" << i + 1 << std::endl;
         simulationTime += dt;
         std::cout << "Time delta:\t" << simulationTime << std::endl;
+        if (src_every > 0) std::cout << "Particles:\t" << fluid_num_particles(sim) << std::endl;
         if (!outdir.empty()) {
             if (fluid_download_field(sim, FLUID_FIELD_OUTPUT, out.data(), ncell * sizeof(float)) != FLUID_OK) {
                 std::cerr << "fluid_download_field: " << fluid_last_error() << std::endl;

@@ -175,6 +175,20 @@ struct fluid_sim {
     long p_off = 0;              // my live particles are pa[p_off .. p_off+np)
     int* d_small = nullptr;      // device scratch ints
     int* h_small = nullptr;      // pinned mirror
+    // particle sources and sinks (fluid_sources.hip), applied at the end of fluid_step when any slot is set
+    struct SrcSlot {
+        bool on = false;
+        fluid_source_t src{};
+        Box box{};
+        int* buf = nullptr;   // box cells x 3 ints: FILL histogram | kept points per cell | their exclusive scan
+    };
+    SrcSlot src[FLUID_MAX_SOURCES];
+    Box sink[FLUID_MAX_SINKS] = {};
+    bool sink_on[FLUID_MAX_SINKS] = {};
+    int* src_sums = nullptr;      // block sums of the scans over a box or over the particles (any count up to INT32_MAX)
+    long n_steps = 0;             // fluid_step calls completed: the t of the sources
+    bool vel_ok = false;          // u, v, w are the velocities a completed step left (fluid_add_particles with vel == NULL)
+    long src_emit_last = 0, src_rm_last = 0, src_emit_total = 0, src_rm_total = 0;
     // profiling
     int prof_every = 0;
     ProfClass prof[FLUID_PROF_COUNT];
@@ -209,6 +223,10 @@ int phase_flags(fluid_sim* s);
 int phase_pressure_pass(fluid_sim* s, double* error);
 int pic_fields(fluid_sim* s);
 int fluid_create_window(const fluid_params_t* p, const Grid& g, fluid_sim_t** out);   // fluid_create on a window of the grid
+
+// fluid_sources.hip
+int sources_apply(fluid_sim* s);     // end of fluid_step: the sinks, then the sources in slot order (no launch when none is set)
+void sources_free(fluid_sim* s);
 
 // fluid_dist.hip
 int dist_step(fluid_sim* s, fluid_step_stats_t* stats);

@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 
-from ._lib import lib, check, Params, StepStats, FIELD
+from ._lib import lib, check, Params, StepStats, FIELD, Source
 
 _FIELD_DTYPE = {
     FIELD.CONTAINER: (np.float32, 1), FIELD.WEIGHTS: (np.float32, 1), FIELD.OUTPUT: (np.float32, 1),
@@ -158,6 +158,51 @@ class FluidSim:
     @dt.setter
     def dt(self, v):
         check(lib.fluid_set_dt(self._h, float(v)))
+
+    # ---- particle sources and sinks (single GPU; include/fluid_hip.h) ---------------------
+    def add_particles(self, pos, vel=None):
+        """Append particles after the live ones (pids np .. np+n-1).  vel=None: the reference's interpFromGrid
+        (fluid.cc:883-894) over the grid velocities of the last completed step."""
+        pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
+        v = None
+        if vel is not None:
+            vel = np.ascontiguousarray(vel, dtype=np.float64).reshape(-1, 3)
+            assert vel.shape == pos.shape
+            v = vel.ctypes.data_as(C.c_void_p)
+        check(lib.fluid_add_particles(self._h, pos.shape[0], pos.ctypes.data_as(C.c_void_p), v))
+
+    def set_source(self, slot, lo, hi, per_cell, mode="add", every=1, vel=None, seed=0):
+        """A persistent source over the inclusive index box [lo, hi]: mode "add" puts per_cell new points in every eligible
+        cell, "fill" tops every eligible cell up to per_cell; at the end of step t iff t % every == 0.  vel=None: the
+        velocity is interpolated from the grid; else the fixed (x, y, z)."""
+        src = Source()
+        src.lo[:] = [int(x) for x in lo]
+        src.hi[:] = [int(x) for x in hi]
+        src.per_cell = int(per_cell)
+        src.mode = {"add": 0, "fill": 1}[mode]
+        src.every = int(every)
+        src.vel_mode = 1 if vel is None else 0
+        if vel is not None:
+            src.vel[:] = [float(x) for x in vel]
+        src.seed = int(seed)
+        check(lib.fluid_set_source(self._h, int(slot), C.byref(src)))
+
+    def clear_source(self, slot):
+        check(lib.fluid_set_source(self._h, int(slot), None))
+
+    def set_sink(self, slot, lo, hi):
+        """Remove, at the end of every step, the particles whose base cell round(p) lies in the inclusive index box [lo, hi]."""
+        l3 = (C.c_int32 * 3)(*[int(x) for x in lo])
+        h3 = (C.c_int32 * 3)(*[int(x) for x in hi])
+        check(lib.fluid_set_sink(self._h, int(slot), l3, h3))
+
+    def clear_sink(self, slot):
+        check(lib.fluid_set_sink(self._h, int(slot), None, None))
+
+    def source_stats(self):
+        v = [C.c_int64() for _ in range(4)]
+        check(lib.fluid_get_source_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("emitted_last", "removed_last", "emitted_total", "removed_total"), (x.value for x in v)))
 
     # ---- step + phases -----------------------------------------------------------------
     def step(self):

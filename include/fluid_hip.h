@@ -198,6 +198,54 @@ int fluid_upload_field(fluid_sim_t* s, int field, const void* src, size_t bytes)
 int fluid_extrapolate(fluid_sim_t* s, int32_t* n_layers);
 int fluid_resample(fluid_sim_t* s, int32_t per_cell, int64_t* n_parked);
 
+/* ---- particle sources and sinks (single GPU; SURVEY 8(f): the reference's commented-out emitter) ----------------------
+ * The reference builds a UniformPointScatter over fluidGrid every step (fluid.cc:1374-1375) and has its call, with
+ * pos.interpFromGrid(vels, 60, containerGrid) after it, commented out after FLIPadvect (fluid.cc:1495-1497; also under
+ * `if (i%5 == 0)` at :1379-1382).  fluid_add_particles is that call; persistent sources and sinks are its general form, applied
+ * by fluid_step itself at the end of every step, after FLIPadvect: first every sink, then every source in slot order.
+ * A decomposed handle (fluid_create_dist) returns FLUID_ERR_STATE from every entry point of this block: global particle ids
+ * across ranks are not provided for appended particles.
+ *
+ * Where a source puts its points (a fixed function of seed, t, cell and k; SplitMix64):
+ *   sm(x):  z = x + 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB;
+ *           return z ^ z >> 31                                                        (all uint64, wrapping)
+ *   for step t (0-based fluid_step count of the handle), cell c (linear index of the Conventions block) and point k of it:
+ *   key = sm(sm(sm(seed) ^ t) ^ linear) ^ k;  u_a = (sm(key + a) >> 11) * 2^-53 (a = 0, 1, 2);  p_a = c_a + (u_a - 0.5)
+ * A cell is eligible if it lies in the box, inside W and is not solid; a point is kept iff round(p) == c on all three axes.
+ * Kept points take pids np, np+1, ... in ascending (linear, k) order. */
+#define FLUID_MAX_SOURCES 8
+#define FLUID_MAX_SINKS 8
+#define FLUID_SOURCE_ADD 0        /* per_cell new points in every eligible cell                                       */
+#define FLUID_SOURCE_FILL 1       /* top every eligible cell up to per_cell particles (counted by base cell round(p))  */
+#define FLUID_SOURCE_VEL_FIXED 0  /* new points take vel[]                                                            */
+#define FLUID_SOURCE_VEL_GRID 1   /* new points take interpFromGrid's velocity (see fluid_add_particles)              */
+#define FLUID_PATH_SOURCES 512    /* fluid_step_stats.paths: a sink or a source changed the particle set this step    */
+typedef struct fluid_source {
+    int32_t lo[3], hi[3];   /* inclusive cell box (index space of the Conventions block: 0 .. N-1)                   */
+    int32_t per_cell;       /* 1..64                                                                                 */
+    int32_t mode;           /* FLUID_SOURCE_ADD / FLUID_SOURCE_FILL                                                  */
+    int32_t every;          /* emit at the end of step t iff t % every == 0 (>= 1)                                   */
+    int32_t vel_mode;       /* FLUID_SOURCE_VEL_FIXED / FLUID_SOURCE_VEL_GRID                                        */
+    double vel[3];
+    uint64_t seed;
+} fluid_source_t;
+/* Appends n particles (AoS xyz doubles, like fluid_upload_particles) after the live ones, with pids np .. np+n-1, so that
+ * fluid_download_particles returns the old particles and then the new ones.  vel == NULL is the reference's interpFromGrid
+ * (fluid.cc:883-894): each new particle's velocity is clampedCatmullRom (fluid.cc:125-207) at its position over the grid velocities
+ * of the last completed fluid_step (after the update), averaged to cell centres as getVelocity does (fluid.cc:58-70); cells outside
+ * W are skipped, (0,0,0) when the weights sum to 0; FLUID_ERR_STATE when no step has completed since the last upload.
+ * The warm start of the solve is kept. */
+int fluid_add_particles(fluid_sim_t* s, int64_t n, const double* pos, const double* vel);
+/* slot in [0, FLUID_MAX_SOURCES); src == NULL clears the slot.  FLUID_ERR_ARG on an empty or off-grid box, per_cell outside
+ * 1..64, a bad mode or vel_mode, every < 1. */
+int fluid_set_source(fluid_sim_t* s, int32_t slot, const fluid_source_t* src);
+/* slot in [0, FLUID_MAX_SINKS); lo == NULL clears the slot.  At the end of every step each particle whose base cell round(p) lies
+ * in the inclusive box [lo, hi] is removed; the others keep their order and are renumbered 0 .. np'-1. */
+int fluid_set_sink(fluid_sim_t* s, int32_t slot, const int32_t lo[3], const int32_t hi[3]);
+/* Particles added by the sources / removed by the sinks in the last step, and in all steps since the handle was created
+ * (fluid_add_particles is not counted).  Any pointer may be NULL. */
+int fluid_get_source_stats(fluid_sim_t* s, int64_t* emitted_last, int64_t* removed_last, int64_t* emitted_total, int64_t* removed_total);
+
 /* The closed pockets of the last step's pressure system that were solved apart from the global solve (FLUID_PATH_DROPLETS;
  * kernels_droplets.hip): n_components of them; cells (may be NULL) receives 64 entries per component — the window-array cell
  * indices (ix * ny + iy) * nz + iz of its unknowns, ascending, padded with -1 — for at most cap_components components. */
