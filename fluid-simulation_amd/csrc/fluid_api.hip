@@ -1192,6 +1192,7 @@ static int phase_flip_advect(fluid_sim* s)
         // particle by particle: 357 / 407 us at steps 195 / 445 of the 256^3 drop against ~340 for this kernel alone, dropped,
         // profiles/r04/NOTES.md): gather through LDS tiles; the off-grid bucket (the array's tail) only has its speeds counted
         launch_g2p_tiled(s->st, s->g, s->Pb, s->pa, s->cell_start, s->dcx, s->dcy, s->dcz, s->pcx, s->pcy, s->pcz, s->prm.flip_blend, s->ss);
+        if (!box_empty(s->Pb)) s->stats.paths |= FLUID_PATH_G2P_TILES;   // (an empty box launches no tile: only the bucket below runs)
         if (s->n_out > 0)
             launch_g2p(s->st, s->g, s->n_out, s->pa.shifted(s->np - s->n_out), s->dcx, s->dcy, s->dcz, s->pcx, s->pcy, s->pcz, s->prm.flip_blend, s->ss);
     } else {

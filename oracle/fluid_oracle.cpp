@@ -801,6 +801,18 @@ int oracle_get_field(void* h, int id, void* dst)
     return -1;
 }
 
+// test infrastructure: load vel (2) or velBefore (3) from the SoA planes oracle_get_field returns; the step is unchanged
+int oracle_set_field(void* h, int id, const void* src)
+{
+    Oracle* o = (Oracle*)h;
+    if (id != 2 && id != 3) return -1;
+    std::vector<double>& v = id == 2 ? o->vel : o->velBefore;
+    const size_t n = o->ncell;
+    const double* s = (const double*)src;
+    for (size_t k = 0; k < n; ++k) { v[3 * k] = s[k]; v[3 * k + 1] = s[n + k]; v[3 * k + 2] = s[2 * n + k]; }
+    return 0;
+}
+
 // raw vectors of the last pass (index space)
 int oracle_num_active(void* h) { return ((Oracle*)h)->numActive; }
 void oracle_get_b(void* h, double* b, double* b2, double* p)

@@ -53,6 +53,8 @@ _lib.oracle_resample.argtypes = [_P, C.c_int]
 _lib.oracle_stats.argtypes = [_P, _P]
 _lib.oracle_get_field.restype = C.c_int
 _lib.oracle_get_field.argtypes = [_P, C.c_int, _P]
+_lib.oracle_set_field.restype = C.c_int
+_lib.oracle_set_field.argtypes = [_P, C.c_int, _P]
 _lib.oracle_num_active.restype = C.c_int
 _lib.oracle_num_active.argtypes = [_P]
 _lib.oracle_get_b.argtypes = [_P, _P, _P, _P]
@@ -235,6 +237,13 @@ class Oracle:
         if _lib.oracle_get_field(self._h, fid, _ptr(arr)) != 0:
             raise ValueError("unknown field")
         return arr
+
+    def set_field(self, fid, arr):
+        """Test infrastructure: load vel (2) or velBefore (3), (3, n, n, n) float64 as field() returns them."""
+        n = self.n
+        a = np.ascontiguousarray(arr, dtype=np.float64)
+        if fid not in (2, 3) or a.shape != (3, n, n, n) or _lib.oracle_set_field(self._h, fid, _ptr(a)) != 0:
+            raise ValueError("set_field takes vel (2) or velBefore (3) as (3, n, n, n)")
 
     def system(self):
         """(rows, cols, vals, b, b2, p) of the last pass in index space.  b is re-read from DIVER (setA2, fluid.cc:535): after a
