@@ -224,7 +224,12 @@ __global__ __launch_bounds__(256) void k_weights(long n, Particles p, double* __
 // (:288; "within W" is implied by non-solid, see fluid_set_solid).  weights is a float32
 // accumulator updated as float(weights + w) (:292); the velocity sum is fp64 (:293) and is
 // divided by double(weights) where weights>0 (:1138-1142).  container (:873) accumulates the
-// same w under "w>0", i.e. the same float sequence, so one array serves both.
+// same w under "w>0" and ONE array serves both here.  That is the same float sequence except for
+// addends w <= 0: spline() returns rounding noise of either sign (|w| <= 1e-15) for
+// 1 - 6.5e-6 < |x| < 1, which P2Gtransfer adds to weights (no sign test) and interpolate leaves out
+// of container.  The array here holds the sum of ALL addends (the reference's weights).  In a cell
+// with any ordinary addend the two agree at float precision; in a cell fed by such noise alone the
+// container, and with it the fluid flag, can differ from the reference's.
 // The post-P2G velocity is also stored as velBeforeUpdate (fluid.cc:1455).
 //
 // Separable weights: w(p,c) = sx*sy*sz with s_a = spline(pos_a - c_a) (fluid.cc:291), and a particle only ever

@@ -138,6 +138,16 @@ class FluidSim:
             v = vel.ctypes.data_as(C.c_void_p)
         check(lib.fluid_upload_particles(self._h, pos.shape[0], pos.ctypes.data_as(C.c_void_p), v))
 
+    def upload_particles_ids(self, pos, vel, ids):
+        """Like upload_particles with caller-chosen ids (uint32, unique): the ids, not the upload order, break the ties of
+        the counting sort, so the same set uploaded in another order with the same ids gives the same sums bit for bit."""
+        pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
+        vel = np.ascontiguousarray(vel, dtype=np.float64).reshape(-1, 3)
+        ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        assert vel.shape == pos.shape and ids.shape[0] == pos.shape[0]
+        check(lib.fluid_upload_particles_ids(self._h, pos.shape[0], pos.ctypes.data_as(C.c_void_p), vel.ctypes.data_as(C.c_void_p),
+                                             ids.ctypes.data_as(C.c_void_p)))
+
     def download_particles(self):
         n = lib.fluid_num_particles(self._h)
         pos = np.empty((n, 3), dtype=np.float64)

@@ -39,7 +39,7 @@ typedef struct fluid_sim fluid_sim_t;
 
 /* field ids for fluid_download_field / fluid_upload_field */
 #define FLUID_FIELD_CONTAINER 0   /* float32 N^3  particle weight density (fluid.cc:1157,1413)        */
-#define FLUID_FIELD_WEIGHTS 1     /* float32 N^3  P2G weights (fluid.cc:809,1108); == container here  */
+#define FLUID_FIELD_WEIGHTS 1     /* float32 N^3  P2G weights (fluid.cc:809,1108); == container here (grazing addends) */
 #define FLUID_FIELD_VEL 2         /* float64 3*N^3, SoA planes [u|v|w] (Vec3dGrid vels, :1240)        */
 #define FLUID_FIELD_VEL_BEFORE 3  /* float64 3*N^3  velBeforeUpdate (:1455)                           */
 #define FLUID_FIELD_INDICES 4     /* int32   N^3   unknown numbering, -1 elsewhere (:1388,1416-1433)  */

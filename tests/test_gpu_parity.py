@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import rel_l2
+import p2g_scenes   # the pile and threshold scenes, shared with test_gpu_p2g.py
 
 pytestmark = pytest.mark.gpu
 
@@ -81,19 +82,7 @@ def test_p2g_forms_agree_on_piles(fs, oracle, seed, monkeypatch):
     cells, rows longer than a staged chunk and the work list's cut of crowded planes (more than 8192 particles in a plane
     segment) in the row-marching form, the crowded cells' sums on the matrix cores (pieces of 512 particles, steps of four), against
     the tile form and the oracle."""
-    n = 24
-    rng = np.random.default_rng(100 + seed)
-    lo, hi = fs.grid_bounds(n)
-    parts = [fs.water_cube_drop(n, 2, seed=seed)]
-    for k in (60, 200, 500, 2000, 12000)[: 3 + seed % 3]:
-        for _ in range(2):
-            c = rng.integers(lo + 3, hi - 2, size=3).astype(np.float64)
-            if rng.random() < 0.5:
-                c[rng.integers(0, 3)] = (lo + 3) if rng.random() < 0.5 else (hi - 3)   # first / last cell inside the walls
-            parts.append(c + rng.uniform(-0.49, 0.49, size=(k, 3)))
-    pos = np.concatenate(parts)
-    pos = pos[rng.permutation(len(pos))]
-    vel = rng.standard_normal(pos.shape)
+    n, pos, vel, _ = p2g_scenes.piles(seed, background=fs.water_cube_drop(24, 2, seed=seed))
     orc = oracle.Oracle(n=n); orc.set_particles(pos, vel); orc.p2g(); orc.flags_index()
     out = {}
     for form in ("rows", "tiles", "crowd"):
@@ -117,22 +106,7 @@ def test_p2g_crowded_cells_at_the_thresholds(fs, oracle, monkeypatch):
     511 / 512 / 513 and 1024 / 1025 (one, two, three pieces of a cell), alone, side by side along z (one wave's lanes), in a wall
     corner and next to the walls, over a thin background: the crowded-cell form against the row form and the oracle, and the same
     bits from two runs."""
-    n = 32
-    rng = np.random.default_rng(77)
-    lo, hi = fs.grid_bounds(n)
-    counts = (17, 18, 19, 63, 64, 65, 511, 512, 513, 1024, 1025)
-    parts = [fs.water_cube_drop(n, 1, seed=5)]
-    cells = []
-    for k, cnt in enumerate(counts):          # alone: cells two apart along z in one row, then scattered
-        cells.append(((lo + 5, lo + 6, lo + 4 + 2 * k), cnt))
-    for k, cnt in enumerate(counts):          # side by side along z, another row
-        cells.append(((lo + 9, lo + 9, lo + 4 + k), cnt))
-    cells += [((lo + 3, lo + 3, lo + 3), 600), ((hi - 3, hi - 3, hi - 3), 18), ((lo + 3, hi - 3, lo + 12), 513), ((hi - 3, lo + 3, hi - 3), 64)]
-    for c, cnt in cells:
-        parts.append(np.asarray(c, dtype=np.float64) + rng.uniform(-0.49, 0.49, size=(cnt, 3)))
-    pos = np.concatenate(parts)
-    pos = pos[rng.permutation(len(pos))]
-    vel = rng.standard_normal(pos.shape)
+    n, pos, vel, _ = p2g_scenes.thresholds(background=fs.water_cube_drop(32, 1, seed=5))
     orc = oracle.Oracle(n=n); orc.set_particles(pos, vel); orc.p2g(); orc.flags_index()
     F = fs.FIELD
     out = {}
