@@ -47,6 +47,11 @@ class Source(C.Structure):
                 ("every", C.c_int32), ("vel_mode", C.c_int32), ("vel", C.c_double * 3), ("seed", C.c_uint64)]
 
 
+class LeafGridC(C.Structure):
+    """fluid_leaf_grid_t: a grid as the list of its non-zero 8^3 leaves (include/fluid_hip.h, "output as non-zero leaves")."""
+    _fields_ = [("n", C.c_int32), ("n_leaves", C.c_int32), ("origin", C.c_void_p), ("values", C.c_void_p)]
+
+
 class MpmParams(C.Structure):
     """mpm_params_t (include/mpm_hip.h); defaults = the literals of mpm.cc."""
     _fields_ = [("B", C.c_int32), ("W", C.c_int32), ("device", C.c_int32), ("cg_max_iters", C.c_int32),
@@ -126,6 +131,12 @@ SYMBOLS = [
     ("fluid_vdb_open", C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P)]),
     ("fluid_vdb_append", C.c_int, [_P, _P]),
     ("fluid_vdb_close", C.c_int, [_P]),
+    ("fluid_output_snapshot", C.c_int, [_P]),
+    ("fluid_output_wait", C.c_int, [_P, C.POINTER(LeafGridC)]),
+    ("fluid_output_stats", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("fluid_leaves_to_dense", C.c_int, [C.POINTER(LeafGridC), _P]),
+    ("fluid_vdb_append_leaves", C.c_int, [C.POINTER(_P), C.c_int32, C.POINTER(LeafGridC)]),
+    ("fluid_write_vdb_leaves", C.c_int, [C.c_char_p, C.POINTER(LeafGridC), C.c_int32]),
     # the snow-MPM step (include/mpm_hip.h)
     ("mpm_default_params", C.c_int, [C.POINTER(MpmParams)]),
     ("mpm_create", C.c_int, [C.POINTER(MpmParams), C.POINTER(_P)]),

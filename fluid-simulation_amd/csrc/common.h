@@ -259,6 +259,9 @@ void launch_pack_ids(hipStream_t st, long n, Particles p, long off, double* pos,
 void launch_unpack_particles(hipStream_t st, long n, const double* pos_aos, const double* vel_aos, Particles p);
 
 // grid
+void launch_out_mark(hipStream_t st, const float* f, int N, int off, int nl, int* flags);   // kernels_output.hip
+void launch_out_pack(hipStream_t st, const float* f, int N, int lo, int off, int nl, const int* flags, const int* slot, float* values,
+                     int* origin);
 void launch_exclusive_scan(hipStream_t st, const int* in, int* out, long n, int* block_sums, int* total);
 void launch_sort_tail(hipStream_t st, const int* cell_count, int* cell_start, long c1, long ncell);
 void launch_index_scan(hipStream_t st, Grid g, const uint8_t* flags, int* indices, int* block_sums, int* total);

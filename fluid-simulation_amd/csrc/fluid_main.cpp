@@ -6,6 +6,11 @@
 // Like the reference it takes no arguments.  Environment overrides (all optional):
 //   FLUID_N (121)  FLUID_PPC (10)  FLUID_STEPS (500)  FLUID_SEED (0)  FLUID_DEVICE (0)  FLUID_FLIP_BLEND (1)
 //   FLUID_OUT (simulation)  — directory for mygrids<i>.vdb (fluid.cc:1371,1503-1510); "" disables output; FLUID_RAW=1 adds .f32 dumps.
+//   FLUID_OUT_DENSE (0)  — 1: every step downloads the dense grid and writes both files from it on the main thread (the loop this
+// program had before the leaf snapshots; same files, for comparison).
+// Output by default: after step i fluid_output_snapshot lists the grid's non-zero 8^3 leaves on the device and starts their copy
+// to pinned memory; the main thread goes on with step i + 1, waits for the copy (long over by then) and hands the leaf list to
+// a writer thread that zips the listed leaves once and appends the grid to both files while step i + 2 runs.
 // Initial particles: with the defaults (N = 121, 10 per voxel) exactly the reference's — fill(CoordBBox(-20, 20)) scattered by
 // UniformPointScatter with std::mt19937(FLUID_SEED) (fluid_scene_uniform_scatter: 689210 points); any other N / PPC takes the
 // scaled synthetic cube (fluid_scene_water_cube_drop).
@@ -16,10 +21,13 @@
 // (fluid.cc:1379) is K here.  The box is the one of the initial scene (-20..20 at N = 121, scaled with N like the cube); the
 // particle count is printed after every step.
 #include <chrono>
+#include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
+#include <mutex>
 #include <string>
+#include <thread>
 #include <vector>
 #include <sys/stat.h>
 
@@ -30,6 +38,89 @@ static long env_long(const char* k, long d)
     const char* v = getenv(k);
     return v && *v ? atol(v) : d;
 }
+
+// FLUID_RAW=1: the bare float32 dump (int32 n, then n^3 floats, z fastest)
+static bool write_f32(const std::string& fr, int32_t n32, const float* v, size_t ncell)
+{
+    FILE* f = fopen(fr.c_str(), "wb");
+    if (!f) return false;
+    bool ok = fwrite(&n32, sizeof(n32), 1, f) == 1 && fwrite(v, sizeof(float), ncell, f) == ncell;
+    return fclose(f) == 0 && ok;
+}
+
+// The writer thread: one grid at a time, in step order.  It reads the leaf list's pointers only (valid until the second following
+// snapshot: the main thread waits for grid i - 2 to be written before it takes snapshot i), never the handle.
+struct LeafWriter {
+    std::string outdir, fin;
+    fluid_vdb_writer_t* all = nullptr;
+    bool raw_f32 = false;
+    std::mutex m;
+    std::condition_variable cv;
+    fluid_leaf_grid_t job{};
+    int job_step = -1;        // step whose grid is waiting (-1: none)
+    int done = 0;             // grids written
+    bool quit = false;
+    std::string error;        // first failure: the file that could not be written
+    std::thread th;
+    void start() { th = std::thread([this] { run(); }); }
+    ~LeafWriter() { stop(); }   // (an early return of main: the grid in hand is still written)
+    void run()
+    {
+        std::vector<float> dense;
+        for (;;) {
+            std::unique_lock<std::mutex> lk(m);
+            cv.wait(lk, [&] { return job_step >= 0 || quit; });
+            if (job_step < 0) return;
+            const fluid_leaf_grid_t g = job;
+            const int i = job_step;
+            lk.unlock();
+            std::string bad;
+            // file2.write(grids2) of fluid.cc:1503-1504 and this step's grid of file.write(grids), :1508: zipped once, written twice
+            const std::string fn = outdir + "/mygrids" + std::to_string(i) + ".vdb";
+            fluid_vdb_writer_t* ws[2] = {nullptr, all};
+            if (fluid_vdb_open(fn.c_str(), g.n, 1, FLUID_VDB_ZIP_ACTIVE_MASK, &ws[0]) != FLUID_OK) bad = fn;
+            else {
+                if (fluid_vdb_append_leaves(ws, 2, &g) != FLUID_OK) bad = fn + " / " + fin;
+                if (fluid_vdb_close(ws[0]) != FLUID_OK && bad.empty()) bad = fn;
+            }
+            if (raw_f32 && bad.empty()) {
+                const size_t ncell = (size_t)g.n * g.n * g.n;
+                dense.resize(ncell);
+                const std::string fr = outdir + "/mygrids" + std::to_string(i) + ".f32";
+                if (fluid_leaves_to_dense(&g, dense.data()) != FLUID_OK || !write_f32(fr, g.n, dense.data(), ncell)) bad = fr;
+            }
+            lk.lock();
+            if (!bad.empty() && error.empty()) error = bad;
+            job_step = -1;
+            done = i + 1;
+            cv.notify_all();
+        }
+    }
+    // blocks until grids 0 .. n - 1 are written; false after a failure
+    bool wait_done(int n)
+    {
+        std::unique_lock<std::mutex> lk(m);
+        cv.wait(lk, [&] { return done >= n; });
+        return error.empty();
+    }
+    void submit(int step, const fluid_leaf_grid_t& g)
+    {
+        std::unique_lock<std::mutex> lk(m);
+        cv.wait(lk, [&] { return job_step < 0; });
+        job = g;
+        job_step = step;
+        cv.notify_all();
+    }
+    void stop()
+    {
+        {
+            std::lock_guard<std::mutex> lk(m);
+            quit = true;
+        }
+        cv.notify_all();
+        if (th.joinable()) th.join();
+    }
+};
 
 int main(int, char**)
 {
@@ -46,6 +137,7 @@ int main(int, char**)
     const std::string outdir = outenv ? outenv : "simulation";
     const bool raw_f32 = env_long("FLUID_RAW", 0) != 0;
     const long src_every = env_long("FLUID_SOURCE_EVERY", 0);
+    const bool out_dense = env_long("FLUID_OUT_DENSE", 0) != 0;
 
     fluid_sim_t* sim = nullptr;
     if (fluid_create(&prm, &sim) != FLUID_OK) {
@@ -70,7 +162,7 @@ int main(int, char**)
     }
     if (!outdir.empty()) mkdir(outdir.c_str(), 0755);  // the reference aborts when simulation/ is missing
     const size_t ncell = (size_t)prm.n * prm.n * prm.n;
-    std::vector<float> out(outdir.empty() ? 0 : ncell);
+    std::vector<float> out(outdir.empty() || !out_dense ? 0 : ncell);
     // file.write(grids) of fluid.cc:1508: `grids` is declared outside the loop (:1366) and receives every step's grid
     // (:1450), so the final mygrids.vdb holds all of them — streamed here, one grid appended per step
     fluid_vdb_writer_t* all = nullptr;
@@ -80,6 +172,23 @@ int main(int, char**)
         fin = (slash == std::string::npos ? std::string() : outdir.substr(0, slash + 1)) + "mygrids.vdb";
         if (fluid_vdb_open(fin.c_str(), prm.n, steps, FLUID_VDB_ZIP_ACTIVE_MASK, &all) != FLUID_OK) { std::cerr << "cannot write " << fin << std::endl; return 1; }
     }
+
+    LeafWriter lw;
+    const bool leaves = !outdir.empty() && steps > 0 && !out_dense;
+    if (leaves) {
+        lw.outdir = outdir, lw.fin = fin, lw.all = all, lw.raw_f32 = raw_f32;
+        lw.start();
+    }
+    // hands the oldest snapshot to the writer thread
+    auto pass_on = [&](int step) {
+        fluid_leaf_grid_t g;
+        if (fluid_output_wait(sim, &g) != FLUID_OK) {
+            std::cerr << "fluid_output_wait: " << fluid_last_error() << std::endl;
+            return false;
+        }
+        lw.submit(step, g);
+        return true;
+    };
 
     double dt = prm.max_dt;  // fluid.cc:1367
     double simulationTime = 0;
@@ -110,7 +219,16 @@ int main(int, char**)
         simulationTime += dt;
         std::cout << "Time delta:\t" << simulationTime << std::endl;
         if (src_every > 0) std::cout << "Particles:\t" << fluid_num_particles(sim) << std::endl;
-        if (!outdir.empty()) {
+        if (leaves) {
+            // snapshot i reuses the slot of grid i - 2: that grid must be on disk
+            if (!lw.wait_done(i - 1)) { std::cerr << "cannot write " << lw.error << std::endl; lw.stop(); return 1; }
+            if (fluid_output_snapshot(sim) != FLUID_OK) {
+                std::cerr << "fluid_output_snapshot: " << fluid_last_error() << std::endl;
+                lw.stop();
+                return 1;
+            }
+            if (i > 0 && !pass_on(i - 1)) { lw.stop(); return 1; }   // its copy ran beside this step
+        } else if (!outdir.empty()) {
             if (fluid_download_field(sim, FLUID_FIELD_OUTPUT, out.data(), ncell * sizeof(float)) != FLUID_OK) {
                 std::cerr << "fluid_download_field: " << fluid_last_error() << std::endl;
                 return 1;
@@ -121,15 +239,18 @@ int main(int, char**)
             const float* gp[1] = {out.data()};
             if (fluid_write_vdb(fn.c_str(), prm.n, 1, gp) != FLUID_OK) { std::cerr << "cannot write " << fn << std::endl; return 1; }
             if (fluid_vdb_append(all, out.data()) != FLUID_OK) { std::cerr << "cannot write " << fin << std::endl; return 1; }
-            if (raw_f32) {  // FLUID_RAW=1: also the bare float32 dump (int32 n, then n^3 floats, z fastest)
+            if (raw_f32) {
                 const std::string fr = outdir + "/mygrids" + std::to_string(i) + ".f32";
-                FILE* f = fopen(fr.c_str(), "wb");
-                if (!f) { std::cerr << "cannot write " << fr << std::endl; return 1; }
-                int32_t n32 = prm.n;
-                fwrite(&n32, sizeof(n32), 1, f);
-                fwrite(out.data(), sizeof(float), ncell, f);
-                fclose(f);
+                if (!write_f32(fr, prm.n, out.data(), ncell)) { std::cerr << "cannot write " << fr << std::endl; return 1; }
             }
+        }
+    }
+    if (leaves) {
+        const bool ok = pass_on(steps - 1) && lw.wait_done(steps);
+        lw.stop();
+        if (!ok) {
+            if (!lw.error.empty()) std::cerr << "cannot write " << lw.error << std::endl;
+            return 1;
         }
     }
     if (all && fluid_vdb_close(all) != FLUID_OK) { std::cerr << "cannot write " << fin << std::endl; return 1; }

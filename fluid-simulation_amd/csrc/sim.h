@@ -189,6 +189,7 @@ struct fluid_sim {
     long n_steps = 0;             // fluid_step calls completed: the t of the sources
     bool vel_ok = false;          // u, v, w are the velocities a completed step left (fluid_add_particles with vel == NULL)
     long src_emit_last = 0, src_rm_last = 0, src_emit_total = 0, src_rm_total = 0;
+    struct OutState* out = nullptr;   // leaf snapshots of the output grid (fluid_output.hip), made by the first fluid_output_snapshot
     // profiling
     int prof_every = 0;
     ProfClass prof[FLUID_PROF_COUNT];
@@ -227,6 +228,9 @@ int fluid_create_window(const fluid_params_t* p, const Grid& g, fluid_sim_t** ou
 // fluid_sources.hip
 int sources_apply(fluid_sim* s);     // end of fluid_step: the sinks, then the sources in slot order (no launch when none is set)
 void sources_free(fluid_sim* s);
+
+// fluid_output.hip
+void output_free(fluid_sim* s);      // waits for the copies in flight, frees the staging and pinned buffers
 
 // fluid_dist.hip
 int dist_step(fluid_sim* s, fluid_step_stats_t* stats);

@@ -34,6 +34,7 @@
 #include <cstdio>
 #include <cstring>
 #include <ctime>
+#include <map>
 #include <random>
 #include <string>
 #include <thread>
@@ -59,7 +60,7 @@ struct Out {
         const char* c = (const char*)p;
         buf.insert(buf.end(), c, c + n);
         at += n;
-        if (buf.size() >= (size_t)8 << 20) flush();
+        if (buf.size() >= (size_t)1 << 20) flush();
     }
     template <typename T> void put(T v) { raw(&v, sizeof(T)); }
     void str(const std::string& s) { put<uint32_t>((uint32_t)s.size()); raw(s.data(), s.size()); }   // util/Name.h:57-63
@@ -138,6 +139,18 @@ struct LeafJob {
     int64_t head;                       // zip: the int64 in front (compressed size, or -raw size)
     std::vector<unsigned char> z;       // zip: the compressed bytes (empty: the raw values follow)
 };
+// zipToStream's framing of na floats: the int64 in front (compressed size, or -raw size when zipping did not shrink them: the
+// raw bytes then follow and z is left empty)
+int64_t zip_values(const float* act, int na, std::vector<unsigned char>& z)
+{
+    const size_t n = (size_t)na * sizeof(float);
+    uLongf zn = compressBound((uLong)n);
+    z.resize(zn);
+    const int st = compress2(z.data(), &zn, (const Bytef*)act, (uLong)n, Z_DEFAULT_COMPRESSION);
+    if (st == Z_OK && zn < n) { z.resize(zn); return (int64_t)zn; }
+    z.clear();
+    return -(int64_t)n;
+}
 void prepare_leaf(const Dense& g, LeafJob& j, uint32_t compression)
 {
     leaf_mask(g, j.lx, j.ly, j.lz, j.vm);
@@ -148,14 +161,7 @@ void prepare_leaf(const Dense& g, LeafJob& j, uint32_t compression)
                 if (g.inside(j.lx + x, j.ly + y, j.lz + z)) j.act[j.na++] = g.at(j.lx + x, j.ly + y, j.lz + z);
     j.z.clear();
     j.head = 0;
-    if (compression & COMPRESS_ZIP) {
-        const size_t n = (size_t)j.na * sizeof(float);
-        uLongf zn = compressBound((uLong)n);
-        j.z.resize(zn);
-        const int st = compress2(j.z.data(), &zn, (const Bytef*)j.act, (uLong)n, Z_DEFAULT_COMPRESSION);
-        if (st == Z_OK && zn < n) { j.head = (int64_t)zn; j.z.resize(zn); }
-        else { j.head = -(int64_t)n; j.z.clear(); }
-    }
+    if (compression & COMPRESS_ZIP) j.head = zip_values(j.act, j.na, j.z);
 }
 void flush_leaves(Out& o, const Dense& g, std::vector<LeafJob>& jobs, uint32_t compression)
 {
@@ -267,6 +273,7 @@ struct Writer {
     Out o;
     int n = 0, n_grids = 0, written = 0;
     uint32_t compression = 0;
+    std::map<int, std::vector<unsigned char>> zero_values;   // leaf path: the value bytes of a leaf of na zeros, by na
 };
 
 int writer_open(Writer& w, const char* path, int32_t n, int32_t n_grids, int32_t compression)
@@ -294,13 +301,13 @@ int writer_open(Writer& w, const char* path, int32_t n, int32_t n_grids, int32_t
     return FLUID_OK;
 }
 
-int writer_append(Writer& w, const float* grid)
+// everything of a grid in front of its tree: descriptor, compression flags, metadata, transform, the root's head.
+// Returns the position of the descriptor's three stream offsets (the grid position is already patched in).
+size_t grid_head(Writer& w)
 {
-    if (w.written >= w.n_grids) return FLUID_ERR_STATE;
     Out& o = w.o;
     const int n = w.n, k = w.written;
     const int lo = -(n / 2), hi = lo + n - 1;
-    const Dense g{n, lo, hi, grid};
     // ---- descriptor (io/GridDescriptor.cc:53-73); unnamed grids become "\x1e<k>" (io/Archive.cc:1196-1206) ----
     o.str(std::string("\x1e") + std::to_string(k));
     o.str("Tree_float_5_4_3");
@@ -330,6 +337,17 @@ int writer_append(Writer& w, const float* grid)
     uint32_t nroot = 0;
     for (int x = floor_to(lo, INT2); x <= hi; x += INT2) ++nroot;
     o.put<uint32_t>(nroot * nroot * nroot);
+    return off;
+}
+
+int writer_append(Writer& w, const float* grid)
+{
+    if (w.written >= w.n_grids) return FLUID_ERR_STATE;
+    Out& o = w.o;
+    const int n = w.n;
+    const int lo = -(n / 2), hi = lo + n - 1;
+    const Dense g{n, lo, hi, grid};
+    const size_t off = grid_head(w);
     write_tree(o, g, false, w.compression);
     o.patch64(off + 8, (int64_t)o.pos());   // block position
     write_tree(o, g, true, w.compression);
@@ -344,6 +362,232 @@ int writer_close(Writer& w)
     const int rc = w.o.f ? fclose(w.o.f) : 0;
     w.o.f = nullptr;
     return (w.o.ok && rc == 0 && w.written == w.n_grids) ? FLUID_OK : FLUID_ERR_ARG;
+}
+
+// ---- the same grid from the list of its non-zero leaves (fluid_vdb_append_leaves) ---------------------------------------------
+// The file is the dense path's, byte for byte: every leaf of [lo,hi]^3 is written with its full value mask.  What differs is the
+// work: a leaf the list does not name holds zeros only, so its value bytes are a constant of its active-voxel count; masks come
+// from the leaf's per-axis in-grid ranges (a leaf is the first, an inner or the last of its axis: 4 classes per axis, 64 masks);
+// the listed leaves are gathered and zipped once for all writers of the call.
+struct LeafGeom {
+    int n, lo, hi, L0, nl;
+    int a0[4], a1[4];              // in-grid voxel range of a leaf by axis class: bit 0 = first leaf of the axis, bit 1 = last
+    uint64_t mask[64][8];          // value mask by (cx * 4 + cy) * 4 + cz
+    int na[64];
+    explicit LeafGeom(int n_) : n(n_), lo(-(n_ / 2)), hi(lo + n_ - 1), L0(floor_to(lo, LEAF)), nl((floor_to(hi, LEAF) - L0) / LEAF + 1)
+    {
+        for (int c = 0; c < 4; ++c) {
+            a0[c] = (c & 1) ? lo - L0 : 0;
+            a1[c] = (c & 2) ? hi - floor_to(hi, LEAF) : LEAF - 1;
+        }
+        for (int cx = 0; cx < 4; ++cx)
+            for (int cy = 0; cy < 4; ++cy)
+                for (int cz = 0; cz < 4; ++cz) {
+                    const int c = (cx * 4 + cy) * 4 + cz;
+                    na[c] = 0;
+                    for (int x = 0; x < 8; ++x) mask[c][x] = 0;
+                    if (a1[cx] < a0[cx] || a1[cy] < a0[cy] || a1[cz] < a0[cz]) continue;   // "first and last" of an axis with several leaves: no such leaf
+                    const uint64_t zb = ((1ull << (a1[cz] - a0[cz] + 1)) - 1) << a0[cz];   // one (x, y) row: bits z
+                    uint64_t word = 0;                                                     // one x: 8 rows
+                    for (int y = a0[cy]; y <= a1[cy]; ++y) word |= zb << (8 * y);
+                    for (int x = 0; x < 8; ++x) mask[c][x] = (x >= a0[cx] && x <= a1[cx]) ? word : 0;
+                    na[c] = (a1[cx] - a0[cx] + 1) * (a1[cy] - a0[cy] + 1) * (a1[cz] - a0[cz] + 1);
+                }
+    }
+    int axis_class(int i) const { return (i == 0 ? 1 : 0) | (i == nl - 1 ? 2 : 0); }
+    int leaf_class(int i, int j, int k) const { return (axis_class(i) * 4 + axis_class(j)) * 4 + axis_class(k); }
+};
+
+// FLUID_OK, or FLUID_ERR_ARG: an origin off the 8-grid, outside the leaves of [lo,hi]^3, or not strictly ascending in (x, y, z)
+int check_leaf_list(const fluid_leaf_grid_t* g)
+{
+    if (!g || g->n < 1 || g->n > 4096 || g->n_leaves < 0) return FLUID_ERR_ARG;
+    if (g->n_leaves > 0 && (!g->origin || !g->values)) return FLUID_ERR_ARG;
+    const int lo = -(g->n / 2), hi = lo + g->n - 1, L0 = floor_to(lo, LEAF), L1 = floor_to(hi, LEAF);
+    for (int i = 0; i < g->n_leaves; ++i) {
+        const int32_t* o = g->origin + 3 * (size_t)i;
+        for (int a = 0; a < 3; ++a)
+            if ((o[a] & (LEAF - 1)) != 0 || o[a] < L0 || o[a] > L1) return FLUID_ERR_ARG;
+        if (i > 0) {
+            const int32_t* p = o - 3;
+            const bool after = o[0] != p[0] ? o[0] > p[0] : o[1] != p[1] ? o[1] > p[1] : o[2] > p[2];
+            if (!after) return FLUID_ERR_ARG;
+        }
+    }
+    return FLUID_OK;
+}
+
+// the bytes that follow a leaf's metadata byte in the buffers pass, for its na active values
+void value_bytes(const float* act, int na, uint32_t compression, std::vector<unsigned char>& out, std::vector<unsigned char>& z)
+{
+    const unsigned char* raw = (const unsigned char*)act;
+    const size_t n = (size_t)na * sizeof(float);
+    if (!(compression & COMPRESS_ZIP)) { out.insert(out.end(), raw, raw + n); return; }
+    const int64_t head = zip_values(act, na, z);
+    out.insert(out.end(), (const unsigned char*)&head, (const unsigned char*)&head + 8);
+    if (head > 0) out.insert(out.end(), z.begin(), z.end());
+    else out.insert(out.end(), raw, raw + n);
+}
+
+struct Span { const unsigned char* p; size_t n; };
+
+// every writer of the call receives the same bytes
+struct Fan {
+    Writer* const* w;
+    int n;
+    void raw(const void* p, size_t len) const { for (int i = 0; i < n; ++i) w[i]->o.raw(p, len); }
+};
+
+void write_tree_leaves(const Fan& f, const LeafGeom& G, bool buffers, uint32_t compression, const std::vector<int>& table,
+                       const std::vector<Span>& listed, const Span zero[64])
+{
+    const Dense g{G.n, G.lo, G.hi, nullptr};   // the box tests of write_tree; no value is read through it
+    const int8_t meta_byte = NO_MASK_OR_INACTIVE_VALS;
+    std::vector<unsigned char> chunk;
+    auto add = [&](const void* p, size_t len) { chunk.insert(chunk.end(), (const unsigned char*)p, (const unsigned char*)p + len); };
+    for (int rx = floor_to(g.lo, INT2); rx <= g.hi; rx += INT2)
+        for (int ry = floor_to(g.lo, INT2); ry <= g.hi; ry += INT2)
+            for (int rz = floor_to(g.lo, INT2); rz <= g.hi; rz += INT2) {
+                if (!buffers) {
+                    const int32_t org[3] = {rx, ry, rz};
+                    f.raw(org, sizeof(org));
+                    std::vector<uint64_t> cm(32 * 32 * 32 / 64, 0);
+                    for (int a = 0; a < 32; ++a)
+                        for (int b = 0; b < 32; ++b)
+                            for (int c = 0; c < 32; ++c)
+                                if (g.overlaps(rx + a * INT1, ry + b * INT1, rz + c * INT1, INT1)) {
+                                    const int n = (a << 10) + (b << 5) + c;
+                                    cm[n >> 6] |= 1ull << (n & 63);
+                                }
+                    f.raw(cm.data(), cm.size() * 8);
+                    for (int i = 0; i < f.n; ++i) internal_values(f.w[i]->o, cm.size() * 8, compression);
+                }
+                for (int a = 0; a < 32; ++a)
+                    for (int b = 0; b < 32; ++b)
+                        for (int c = 0; c < 32; ++c) {
+                            const int ix = rx + a * INT1, iy = ry + b * INT1, iz = rz + c * INT1;
+                            if (!g.overlaps(ix, iy, iz, INT1)) continue;
+                            if (!buffers) {
+                                uint64_t cm[64] = {};
+                                for (int p = 0; p < 16; ++p)
+                                    for (int q = 0; q < 16; ++q)
+                                        for (int r = 0; r < 16; ++r)
+                                            if (g.overlaps(ix + p * LEAF, iy + q * LEAF, iz + r * LEAF, LEAF)) {
+                                                const int n = (p << 8) + (q << 4) + r;
+                                                cm[n >> 6] |= 1ull << (n & 63);
+                                            }
+                                f.raw(cm, sizeof(cm));
+                                for (int i = 0; i < f.n; ++i) internal_values(f.w[i]->o, sizeof(cm), compression);
+                            }
+                            for (int p = 0; p < 16; ++p)
+                                for (int q = 0; q < 16; ++q)
+                                    for (int r = 0; r < 16; ++r) {
+                                        const int lx = ix + p * LEAF, ly = iy + q * LEAF, lz = iz + r * LEAF;
+                                        if (!g.overlaps(lx, ly, lz, LEAF)) continue;
+                                        const int i = (lx - G.L0) / LEAF, j = (ly - G.L0) / LEAF, k = (lz - G.L0) / LEAF;
+                                        const int cls = G.leaf_class(i, j, k);
+                                        add(G.mask[cls], sizeof(G.mask[cls]));
+                                        if (!buffers) continue;
+                                        add(&meta_byte, 1);
+                                        const int t = table[((size_t)i * G.nl + j) * G.nl + k];
+                                        const Span& s = t >= 0 ? listed[(size_t)t] : zero[cls];
+                                        add(s.p, s.n);
+                                    }
+                            f.raw(chunk.data(), chunk.size());   // the leaves of this 128^3 node, to every writer at once
+                            chunk.clear();
+                        }
+            }
+}
+
+int append_leaves(Writer* const* ws, int nw, const fluid_leaf_grid_t* g)
+{
+    const uint32_t compression = ws[0]->compression;
+    for (int i = 0; i < nw; ++i)
+        if (ws[i]->n != g->n || ws[i]->compression != compression) return FLUID_ERR_ARG;
+    int rc = check_leaf_list(g);
+    if (rc) return rc;
+    for (int i = 0; i < nw; ++i)
+        if (ws[i]->written >= ws[i]->n_grids) return FLUID_ERR_STATE;
+    const LeafGeom G(g->n);
+    const size_t nlist = (size_t)g->n_leaves;
+    // table over the grid's leaves: the tree walk (root -> 128^3 nodes -> leaves) is not the list's order for N > 128
+    std::vector<int> table((size_t)G.nl * G.nl * G.nl, -1);
+    std::vector<int> cls(nlist);
+    for (size_t t = 0; t < nlist; ++t) {
+        const int32_t* o = g->origin + 3 * t;
+        const int i = (o[0] - G.L0) / LEAF, j = (o[1] - G.L0) / LEAF, k = (o[2] - G.L0) / LEAF;
+        table[((size_t)i * G.nl + j) * G.nl + k] = (int)t;
+        cls[t] = G.leaf_class(i, j, k);
+    }
+    // the listed leaves' value bytes, once for every writer: contiguous shares of the list on at most 16 threads
+    const bool zip = (compression & COMPRESS_ZIP) != 0;
+    unsigned nt = std::thread::hardware_concurrency();
+    nt = nt < 1 ? 1 : (nt > 16 ? 16 : nt);
+    if (nlist < 64 || !zip) nt = 1;
+    std::vector<std::vector<unsigned char>> arena(nt);
+    std::vector<size_t> at(nlist), len(nlist);
+    auto share = [&](unsigned t) {
+        std::vector<unsigned char> z;
+        float act[512];
+        for (size_t l = nlist * t / nt; l < nlist * (t + 1) / nt; ++l) {
+            const int c = cls[l], cx = c >> 4, cy = (c >> 2) & 3, cz = c & 3;
+            const float* v = g->values + 512 * l;
+            at[l] = arena[t].size();
+            if (!zip && G.na[c] == 512) { len[l] = 0; continue; }   // a whole leaf, stored raw: written straight from the list
+            int na = 0;
+            for (int x = G.a0[cx]; x <= G.a1[cx]; ++x)
+                for (int y = G.a0[cy]; y <= G.a1[cy]; ++y)
+                    for (int zz = G.a0[cz]; zz <= G.a1[cz]; ++zz) act[na++] = v[(x * 8 + y) * 8 + zz];
+            value_bytes(act, na, compression, arena[t], z);
+            len[l] = arena[t].size() - at[l];
+        }
+    };
+    if (nt == 1) {
+        share(0);
+    } else {
+        std::vector<std::thread> th;
+        for (unsigned t = 0; t < nt; ++t) th.emplace_back(share, t);
+        for (auto& x : th) x.join();
+    }
+    std::vector<Span> listed(nlist);
+    for (unsigned t = 0; t < nt; ++t)
+        for (size_t l = nlist * t / nt; l < nlist * (t + 1) / nt; ++l) {
+            if (len[l] == 0) listed[l] = Span{(const unsigned char*)(g->values + 512 * l), 2048};
+            else listed[l] = Span{arena[t].data() + at[l], len[l]};
+        }
+    // unlisted leaves: the value bytes of na zeros, from whichever writer of the call has them already
+    Span zero[64];
+    {
+        std::vector<unsigned char> z;
+        const float zeros[512] = {};
+        for (int c = 0; c < 64; ++c) {
+            const int na = G.na[c];
+            const std::vector<unsigned char>* have = nullptr;
+            for (int i = 0; i < nw && !have; ++i) {
+                auto it = ws[i]->zero_values.find(na);
+                if (it != ws[i]->zero_values.end()) have = &it->second;
+            }
+            std::vector<unsigned char> made;
+            if (!have) value_bytes(zeros, na, compression, made, z);
+            for (int i = 0; i < nw; ++i)
+                if (!ws[i]->zero_values.count(na)) ws[i]->zero_values[na] = have ? *have : made;
+            const std::vector<unsigned char>& b = ws[0]->zero_values[na];
+            zero[c] = Span{b.data(), b.size()};
+        }
+    }
+    const Fan f{ws, nw};
+    std::vector<size_t> off((size_t)nw);
+    for (int i = 0; i < nw; ++i) off[(size_t)i] = grid_head(*ws[i]);
+    write_tree_leaves(f, G, false, compression, table, listed, zero);
+    for (int i = 0; i < nw; ++i) ws[i]->o.patch64(off[(size_t)i] + 8, (int64_t)ws[i]->o.pos());    // block position
+    write_tree_leaves(f, G, true, compression, table, listed, zero);
+    bool ok = true;
+    for (int i = 0; i < nw; ++i) {
+        ws[i]->o.patch64(off[(size_t)i] + 16, (int64_t)ws[i]->o.pos());   // end position
+        ws[i]->written++;
+        ok = ok && ws[i]->o.ok;
+    }
+    return ok ? FLUID_OK : FLUID_ERR_ARG;
 }
 
 }  // namespace
@@ -395,6 +639,53 @@ int fluid_write_vdb_ex(const char* path, int32_t n, int32_t n_grids, const float
 int fluid_write_vdb(const char* path, int32_t n, int32_t n_grids, const float* const* grids)
 {
     return fluid_write_vdb_ex(path, n, n_grids, grids, FLUID_VDB_ZIP_ACTIVE_MASK);
+}
+
+int fluid_leaves_to_dense(const fluid_leaf_grid_t* g, float* dense)
+{
+    if (!dense) return FLUID_ERR_ARG;
+    const int rc = check_leaf_list(g);
+    if (rc) return rc;
+    const int n = g->n, lo = -(n / 2);
+    memset(dense, 0, (size_t)n * n * n * sizeof(float));
+    for (int l = 0; l < g->n_leaves; ++l) {
+        const int32_t* o = g->origin + 3 * (size_t)l;
+        const float* v = g->values + 512 * (size_t)l;
+        for (int x = 0; x < 8; ++x)
+            for (int y = 0; y < 8; ++y)
+                for (int z = 0; z < 8; ++z) {
+                    const int ax = o[0] + x - lo, ay = o[1] + y - lo, az = o[2] + z - lo;
+                    if (ax < 0 || ax >= n || ay < 0 || ay >= n || az < 0 || az >= n) continue;
+                    dense[((size_t)ax * n + ay) * n + az] = v[(x * 8 + y) * 8 + z];
+                }
+    }
+    return FLUID_OK;
+}
+
+int fluid_vdb_append_leaves(fluid_vdb_writer_t* const* writers, int32_t n_writers, const fluid_leaf_grid_t* g)
+{
+    if (!writers || n_writers < 1 || n_writers > 64 || !g) return FLUID_ERR_ARG;
+    Writer* ws[64];
+    for (int i = 0; i < n_writers; ++i) {
+        if (!writers[i]) return FLUID_ERR_ARG;
+        for (int j = 0; j < i; ++j)
+            if (writers[j] == writers[i]) return FLUID_ERR_ARG;
+        ws[i] = &writers[i]->w;
+    }
+    return append_leaves(ws, n_writers, g);
+}
+
+int fluid_write_vdb_leaves(const char* path, const fluid_leaf_grid_t* g, int32_t compression)
+{
+    if (!g) return FLUID_ERR_ARG;
+    int rc = check_leaf_list(g);   // before the file is created
+    if (rc) return rc;
+    fluid_vdb_writer_t* h = nullptr;
+    rc = fluid_vdb_open(path, g->n, 1, compression, &h);
+    if (rc) return rc;
+    rc = fluid_vdb_append_leaves(&h, 1, g);
+    const int rc2 = fluid_vdb_close(h);
+    return rc ? rc : rc2;
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 
-from ._lib import lib, check, Params, StepStats, FIELD, Source
+from ._lib import lib, check, Params, StepStats, FIELD, Source, LeafGridC
 
 _FIELD_DTYPE = {
     FIELD.CONTAINER: (np.float32, 1), FIELD.WEIGHTS: (np.float32, 1), FIELD.OUTPUT: (np.float32, 1),
@@ -48,10 +48,47 @@ class VdbStream:
         assert a.shape == (self.n,) * 3
         check(lib.fluid_vdb_append(self._h, a.ctypes.data))
 
+    def append_leaves(self, leaves, also=()):
+        """Append the grid a LeafGrid describes: the bytes of append(leaves_to_dense(leaves)).  `also`: more open streams of the
+        same n and compression that receive the same grid in the same call (the listed leaves are compressed once)."""
+        ws = [self, *also]
+        hs = (C.c_void_p * len(ws))(*[w._h.value for w in ws])
+        check(lib.fluid_vdb_append_leaves(hs, len(ws), C.byref(leaves._c())))
+
     def close(self):
         h, self._h = self._h, None
         if h:
             check(lib.fluid_vdb_close(h))
+
+
+class LeafGrid:
+    """fluid_leaf_grid_t on the host: n cells per axis, origin (k, 3) int32 — index-space origins of the listed 8^3 leaves,
+    multiples of 8, ascending (x, y, z) — and values (k, 512) float32, ((x&7)*8 + (y&7))*8 + (z&7), +0 outside [lo,hi]^3."""
+
+    def __init__(self, n, origin, values):
+        self.n = int(n)
+        self.origin = np.ascontiguousarray(origin, dtype=np.int32).reshape(-1, 3)
+        self.values = np.ascontiguousarray(values, dtype=np.float32).reshape(-1, 512)
+        assert self.origin.shape[0] == self.values.shape[0]
+
+    @property
+    def n_leaves(self):
+        return self.origin.shape[0]
+
+    def _c(self):
+        return LeafGridC(self.n, self.n_leaves, self.origin.ctypes.data, self.values.ctypes.data)
+
+
+def leaves_to_dense(leaves):
+    """The dense float32 (n, n, n) array a LeafGrid describes (fluid_leaves_to_dense: host only)."""
+    out = np.empty((leaves.n,) * 3, dtype=np.float32)
+    check(lib.fluid_leaves_to_dense(C.byref(leaves._c()), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def write_vdb_leaves(path, leaves, compression="zip"):
+    """write_vdb(path, leaves_to_dense(leaves)) without the dense array: the same file."""
+    check(lib.fluid_write_vdb_leaves(str(path).encode(), C.byref(leaves._c()), _VDB_COMPRESSION[compression]))
 
 
 def water_cube_drop(n, ppc, seed=0):
@@ -269,6 +306,27 @@ class FluidSim:
             dt = _FIELD_DTYPE[fid][0]
         a = np.ascontiguousarray(arr, dtype=dt)
         check(lib.fluid_upload_field(self._h, fid, a.ctypes.data_as(C.c_void_p), a.nbytes))
+
+    # ---- output as non-zero leaves (single GPU; include/fluid_hip.h) -----------------------
+    def output_snapshot(self):
+        """Enqueue a leaf snapshot of FIELD.OUTPUT as it is now; a step() called next overlaps its copy to the host."""
+        check(lib.fluid_output_snapshot(self._h))
+
+    def output_wait(self):
+        """The oldest snapshot not yet waited for, as a LeafGrid (copied out of the handle's pinned buffer)."""
+        g = LeafGridC()
+        check(lib.fluid_output_wait(self._h, C.byref(g)))
+        k = g.n_leaves
+        if k == 0:
+            return LeafGrid(g.n, np.empty((0, 3), np.int32), np.empty((0, 512), np.float32))
+        org = np.ctypeslib.as_array(C.cast(g.origin, C.POINTER(C.c_int32)), shape=(k, 3)).copy()
+        val = np.ctypeslib.as_array(C.cast(g.values, C.POINTER(C.c_float)), shape=(k, 512)).copy()
+        return LeafGrid(g.n, org, val)
+
+    def output_stats(self):
+        v = [C.c_int64() for _ in range(3)]
+        check(lib.fluid_output_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("leaves_in_grid", "leaves_listed", "bytes_to_host"), (x.value for x in v)))
 
     def extrapolate(self):
         """fluid.cc:705-802 after p2g(): velocities for every cell inside W (dead code in the reference; optional here).  Returns the passes run."""

@@ -403,6 +403,47 @@ int fluid_vdb_close(fluid_vdb_writer_t* w);                         /* FLUID_ERR
 int fluid_write_vdb(const char* path, int32_t n, int32_t n_grids, const float* const* grids);
 int fluid_write_vdb_ex(const char* path, int32_t n, int32_t n_grids, const float* const* grids, int32_t compression);
 
+/* ---- output as non-zero leaves (single GPU) ------------------------------------------------------------------------------
+ * The density grid of a step is mostly +0 (a falling cube fills ~ 5 % of OpenVDB's 8^3 leaves, a settled pool ~ 15 %), and the
+ * file needs every leaf all the same (fill([lo,hi]^3, 0, active), fluid.cc:1163).  So the grid leaves the device as the list of
+ * its leaves that hold anything else, and the writer produces from that list the bytes it produces from the dense array.
+ * Leaves are OpenVDB's: origins at multiples of 8 in index space (lo = -(N/2): for N = 121 the first leaf starts at -64 and holds
+ * 4 in-grid cells per axis).  A leaf is listed iff an in-grid voxel of it has a non-zero BIT PATTERN (-0.0f and NaN count).
+ *
+ *   fluid_step(s, &st);  fluid_output_snapshot(s);            enqueue only: the next fluid_step overlaps the copy
+ *   fluid_step(s, &st);  fluid_output_wait(s, &g);            g = the grid of the FIRST step
+ *   fluid_vdb_append_leaves(writers, 2, &g);                  may run on another host thread: it reads g's pointers only
+ */
+typedef struct fluid_leaf_grid {
+    int32_t n;               /* cells per axis of the grid the leaves belong to                                  */
+    int32_t n_leaves;
+    const int32_t* origin;   /* 3 per leaf: index-space origin, multiples of 8, ascending (x, y, z)               */
+    const float* values;     /* 512 per leaf, ((x&7)*8 + (y&7))*8 + (z&7); voxels outside [lo,hi]^3 hold +0       */
+} fluid_leaf_grid_t;
+#define FLUID_OUTPUT_LEAF_BYTES (2048 + 12)   /* what a listed leaf costs on the way to the host: 512 floats + its origin  */
+#define FLUID_OUTPUT_HEADER_BYTES 4           /* ... and the count of listed leaves, once per snapshot                     */
+/* Captures FLUID_FIELD_OUTPUT as it is at the call: mark, scan and pack kernels on the handle's stream (ordered before the next
+ * step clears the grid), the count of listed leaves read back (4 bytes), then the packed records copied to pinned host memory on a
+ * second stream — not waited for here.  Two snapshots may be outstanding; a third returns FLUID_ERR_STATE.  Buffers belong to the
+ * handle, grow on demand here (never inside a step) and are freed by fluid_destroy after the copies in flight have ended.
+ * A decomposed handle (fluid_create_dist) returns FLUID_ERR_STATE from these three entry points. */
+int fluid_output_snapshot(fluid_sim_t* s);
+/* The oldest snapshot not yet waited for (FLUID_ERR_STATE when there is none); a grid of zeros has n_leaves = 0 and NULL
+ * pointers.  The pointers stay valid until the SECOND following fluid_output_snapshot on the handle. */
+int fluid_output_wait(fluid_sim_t* s, fluid_leaf_grid_t* out);
+/* Of the last snapshot (any pointer may be NULL): bytes_to_host = leaves_listed * FLUID_OUTPUT_LEAF_BYTES + FLUID_OUTPUT_HEADER_BYTES. */
+int fluid_output_stats(fluid_sim_t* s, int64_t* leaves_in_grid, int64_t* leaves_listed, int64_t* bytes_to_host);
+/* Host only: dense[n^3] (z fastest) = +0 everywhere, then the in-grid voxels of every listed leaf.  FLUID_ERR_ARG on a bad list
+ * (see fluid_vdb_append_leaves). */
+int fluid_leaves_to_dense(const fluid_leaf_grid_t* g, float* dense);
+/* Appends the grid `g` describes to each of n_writers open writers (same n and compression as g->n / each other).
+ * The bytes appended are those fluid_vdb_append writes for fluid_leaves_to_dense(g); the listed leaves are compressed once for
+ * all writers of the call, every other leaf's bytes are constants of the writer.  FLUID_ERR_ARG on an origin that is
+ * not a multiple of 8, lies outside the leaves of [lo,hi]^3, or is not strictly ascending; FLUID_ERR_STATE on a full writer
+ * (nothing is then written to any of them).  Host only. */
+int fluid_vdb_append_leaves(fluid_vdb_writer_t* const* writers, int32_t n_writers, const fluid_leaf_grid_t* g);
+int fluid_write_vdb_leaves(const char* path, const fluid_leaf_grid_t* g, int32_t compression);
+
 #ifdef __cplusplus
 }
 #endif
