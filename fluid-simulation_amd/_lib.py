@@ -126,6 +126,7 @@ SYMBOLS = [
     ("fluid_profile_reset", C.c_int, [_P]),
     ("fluid_spline_eval", C.c_int, [C.c_int32, C.c_int32, C.c_int64, _P, _P]),
     ("fluid_dot_eval", C.c_int, [C.c_int32, C.c_int64, _P, _P, _P]),
+    ("fluid_scan_eval", C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P]),
     ("fluid_write_vdb", C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.POINTER(_P)]),
     ("fluid_write_vdb_ex", C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.POINTER(_P), C.c_int32]),
     ("fluid_vdb_open", C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P)]),

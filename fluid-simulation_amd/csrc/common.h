@@ -112,6 +112,7 @@ struct StepState {
     double err_den;           // |b|^2
 };
 
+constexpr size_t STATE_PS_OFF = 256;   // a handle keeps its PcgState this many bytes behind its StepState, on the device and in the pinned mirror
 constexpr int MAX_PARTIALS = 8192;
 
 // fluid.cc:22-37
@@ -237,7 +238,8 @@ void launch_bin_rank(hipStream_t st, long n_pos, long pos0, const int* key, cons
                      int* order2);
 void launch_reorder(hipStream_t st, long n, const int* order, Particles src, Particles dst, double* w = nullptr, long wstride = 0);
 void launch_weights(hipStream_t st, long n, Particles p, double* w, long stride);
-void launch_axpby_box(hipStream_t st, Grid g, Box box, double a, const double* x, double b, const double* y, double* out);   // out = a x + b y on box
+// gate != nullptr (here and below): the kernels return at once unless gate->done is set
+void launch_axpby_box(hipStream_t st, Grid g, Box box, double a, const double* x, double b, const double* y, double* out, const PcgState* gate = nullptr);   // out = a x + b y on box
 long p2g_max_items(Box box);
 size_t p2g_part_doubles(Box box);   // size of launch_p2g's `part`
 constexpr int P2G_PILED = 256;   // a cell with more particles: the particles have piled up (walls, floor), P2G takes the tile form
@@ -251,6 +253,8 @@ void launch_g2p_tiled(hipStream_t st, Grid g, Box pb, Particles p, const int* ce
 void launch_g2p(hipStream_t st, Grid g, long n, Particles p, const double* dcx, const double* dcy, const double* dcz, const double* pcx,
                 const double* pcy, const double* pcz, double blend, StepState* ss);
 void launch_advect(hipStream_t st, Grid g, long n, Particles p, const uint8_t* flags, double max_dt, double dx, StepState* ss);
+void launch_advect_bin(hipStream_t st, Grid g, long n, Particles p, const uint8_t* flags, double max_dt, double dx, StepState* ss, int* key,
+                       int* slot, int* cell_count, int* part);   // + the next sort's binning (launch_bin_count) in the same pass
 void launch_pack_particles(hipStream_t st, long n, Particles p, double* pos_aos, double* vel_aos);
 void launch_unpack_records(hipStream_t st, long n, const double* rec, Particles p, long off);
 void launch_pack_records(hipStream_t st, long n, Particles p, long off, double* rec);
@@ -265,15 +269,17 @@ void launch_out_pack(hipStream_t st, const float* f, int N, int lo, int off, int
 void launch_exclusive_scan(hipStream_t st, const int* in, int* out, long n, int* block_sums, int* total);
 void launch_sort_tail(hipStream_t st, const int* cell_count, int* cell_start, long c1, long ncell);
 void launch_index_scan(hipStream_t st, Grid g, const uint8_t* flags, int* indices, int* block_sums, int* total);
+void launch_index_scan_flat(hipStream_t st, const uint8_t* flags, int* indices, long n, int* block_sums, int* total);   // any n flag bytes
 void launch_flags(hipStream_t st, Grid g, const uint8_t* solid, const float* container, uint8_t* flags, int x0, int x1);
 void launch_index_scan_range(hipStream_t st, Grid g, const uint8_t* flags, int* indices, int* block_sums, int* total, int x0, int x1);
 void launch_rhs_div(hipStream_t st, Grid g, Box box, const uint8_t* flags, const double* u, const double* v, const double* w,
-                    float* rhs, float* diver, double dx, double gdt0, double gdt1, double gdt2, bool rows = false);
+                    float* rhs, float* diver, double dx, double gdt0, double gdt1, double gdt2, bool rows = false, const PcgState* gate = nullptr);
 void launch_vel_update(hipStream_t st, Grid g, Box box, const uint8_t* flags, const double* p, double* u, double* v, double* w,
-                       double k, double g0, double g1, double g2, bool rows = false);
+                       double k, double g0, double g1, double g2, bool rows = false, const PcgState* gate = nullptr);
 void launch_flip_delta(hipStream_t st, Grid g, Box box, const double* u, const double* v, const double* w,
                        const double* ub, const double* vb, const double* wb, double* dcx, double* dcy, double* dcz, double* pcx, double* pcy, double* pcz);
-void launch_err_norm(hipStream_t st, Grid g, Box box, const uint8_t* flags, const float* b, const float* b2, double* part, StepState* ss);
+void launch_err_norm(hipStream_t st, Grid g, Box box, const uint8_t* flags, const float* b, const float* b2, double* part, StepState* ss,
+                     const PcgState* gate = nullptr);
 void launch_zero_step_state(hipStream_t st, StepState* ss, int N);
 struct ZeroList { float* f4[4]; double* f8[7]; };
 void launch_zero_fields(hipStream_t st, const ZeroList& z, Grid g, Box box, bool rows = false);
@@ -336,7 +342,7 @@ constexpr int DROP_CAP = 65536;   // components the buffers hold (64 cells each)
 constexpr int DROP_NCTR = 64;     // ... in as many ranges, each with a counter of its own
 void launch_drop_find(hipStream_t st, LBox L, uint8_t* cnt, int* ctr, int* pre, int* total, int* comp_n, int* comp_cells, const Box* own = nullptr);   // own (local-box coordinates): a claimed pocket lies wholly inside (decomposed run: the owned cells)
 void launch_drop_solve(hipStream_t st, Grid g, LBox L, int n_comp, const int* pre, const int* comp_n, const int* comp_cells, const uint8_t* flags,
-                       const float* b, Coef<double> cf, double tol, double* pressure, double* keep, int* n_fail = nullptr);   // n_fail += droplets whose CG stopped short of the tolerance
+                       const float* b, Coef<double> cf, double tol, double* pressure, double* keep, int* n_fail = nullptr, const PcgState* gate = nullptr);   // n_fail += droplets whose CG stopped short of the tolerance
 template <typename T>
 void launch_pcg_xr_rows(hipStream_t st, LBox L, const uint8_t* cnt, T* x, T* r, const T* s, const T* q, Coef<T> cf, const double* part_rz_cur,
                         int n_rz, const double* part_pq, int n_pq, double* part_rr, double* part_rz_next, PcgState* ps, const int* rlist, int nrows);
@@ -367,7 +373,7 @@ template <typename T>
 bool launch_stencil_march(hipStream_t st, Grid g, const uint8_t* flags, const T* s, T* q, Coef<T> cf, int variant, int cxcode);
 template <typename T>
 void launch_store_pressure(hipStream_t st, Grid g, LBox L, const uint8_t* cnt, const T* x, double* pressure, double* keep = nullptr,
-                           const PcgState* ps = nullptr);
+                           const PcgState* ps = nullptr, bool gated = false);   // gated: nothing is stored unless ps->done
 template <typename T>
 void launch_pcg_init_guess(hipStream_t st, Grid g, LBox L, const uint8_t* cnt, const float* b, const double* guess, const double* guess2, double ca,
                            double cb, T* x, T* r, Coef<T> cf, double* part_bb, double* part_rr0, PcgState* ps);

@@ -78,6 +78,7 @@ static void free_particles(fluid_sim* s)
     s->order2 = nullptr; s->spid = nullptr; hipFree(s->pw);
     s->pw = nullptr;
     s->key = s->slot = s->order = nullptr;
+    s->binned = false;   // key and slot are gone
     s->stage_pos = s->stage_vel = nullptr;
     s->cap = 0;
 }
@@ -174,10 +175,9 @@ int fluid_destroy(fluid_sim_t* s)
     output_free(s);
     void* ptrs[] = {s->solid, s->flags, s->container, s->rhs, s->diver, s->diver2, s->u, s->v, s->w, s->ub, s->vb, s->wb, s->dcx, s->dcy,
                     s->dcz, s->pressure, s->p_guess, s->p_guess2, s->p_q, s->indices, s->scan_sums, s->ipart, s->R, s->S[0], s->Q, s->X, s->mg_slab, s->mg_part, s->cntL, s->part_bb, s->part_rr,
-                    s->part_rz[0], s->part_rz[1], s->part_pq, s->part_err, s->ps, s->cell_count, s->cell_start, s->ss,
+                    s->part_rz[0], s->part_rz[1], s->part_pq, s->part_err, s->cell_count, s->cell_start, s->ss,
                     s->pcx, s->pcy, s->pcz, s->p2g_part, s->p2g_items, s->p2g_crowd, s->tl_flags, s->tl_mg, s->tl_sq, s->d_small, s->row_flags, s->row_pos, s->row_list, s->drop_n, s->drop_cells, s->drop_ctr, s->gal_slab};
     for (void* p : ptrs) if (p) hipFree(p);
-    if (s->h_ps) hipHostFree(s->h_ps);
     for (int i = 0; i < 2; ++i) if (s->ev_poll[i]) hipEventDestroy(s->ev_poll[i]);
     if (s->h_ss) hipHostFree(s->h_ss);
     if (s->h_small) hipHostFree(s->h_small);
@@ -231,6 +231,8 @@ int fl::fluid_create_window(const fluid_params_t* p, const Grid& g, fluid_sim_t*
     if (const char* e = getenv("FLUID_DROPLETS")) s->drops_on = atoi(e) != 0;
     if (const char* e = getenv("FLUID_ROW_SWEEPS")) s->row_sweeps = atoi(e) != 0;
     if (const char* e = getenv("FLUID_DROPLETS_MIN")) s->drop_min = atoi(e);
+    if (const char* e = getenv("FLUID_ADVECT_BIN")) s->advect_bin = atoi(e) != 0;
+    if (const char* e = getenv("FLUID_SOLVE_TAIL")) s->solve_tail = atoi(e) != 0;
     *out = nullptr;
     auto bail = [&](int rc) { fluid_destroy(s); return rc; };
 #define A(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return bail(fail(FLUID_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_))); } while (0)
@@ -261,14 +263,17 @@ int fl::fluid_create_window(const fluid_params_t* p, const Grid& g, fluid_sim_t*
     A(dalloc(&s->part_bb, (size_t)MAX_PARTIALS)); A(dalloc(&s->part_rr, (size_t)MAX_PARTIALS));
     A(dalloc(&s->part_rz[0], (size_t)MAX_PARTIALS)); A(dalloc(&s->part_rz[1], (size_t)MAX_PARTIALS));
     A(dalloc(&s->part_pq, (size_t)MAX_PARTIALS)); A(dalloc(&s->part_err, (size_t)2 * MAX_PARTIALS));
-    A(dalloc(&s->ps, (size_t)1)); A(dalloc(&s->ss, (size_t)1));
+    // StepState and PcgState share one allocation (and one pinned mirror) so that one copy can bring both back (solve_mg)
+    static_assert(sizeof(StepState) <= STATE_PS_OFF, "PcgState overlaps StepState");
+    A(dalloc((char**)&s->ss, STATE_PS_OFF + sizeof(PcgState)));
+    s->ps = (PcgState*)((char*)s->ss + STATE_PS_OFF);
     A(dalloc(&s->cell_count, n + 4)); A(dalloc(&s->cell_start, n + 4));
     A(dalloc(&s->d_small, (size_t)32));
     A(hipHostMalloc((void**)&s->h_small, 32 * sizeof(int)));
-    A(hipHostMalloc((void**)&s->h_ps, 2 * sizeof(PcgState)));
     A(hipEventCreateWithFlags(&s->ev_poll[0], hipEventDisableTiming));
     A(hipEventCreateWithFlags(&s->ev_poll[1], hipEventDisableTiming));
-    A(hipHostMalloc((void**)&s->h_ss, sizeof(StepState)));
+    A(hipHostMalloc((void**)&s->h_ss, STATE_PS_OFF + 2 * sizeof(PcgState)));
+    s->h_ps = (PcgState*)((char*)s->h_ss + STATE_PS_OFF);
 #undef A
     // default solid shell: solid outside W (fluid.cc:1256-1266)
     std::vector<uint8_t> sol(n, 0);
@@ -337,6 +342,7 @@ int fluid_upload_particles(fluid_sim_t* s, int64_t n, const double* pos, const d
     s->sorted = s->have_p2g = s->have_flags = false;
     s->have_guess = false;  // a new particle set: the first solve starts from 0
     s->sort_hint = false;
+    s->binned = false;
     s->vel_ok = false;
     return FLUID_OK;
 }
@@ -446,6 +452,25 @@ int fl::sort_pass(fluid_sim* s, int ax0, int ax1, int* h_tail)
     return read_ss(s);
 }
 
+// FLIPadvect of the last step already binned these particles (fluid_sim::binned): the sort from its scan on, nothing read back
+static int sort_binned(fluid_sim* s)
+{
+    const Grid g = s->g;
+    const long ncell = (long)s->ncell, n2 = g.sx();
+    const long c0 = (long)s->bin_x0 * n2, c1 = (long)(s->bin_x1 + 1) * n2;
+    launch_zero_step_state(s->st, s->ss, g.N);
+    launch_exclusive_scan(s->st, s->cell_count + c0, s->cell_start + c0, c1 - c0, s->scan_sums, s->cell_start + c1);
+    launch_sort_tail(s->st, s->cell_count, s->cell_start, c1, ncell);
+    launch_bin_scatter(s->st, s->np, s->key, s->slot, s->cell_start, s->pa.shifted(s->p_off).pid, s->order, s->spid);
+    launch_bin_rank(s->st, s->np, 0, s->key, s->cell_start, s->order, s->spid, s->order2);
+    HIPCHK(hipGetLastError());
+    StepState& h = *s->h_ss;   // where the code below looks for what a sort pass reads back
+    for (int a = 0; a < 3; ++a) h.bbox_min[a] = s->bin_min[a], h.bbox_max[a] = s->bin_max[a];
+    h.n_out = s->bin_n_out;
+    h.max_cell = s->bin_max_cell;
+    return FLUID_OK;
+}
+
 static int phase_sort(fluid_sim* s)
 {
     const Grid g = s->g;
@@ -456,10 +481,21 @@ static int phase_sort(fluid_sim* s)
         ax0 = std::max(0, s->Pb.x0 - 3);
         ax1 = std::min(g.nx - 1, s->Pb.x1 + 3);
     }
-    int rc = sort_pass(s, ax0, ax1);
-    if (rc) return rc;
-    if (guess && s->h_ss->bbox_max[0] >= 0 && (s->h_ss->bbox_min[0] < std::min(ax0 + 2, s->Pb.x0) || s->h_ss->bbox_max[0] > std::max(ax1 - 2, s->Pb.x1))) {
-        if ((rc = sort_pass(s, 0, g.nx - 1))) return rc;   // the guess did not hold
+    const bool binned = s->binned && guess && ax0 == s->bin_x0 && ax1 == s->bin_x1 && s->np > 0;
+    s->binned = false;
+    const auto missed = [&](const int* bmin, const int* bmax) {
+        return guess && bmax[0] >= 0 && (bmin[0] < std::min(ax0 + 2, s->Pb.x0) || bmax[0] > std::max(ax1 - 2, s->Pb.x1));
+    };
+    int rc;
+    if (binned && !missed(s->bin_min, s->bin_max)) {
+        if ((rc = sort_binned(s))) return rc;
+    } else {
+        // (binned, but a particle left the window: the full sort below bins again)
+        rc = binned ? FLUID_OK : sort_pass(s, ax0, ax1);
+        if (rc) return rc;
+        if (binned || missed(s->h_ss->bbox_min, s->h_ss->bbox_max)) {
+            if ((rc = sort_pass(s, 0, g.nx - 1))) return rc;   // the guess did not hold
+        }
     }
     s->sort_hint = true;
     s->n_out = s->h_ss->n_out;
@@ -813,8 +849,11 @@ static int mg_vcycle(fluid_sim* s, const double* rhs0, void* z0, double* part_rz
     return s->mg_fp32 ? mg_vcycle_t<float>(s, rhs0, (float*)z0, part_rz) : mg_vcycle_t<double>(s, rhs0, (double*)z0, part_rz);
 }
 
+static int phase_vel_update(fluid_sim* s, const PcgState* gate = nullptr);
+static int phase_rhs_div(fluid_sim* s, int which, const PcgState* gate = nullptr);
 // PCG loop of ConjugateGradient.h:28-90 with z = V-cycle(r); same start, stopping rule and cap as solve_impl.
-static int solve_mg(fluid_sim* s)
+// with_tail (phase_pressure_pass): the first poll may carry the rest of the pass, see below; s->tail_ran tells
+static int solve_mg(fluid_sim* s, bool with_tail)
 {
     typedef double T;
     const Grid g = s->g;
@@ -876,6 +915,19 @@ static int solve_mg(fluid_sim* s)
         else
             launch_pcg_sq<T>(s->st, L, cnt, Z, Sx[prv], Sx[cur], Q, cf, part_rr, rz_new, rz_old, s->part_pq, s->ps, first, tol, n_rz, 1, sp, n_prev);
     };
+    // The solution leaves the solver layout: the new pressure goes into the buffer of the older guess (rotate_guess then makes
+    // it the latest), the droplets are solved, and after the second pass of a step q = p_1 - (1 - f) p_0 is formed over the box
+    // for the next steps' second passes (start_guess; one GPU and the replicated solve of a multi-GPU run — the decomposed step
+    // forms it after its halo exchange).  will_make_q is make_q() as it reads once rotate_guess has run.
+    const bool will_make_q = s->warm && s->p_q && s->stats.outer_passes == 1 && s->guess_step == s->step_counter && s->guess_pass == 0;
+    auto solution_out = [&](const PcgState* gate) {
+        launch_store_pressure<T>(s->st, g, L, cnt, X, s->pressure, s->warm ? s->p_guess2 : nullptr, s->ps, gate != nullptr);
+        launch_drop_solve(s->st, g, L, s->n_drop, s->drop_ctr + 64 * DROP_NCTR, s->drop_n, s->drop_cells, s->flags, s->diver, make_coef<double>(s), tol,
+                          s->pressure, s->warm ? s->p_guess2 : nullptr, &s->ss->n_drop_fail, gate);
+        if (will_make_q) launch_axpby_box(s->st, g, s->Rb, 1.0, s->p_guess2, -(1.0 - s->prm.update_frac), s->p_guess, s->p_q, gate);
+    };
+    bool first_poll = true;
+    s->tail_ran = false;
     while (!done) {
         for (long k = 0; k < batch && it < max_it; ++k, ++it) {
             const int cur = (int)(it & 1), prv = cur ^ 1;
@@ -903,9 +955,27 @@ static int solve_mg(fluid_sim* s)
             const int cur = (int)(it & 1), prv = cur ^ 1;
             sq(cur, s->part_rr, lists ? n_list : n_init, s->part_rz[prv], s->part_rz[prv], 0, 0);
         }
-        HIPCHK(hipMemcpyAsync(&s->h_ps[0], s->ps, sizeof(PcgState), hipMemcpyDeviceToHost, s->st));
+        // The first poll of a solve usually finds it finished (the batch ran the bodies the last solve needed), and then the
+        // rest of the pass would follow 4 short kernels later with a wait of its own for the pass error.  So that rest is
+        // enqueued here, ahead of the answer: each of its kernels returns at once unless ps->done is set.  One copy then
+        // brings PcgState and StepState (the error sums) back together.  Not finished: nothing ran, the solve goes on as
+        // ever and the tail follows it unguarded.  (A solve the cap ends has no head-only launch and no done flag: unguarded.)
+        const bool spec = with_tail && s->solve_tail && !s->dist && first_poll && it < max_it;
+        first_poll = false;
+        if (spec) {
+            int rc2;
+            solution_out(s->ps);
+            if ((rc2 = phase_vel_update(s, s->ps))) return rc2;
+            if ((rc2 = phase_rhs_div(s, 1, s->ps))) return rc2;
+            launch_err_norm(s->st, s->g, s->Rb, s->flags, s->diver, s->diver2, s->part_err, s->ss, s->ps);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(s->h_ss, s->ss, STATE_PS_OFF + sizeof(PcgState), hipMemcpyDeviceToHost, s->st));   // h_ss and h_ps[0]
+        } else {
+            HIPCHK(hipMemcpyAsync(&s->h_ps[0], s->ps, sizeof(PcgState), hipMemcpyDeviceToHost, s->st));
+        }
         HIPCHK(hipStreamSynchronize(s->st));
         done = s->h_ps[0].done || it >= max_it;
+        if (spec && s->h_ps[0].done) s->tail_ran = true;
         if (!done) {
             s->h_ps[1] = s->h_ps[0];   // pinned slot: stays valid while the copy is in flight
             s->h_ps[1].iters -= 1;     // the head-only launch counted a body that the next real launch counts again
@@ -916,16 +986,11 @@ static int solve_mg(fluid_sim* s)
     int iters = s->h_ps->iters;
     const double rr = s->h_ps->rr;
     if (!s->h_ps->done) iters = (int)max_it;
-    // the new solution goes into the buffer of the older guess, which then becomes the latest
-    launch_store_pressure<T>(s->st, g, L, cnt, X, s->pressure, s->warm ? s->p_guess2 : nullptr, s->ps);
-    launch_drop_solve(s->st, g, L, s->n_drop, s->drop_ctr + 64 * DROP_NCTR, s->drop_n, s->drop_cells, s->flags, s->diver, make_coef<double>(s), tol,
-                      s->pressure, s->warm ? s->p_guess2 : nullptr, &s->ss->n_drop_fail);
+    if (!s->tail_ran) solution_out(nullptr);
     if (s->warm) s->rotate_guess();
     s->have_guess = s->warm;
-    if (s->make_q()) {   // (one GPU and the replicated solve of a multi-GPU run; the decomposed step forms it after its halo exchange) q = p_1 - (1 - f) p_0 over the box, for the next steps' second passes (start_guess)
-        launch_axpby_box(s->st, g, s->Rb, 1.0, s->p_guess, -(1.0 - s->prm.update_frac), s->p_guess2, s->p_q);
-        s->q_step = s->step_counter;
-    }
+    if (s->make_q() != will_make_q) return fail(FLUID_ERR_STATE, "solve_mg: q formed for the wrong pass");
+    if (will_make_q) s->q_step = s->step_counter;
     HIPCHK(hipGetLastError());
     prof_end(s, FLUID_PROF_SOLVE, tsolve);
     s->stats.cg_iters_last = iters;
@@ -1043,13 +1108,13 @@ int fl::phase_flags(fluid_sim* s)
     return FLUID_OK;
 }
 
-static int phase_rhs_div(fluid_sim* s, int which)
+static int phase_rhs_div(fluid_sim* s, int which, const PcgState* gate)
 {
     if (!s->have_flags) return fail(FLUID_ERR_STATE, "rhs_div before flags_index");
     if (box_empty(s->Rb)) return FLUID_OK;
     const double dt = s->dt;
     launch_rhs_div(s->st, s->g, s->Rb, s->flags, s->u, s->v, s->w, s->rhs, which ? s->diver2 : s->diver, s->prm.dx,
-                   s->prm.gravity[0] * dt, s->prm.gravity[1] * dt, s->prm.gravity[2] * dt, !s->dist && s->row_sweeps);  // gravity*dt, fluid.cc:420
+                   s->prm.gravity[0] * dt, s->prm.gravity[1] * dt, s->prm.gravity[2] * dt, !s->dist && s->row_sweeps, gate);  // gravity*dt, fluid.cc:420
     HIPCHK(hipGetLastError());
     return FLUID_OK;
 }
@@ -1125,22 +1190,23 @@ static int solve_impl(fluid_sim* s)
     return FLUID_OK;
 }
 
-static int phase_solve(fluid_sim* s)
+static int phase_solve(fluid_sim* s, bool with_tail = false)
 {
+    s->tail_ran = false;
     if (!s->have_flags) return fail(FLUID_ERR_STATE, "solve before flags_index");
     if (box_empty(s->Rb)) return FLUID_OK;
-    if (use_mg(s) && s->mg_nl >= 2) return solve_mg(s);  // a box that is already <= 8^3 has no coarser level: Jacobi
+    if (use_mg(s) && s->mg_nl >= 2) return solve_mg(s, with_tail);  // a box that is already <= 8^3 has no coarser level: Jacobi
     return s->prm.precision == FLUID_PRECISION_FP32 ? solve_impl<float>(s) : solve_impl<double>(s);
 }
 
-static int phase_vel_update(fluid_sim* s)
+static int phase_vel_update(fluid_sim* s, const PcgState* gate)
 {
     if (!s->have_flags) return fail(FLUID_ERR_STATE, "vel_update before flags_index");
     if (box_empty(s->Sb)) return FLUID_OK;
     const double dtp = s->dt * s->prm.update_frac;      // dt/10, fluid.cc:1475
     const double k = dtp / (s->prm.rho * s->prm.dx);    // :614
     launch_vel_update(s->st, s->g, s->Sb, s->flags, s->pressure, s->u, s->v, s->w, k, s->prm.gravity[0] * dtp, s->prm.gravity[1] * dtp,
-                      s->prm.gravity[2] * dtp, !s->dist && s->row_sweeps);         // gravity*dt, :638
+                      s->prm.gravity[2] * dtp, !s->dist && s->row_sweeps, gate);   // gravity*dt, :638
     HIPCHK(hipGetLastError());
     return FLUID_OK;
 }
@@ -1149,14 +1215,20 @@ int fl::phase_pressure_pass(fluid_sim* s, double* error)
 {
     int rc;
     if ((rc = phase_rhs_div(s, 0))) return rc;
-    if ((rc = phase_solve(s))) return rc;
-    if ((rc = phase_vel_update(s))) return rc;
-    if ((rc = phase_rhs_div(s, 1))) return rc;
+    if ((rc = phase_solve(s, true))) return rc;
+    const bool tail_ran = s->tail_ran;   // solve_mg's first poll carried the rest of this pass: *h_ss holds its error sums
+    s->tail_ran = false;
+    if (!tail_ran) {
+        if ((rc = phase_vel_update(s))) return rc;
+        if ((rc = phase_rhs_div(s, 1))) return rc;
+    }
     double err = NAN;
     if (!box_empty(s->Rb)) {
-        launch_err_norm(s->st, s->g, s->Rb, s->flags, s->diver, s->diver2, s->part_err, s->ss);
-        HIPCHK(hipGetLastError());
-        if ((rc = read_ss(s))) return rc;
+        if (!tail_ran) {
+            launch_err_norm(s->st, s->g, s->Rb, s->flags, s->diver, s->diver2, s->part_err, s->ss);
+            HIPCHK(hipGetLastError());
+            if ((rc = read_ss(s))) return rc;
+        }
         if (s->h_ss->n_drop_fail > 0) s->stats.paths |= FLUID_PATH_DROPLETS_SHORT;   // a pocket solved apart stopped short of the tolerance: reported, not hidden
         err = std::sqrt(s->h_ss->err_num) / std::sqrt(s->h_ss->err_den);  // fluid.cc:1483
     }
@@ -1200,10 +1272,31 @@ static int phase_flip_advect(fluid_sim* s)
         launch_g2p(s->st, s->g, s->np, s->pa.shifted(s->p_off), s->dcx, s->dcy, s->dcz, s->pcx, s->pcy, s->pcz, s->prm.flip_blend, s->ss);
     }
     prof_end(s, FLUID_PROF_G2P, tok);
-    launch_advect(s->st, s->g, s->np, s->pa.shifted(s->p_off), s->flags, s->prm.max_dt, s->prm.dx, s->ss);
+    // The next sort's binning in the same pass, over the window that sort will guess (phase_sort): the planes of this step's
+    // box +- 3 and the tail buckets of cell_count, which nothing reads after this step's k_sort_tail.
+    const bool bin = s->advect_bin && !s->dist && s->np > 0 && s->sorted && s->sort_hint && !box_empty(s->Pb);
+    s->binned = false;
+    if (bin) {
+        const Grid g = s->g;
+        s->bin_x0 = std::max(0, s->Pb.x0 - 3);
+        s->bin_x1 = std::min(g.nx - 1, s->Pb.x1 + 3);
+        const long n2 = g.sx(), c0 = (long)s->bin_x0 * n2, c1 = (long)(s->bin_x1 + 1) * n2;
+        HIPCHK(hipMemsetAsync(s->cell_count + c0, 0, (c1 - c0) * sizeof(int), s->st));
+        HIPCHK(hipMemsetAsync(s->cell_count + s->ncell, 0, 4 * sizeof(int), s->st));
+        launch_advect_bin(s->st, g, s->np, s->pa.shifted(s->p_off), s->flags, s->prm.max_dt, s->prm.dx, s->ss, s->key, s->slot, s->cell_count, s->ipart);
+    } else {
+        launch_advect(s->st, s->g, s->np, s->pa.shifted(s->p_off), s->flags, s->prm.max_dt, s->prm.dx, s->ss);
+    }
     HIPCHK(hipGetLastError());
     int rc = read_ss(s);
     if (rc) return rc;
+    if (bin) {
+        const StepState& h = *s->h_ss;
+        for (int a = 0; a < 3; ++a) s->bin_min[a] = h.bbox_min[a], s->bin_max[a] = h.bbox_max[a];
+        s->bin_n_out = h.n_out;
+        s->bin_max_cell = h.max_cell;
+        s->binned = true;
+    }
     s->dt = s->h_ss->dt;
     double ms;
     memcpy(&ms, &s->h_ss->max_speed_bits, sizeof(double));
@@ -1222,9 +1315,9 @@ extern "C" {
     if ((s)->dist) return fail(FLUID_ERR_STATE, "per-phase entry points are single-GPU only; a decomposed run steps with fluid_step")
 int fluid_p2g(fluid_sim_t* s) { PHASE_GUARD(s); return phase_p2g(s); }
 int fluid_flags_index(fluid_sim_t* s) { PHASE_GUARD(s); return phase_flags(s); }
-int fluid_rhs_div(fluid_sim_t* s, int which) { PHASE_GUARD(s); return phase_rhs_div(s, which); }
-int fluid_solve(fluid_sim_t* s) { PHASE_GUARD(s); return phase_solve(s); }
-int fluid_vel_update(fluid_sim_t* s) { PHASE_GUARD(s); return phase_vel_update(s); }
+int fluid_rhs_div(fluid_sim_t* s, int which) { PHASE_GUARD(s); return phase_rhs_div(s, which, nullptr); }
+int fluid_solve(fluid_sim_t* s) { PHASE_GUARD(s); return phase_solve(s, false); }
+int fluid_vel_update(fluid_sim_t* s) { PHASE_GUARD(s); return phase_vel_update(s, nullptr); }
 int fluid_pressure_pass(fluid_sim_t* s, double* error) { PHASE_GUARD(s); return phase_pressure_pass(s, error); }
 int fluid_flip_advect(fluid_sim_t* s) { PHASE_GUARD(s); return phase_flip_advect(s); }
 
@@ -1312,6 +1405,7 @@ int fluid_resample(fluid_sim_t* s, int32_t per_cell, int64_t* n_parked)
     if (n_parked) *n_parked = s->h_small[0];
     s->sorted = s->have_p2g = s->have_flags = false;   // positions changed
     s->sort_hint = false;
+    s->binned = false;
     return FLUID_OK;
 }
 
@@ -1528,6 +1622,35 @@ int fluid_dot_eval(int32_t device, int64_t n, const double* a, const double* b, 
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(out, dp + nb, sizeof(double), hipMemcpyDeviceToHost));
     hipFree(da); hipFree(db); hipFree(dp);
+    return FLUID_OK;
+}
+
+int fluid_scan_eval(int32_t device, int32_t mode, int64_t n, int32_t in_offset, int32_t out_offset, const void* in, int32_t* out, int32_t* total)
+{
+    if (n <= 0 || n > 0x7fffffffL || mode < 0 || mode > 1 || in_offset < 0 || in_offset > 64 || out_offset < 0 || out_offset > 64 || !in || !out || !total)
+        return fail(FLUID_ERR_ARG, "bad argument");
+    int rc = hook_device(device);
+    if (rc) return rc;
+    const size_t ie = mode == 0 ? sizeof(int) : 1, guard = 16;
+    const int fill = 0x5a5a5a5a;
+    char* din = nullptr;
+    int *dout = nullptr, *dsums = nullptr;
+    HIPCHK(hipMalloc((void**)&din, ((size_t)n + in_offset + 64) * ie));
+    HIPCHK(hipMalloc((void**)&dout, ((size_t)n + out_offset + 2 * guard + 1) * sizeof(int)));
+    HIPCHK(hipMalloc((void**)&dsums, ((size_t)n / 2048 + 16) * sizeof(int)));
+    HIPCHK(hipMemset(dout, 0x5a, ((size_t)n + out_offset + 2 * guard + 1) * sizeof(int)));
+    HIPCHK(hipMemcpy(din + (size_t)in_offset * ie, in, (size_t)n * ie, hipMemcpyHostToDevice));
+    int* o = dout + guard + out_offset;   // the total lands behind the far guard
+    if (mode == 0) launch_exclusive_scan(nullptr, (const int*)din + in_offset, o, (long)n, dsums, o + n + guard);
+    else launch_index_scan_flat(nullptr, (const uint8_t*)din + in_offset, o, (long)n, dsums, o + n + guard);
+    HIPCHK(hipGetLastError());
+    std::vector<int> h((size_t)n + 2 * guard + 1);
+    HIPCHK(hipMemcpy(h.data(), o - guard, h.size() * sizeof(int), hipMemcpyDeviceToHost));
+    hipFree(din); hipFree(dout); hipFree(dsums);
+    for (size_t i = 0; i < guard; ++i)
+        if (h[i] != fill || h[guard + (size_t)n + i] != fill) return fail(FLUID_ERR_STATE, "scan wrote outside out[0, n)");
+    memcpy(out, h.data() + guard, (size_t)n * sizeof(int));
+    *total = h[2 * guard + (size_t)n];
     return FLUID_OK;
 }
 

@@ -127,6 +127,7 @@ int fl::sources_apply(fluid_sim* s)
     for (int i = 0; i < FLUID_MAX_SINKS; ++i) any = any || s->sink_on[i];
     for (const auto& q : s->src) any = any || q.on;
     if (!any) return FLUID_OK;
+    s->binned = false;   // the sinks use key / slot as scratch, both change the particle set: the next sort bins for itself
     const long t = s->n_steps;
     long removed = 0, emitted = 0;
     int rc = apply_sinks(s, &removed);
@@ -170,6 +171,7 @@ int fluid_add_particles(fluid_sim_t* s, int64_t n, const double* pos, const doub
     s->np += (long)n;
     s->sorted = s->have_p2g = s->have_flags = false;
     s->sort_hint = false;   // (the warm start, have_guess, stays: the same scene a little fuller)
+    s->binned = false;
     return FLUID_OK;
 }
 

@@ -231,9 +231,10 @@ __global__ __launch_bounds__(256) void k_drop_clear(const int* __restrict__ ctr,
 // one wave per droplet
 __global__ __launch_bounds__(256) void k_drop_solve(Grid g, LBox L, int n_comp, const int* __restrict__ pre, const int* __restrict__ comp_n, const int* __restrict__ comp_cells,
                                                     const uint8_t* __restrict__ flags, const float* __restrict__ b, Coef<double> cf, double tol,
-                                                    double* __restrict__ pressure, double* __restrict__ keep, int* __restrict__ n_fail)
+                                                    double* __restrict__ pressure, double* __restrict__ keep, int* __restrict__ n_fail, const PcgState* gate)
 {
     __shared__ int skey[4][64];
+    if (gate && !gate->done) return;   // enqueued ahead of the global solve's poll
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int dense = blockIdx.x * 4 + wv;
     if (dense >= n_comp) return;
@@ -329,10 +330,10 @@ void launch_drop_find(hipStream_t st, LBox L, uint8_t* cnt, int* ctr, int* pre, 
     hipLaunchKernelGGL(k_drop_clear, dim3((unsigned)((size_t)DROP_CAP * 64 / 256)), dim3(256), 0, st, ctr, comp_n, comp_cells, cnt, pre, total);
 }
 void launch_drop_solve(hipStream_t st, Grid g, LBox L, int n_comp, const int* pre, const int* comp_n, const int* comp_cells, const uint8_t* flags,
-                       const float* b, Coef<double> cf, double tol, double* pressure, double* keep, int* n_fail)
+                       const float* b, Coef<double> cf, double tol, double* pressure, double* keep, int* n_fail, const PcgState* gate)
 {
     if (n_comp <= 0) return;
-    hipLaunchKernelGGL(k_drop_solve, dim3((unsigned)((n_comp + 3) / 4)), dim3(256), 0, st, g, L, n_comp, pre, comp_n, comp_cells, flags, b, cf, tol, pressure, keep, n_fail);
+    hipLaunchKernelGGL(k_drop_solve, dim3((unsigned)((n_comp + 3) / 4)), dim3(256), 0, st, g, L, n_comp, pre, comp_n, comp_cells, flags, b, cf, tol, pressure, keep, n_fail, gate);
 }
 
 }  // namespace fl

@@ -20,15 +20,42 @@ __device__ __forceinline__ int scan_load(const void* in, long i)
     return (((const uint8_t*)in)[i] & F_FLUID) ? 1 : 0;
 }
 
-template <int MODE>
-__global__ __launch_bounds__(SCAN_T) void k_scan_sums(const void* __restrict__ in, long n, int* __restrict__ block_sums)
+// The 8 elements of one thread, element `base` first.  VEC: the launcher shifted the thread grid `lead` elements in front of
+// in[0] so that every thread's group starts on a 16-byte boundary of in and of out (8 bytes of flag bytes): a group that
+// lies inside [0, n) moves as two 16-byte words (one 8-byte word of flags); the groups across the two ends go element by
+// element.
+template <int MODE, bool VEC>
+__device__ __forceinline__ void scan_load8(const void* in, long base, long n, int v[SCAN_E])
+{
+    if (VEC && base >= 0 && base + SCAN_E <= n) {
+        if (MODE == 0) {
+            const int4 a = *(const int4*)((const int*)in + base), b = *(const int4*)((const int*)in + base + 4);
+            v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+            v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+        } else {
+            const uint2 w = *(const uint2*)((const uint8_t*)in + base);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                v[e] = ((w.x >> (8 * e)) & F_FLUID) ? 1 : 0;
+                v[4 + e] = ((w.y >> (8 * e)) & F_FLUID) ? 1 : 0;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < SCAN_E; ++e) v[e] = (base + e >= 0 && base + e < n) ? scan_load<MODE>(in, base + e) : 0;
+    }
+}
+
+template <int MODE, bool VEC>
+__global__ __launch_bounds__(SCAN_T) void k_scan_sums(const void* __restrict__ in, long n, int lead, int* __restrict__ block_sums)
 {
     __shared__ int sm[4];
-    long base = (long)blockIdx.x * SCAN_CHUNK + (long)threadIdx.x * SCAN_E;
+    const long base = (long)blockIdx.x * SCAN_CHUNK + (long)threadIdx.x * SCAN_E - lead;
+    int v[SCAN_E];
+    scan_load8<MODE, VEC>(in, base, n, v);
     int s = 0;
 #pragma unroll
-    for (int e = 0; e < SCAN_E; ++e)
-        if (base + e < n) s += scan_load<MODE>(in, base + e);
+    for (int e = 0; e < SCAN_E; ++e) s += v[e];
     s = block_sum<int, 4>(s, sm);
     if (threadIdx.x == 0) block_sums[blockIdx.x] = s;
 }
@@ -63,19 +90,17 @@ __global__ __launch_bounds__(1024) void k_scan_block_sums(int* __restrict__ bloc
     if (threadIdx.x == 0) *total = carry_s;
 }
 
-template <int MODE>
-__global__ __launch_bounds__(SCAN_T) void k_scan_final(const void* __restrict__ in, long n, const int* __restrict__ block_sums,
+template <int MODE, bool VEC>
+__global__ __launch_bounds__(SCAN_T) void k_scan_final(const void* __restrict__ in, long n, int lead, const int* __restrict__ block_sums,
                                                        int* __restrict__ out)
 {
     __shared__ int wsum[4];
-    long base = (long)blockIdx.x * SCAN_CHUNK + (long)threadIdx.x * SCAN_E;
+    const long base = (long)blockIdx.x * SCAN_CHUNK + (long)threadIdx.x * SCAN_E - lead;
     int v[SCAN_E];
+    scan_load8<MODE, VEC>(in, base, n, v);
     int s = 0;
 #pragma unroll
-    for (int e = 0; e < SCAN_E; ++e) {
-        v[e] = (base + e < n) ? scan_load<MODE>(in, base + e) : 0;
-        s += v[e];
-    }
+    for (int e = 0; e < SCAN_E; ++e) s += v[e];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     int inc = s;
 #pragma unroll
@@ -87,28 +112,49 @@ __global__ __launch_bounds__(SCAN_T) void k_scan_final(const void* __restrict__ 
     __syncthreads();
     int off = block_sums[blockIdx.x] + inc - s;
     for (int k = 0; k < w; ++k) off += wsum[k];
+    int r[SCAN_E];
 #pragma unroll
     for (int e = 0; e < SCAN_E; ++e) {
-        if (base + e < n) {
-            if (MODE == 0) out[base + e] = off;
-            else out[base + e] = v[e] ? off : -1;
-        }
+        r[e] = (MODE == 0 || v[e]) ? off : -1;
         off += v[e];
+    }
+    if (VEC && base >= 0 && base + SCAN_E <= n) {
+        *(int4*)(out + base) = make_int4(r[0], r[1], r[2], r[3]);
+        *(int4*)(out + base + 4) = make_int4(r[4], r[5], r[6], r[7]);
+    } else {
+#pragma unroll
+        for (int e = 0; e < SCAN_E; ++e)
+            if (base + e >= 0 && base + e < n) out[base + e] = r[e];
     }
 }
 
+// block_sums: room for n / SCAN_CHUNK + 2 ints (the shifted grid can take one chunk more than the elements fill)
 template <int MODE>
 static void scan_impl(hipStream_t st, const void* in, int* out, long n, int* block_sums, int* total)
 {
-    int nb = (int)((n + SCAN_CHUNK - 1) / SCAN_CHUNK);
-    hipLaunchKernelGGL(k_scan_sums<MODE>, dim3(nb), dim3(SCAN_T), 0, st, in, n, block_sums);
-    hipLaunchKernelGGL(k_scan_block_sums, dim3(1), dim3(1024), 0, st, block_sums, nb, total);
-    hipLaunchKernelGGL(k_scan_final<MODE>, dim3(nb), dim3(SCAN_T), 0, st, in, n, (const int*)block_sums, out);
+    // elements in front of in[0] up to the last 16-byte boundary (8 bytes of flags); out must reach its own boundary there too
+    const int lead = MODE == 0 ? (int)(((uintptr_t)in & 15) / 4) : (int)((uintptr_t)in & 7);
+    const bool vec = (((uintptr_t)out - (uintptr_t)4 * lead) & 15) == 0 && (MODE == 1 || ((uintptr_t)in & 3) == 0);
+    if (vec) {
+        const int nb = (int)((n + lead + SCAN_CHUNK - 1) / SCAN_CHUNK);
+        hipLaunchKernelGGL((k_scan_sums<MODE, true>), dim3(nb), dim3(SCAN_T), 0, st, in, n, lead, block_sums);
+        hipLaunchKernelGGL(k_scan_block_sums, dim3(1), dim3(1024), 0, st, block_sums, nb, total);
+        hipLaunchKernelGGL((k_scan_final<MODE, true>), dim3(nb), dim3(SCAN_T), 0, st, in, n, lead, (const int*)block_sums, out);
+    } else {
+        const int nb = (int)((n + SCAN_CHUNK - 1) / SCAN_CHUNK);
+        hipLaunchKernelGGL((k_scan_sums<MODE, false>), dim3(nb), dim3(SCAN_T), 0, st, in, n, 0, block_sums);
+        hipLaunchKernelGGL(k_scan_block_sums, dim3(1), dim3(1024), 0, st, block_sums, nb, total);
+        hipLaunchKernelGGL((k_scan_final<MODE, false>), dim3(nb), dim3(SCAN_T), 0, st, in, n, 0, (const int*)block_sums, out);
+    }
 }
 
 void launch_exclusive_scan(hipStream_t st, const int* in, int* out, long n, int* block_sums, int* total)
 {
     scan_impl<0>(st, in, out, n, block_sums, total);
+}
+void launch_index_scan_flat(hipStream_t st, const uint8_t* flags, int* indices, long n, int* block_sums, int* total)
+{
+    scan_impl<1>(st, flags, indices, n, block_sums, total);
 }
 void launch_index_scan(hipStream_t st, Grid g, const uint8_t* flags, int* indices, int* block_sums, int* total)
 {
@@ -257,8 +303,9 @@ __device__ __forceinline__ void rhs_div_cell(const Grid& g, const uint8_t* __res
 
 __global__ __launch_bounds__(256) void k_rhs_div(Grid g, Box box, const uint8_t* __restrict__ flags, const double* __restrict__ u,
                                                  const double* __restrict__ v, const double* __restrict__ w, float* __restrict__ rhs,
-                                                 float* __restrict__ diver, double dx, double g0, double g1, double g2)
+                                                 float* __restrict__ diver, double dx, double g0, double g1, double g2, const PcgState* gate)
 {
+    if (gate && !gate->done) return;   // enqueued ahead of the solve's poll: nothing happens unless the solve has finished
     CellIt it = box_cell(g, box);
     if (!it.ok) return;
     const size_t c = it.c;
@@ -273,8 +320,9 @@ __global__ __launch_bounds__(256) void k_rhs_div(Grid g, Box box, const uint8_t*
 // box get the zeros they hold already (one GPU only: `rows`; a rank of a decomposed run does not own them).
 __global__ __launch_bounds__(256) void k_rhs_div4(Grid g, Box box, const uint8_t* __restrict__ flags, const double* __restrict__ u,
                                                   const double* __restrict__ v, const double* __restrict__ w, float* __restrict__ rhs,
-                                                  float* __restrict__ diver, double dx, double g0, double g1, double g2)
+                                                  float* __restrict__ diver, double dx, double g0, double g1, double g2, const PcgState* gate)
 {
+    if (gate && !gate->done) return;   // enqueued ahead of the solve's poll: nothing happens unless the solve has finished
     const int nzq = g.nz >> 2;
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
     if (t >= (long)box.nx() * box.ny() * nzq) return;
@@ -311,15 +359,15 @@ __global__ __launch_bounds__(256) void k_rhs_div4(Grid g, Box box, const uint8_t
 }
 
 void launch_rhs_div(hipStream_t st, Grid g, Box box, const uint8_t* flags, const double* u, const double* v, const double* w, float* rhs,
-                    float* diver, double dx, double gdt0, double gdt1, double gdt2, bool rows)
+                    float* diver, double dx, double gdt0, double gdt1, double gdt2, bool rows, const PcgState* gate)
 {
     if (rows && g.nz % 4 == 0 && 4 * box.nz() >= 3 * g.nz) {
         const long n = (long)box.nx() * box.ny() * (g.nz >> 2);
-        hipLaunchKernelGGL(k_rhs_div4, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g, box, flags, u, v, w, rhs, diver, dx, gdt0, gdt1, gdt2);
+        hipLaunchKernelGGL(k_rhs_div4, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g, box, flags, u, v, w, rhs, diver, dx, gdt0, gdt1, gdt2, gate);
         return;
     }
     hipLaunchKernelGGL(k_rhs_div, dim3((unsigned)((box.cells() + 255) / 256)), dim3(256), 0, st, g, box, flags, u, v, w, rhs, diver, dx,
-                       gdt0, gdt1, gdt2);
+                       gdt0, gdt1, gdt2, gate);
 }
 
 // ---- velUpdate, gather form ------------------------------------------------------------------
@@ -330,8 +378,9 @@ void launch_rhs_div(hipStream_t st, Grid g, Box box, const uint8_t* flags, const
 // solid c.  Gathered per cell the result is bit-identical and needs no atomics.
 __global__ __launch_bounds__(256) void k_vel_update(Grid g, Box box, const uint8_t* __restrict__ flags, const double* __restrict__ p,
                                                     double* __restrict__ u, double* __restrict__ v, double* __restrict__ w, double k,
-                                                    double g0, double g1, double g2)
+                                                    double g0, double g1, double g2, const PcgState* gate)
 {
+    if (gate && !gate->done) return;   // enqueued ahead of the solve's poll: nothing happens unless the solve has finished
     CellIt it = box_cell(g, box);
     if (!it.ok) return;
     const size_t c = it.c;
@@ -360,8 +409,9 @@ __global__ __launch_bounds__(256) void k_vel_update(Grid g, Box box, const uint8
 // late-phase box is air next to air.
 __global__ __launch_bounds__(256) void k_vel_update4(Grid g, Box box, const uint8_t* __restrict__ flags, const double* __restrict__ p,
                                                      double* __restrict__ u, double* __restrict__ v, double* __restrict__ w, double k,
-                                                     double g0, double g1, double g2)
+                                                     double g0, double g1, double g2, const PcgState* gate)
 {
+    if (gate && !gate->done) return;   // enqueued ahead of the solve's poll: nothing happens unless the solve has finished
     const int nzq = g.nz >> 2;
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
     if (t >= (long)box.nx() * box.ny() * nzq) return;
@@ -406,15 +456,15 @@ __global__ __launch_bounds__(256) void k_vel_update4(Grid g, Box box, const uint
 }
 
 void launch_vel_update(hipStream_t st, Grid g, Box box, const uint8_t* flags, const double* p, double* u, double* v, double* w, double k,
-                       double g0, double g1, double g2, bool rows)
+                       double g0, double g1, double g2, bool rows, const PcgState* gate)
 {
     if (rows && g.nz % 4 == 0 && 4 * box.nz() >= 3 * g.nz) {
         const long n = (long)box.nx() * box.ny() * (g.nz >> 2);
-        hipLaunchKernelGGL(k_vel_update4, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g, box, flags, p, u, v, w, k, g0, g1, g2);
+        hipLaunchKernelGGL(k_vel_update4, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g, box, flags, p, u, v, w, k, g0, g1, g2, gate);
         return;
     }
     hipLaunchKernelGGL(k_vel_update, dim3((unsigned)((box.cells() + 255) / 256)), dim3(256), 0, st, g, box, flags, p, u, v, w, k, g0, g1,
-                       g2);
+                       g2, gate);
 }
 
 // ---- FLIP delta field ------------------------------------------------------------------------
@@ -453,8 +503,9 @@ void launch_flip_delta(hipStream_t st, Grid g, Box box, const double* u, const d
 // ---- error = |b-b2| / |b| --------------------------------------------------------------------
 // fluid.cc:1483 over the unknowns that setA2/setOnlyB fill (Adiag != 0, :498,556).
 __global__ __launch_bounds__(256) void k_err_partial(Grid g, Box box, const uint8_t* __restrict__ flags, const float* __restrict__ b,
-                                                     const float* __restrict__ b2, double* __restrict__ part)
+                                                     const float* __restrict__ b2, double* __restrict__ part, const PcgState* gate)
 {
+    if (gate && !gate->done) return;   // enqueued ahead of the solve's poll: nothing happens unless the solve has finished
     __shared__ double sm[4];
     const long ncells = box.cells();
     const int nz = box.nz(), ny = box.ny();
@@ -488,8 +539,9 @@ __global__ __launch_bounds__(256) void k_err_partial(Grid g, Box box, const uint
     den = block_sum<double, 4>(den, sm);
     if (threadIdx.x == 0) { part[2 * blockIdx.x] = num; part[2 * blockIdx.x + 1] = den; }
 }
-__global__ __launch_bounds__(256) void k_err_final(const double* __restrict__ part, int nb, StepState* ss)
+__global__ __launch_bounds__(256) void k_err_final(const double* __restrict__ part, int nb, StepState* ss, const PcgState* gate)
 {
+    if (gate && !gate->done) return;   // enqueued ahead of the solve's poll: nothing happens unless the solve has finished
     __shared__ double sm[4];
     double num = 0, den = 0;
     for (int i = threadIdx.x; i < nb; i += 256) { num += part[2 * i]; den += part[2 * i + 1]; }
@@ -498,13 +550,13 @@ __global__ __launch_bounds__(256) void k_err_final(const double* __restrict__ pa
     if (threadIdx.x == 0) { ss->err_num = num; ss->err_den = den; }
 }
 
-void launch_err_norm(hipStream_t st, Grid g, Box box, const uint8_t* flags, const float* b, const float* b2, double* part, StepState* ss)
+void launch_err_norm(hipStream_t st, Grid g, Box box, const uint8_t* flags, const float* b, const float* b2, double* part, StepState* ss, const PcgState* gate)
 {
     long nb = (box.cells() + 255) / 256;
     if (nb > 1024) nb = 1024;
     if (nb < 1) nb = 1;
-    hipLaunchKernelGGL(k_err_partial, dim3((unsigned)nb), dim3(256), 0, st, g, box, flags, b, b2, part);
-    hipLaunchKernelGGL(k_err_final, dim3(1), dim3(256), 0, st, (const double*)part, (int)nb, ss);
+    hipLaunchKernelGGL(k_err_partial, dim3((unsigned)nb), dim3(256), 0, st, g, box, flags, b, b2, part, gate);
+    hipLaunchKernelGGL(k_err_final, dim3(1), dim3(256), 0, st, (const double*)part, (int)nb, ss, gate);
 }
 
 __global__ void k_zero_step_state(StepState* ss, int N)
@@ -720,18 +772,19 @@ void launch_resample(hipStream_t st, Grid g, long n, Particles p, const int* cel
 
 // out = a x + b y over the cells of box (dense layout)
 __global__ __launch_bounds__(256) void k_axpby_box(Grid g, Box box, double a, const double* __restrict__ x, double b, const double* __restrict__ y,
-                                                   double* __restrict__ out)
+                                                   double* __restrict__ out, const PcgState* gate)
 {
+    if (gate && !gate->done) return;   // enqueued ahead of the solve's poll: nothing happens unless the solve has finished
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= box.cells()) return;
     const int nz = box.nz(), ny = box.ny();
     const size_t c = g.idx(box.x0 + (int)(i / ((long)nz * ny)), box.y0 + (int)((i / nz) % ny), box.z0 + (int)(i % nz));
     out[c] = a * x[c] + b * y[c];
 }
-void launch_axpby_box(hipStream_t st, Grid g, Box box, double a, const double* x, double b, const double* y, double* out)
+void launch_axpby_box(hipStream_t st, Grid g, Box box, double a, const double* x, double b, const double* y, double* out, const PcgState* gate)
 {
     if (box.cells() <= 0) return;
-    hipLaunchKernelGGL(k_axpby_box, dim3((unsigned)((box.cells() + 255) / 256)), dim3(256), 0, st, g, box, a, x, b, y, out);
+    hipLaunchKernelGGL(k_axpby_box, dim3((unsigned)((box.cells() + 255) / 256)), dim3(256), 0, st, g, box, a, x, b, y, out, gate);
 }
 
 }  // namespace fl

@@ -12,54 +12,56 @@ namespace fl {
 // key = linear index of round(pos) (C round(): half away from zero, fluid.cc:267-269), or
 // NCELL for a particle whose base cell is off the grid (it can reach no cell:
 // its clamped support lies in the solid shell, fluid.cc:271-276,288).
-__global__ __launch_bounds__(256) void k_bin_count(Grid g, long n, Particles p, int* __restrict__ key, int* __restrict__ slot,
-                                                   int* __restrict__ cell_count, int* __restrict__ part)
-{
-    // per-block bbox partials (no same-address atomics: 80k waves hammering 6 words cost 5.6 ms)
-    __shared__ int sm[4][8];
+// What a thread gathers over its particles: bounding box of the base cells on the grid, particles off it, the fullest cell seen.
+struct BinAcc {
     int mn[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, mx[3] = {-1, -1, -1};
     int nout = 0, cmax = 0;
-    const long ncell = (long)g.cells();
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        int bx = (int)round(p.px[i]) - g.cx0(), by = (int)round(p.py[i]) - g.cy0(), bz = (int)round(p.pz[i]) - g.cz0();
-        bool in = bx >= 0 && bx < g.nx && by >= 0 && by < g.ny && bz >= 0 && bz < g.nz;
-        int k = in ? (int)g.idx(bx, by, bz) : (int)ncell;
-        const bool dead = p.pid[i] == PID_DEAD;  // migrated to a neighbour rank: last bucket, dropped after the sort
-        if (dead) { k = (int)ncell + 1; in = false; }
-        key[i] = k;
-        // Particles are still in last step's cell order, so neighbouring lanes mostly share a key: one returning
-        // atomic per RUN of equal keys in the wave (its leader adds the run length, the others take base + offset)
-        // instead of one per particle.  Any slot order inside a cell will do: k_bin_rank re-ranks a cell by id.
-        {
-            const int lane = threadIdx.x & 63;
-            const int kp = __shfl_up(k, 1, 64);
-            const bool head = lane == 0 || kp != k;
-            const unsigned long long hm = __ballot(head);  // lanes past n are not here: their bits are 0
-            const unsigned long long below = hm & ((2ull << lane) - 1ull);          // heads at or below me
-            const int start = 63 - __clzll((long long)below);
-            const unsigned long long above = (lane == 63) ? 0ull : (hm >> (lane + 1)) << (lane + 1);
-            const unsigned long long act = __ballot(true);
-            const int stop = above ? __ffsll((long long)above) - 1 : 64 - __clzll((long long)act) + 0;  // first head after me, or one past the last active lane
-            int base = 0;
-            if (head) {
-                base = atomicAdd(&cell_count[k], stop - start);
-                if (in && base + stop - start > cmax) cmax = base + stop - start;  // the last add of a cell sees its full count
-            }
-            base = __shfl(base, start, 64);
-            slot[i] = base + (lane - start);
+};
+// Particle i at (px, py, pz): key, the cell's count, the slot in the cell.  Called by every lane of the wave that has a particle.
+__device__ __forceinline__ void bin_one(const Grid& g, long ncell, long i, double px, double py, double pz, bool dead, int* __restrict__ key,
+                                        int* __restrict__ slot, int* __restrict__ cell_count, BinAcc& acc)
+{
+    int bx = (int)round(px) - g.cx0(), by = (int)round(py) - g.cy0(), bz = (int)round(pz) - g.cz0();
+    bool in = bx >= 0 && bx < g.nx && by >= 0 && by < g.ny && bz >= 0 && bz < g.nz;
+    int k = in ? (int)g.idx(bx, by, bz) : (int)ncell;
+    if (dead) { k = (int)ncell + 1; in = false; }  // migrated to a neighbour rank: last bucket, dropped after the sort
+    key[i] = k;
+    // Particles are still in last step's cell order, so neighbouring lanes mostly share a key: one returning
+    // atomic per RUN of equal keys in the wave (its leader adds the run length, the others take base + offset)
+    // instead of one per particle.  Any slot order inside a cell will do: k_bin_rank re-ranks a cell by id.
+    {
+        const int lane = threadIdx.x & 63;
+        const int kp = __shfl_up(k, 1, 64);
+        const bool head = lane == 0 || kp != k;
+        const unsigned long long hm = __ballot(head);  // lanes past n are not here: their bits are 0
+        const unsigned long long below = hm & ((2ull << lane) - 1ull);          // heads at or below me
+        const int start = 63 - __clzll((long long)below);
+        const unsigned long long above = (lane == 63) ? 0ull : (hm >> (lane + 1)) << (lane + 1);
+        const unsigned long long act = __ballot(true);
+        const int stop = above ? __ffsll((long long)above) - 1 : 64 - __clzll((long long)act) + 0;  // first head after me, or one past the last active lane
+        int base = 0;
+        if (head) {
+            base = atomicAdd(&cell_count[k], stop - start);
+            if (in && base + stop - start > acc.cmax) acc.cmax = base + stop - start;  // the last add of a cell sees its full count
         }
-        if (in) {
-            mn[0] = bx < mn[0] ? bx : mn[0]; mx[0] = bx > mx[0] ? bx : mx[0];
-            mn[1] = by < mn[1] ? by : mn[1]; mx[1] = by > mx[1] ? by : mx[1];
-            mn[2] = bz < mn[2] ? bz : mn[2]; mx[2] = bz > mx[2] ? bz : mx[2];
-        } else if (!dead) {
-            nout++;
-        }
+        base = __shfl(base, start, 64);
+        slot[i] = base + (lane - start);
     }
+    if (in) {
+        acc.mn[0] = bx < acc.mn[0] ? bx : acc.mn[0]; acc.mx[0] = bx > acc.mx[0] ? bx : acc.mx[0];
+        acc.mn[1] = by < acc.mn[1] ? by : acc.mn[1]; acc.mx[1] = by > acc.mx[1] ? by : acc.mx[1];
+        acc.mn[2] = bz < acc.mn[2] ? bz : acc.mn[2]; acc.mx[2] = bz > acc.mx[2] ? bz : acc.mx[2];
+    } else if (!dead) {
+        acc.nout++;
+    }
+}
+// the block's 8 partials: box min, box max, off-grid count, fullest cell
+__device__ __forceinline__ void bin_block_partials(const BinAcc& acc, int (*sm)[8], int* __restrict__ part)
+{
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        int lo = mn[a], hi = mx[a];
+        int lo = acc.mn[a], hi = acc.mx[a];
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             int l2 = __shfl_down(lo, o, 64), h2 = __shfl_down(hi, o, 64);
@@ -68,8 +70,8 @@ __global__ __launch_bounds__(256) void k_bin_count(Grid g, long n, Particles p, 
         }
         if (lane == 0) { sm[w][a] = lo; sm[w][3 + a] = hi; }
     }
-    nout = wave_sum(nout);
-    cmax = wave_max(cmax);
+    const int nout = wave_sum(acc.nout);
+    const int cmax = wave_max(acc.cmax);
     if (lane == 0) { sm[w][6] = nout; sm[w][7] = cmax; }
     __syncthreads();
     if (threadIdx.x < 8) {
@@ -83,9 +85,21 @@ __global__ __launch_bounds__(256) void k_bin_count(Grid g, long n, Particles p, 
     }
 }
 
-__global__ __launch_bounds__(256) void k_bin_bbox(const int* __restrict__ part, int nb, StepState* ss)
+__global__ __launch_bounds__(256) void k_bin_count(Grid g, long n, Particles p, int* __restrict__ key, int* __restrict__ slot,
+                                                   int* __restrict__ cell_count, int* __restrict__ part)
 {
+    // per-block bbox partials (no same-address atomics: 80k waves hammering 6 words cost 5.6 ms)
     __shared__ int sm[4][8];
+    BinAcc acc;
+    const long ncell = (long)g.cells();
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256)
+        bin_one(g, ncell, i, p.px[i], p.py[i], p.pz[i], p.pid[i] == PID_DEAD, key, slot, cell_count, acc);
+    bin_block_partials(acc, sm, part);
+}
+
+// the partials of nb blocks -> the sort's box, off-grid count and fullest cell in *ss (one block of 256 threads)
+__device__ __forceinline__ void bin_reduce(const int* __restrict__ part, int nb, StepState* ss, int (*sm)[8])
+{
     int mn[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, mx[3] = {-1, -1, -1}, nout = 0, cmax = 0;
     for (int b = threadIdx.x; b < nb; b += 256) {
 #pragma unroll
@@ -128,6 +142,12 @@ __global__ __launch_bounds__(256) void k_bin_bbox(const int* __restrict__ part, 
         for (int k = 1; k < 4; ++k) cm = sm[k][7] > cm ? sm[k][7] : cm;
         ss->max_cell = cm;
     }
+}
+
+__global__ __launch_bounds__(256) void k_bin_bbox(const int* __restrict__ part, int nb, StepState* ss)
+{
+    __shared__ int sm[4][8];
+    bin_reduce(part, nb, ss, sm);
 }
 
 __global__ __launch_bounds__(256) void k_bin_scatter(long n, const int* __restrict__ key, const int* __restrict__ slot,
@@ -1019,40 +1039,73 @@ __device__ __forceinline__ bool is_solid(const Grid& g, const uint8_t* flags, in
 }
 
 // fluid.cc:992-1036: new dt from maxSpeed, move, stuck-particle handling with e = 0.
+__device__ __forceinline__ double advect_timestep(double max_dt, double dx, const StepState* ss)
+{
+    const double maxSpeed = __longlong_as_double((long long)ss->max_speed_bits);
+    if (maxSpeed != 0) return max_dt < dx / maxSpeed ? max_dt : dx / maxSpeed;
+    return max_dt;
+}
+// particle i (not dead) moves; its new position is stored and returned
+__device__ __forceinline__ void advect_one(const Grid& g, const Particles& p, const uint8_t* __restrict__ flags, double timestep, long i, double& P0,
+                                           double& P1, double& P2)
+{
+    const double e = 0;
+    P0 = p.px[i], P1 = p.py[i], P2 = p.pz[i];
+    double V0 = p.vx[i], V1 = p.vy[i], V2 = p.vz[i];
+    const double q0 = P0 + timestep * V0, q1 = P1 + timestep * V1, q2 = P2 + timestep * V2;
+    if (is_solid(g, flags, (int)round(q0), (int)round(q1), (int)round(q2))) {
+        const double vx = V0 * timestep, vy = V1 * timestep, vz = V2 * timestep;
+        // Coord(double,double,double): the two untouched axes truncate toward zero (:1017-1025)
+        if (is_solid(g, flags, (int)round(P0 + vx), (int)P1, (int)P2)) V0 *= -1.0 * e;
+        if (is_solid(g, flags, (int)P0, (int)round(P1 + vy), (int)P2)) V1 *= -1.0 * e;
+        if (is_solid(g, flags, (int)P0, (int)P1, (int)round(P2 + vz))) V2 *= -1.0 * e;
+        P0 += V0 * timestep; P1 += V1 * timestep; P2 += V2 * timestep;
+        p.vx[i] = V0; p.vy[i] = V1; p.vz[i] = V2;
+    } else {
+        P0 = q0; P1 = q1; P2 = q2;
+    }
+    p.px[i] = P0; p.py[i] = P1; p.pz[i] = P2;
+}
+
 __global__ __launch_bounds__(256) void k_advect(Grid g, long n, Particles p, const uint8_t* __restrict__ flags, double max_dt, double dx,
                                                 StepState* ss)
 {
-    const double maxSpeed = __longlong_as_double((long long)ss->max_speed_bits);
-    double timestep;
-    if (maxSpeed != 0) timestep = max_dt < dx / maxSpeed ? max_dt : dx / maxSpeed;
-    else timestep = max_dt;
+    const double timestep = advect_timestep(max_dt, dx, ss);
     long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i < n && p.pid[i] != PID_DEAD) {
-        const double e = 0;
-        double P0 = p.px[i], P1 = p.py[i], P2 = p.pz[i];
-        double V0 = p.vx[i], V1 = p.vy[i], V2 = p.vz[i];
-        const double q0 = P0 + timestep * V0, q1 = P1 + timestep * V1, q2 = P2 + timestep * V2;
-        if (is_solid(g, flags, (int)round(q0), (int)round(q1), (int)round(q2))) {
-            const double vx = V0 * timestep, vy = V1 * timestep, vz = V2 * timestep;
-            // Coord(double,double,double): the two untouched axes truncate toward zero (:1017-1025)
-            if (is_solid(g, flags, (int)round(P0 + vx), (int)P1, (int)P2)) V0 *= -1.0 * e;
-            if (is_solid(g, flags, (int)P0, (int)round(P1 + vy), (int)P2)) V1 *= -1.0 * e;
-            if (is_solid(g, flags, (int)P0, (int)P1, (int)round(P2 + vz))) V2 *= -1.0 * e;
-            P0 += V0 * timestep; P1 += V1 * timestep; P2 += V2 * timestep;
-            p.vx[i] = V0; p.vy[i] = V1; p.vz[i] = V2;
-        } else {
-            P0 = q0; P1 = q1; P2 = q2;
-        }
-        p.px[i] = P0; p.py[i] = P1; p.pz[i] = P2;
+        double P0, P1, P2;
+        advect_one(g, p, flags, timestep, i, P0, P1, P2);
     }
 }
 
-// dt is published by its own 1-thread launch AFTER k_advect so that no block of k_advect can
-// read a max_speed/dt pair from two different steps.
-__global__ void k_publish_dt(double max_dt, double dx, StepState* ss)
+// k_advect, then k_bin_count's body on the position just written: the next step's sort starts from key, slot, the cell counts
+// and the block partials without reading the positions again (one GPU; cell_count's window is zeroed before the launch)
+__global__ __launch_bounds__(256) void k_advect_bin(Grid g, long n, Particles p, const uint8_t* __restrict__ flags, double max_dt, double dx,
+                                                    StepState* ss, int* __restrict__ key, int* __restrict__ slot, int* __restrict__ cell_count,
+                                                    int* __restrict__ part)
 {
-    const double maxSpeed = __longlong_as_double((long long)ss->max_speed_bits);
-    ss->dt = (maxSpeed != 0) ? (max_dt < dx / maxSpeed ? max_dt : dx / maxSpeed) : max_dt;
+    __shared__ int sm[4][8];
+    const double timestep = advect_timestep(max_dt, dx, ss);
+    BinAcc acc;
+    const long ncell = (long)g.cells();
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const bool dead = p.pid[i] == PID_DEAD;
+        double P0, P1, P2;
+        if (!dead) advect_one(g, p, flags, timestep, i, P0, P1, P2);
+        else P0 = p.px[i], P1 = p.py[i], P2 = p.pz[i];
+        bin_one(g, ncell, i, P0, P1, P2, dead, key, slot, cell_count, acc);
+    }
+    bin_block_partials(acc, sm, part);
+}
+
+// dt is published by its own launch AFTER k_advect so that no block of k_advect can
+// read a max_speed/dt pair from two different steps.  After k_advect_bin (nb > 0: one block of 256 threads) it also
+// reduces that kernel's nb block partials, which k_bin_bbox does for k_bin_count.
+__global__ __launch_bounds__(256) void k_publish_dt(double max_dt, double dx, StepState* ss, const int* __restrict__ part, int nb)
+{
+    __shared__ int sm[4][8];
+    if (nb > 0) bin_reduce(part, nb, ss, sm);
+    if (threadIdx.x == 0) ss->dt = advect_timestep(max_dt, dx, ss);
 }
 
 // ---- multi-GPU: particle records (7 doubles: pos, vel, id) ----------------------------------------------
@@ -1228,7 +1281,16 @@ void launch_g2p(hipStream_t st, Grid g, long n, Particles p, const double* dcx, 
 void launch_advect(hipStream_t st, Grid g, long n, Particles p, const uint8_t* flags, double max_dt, double dx, StepState* ss)
 {
     if (n > 0) hipLaunchKernelGGL(k_advect, dim3(nblk(n)), dim3(256), 0, st, g, n, p, flags, max_dt, dx, ss);
-    hipLaunchKernelGGL(k_publish_dt, dim3(1), dim3(1), 0, st, max_dt, dx, ss);
+    hipLaunchKernelGGL(k_publish_dt, dim3(1), dim3(1), 0, st, max_dt, dx, ss, (const int*)nullptr, 0);
+}
+// n > 0; part: 8 ints for each of up to 1024 blocks.  Leaves what launch_bin_count leaves, for the positions after the move.
+void launch_advect_bin(hipStream_t st, Grid g, long n, Particles p, const uint8_t* flags, double max_dt, double dx, StepState* ss, int* key,
+                       int* slot, int* cell_count, int* part)
+{
+    unsigned nb = nblk(n);
+    if (nb > 1024) nb = 1024;
+    hipLaunchKernelGGL(k_advect_bin, dim3(nb), dim3(256), 0, st, g, n, p, flags, max_dt, dx, ss, key, slot, cell_count, part);
+    hipLaunchKernelGGL(k_publish_dt, dim3(1), dim3(256), 0, st, max_dt, dx, ss, (const int*)part, (int)nb);
 }
 void launch_unpack_records(hipStream_t st, long n, const double* rec, Particles p, long off)
 {

@@ -799,8 +799,9 @@ __global__ __launch_bounds__(1024) void k_compact_flags(const uint8_t* __restric
 // local x -> global pressure field (VectorXd p scattered back to cells, fluid.cc:637)
 template <typename T>
 __global__ __launch_bounds__(256) void k_store_pressure_l(Grid g, LBox L, const uint8_t* __restrict__ cnt, const T* __restrict__ x,
-                                                          double* __restrict__ pressure, double* __restrict__ keep, const PcgState* ps)
+                                                          double* __restrict__ pressure, double* __restrict__ keep, const PcgState* ps, int gated)
 {
+    if (gated && !ps->done) return;
     // keep != nullptr: a second copy that no per-step clearing touches (the next solve's starting guess); the solve
     // started from a guess, and for b == 0 the answer is x = 0 whatever the guess was (ConjugateGradient.h:45-50)
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
@@ -960,9 +961,9 @@ void launch_pcg_xr_rows(hipStream_t st, LBox L, const uint8_t* cnt, T* x, T* r, 
                        part_rr, part_rz_next, ps, rlist, nrows);
 }
 template <typename T>
-void launch_store_pressure(hipStream_t st, Grid g, LBox L, const uint8_t* cnt, const T* x, double* pressure, double* keep, const PcgState* ps)
+void launch_store_pressure(hipStream_t st, Grid g, LBox L, const uint8_t* cnt, const T* x, double* pressure, double* keep, const PcgState* ps, bool gated)
 {
-    hipLaunchKernelGGL((k_store_pressure_l<T>), dim3((unsigned)((L.cells() + 255) / 256)), dim3(256), 0, st, g, L, cnt, x, pressure, keep, ps);
+    hipLaunchKernelGGL((k_store_pressure_l<T>), dim3((unsigned)((L.cells() + 255) / 256)), dim3(256), 0, st, g, L, cnt, x, pressure, keep, ps, gated ? 1 : 0);
 }
 
 // ================================================================================================
@@ -1091,7 +1092,7 @@ void launch_stencil_apply(hipStream_t st, Grid g, Box box, const uint8_t* flags,
     template void launch_pcg_xr_rows<T>(hipStream_t, LBox, const uint8_t*, T*, T*, const T*, const T*, Coef<T>, const double*, int,      \
                                         const double*, int, double*, double*, PcgState*, const int*, int);                               \
     template void launch_stencil_apply<T>(hipStream_t, Grid, Box, const uint8_t*, const T*, T*, Coef<T>);                              \
-    template void launch_store_pressure<T>(hipStream_t, Grid, LBox, const uint8_t*, const T*, double*, double*, const PcgState*);      \
+    template void launch_store_pressure<T>(hipStream_t, Grid, LBox, const uint8_t*, const T*, double*, double*, const PcgState*, bool);      \
     template void launch_pcg_init_guess<T>(hipStream_t, Grid, LBox, const uint8_t*, const float*, const double*, const double*, double, double, T*, T*, Coef<T>, \
                                            double*, double*, PcgState*);                                                               \
     template void launch_pcg_sq_dist<T>(hipStream_t, LBox, const uint8_t*, const T*, const T*, T*, T*, Coef<T>, const double*, const double*, \

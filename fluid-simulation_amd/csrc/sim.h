@@ -136,6 +136,17 @@ struct fluid_sim {
     bool sorted = false, have_p2g = false, have_flags = false;
     long n_out = 0;           // particles whose base cell is off the grid (last bucket of the sorted array), from the last sort
     bool sort_hint = false;   // Pb is the bounding box of THESE particles one step ago (false after an upload)
+    // One GPU: FLIPadvect's kernel also bins the positions it writes (k_advect_bin), and the box, off-grid count and fullest
+    // cell come back with the read that ends the step: the next sort starts at its scan, with no pass over the positions, no
+    // copy and no wait.  `binned` holds while key, slot, cell_count (the planes bin_x0..bin_x1 and the tail buckets) describe
+    // the particles as they are now; whatever touches the particles, their count, p_off or those arrays in between clears it.
+    bool advect_bin = true;       // FLUID_ADVECT_BIN=0: k_advect alone, every sort bins for itself
+    bool binned = false;
+    int bin_x0 = 0, bin_x1 = -1;  // x planes of cell_count zeroed before the binning
+    int bin_min[3] = {0, 0, 0}, bin_max[3] = {-1, -1, -1}, bin_n_out = 0, bin_max_cell = 0;   // what k_bin_bbox would have found
+    // the first poll of a multigrid PCG solve also carries the rest of the pressure pass, guarded by the solve's done flag
+    bool solve_tail = true;       // FLUID_SOLVE_TAIL=0: the tail is enqueued after the poll
+    bool tail_ran = false;        // solve_mg: this pass's vel_update, rhs_div(1) and err_norm ran, *h_ss holds the pass error
     double dt = 0.1;
     fluid_step_stats_t stats{};
     // multigrid preconditioner (single-GPU fp64 solve)

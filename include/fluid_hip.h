@@ -271,6 +271,11 @@ int fluid_spline_eval(int32_t device, int32_t which, int64_t n, const double* x,
 /* out[0] = sum_i a[i] * b[i] over n doubles with the block-partial + fixed-order re-summation the PCG kernels use for
  * their dot products (restates the long dot-product test of openvdb/unittest/TestConjGradient.cc:212-237). */
 int fluid_dot_eval(int32_t device, int64_t n, const double* a, const double* b, double* out);
+/* The exclusive prefix sum the sort and the unknown numbering use, over n elements that start in_offset / out_offset elements
+ * (0..64) behind an aligned device address, as the sort passes cell_count + c0.  mode 0: in = n int32, out[i] = in[0] + .. +
+ * in[i-1]; mode 1: in = n flag bytes, out[i] = the count of fluid bytes before i where byte i is fluid, -1 elsewhere.
+ * *total = the sum over all n.  Fails when anything outside out[0, n) was written.  Host buffers. */
+int fluid_scan_eval(int32_t device, int32_t mode, int64_t n, int32_t in_offset, int32_t out_offset, const void* in, int32_t* out, int32_t* total);
 
 /* ---- profiling ------------------------------------------------------------------------- */
 /* Kernel classes timed with hipEvent pairs on the handle's stream. */
