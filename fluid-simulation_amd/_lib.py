@@ -138,6 +138,11 @@ SYMBOLS = [
     ("fluid_leaves_to_dense", C.c_int, [C.POINTER(LeafGridC), _P]),
     ("fluid_vdb_append_leaves", C.c_int, [C.POINTER(_P), C.c_int32, C.POINTER(LeafGridC)]),
     ("fluid_write_vdb_leaves", C.c_int, [C.c_char_p, C.POINTER(LeafGridC), C.c_int32]),
+    ("fluid_dist_output_snapshot", C.c_int, [_P]),
+    ("fluid_dist_output_wait", C.c_int, [_P, C.POINTER(LeafGridC)]),
+    ("fluid_dist_output_stats", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("fluid_dist_output_every", C.c_int, [_P, C.c_int32]),
+    ("fluid_leaf_grids_merge", C.c_int64, [C.POINTER(LeafGridC), C.c_int32, C.c_int64, _P, _P]),
     # the snow-MPM step (include/mpm_hip.h)
     ("mpm_default_params", C.c_int, [C.POINTER(MpmParams)]),
     ("mpm_create", C.c_int, [C.POINTER(MpmParams), C.POINTER(_P)]),

@@ -266,6 +266,17 @@ void launch_unpack_particles(hipStream_t st, long n, const double* pos_aos, cons
 void launch_out_mark(hipStream_t st, const float* f, int N, int off, int nl, int* flags);   // kernels_output.hip
 void launch_out_pack(hipStream_t st, const float* f, int N, int lo, int off, int nl, const int* flags, const int* slot, float* values,
                      int* origin);
+// the owned block of a window as the leaf kernels see it (kernels_output.hip, k_out_mark_win / k_out_pack_win)
+struct OutWin {
+    int ny, nz;            // window dims behind the row and plane strides
+    int ox, oy, oz;        // global array index of window cell 0
+    int olo[3], ohi[3];    // owned block [olo, ohi), global array indices
+    int lo, off;           // coordinate of global index 0; global array index of the first global leaf's first voxel, in (-8, 0]
+    int l0[3], nl[3];      // first global leaf that meets the owned block, and how many do, per axis
+    __host__ __device__ inline long leaves() const { return (long)nl[0] * nl[1] * nl[2]; }
+};
+void launch_out_mark_win(hipStream_t st, const float* f, const OutWin& w, int* flags);
+void launch_out_pack_win(hipStream_t st, const float* f, const OutWin& w, const int* flags, const int* slot, float* values, int* origin);
 void launch_exclusive_scan(hipStream_t st, const int* in, int* out, long n, int* block_sums, int* total);
 void launch_sort_tail(hipStream_t st, const int* cell_count, int* cell_start, long c1, long ncell);
 void launch_index_scan(hipStream_t st, Grid g, const uint8_t* flags, int* indices, int* block_sums, int* total);

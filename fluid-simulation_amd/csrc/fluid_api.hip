@@ -1420,8 +1420,9 @@ int fluid_get_stats(fluid_sim_t* s, fluid_step_stats_t* st)
 int fluid_step(fluid_sim_t* s, fluid_step_stats_t* stats)
 {
     if (!s) return fail(FLUID_ERR_ARG, "null handle");
-    if (s->dist) return dist_step(s, stats);
     int rc;
+    if ((rc = output_auto_check(s))) return rc;     // before any work and before any transport call
+    if (s->dist) return dist_step(s, stats);
     if ((rc = phase_p2g(s))) return rc;             // fluid.cc:1378-1413
     if ((rc = phase_flags(s))) return rc;           // :1416-1455
     double error = NAN;
@@ -1431,6 +1432,7 @@ int fluid_step(fluid_sim_t* s, fluid_step_stats_t* stats)
     } while (error > s->prm.outer_tol);             // :1484 (NaN ends the loop, inf continues)
     if ((rc = phase_flip_advect(s))) return rc;     // :1490
     if ((rc = sources_apply(s))) return rc;         // :1495-1497 (the reference's emitter, commented out there): sinks, sources
+    if ((rc = output_auto(s))) return rc;           // fluid_dist_output_every: this step's grid, still in the container
     s->n_steps++;
     if (stats) *stats = s->stats;
     return FLUID_OK;

@@ -1567,6 +1567,7 @@ int dist_rebalance(fluid_sim* s)
     for (int c = 0; c < 3; ++c) t->mg_last_iters_k[c] = s->mg_last_iters_k[c];
     t->prof_every = s->prof_every;
     for (int c = 0; c < FLUID_PROF_COUNT; ++c) std::swap(t->prof[c], s->prof[c]);
+    output_move(s, t);      // snapshots handed out or in flight stay valid: their buffers are the state's, not the window's
     std::swap(*s, *t);      // the caller's handle now holds the new window
     fluid_destroy(t);       // ... and this one the old
     return FLUID_OK;
@@ -1580,7 +1581,14 @@ int fl::dist_step(fluid_sim* s, fluid_step_stats_t* stats)
     int rc = s->ds->repl ? dist_step_replicated(s, stats) : dist_step_decomposed(s, stats);
     if (rc) return rc;
     DistState* d = s->ds;
-    if (d->rb_every > 0 && d->comm.size > 1 && s->step_counter % d->rb_every == 0) {
+    const bool rb_due = d->rb_every > 0 && d->comm.size > 1 && s->step_counter % d->rb_every == 0;
+    // fluid_dist_output_every: this step's grid is captured from THIS window, before the planes move.  The snapshot is rank-local
+    // (no transport call); it may allocate, so when the re-balancing's collectives follow, its result is agreed first.
+    rc = output_auto(s);
+    if (rb_due && s->out_every > 0) rc = dist_agree(s, rc);   // (every rank sets the same `every`)
+    if (rc) return rc;
+    s->n_steps++;
+    if (rb_due) {
         const int before = d->n_rebalanced;
         if ((rc = dist_rebalance(s))) return rc;
         if (s->ds->n_rebalanced != before && stats) stats->paths |= FLUID_PATH_DIST_REBALANCED;
@@ -1649,7 +1657,11 @@ int fluid_create_dist(const fluid_params_t* p, const fluid_comm_t* comm, const f
     // AUTO: the decomposed solve pays >= 4 exchanges per PCG iteration, each a few tens of microseconds over xGMI; below
     // ~2 M unknowns per solve a single GPU runs the whole iteration in less than that, so small grids replicate the block.
     d->repl = p->dist_solve == FLUID_DIST_REPLICATED || (p->dist_solve == FLUID_DIST_AUTO && p->n < 384);
-    if (const char* e = getenv("FLUID_DIST_SOLVE")) d->repl = atoi(e) == 0;   // developer knob, overrides the param
+    if (const char* e = getenv("FLUID_DIST_SOLVE")) {   // developer knob, overrides the param: 0 / 1, or the `fluid` program's words
+        if (!strcmp(e, "decomposed")) d->repl = false;
+        else if (!strcmp(e, "replicated")) d->repl = true;
+        else d->repl = atoi(e) == 0;
+    }
     if (const char* e = getenv("FLUID_DIST_SPLIT")) d->split_force = atoi(e);
     if (d->split_force < 0 || d->split_force > 2) d->split_force = 0;
     if (const char* e = getenv("FLUID_DIST_OVERLAP")) d->overlap = atoi(e) != 0;

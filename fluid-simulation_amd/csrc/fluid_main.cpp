@@ -20,7 +20,16 @@
 // fluid_scene_uniform_scatter(flo, fhi, 10, i+1, hi) + fluid_add_particles(..., NULL); the reference's `if (i%5 == 0)` gate
 // (fluid.cc:1379) is K here.  The box is the one of the initial scene (-20..20 at N = 121, scaled with N like the cube); the
 // particle count is printed after every step.
+//   FLUID_BLOCKS=AxBxC (unset: one GPU, everything above) — the grid cut into A x B x C blocks (fluid_create_dist), one host thread
+// of this process per block over the in-process transport (fluid_local_comm_create); block r runs on device r % FLUID_DEVICES (1).
+// Cut planes by particle count (fluid_partition_blocks on the initial particles), global ids = index in the initial set.
+// FLUID_DIST_SOLVE=decomposed|replicated (unset: the library's choice by N); FLUID_REBALANCE_EVERY=K (0) with FLUID_REBALANCE_RATIO
+// (1.5) moves the planes as the water moves.  Output: fluid_dist_output_every(1) on every block — each step leaves the list of the
+// non-zero leaves of the block it owned — the main thread waits for all blocks, releases the next step, merges the lists
+// (fluid_leaf_grids_merge, two merge buffers in turn) and hands the grid to the same writer thread: the same files.  The stdout
+// lines are rank 0's numbers.  FLUID_SOURCE_EVERY and FLUID_OUT_DENSE=1 are refused with FLUID_BLOCKS.
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
@@ -122,6 +131,203 @@ struct LeafWriter {
     }
 };
 
+// ---- FLUID_BLOCKS ----------------------------------------------------------------------------------------------------------------
+struct BlockCfg {
+    fluid_params_t prm;
+    int dims[3] = {1, 1, 1};
+    int devices = 1, steps = 0, rb_every = 0;
+    double rb_ratio = 1.5;
+    std::string outdir;
+    bool raw_f32 = false;
+};
+
+// What the main thread and the block threads share: `go` = steps released so far, done[i & 1] = blocks that finished step i.
+struct BlockSync {
+    std::mutex m;
+    std::condition_variable cv;
+    int go = 0, ready = 0, done[2] = {0, 0};
+    bool failed = false;
+    std::string error;
+    void* group = nullptr;
+    // the first failure is kept; every waiter — here and inside the transport — is woken
+    void fail(const std::string& what)
+    {
+        {
+            std::lock_guard<std::mutex> lk(m);
+            if (!failed) error = what;
+            failed = true;
+        }
+        fluid_local_group_abort(group);
+        cv.notify_all();
+    }
+};
+
+static int run_blocks(const BlockCfg& cfg, const std::vector<double>& pos, int64_t np, const std::chrono::steady_clock::time_point t0)
+{
+    const int R = cfg.dims[0] * cfg.dims[1] * cfg.dims[2], n = cfg.prm.n, steps = cfg.steps;
+    std::vector<int32_t> cuts[3];
+    for (int a = 0; a < 3; ++a) cuts[a].assign(cfg.dims[a] + 1, 0);
+    const int32_t dims32[3] = {cfg.dims[0], cfg.dims[1], cfg.dims[2]};
+    if (fluid_partition_blocks(n, np, pos.data(), dims32, cuts[0].data(), cuts[1].data(), cuts[2].data()) != FLUID_OK) {
+        std::cerr << "fluid_partition_blocks: " << fluid_last_error() << std::endl;
+        return 1;
+    }
+    // the particles of every block: base cell round(p) (half away from zero, fluid.cc:267), clamped to the grid like the library's owner rule
+    std::vector<std::vector<double>> bpos(R);
+    std::vector<std::vector<uint32_t>> bids(R);
+    const int lo = -(n / 2);
+    for (int64_t i = 0; i < np; ++i) {
+        int b[3];
+        for (int a = 0; a < 3; ++a) {
+            long c = std::lround(pos[3 * i + a]) - lo;
+            c = c < 0 ? 0 : (c > n - 1 ? n - 1 : c);
+            int k = 0;
+            while (k + 1 < cfg.dims[a] && c >= cuts[a][k + 1]) ++k;
+            b[a] = k;
+        }
+        const int r = (b[0] * cfg.dims[1] + b[1]) * cfg.dims[2] + b[2];
+        bpos[r].insert(bpos[r].end(), &pos[3 * i], &pos[3 * i] + 3);
+        bids[r].push_back((uint32_t)i);
+    }
+    BlockSync sy;
+    if (fluid_local_group_create(R, &sy.group) != FLUID_OK) {
+        std::cerr << "fluid_local_group_create: " << fluid_last_error() << std::endl;
+        return 1;
+    }
+    const bool output = !cfg.outdir.empty() && steps > 0;
+    std::vector<fluid_leaf_grid_t> part[2] = {std::vector<fluid_leaf_grid_t>(R), std::vector<fluid_leaf_grid_t>(R)};
+    std::vector<fluid_step_stats_t> st0(2);   // rank 0's stats of step i in st0[i & 1]
+    auto block = [&](int r) {
+        fluid_sim_t* sim = nullptr;
+        auto err = [&](const char* what) { sy.fail(std::string("block ") + std::to_string(r) + ": " + what + ": " + fluid_last_error()); };
+        fluid_comm_t comm;
+        fluid_params_t prm = cfg.prm;
+        prm.device = cfg.prm.device + r % cfg.devices;
+        fluid_decomp_t dc;
+        for (int a = 0; a < 3; ++a) { dc.dims[a] = cfg.dims[a]; dc.cuts[a] = cuts[a].data(); }
+        bool ok = true;
+        if (fluid_local_comm_create(sy.group, r, &comm) != FLUID_OK) { err("fluid_local_comm_create"); ok = false; }
+        else if (fluid_create_dist(&prm, &comm, &dc, &sim) != FLUID_OK) { err("fluid_create_dist"); ok = false; }
+        else if (fluid_upload_particles_ids(sim, (int64_t)bids[r].size(), bpos[r].data(), nullptr, bids[r].data()) != FLUID_OK) { err("fluid_upload_particles_ids"); ok = false; }
+        else if (cfg.rb_every > 0 && fluid_dist_set_rebalance(sim, cfg.rb_every, cfg.rb_ratio) != FLUID_OK) { err("fluid_dist_set_rebalance"); ok = false; }
+        else if (output && fluid_dist_output_every(sim, 1) != FLUID_OK) { err("fluid_dist_output_every"); ok = false; }
+        {
+            std::lock_guard<std::mutex> lk(sy.m);
+            sy.ready++;
+        }
+        sy.cv.notify_all();
+        for (int i = 0; ok && i < steps; ++i) {
+            {
+                std::unique_lock<std::mutex> lk(sy.m);
+                sy.cv.wait(lk, [&] { return sy.go > i || sy.failed; });
+                if (sy.failed) break;
+            }
+            fluid_step_stats_t st;
+            if (fluid_step(sim, &st) != FLUID_OK) { err("fluid_step"); break; }
+            // (the copy of this step's list is the only thing waited for here: the next step starts when the main thread says so)
+            if (output && fluid_dist_output_wait(sim, &part[i & 1][r]) != FLUID_OK) { err("fluid_dist_output_wait"); break; }
+            {
+                std::lock_guard<std::mutex> lk(sy.m);
+                if (r == 0) st0[i & 1] = st;
+                sy.done[i & 1]++;
+            }
+            sy.cv.notify_all();
+        }
+        // the lists handed out belong to the handle: it stays until the main thread has merged the last one
+        {
+            std::unique_lock<std::mutex> lk(sy.m);
+            sy.cv.wait(lk, [&] { return sy.go > steps || sy.failed; });
+        }
+        if (sim) fluid_destroy(sim);
+    };
+    std::vector<std::thread> th;
+    for (int r = 0; r < R; ++r) th.emplace_back(block, r);
+    auto finish = [&](int code) {
+        {
+            std::lock_guard<std::mutex> lk(sy.m);
+            sy.go = steps + 1;
+        }
+        sy.cv.notify_all();
+        for (auto& t : th) t.join();
+        fluid_local_group_destroy(sy.group);
+        if (sy.failed) std::cerr << sy.error << std::endl;
+        return sy.failed && code == 0 ? 1 : code;
+    };
+    {
+        std::unique_lock<std::mutex> lk(sy.m);
+        sy.cv.wait(lk, [&] { return sy.ready == R; });
+    }
+    if (sy.failed) return finish(1);
+
+    if (output) mkdir(cfg.outdir.c_str(), 0755);
+    fluid_vdb_writer_t* all = nullptr;
+    std::string fin;
+    LeafWriter lw;
+    if (output) {
+        const size_t slash = cfg.outdir.find_last_of('/');
+        fin = (slash == std::string::npos ? std::string() : cfg.outdir.substr(0, slash + 1)) + "mygrids.vdb";
+        if (fluid_vdb_open(fin.c_str(), n, steps, FLUID_VDB_ZIP_ACTIVE_MASK, &all) != FLUID_OK) {
+            sy.fail("cannot write " + fin);
+            return finish(1);
+        }
+        lw.outdir = cfg.outdir, lw.fin = fin, lw.all = all, lw.raw_f32 = cfg.raw_f32;
+        lw.start();
+    }
+    // the merged grid of step i lives in buffer i & 1 until the writer thread has put grid i on disk
+    std::vector<int32_t> m_org[2];
+    std::vector<float> m_val[2];
+    double dt = cfg.prm.max_dt, simulationTime = 0;
+    auto release = [&](int upto) {
+        {
+            std::lock_guard<std::mutex> lk(sy.m);
+            sy.go = upto;
+            sy.done[(upto - 1) & 1] = 0;
+        }
+        sy.cv.notify_all();
+    };
+    if (steps > 0) release(1);
+    for (int i = 0; i < steps; ++i) {
+        {
+            std::unique_lock<std::mutex> lk(sy.m);
+            sy.cv.wait(lk, [&] { return sy.done[i & 1] == R || sy.failed; });
+            if (sy.failed) break;
+        }
+        const fluid_step_stats_t st = st0[i & 1];
+        if (i + 1 < steps) release(i + 2);   // step i + 1 runs beside the merge; its lists go to the other half of `part`
+        std::cout << "2" << std::endl;
+        std::cout << "3" << std::endl;
+        std::cout << "DT " << dt << std::endl;
+        std::cout << "Before" << std::endl;
+        std::cout << "After" << std::endl;
+        dt = st.dt_out;
+        std::cout << "DT " << dt << std::endl;
+        std::cout << "Error:\t" << st.error << std::endl;
+        std::cout << "Iteration:\t" << i + 1 << std::endl;
+        simulationTime += dt;
+        std::cout << "Time delta:\t" << simulationTime << std::endl;
+        if (!output) continue;
+        if (!lw.wait_done(i - 1)) { sy.fail("cannot write " + lw.error); break; }
+        const int64_t k = fluid_leaf_grids_merge(part[i & 1].data(), R, 0, nullptr, nullptr);
+        if (k < 0) { sy.fail("fluid_leaf_grids_merge: the blocks' leaf lists do not merge"); break; }
+        auto& org = m_org[i & 1];
+        auto& val = m_val[i & 1];
+        if (org.size() < 3 * (size_t)k) { org.resize(3 * (size_t)k + 3 * 64); val.resize(512 * ((size_t)k + 64)); }
+        if (fluid_leaf_grids_merge(part[i & 1].data(), R, k, org.data(), val.data()) != k) { sy.fail("fluid_leaf_grids_merge: the blocks' leaf lists do not merge"); break; }
+        lw.submit(i, fluid_leaf_grid_t{n, (int32_t)k, k ? org.data() : nullptr, k ? val.data() : nullptr});
+    }
+    bool ok = !sy.failed;
+    if (output) {
+        if (ok && !lw.wait_done(steps)) { sy.fail("cannot write " + lw.error); ok = false; }
+        lw.stop();
+        if (all && fluid_vdb_close(all) != FLUID_OK && ok) { sy.fail("cannot write " + fin); ok = false; }
+    }
+    const int code = finish(ok ? 0 : 1);
+    if (code) return code;
+    const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    std::cout << "Time Taken " << sec / 60 << " minutes" << std::endl;
+    return 0;
+}
+
 int main(int, char**)
 {
     const auto t0 = std::chrono::steady_clock::now();
@@ -138,9 +344,34 @@ int main(int, char**)
     const bool raw_f32 = env_long("FLUID_RAW", 0) != 0;
     const long src_every = env_long("FLUID_SOURCE_EVERY", 0);
     const bool out_dense = env_long("FLUID_OUT_DENSE", 0) != 0;
+    const char* blocks = getenv("FLUID_BLOCKS");
+    BlockCfg bc;
+    if (blocks && *blocks) {
+        char tail = 0;
+        if (sscanf(blocks, "%dx%dx%d%c", &bc.dims[0], &bc.dims[1], &bc.dims[2], &tail) != 3 || bc.dims[0] < 1 || bc.dims[1] < 1 || bc.dims[2] < 1 ||
+            (long)bc.dims[0] * bc.dims[1] * bc.dims[2] > FLUID_MAX_RANKS) {
+            std::cerr << "FLUID_BLOCKS must be AxBxC with at most " << FLUID_MAX_RANKS << " blocks, e.g. 2x2x2" << std::endl;
+            return 1;
+        }
+        if (src_every > 0 || out_dense) {
+            std::cerr << "FLUID_BLOCKS cannot be combined with " << (src_every > 0 ? "FLUID_SOURCE_EVERY (sources need one GPU)" : "FLUID_OUT_DENSE=1 (a block run leaves its grid as leaf lists)") << std::endl;
+            return 1;
+        }
+        if (const char* m = getenv("FLUID_DIST_SOLVE")) {
+            const std::string v = m;
+            if (v == "decomposed") prm.dist_solve = FLUID_DIST_DECOMPOSED;
+            else if (v == "replicated") prm.dist_solve = FLUID_DIST_REPLICATED;
+            else { std::cerr << "FLUID_DIST_SOLVE must be decomposed or replicated" << std::endl; return 1; }
+        }
+        bc.devices = (int)env_long("FLUID_DEVICES", 1);
+        if (bc.devices < 1) bc.devices = 1;
+        bc.rb_every = (int)env_long("FLUID_REBALANCE_EVERY", 0);
+        if (const char* r = getenv("FLUID_REBALANCE_RATIO")) bc.rb_ratio = atof(r);
+        if (bc.rb_every < 0 || !(bc.rb_ratio >= 1.0)) { std::cerr << "FLUID_REBALANCE_EVERY must be >= 0 and FLUID_REBALANCE_RATIO >= 1" << std::endl; return 1; }
+    }
 
     fluid_sim_t* sim = nullptr;
-    if (fluid_create(&prm, &sim) != FLUID_OK) {
+    if (!(blocks && *blocks) && fluid_create(&prm, &sim) != FLUID_OK) {
         std::cerr << "fluid_create: " << fluid_last_error() << std::endl;
         return 1;
     }
@@ -156,6 +387,10 @@ int main(int, char**)
     std::vector<double> pos((size_t)3 * np);
     if (ref_scene) fluid_scene_uniform_scatter(flo, fhi, 10.f, (uint32_t)seed, 60, pos.data());
     else fluid_scene_water_cube_drop(prm.n, ppc, seed, pos.data());
+    if (blocks && *blocks) {
+        bc.prm = prm, bc.steps = steps, bc.outdir = outdir, bc.raw_f32 = raw_f32;
+        return run_blocks(bc, pos, np, t0);
+    }
     if (fluid_upload_particles(sim, np, pos.data(), nullptr) != FLUID_OK) {
         std::cerr << "fluid_upload_particles: " << fluid_last_error() << std::endl;
         return 1;

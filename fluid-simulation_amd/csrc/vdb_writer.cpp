@@ -30,6 +30,7 @@
 // reference tree); tests/test_vdb.py re-reads the files with an independent restatement of the READ side.
 #include <zlib.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -660,6 +661,56 @@ int fluid_leaves_to_dense(const fluid_leaf_grid_t* g, float* dense)
                 }
     }
     return FLUID_OK;
+}
+
+// One k-way merge over the parts' (already ascending) lists, run twice: the first pass counts and checks and writes nothing, the
+// second writes.  A leaf listed by one part is copied; one listed by several is OR-ed as bit patterns — exact, because a voxel is
+// owned by one part and +0 in the others, which the first pass verifies.
+int64_t fluid_leaf_grids_merge(const fluid_leaf_grid_t* parts, int32_t n_parts, int64_t cap_leaves, int32_t* origin, float* values)
+{
+    if (!parts || n_parts < 1 || (origin == nullptr) != (values == nullptr)) return -FLUID_ERR_ARG;
+    for (int p = 0; p < n_parts; ++p)
+        if (check_leaf_list(&parts[p]) != FLUID_OK || parts[p].n != parts[0].n) return -FLUID_ERR_ARG;
+    auto before = [](const int32_t* a, const int32_t* b) { return a[0] != b[0] ? a[0] < b[0] : a[1] != b[1] ? a[1] < b[1] : a[2] < b[2]; };
+    std::vector<int32_t> cur((size_t)n_parts);
+    int64_t count = 0;
+    for (int pass = 0; pass < (origin ? 2 : 1); ++pass) {
+        if (pass == 1 && count > cap_leaves) return -FLUID_ERR_ARG;
+        std::fill(cur.begin(), cur.end(), 0);
+        count = 0;
+        for (;;) {
+            const int32_t* o = nullptr;   // the smallest origin at the parts' cursors
+            for (int p = 0; p < n_parts; ++p) {
+                if (cur[p] >= parts[p].n_leaves) continue;
+                const int32_t* c = parts[p].origin + 3 * (size_t)cur[p];
+                if (!o || before(c, o)) o = c;
+            }
+            if (!o) break;
+            const int32_t o3[3] = {o[0], o[1], o[2]};
+            uint32_t acc[512];
+            int n_in = 0;
+            for (int p = 0; p < n_parts; ++p) {
+                if (cur[p] >= parts[p].n_leaves) continue;
+                const int32_t* c = parts[p].origin + 3 * (size_t)cur[p];
+                if (c[0] != o3[0] || c[1] != o3[1] || c[2] != o3[2]) continue;
+                const float* v = parts[p].values + 512 * (size_t)cur[p];
+                cur[p]++;
+                if (n_in++ == 0) { memcpy(acc, v, sizeof acc); continue; }
+                for (int i = 0; i < 512; ++i) {
+                    uint32_t b;
+                    memcpy(&b, v + i, sizeof b);
+                    if (pass == 0 && b && acc[i]) return -FLUID_ERR_ARG;   // two parts claim the voxel
+                    acc[i] |= b;
+                }
+            }
+            if (pass == 1) {
+                memcpy(origin + 3 * (size_t)count, o3, sizeof o3);
+                memcpy(values + 512 * (size_t)count, acc, sizeof acc);
+            }
+            count++;
+        }
+    }
+    return count;
 }
 
 int fluid_vdb_append_leaves(fluid_vdb_writer_t* const* writers, int32_t n_writers, const fluid_leaf_grid_t* g)

@@ -15,8 +15,8 @@ import threading
 
 import numpy as np
 
-from ._lib import lib, check, Params, StepStats
-from .sim import FluidSim, grid_bounds
+from ._lib import lib, check, Params, StepStats, LeafGridC
+from .sim import FluidSim, grid_bounds, merge_leaf_grids, _leaf_grid_copy  # noqa: F401
 
 EXCHANGE_T = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                          C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p)
@@ -387,6 +387,27 @@ class DistFluidSim(FluidSim):
         a = self.window_field(fid)
         sl = tuple(slice(self.own_lo[k] - self.origin[k], self.own_hi[k] - self.origin[k]) for k in range(3))
         return a[(slice(None),) + sl] if a.ndim == 4 else a[sl]
+
+    # ---- output as non-zero leaves of the owned block (include/fluid_hip.h, "decomposed runs"); rank-local, no transport call ----
+    def output_snapshot(self):
+        """Enqueue a leaf snapshot of the owned block of FIELD.OUTPUT as it is now."""
+        check(lib.fluid_dist_output_snapshot(self._h))
+
+    def output_wait(self):
+        """The oldest snapshot not yet waited for, as a LeafGrid with global origins (merge_leaf_grids joins the ranks')."""
+        g = LeafGridC()
+        check(lib.fluid_dist_output_wait(self._h, C.byref(g)))
+        return _leaf_grid_copy(g)
+
+    def output_stats(self):
+        v = [C.c_int64() for _ in range(3)]
+        check(lib.fluid_dist_output_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("leaves_in_block", "leaves_listed", "bytes_to_host"), (x.value for x in v)))
+
+    def output_every(self, k):
+        """step() itself snapshots the owned block at the end of every step t with t % k == 0 (0 = off), before a re-balancing
+        moves the planes; the same k on every rank, and every rank waits alike."""
+        check(lib.fluid_dist_output_every(self._h, int(k)))
 
     def step(self):
         st = StepStats()

@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 
-from ._lib import lib, check, Params, StepStats, FIELD, Source, LeafGridC
+from ._lib import lib, check, FluidError, Params, StepStats, FIELD, Source, LeafGridC
 
 _FIELD_DTYPE = {
     FIELD.CONTAINER: (np.float32, 1), FIELD.WEIGHTS: (np.float32, 1), FIELD.OUTPUT: (np.float32, 1),
@@ -89,6 +89,30 @@ def leaves_to_dense(leaves):
 def write_vdb_leaves(path, leaves, compression="zip"):
     """write_vdb(path, leaves_to_dense(leaves)) without the dense array: the same file."""
     check(lib.fluid_write_vdb_leaves(str(path).encode(), C.byref(leaves._c()), _VDB_COMPRESSION[compression]))
+
+
+def _leaf_grid_copy(g):
+    """LeafGrid copied out of the buffers a fluid_leaf_grid_t points into."""
+    k = g.n_leaves
+    if k == 0:
+        return LeafGrid(g.n, np.empty((0, 3), np.int32), np.empty((0, 512), np.float32))
+    org = np.ctypeslib.as_array(C.cast(g.origin, C.POINTER(C.c_int32)), shape=(k, 3)).copy()
+    val = np.ctypeslib.as_array(C.cast(g.values, C.POINTER(C.c_float)), shape=(k, 512)).copy()
+    return LeafGrid(g.n, org, val)
+
+
+def merge_leaf_grids(parts):
+    """The LeafGrid of the whole grid from the blocks' LeafGrids (DistFluidSim.output_wait of every rank): the union of their
+    leaves, ascending; a leaf a cut plane splits is the bitwise OR of the ranks' records (fluid_leaf_grids_merge: host only)."""
+    parts = list(parts)
+    arr = (LeafGridC * len(parts))(*[p._c() for p in parts])
+    k = lib.fluid_leaf_grids_merge(arr, len(parts), 0, None, None)
+    if k < 0:
+        raise FluidError(-k, "fluid_leaf_grids_merge: the parts do not merge (different n, a bad list, or a voxel two parts hold)")
+    org, val = np.empty((k, 3), np.int32), np.empty((k, 512), np.float32)
+    if k and lib.fluid_leaf_grids_merge(arr, len(parts), k, org.ctypes.data_as(C.c_void_p), val.ctypes.data_as(C.c_void_p)) != k:
+        raise FluidError(1, "fluid_leaf_grids_merge: the second call disagrees with the count")
+    return LeafGrid(parts[0].n, org, val)
 
 
 def water_cube_drop(n, ppc, seed=0):
@@ -316,12 +340,7 @@ class FluidSim:
         """The oldest snapshot not yet waited for, as a LeafGrid (copied out of the handle's pinned buffer)."""
         g = LeafGridC()
         check(lib.fluid_output_wait(self._h, C.byref(g)))
-        k = g.n_leaves
-        if k == 0:
-            return LeafGrid(g.n, np.empty((0, 3), np.int32), np.empty((0, 512), np.float32))
-        org = np.ctypeslib.as_array(C.cast(g.origin, C.POINTER(C.c_int32)), shape=(k, 3)).copy()
-        val = np.ctypeslib.as_array(C.cast(g.values, C.POINTER(C.c_float)), shape=(k, 512)).copy()
-        return LeafGrid(g.n, org, val)
+        return _leaf_grid_copy(g)
 
     def output_stats(self):
         v = [C.c_int64() for _ in range(3)]

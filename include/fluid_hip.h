@@ -418,6 +418,7 @@ int fluid_write_vdb_ex(const char* path, int32_t n, int32_t n_grids, const float
  *   fluid_step(s, &st);  fluid_output_snapshot(s);            enqueue only: the next fluid_step overlaps the copy
  *   fluid_step(s, &st);  fluid_output_wait(s, &g);            g = the grid of the FIRST step
  *   fluid_vdb_append_leaves(writers, 2, &g);                  may run on another host thread: it reads g's pointers only
+ * A decomposed run takes its grid out block by block with the next section ("output as non-zero leaves (decomposed runs)").
  */
 typedef struct fluid_leaf_grid {
     int32_t n;               /* cells per axis of the grid the leaves belong to                                  */
@@ -448,6 +449,45 @@ int fluid_leaves_to_dense(const fluid_leaf_grid_t* g, float* dense);
  * (nothing is then written to any of them).  Host only. */
 int fluid_vdb_append_leaves(fluid_vdb_writer_t* const* writers, int32_t n_writers, const fluid_leaf_grid_t* g);
 int fluid_write_vdb_leaves(const char* path, const fluid_leaf_grid_t* g, int32_t compression);
+
+/* ---- output as non-zero leaves (decomposed runs) ---------------------------------------------------------------------------
+ * The same list, per block: every rank lists the GLOBAL leaves that meet its owned block [own_lo, own_hi) (fluid_window) and have
+ * an owned, in-grid voxel with a non-zero bit pattern.  Origins are global index-space coordinates, ascending (x, y, z); a record
+ * is the leaf's 512 floats in the leaf's own voxel order, with +0 in EVERY voxel this rank does not own (halo cells of its window,
+ * other ranks' cells — in replicated mode the rest of its full-size array — and voxels outside [lo,hi]^3).  A leaf that a cut plane
+ * splits is therefore listed by each rank that owns a non-zero voxel of it, and the ranks' records of it have disjoint support:
+ * fluid_leaf_grids_merge ORs them, exactly.  Rank-local: no transport call is made, moving the lists to one place is the caller's
+ * (plain host arrays with global origins).
+ *
+ *   fluid_dist_output_every(s, 1);                                     once, the same on every rank
+ *   per step, every rank:    fluid_step(s, &st);  fluid_dist_output_wait(s, &part[rank]);
+ *   one place:               k = fluid_leaf_grids_merge(part, R, cap, origin, values);
+ *                            g = {n, k, origin, values};  fluid_vdb_append_leaves(writers, 2, &g);
+ */
+/* Captures the owned block of FLUID_FIELD_OUTPUT as it is at the call; otherwise fluid_output_snapshot in every respect: kernels on
+ * the handle's stream, the 4-byte count read back, the records copied on a second stream and not waited for, two snapshots may be
+ * outstanding (a third: FLUID_ERR_STATE), buffers grow here.  A plain fluid_create handle is accepted: its owned block is the
+ * grid, the list is fluid_output_snapshot's, and both forms share the handle's two slots and its count of outstanding snapshots. */
+int fluid_dist_output_snapshot(fluid_sim_t* s);
+/* The oldest snapshot not yet waited for, as fluid_output_wait; out->n is the global N.  The pointers stay valid until the SECOND
+ * following snapshot on the handle — also across a step that moves the cut planes (FLUID_PATH_DIST_REBALANCED): the list is then
+ * still the old window's block. */
+int fluid_dist_output_wait(fluid_sim_t* s, fluid_leaf_grid_t* out);
+/* leaves_in_block = global leaves that meet the owned block now; the other two of the last snapshot:
+ * bytes_to_host = leaves_listed * FLUID_OUTPUT_LEAF_BYTES + FLUID_OUTPUT_HEADER_BYTES.  Any pointer may be NULL. */
+int fluid_dist_output_stats(fluid_sim_t* s, int64_t* leaves_in_block, int64_t* leaves_listed, int64_t* bytes_to_host);
+/* every = 0 (default): off.  every >= 1: fluid_step itself takes the snapshot at the end of every step t with t % every == 0, t = the
+ * 0-based count of fluid_step calls on the handle (kept when the planes move): after FLIPadvect and BEFORE the re-balancing, so the
+ * grid of a step that moves the planes is captured from the old window (afterwards the fields of the new one are zero).  A step that
+ * would take the third outstanding snapshot returns FLUID_ERR_STATE at once, before any work and any transport call.  Every rank of
+ * a run sets the same `every` and waits alike (as for fluid_dist_set_rebalance): a rank refused alone leaves its peers in the step. */
+int fluid_dist_output_every(fluid_sim_t* s, int32_t every);
+/* Host only.  The union of the parts' leaves, ascending (x, y, z), into origin[3 * cap_leaves] / values[512 * cap_leaves]; a leaf that
+ * several parts list receives the bitwise OR of their records.  For the lists fluid_dist_output_wait gives on the ranks of a run this
+ * is the list fluid_output_snapshot gives for the assembled grid.  Returns the merged leaf count (origin == values == NULL: the count
+ * only, cap_leaves is ignored), or -FLUID_ERR_ARG with nothing written: n_parts < 1, the parts' n differ, a part breaks the list
+ * rules of fluid_vdb_append_leaves, two parts hold a non-zero bit pattern for the same voxel, cap_leaves is too small. */
+int64_t fluid_leaf_grids_merge(const fluid_leaf_grid_t* parts, int32_t n_parts, int64_t cap_leaves, int32_t* origin, float* values);
 
 #ifdef __cplusplus
 }
