@@ -120,6 +120,10 @@ SYMBOLS = [
     ("fluid_set_source", C.c_int, [_P, C.c_int32, C.POINTER(Source)]),
     ("fluid_set_sink", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("fluid_get_source_stats", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("fluid_dist_set_source", C.c_int, [_P, C.c_int32, C.POINTER(Source)]),
+    ("fluid_dist_set_sink", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("fluid_dist_get_source_stats", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("fluid_dist_add_particles", C.c_int, [_P, C.c_int64, _P, _P, _P]),
     ("fluid_stencil_apply_hbm", C.c_int, [_P, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
     ("fluid_profile_enable", C.c_int, [_P, C.c_int]),
     ("fluid_profile_read", C.c_int, [_P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -139,6 +139,20 @@ struct DistState {
     std::vector<int> h_tl;            // host copy behind the (stream-ordered) upload
     uint8_t* tl_cls = nullptr;        // per level-0 leg tile: 1 = reads a received cell (the class the two lists above are cut by)
     std::vector<uint8_t> h_cls;
+    // particle sources and sinks (fluid_dist_set_source / fluid_dist_set_sink; dist_sources_apply).  Boxes are global index boxes,
+    // a slot's buffer is box-sized and holds nothing that depends on the window: re-balancing hands it on as it is.
+    struct SrcSlot {
+        bool on = false, mask_ok = false;
+        fluid_source_t src{};
+        Box box{};
+        int* buf = nullptr;   // box cells x 5 ints: FILL histogram | kept per cell | its scan | kept per owned cell | its scan; then the global solid mask of the box (bytes)
+    };
+    SrcSlot src[FLUID_MAX_SOURCES];
+    Box sink[FLUID_MAX_SINKS] = {};
+    bool sink_on[FLUID_MAX_SINKS] = {};
+    long long max_id = -1;            // largest id this handle was ever handed (fluid_upload_particles_ids, fluid_dist_add_particles)
+    long long next_id = 0;            // id of the next emitted point as last agreed (MAX over the ranks in every step where a source is due)
+    long long *src_d = nullptr, *src_h = nullptr;   // device / pinned: [0] removed by the sinks (SUM), [1] next_id (MAX)
 };
 
 namespace {
@@ -1370,6 +1384,157 @@ int dist_step_decomposed(fluid_sim* s, fluid_step_stats_t* stats)
     return dist_g2p_advect(s, stats);
 }
 
+// ---- particle sources and sinks (include/fluid_hip.h, "particle sources and sinks of a decomposed run") ---------------------------
+uint64_t sm64_host(uint64_t x)
+{
+    uint64_t z = x + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// The global solid array over a slot's box, behind the slot's five int arrays: a window holds only a part of the box, and every
+// rank counts the kept points of ALL its cells (the ids follow from that count alone, with no exchange).
+int src_mask_upload(fluid_sim* s, DistState::SrcSlot& q)
+{
+    DistState* d = s->ds;
+    const Box b = q.box;
+    const long N = s->g.N;
+    std::vector<uint8_t> m((size_t)b.cells());
+    size_t l = 0;
+    for (long x = b.x0; x <= b.x1; ++x)
+        for (long y = b.y0; y <= b.y1; ++y)
+            for (long z = b.z0; z <= b.z1; ++z, ++l) {
+                const bool outsideW = x < 2 || x > N - 3 || y < 2 || y > N - 3 || z < 2 || z > N - 3;   // the default shell (fluid_create_window)
+                m[l] = d->solid_global.empty() ? outsideW : d->solid_global[((size_t)x * N + y) * N + z] != 0;
+            }
+    HIPCHK(hipStreamSynchronize(s->st));
+    HIPCHK(hipMemcpy(q.buf + 5 * (size_t)b.cells(), m.data(), m.size(), hipMemcpyHostToDevice));
+    q.mask_ok = true;
+    return FLUID_OK;
+}
+
+// Cell-centre velocities getVelocity(c, vels) on the owned cells of `need` (global, half-open) inside W, into the FLIP delta arrays
+// (free after G2P; the next step's flip_delta and halo exchange rewrite every cell its gather reads), and their 1-wide halo
+// from the neighbours: a point of an owned cell c reads the centres c +- 1, and the centre of c + 1 needs the face at c + 2,
+// which u / v / w (1-wide halo, plan_f1) do not hold.  Collective: every rank calls it with the same `need`.
+int centre_halo(fluid_sim* s, const IBox& need)
+{
+    DistState* d = s->ds;
+    const Grid g = s->g;
+    const int N = g.N, org[3] = {g.ox, g.oy, g.oz};
+    const IBox W{{2, 2, 2}, {N - 2, N - 2, N - 2}};
+    const IBox lim = ib_isect(need, W);
+    auto own = [&](int r) { return ib_isect(block_of(d, r), lim); };
+    launch_centre_avg(s->st, g, to_box(own(d->comm.rank), org), s->u, s->v, s->w, s->dcx, s->dcy, s->dcz);
+    HIPCHK(hipGetLastError());
+    HaloPlan plan;
+    make_plan(d, plan, own, 1, org, 0, g.sx(), g.nz);
+    void* a[3] = {s->dcx, s->dcy, s->dcz};
+    return halo_exchange(s, plan, 8, 3, a);
+}
+
+// After FLIPadvect of step t = n_steps, before the output snapshot and the re-balancing: the sinks, then the sources in slot
+// order.  A step with no sink set and no source due returns before any launch, transport call or wait.
+int dist_sources_apply(fluid_sim* s, bool* changed)
+{
+    DistState* d = s->ds;
+    const Grid g = s->g;
+    const long t = s->n_steps;
+    *changed = false;
+    s->src_emit_last = s->src_rm_last = 0;
+    SinkSet sk{};
+    for (int i = 0; i < FLUID_MAX_SINKS; ++i)
+        if (d->sink_on[i]) sk.box[sk.n++] = d->sink[i];
+    bool due = false;
+    for (const auto& q : d->src) due = due || (q.on && t % q.src.every == 0);
+    if (sk.n == 0 && !due) return FLUID_OK;
+    int rc;
+    // the sinks' global count (SUM) and the agreed id of the next new point (MAX): one read-back for both
+    d->src_h[0] = 0;
+    d->src_h[1] = std::max(d->next_id, d->max_id + 1);
+    HIPCHK(hipMemcpyAsync(d->src_d, d->src_h, 2 * sizeof(long long), hipMemcpyHostToDevice, s->st));
+    if (sk.n) {
+        launch_sink_kill(s->st, g, s->np, s->pa.shifted(s->p_off), sk, (unsigned long long*)d->src_d);
+        HIPCHK(hipGetLastError());
+        if ((rc = comm_allreduce(s, d->src_d, 1, FLUID_DT_I64, FLUID_OP_SUM))) return rc;
+    }
+    if (due && (rc = comm_allreduce(s, d->src_d + 1, 1, FLUID_DT_I64, FLUID_OP_MAX))) return rc;
+    HIPCHK(hipMemcpyAsync(d->src_h, d->src_d, 2 * sizeof(long long), hipMemcpyDeviceToHost, s->st));
+    HIPCHK(hipStreamSynchronize(s->st));
+    const long removed = (long)d->src_h[0];
+    if (due) d->next_id = d->src_h[1];
+    long emitted = 0;
+    for (auto& q : d->src) {
+        if (!q.on || t % q.src.every != 0) continue;
+        const fluid_source_t& c = q.src;
+        const Box b = q.box;
+        const long B = b.cells();
+        int *hist = q.buf, *cnt = q.buf + B, *off = q.buf + 2 * B, *cnt_own = q.buf + 3 * B, *off_own = q.buf + 4 * B;
+        const uint8_t* mask = (const uint8_t*)(q.buf + 5 * B);
+        const bool fill = c.mode == FLUID_SOURCE_FILL;
+        const uint64_t h0 = sm64_host(sm64_host(c.seed) ^ (uint64_t)t);
+        if (!q.mask_ok && (rc = dist_agree(s, src_mask_upload(s, q)))) return rc;   // (fluid_set_solid after the slot was set: every rank alike)
+        if (fill) {   // live particles per cell after the sinks, over all their holders
+            HIPCHK(hipMemsetAsync(hist, 0, B * sizeof(int), s->st));
+            launch_src_count_live(s->st, g, s->np, s->pa.shifted(s->p_off), b, hist);
+            HIPCHK(hipGetLastError());
+            if ((rc = comm_allreduce(s, hist, B, FLUID_DT_I32, FLUID_OP_SUM))) return rc;
+        }
+        launch_src_plan_win(s->st, g, b, h0, c.per_cell, fill, d->ob, mask, hist, cnt, cnt_own);
+        launch_exclusive_scan(s->st, cnt, off, B, s->src_sums, s->d_small + 1);
+        launch_exclusive_scan(s->st, cnt_own, off_own, B, s->src_sums, s->d_small + 2);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(s->h_small + 1, s->d_small + 1, 2 * sizeof(int), hipMemcpyDeviceToHost, s->st));
+        HIPCHK(hipStreamSynchronize(s->st));
+        const long m = s->h_small[1], mo = s->h_small[2];   // all ranks' new points (the same number everywhere) / this rank's
+        if (m == 0) continue;
+        if (d->next_id + m >= (long long)PID_DEAD) return fail(FLUID_ERR_STATE, "a source would take the particle ids up to 0xFFFFFFFF, the mark of a dead particle");
+        // room for this rank's share: the one allocation here that can fail on ONE rank, agreed before the next transport call
+        auto grow = [&]() -> int {
+            if (s->np + mo > (long)INT32_MAX) return fail(FLUID_ERR_STATE, "a source would take the particle count past INT32_MAX");
+            const long need = s->p_off + s->np + mo;
+            if (need > s->cap && d->fail_grow_rank == d->comm.rank)   // (tests: a rank that cannot grow)
+                return fail(FLUID_ERR_HIP, "particle arrays for emitted points: allocation refused (FLUID_DIST_FAIL_GROW)");
+            return grow_particles(s, need);
+        };
+        if ((rc = dist_agree(s, grow()))) return rc;
+        const Particles p = s->pa.shifted(s->p_off + s->np);
+        const double zero[3] = {0, 0, 0};
+        if (mo > 0)
+            launch_src_emit_win(s->st, g, b, h0, c.per_cell, fill, d->ob, mask, hist, off, off_own, p, (uint32_t)d->next_id,
+                                c.vel_mode == FLUID_SOURCE_VEL_FIXED ? c.vel : zero);
+        HIPCHK(hipGetLastError());
+        const IBox bi{{b.x0, b.y0, b.z0}, {b.x1 + 1, b.y1 + 1, b.z1 + 1}};
+        if (c.vel_mode == FLUID_SOURCE_VEL_GRID) {
+            if (d->repl) {
+                launch_interp_from_grid(s->st, g, mo, p, s->u, s->v, s->w);   // full-size arrays: the one-GPU kernel as it is
+            } else {
+                if ((rc = centre_halo(s, ib_grow(bi, 1)))) return rc;
+                launch_interp_from_centres(s->st, g, mo, p, s->dcx, s->dcy, s->dcz);
+            }
+            HIPCHK(hipGetLastError());
+        }
+        s->np += mo;
+        d->next_id += m;
+        emitted += m;
+        {   // the next sort's x-plane guess (Pb +- 3) covers the new points of this rank and those that arrive as ghosts
+            const int org[3] = {g.ox, g.oy, g.oz};
+            const IBox win{{g.ox, g.oy, g.oz}, {g.ox + g.nx, g.oy + g.ny, g.oz + g.nz}};
+            const Box w = to_box(ib_isect(bi, win), org);
+            Box& P = s->Pb;
+            if (!box_empty(w))
+                P = box_empty(P) ? w
+                                 : Box{std::min(P.x0, w.x0), std::min(P.y0, w.y0), std::min(P.z0, w.z0), std::max(P.x1, w.x1), std::max(P.y1, w.y1),
+                                       std::max(P.z1, w.z1)};
+        }
+    }
+    s->src_emit_last = emitted, s->src_rm_last = removed;
+    s->src_emit_total += emitted, s->src_rm_total += removed;
+    *changed = emitted || removed;
+    return FLUID_OK;
+}
+
 }  // namespace
 
 // Cut planes of one axis from the histogram of the particles' base cells: slabs of about equal count, interior cuts multiples
@@ -1561,6 +1726,17 @@ int dist_rebalance(fluid_sim* s)
     DistState* nd = t->ds;
     nd->rb_every = d->rb_every; nd->rb_ratio = d->rb_ratio; nd->n_rebalanced = d->n_rebalanced + 1; nd->n_routed = d->n_routed;
     nd->solid_global.swap(d->solid_global);
+    // sources and sinks: the slots (their buffers are box-sized, global: nothing in them belongs to the old window), the ids and
+    // the four counters; n_steps, the t of the sources, goes with output_move
+    for (int i = 0; i < FLUID_MAX_SOURCES; ++i) std::swap(nd->src[i], d->src[i]);
+    for (int i = 0; i < FLUID_MAX_SINKS; ++i) { nd->sink[i] = d->sink[i]; nd->sink_on[i] = d->sink_on[i]; }
+    nd->max_id = std::max(nd->max_id, d->max_id);
+    nd->next_id = d->next_id;
+    std::swap(nd->src_d, d->src_d);
+    std::swap(nd->src_h, d->src_h);
+    std::swap(t->src_sums, s->src_sums);
+    t->src_emit_last = s->src_emit_last, t->src_rm_last = s->src_rm_last;
+    t->src_emit_total = s->src_emit_total, t->src_rm_total = s->src_rm_total;
     t->dt = s->dt;
     t->step_counter = s->step_counter;
     t->stats = s->stats;
@@ -1581,7 +1757,16 @@ int fl::dist_step(fluid_sim* s, fluid_step_stats_t* stats)
     int rc = s->ds->repl ? dist_step_replicated(s, stats) : dist_step_decomposed(s, stats);
     if (rc) return rc;
     DistState* d = s->ds;
-    const bool rb_due = d->rb_every > 0 && d->comm.size > 1 && s->step_counter % d->rb_every == 0;
+    // fluid_dist_set_source / fluid_dist_set_sink: after FLIPadvect, before the snapshot and the re-balancing (which counts and
+    // routes the new particles like any others)
+    bool changed = false;
+    if ((rc = dist_sources_apply(s, &changed))) return rc;
+    if (changed) {
+        s->stats.paths |= FLUID_PATH_SOURCES;
+        if (stats) stats->paths |= FLUID_PATH_SOURCES;
+    }
+    s->vel_ok = true;   // u, v, w: this step's velocities after the update (fluid_dist_add_particles with vel == NULL)
+    const bool rb_due =d->rb_every > 0 && d->comm.size > 1 && s->step_counter % d->rb_every == 0;
     // fluid_dist_output_every: this step's grid is captured from THIS window, before the planes move.  The snapshot is rank-local
     // (no transport call); it may allocate, so when the re-balancing's collectives follow, its result is agreed first.
     rc = output_auto(s);
@@ -1598,7 +1783,9 @@ int fl::dist_step(fluid_sim* s, fluid_step_stats_t* stats)
 
 void fl::dist_keep_solid(fluid_sim* s, const uint8_t* solid_global)
 {
-    if (s->ds) s->ds->solid_global.assign(solid_global, solid_global + (size_t)s->g.N * s->g.N * s->g.N);
+    if (!s->ds) return;
+    s->ds->solid_global.assign(solid_global, solid_global + (size_t)s->g.N * s->g.N * s->g.N);
+    for (auto& q : s->ds->src) q.mask_ok = false;   // the sources' copies of the mask are made anew when next due
 }
 
 void fl::dist_destroy(fluid_sim* s)
@@ -1607,6 +1794,9 @@ void fl::dist_destroy(fluid_sim* s)
     if (!d) return;
     void* ptrs[] = {d->hs, d->hr, d->mig_s, d->mig_r, d->d_cnt, d->repl_buf, d->rows, d->row_starts, d->cnt_pcg, d->gstage[0], d->gstage[1], d->gpq, d->gcg, d->tl_int, d->tl_bnd, d->tl_cls, d->rb_buf};
     for (void* p : ptrs) if (p) hipFree(p);
+    for (auto& q : d->src) if (q.buf) hipFree(q.buf);
+    if (d->src_d) hipFree(d->src_d);
+    if (d->src_h) hipHostFree(d->src_h);
     if (d->st2) { hipStreamSynchronize(d->st2); hipStreamDestroy(d->st2); }
     if (d->ev_pack) hipEventDestroy(d->ev_pack);
     if (d->ev_halo) hipEventDestroy(d->ev_halo);
@@ -1814,6 +2004,10 @@ int fluid_upload_particles_ids(fluid_sim_t* s, int64_t n, const double* pos, con
     s->sorted = s->have_p2g = s->have_flags = false;
     s->have_guess = false;  // a new particle set: the first solve starts from 0
     s->sort_hint = false;
+    if (d) {   // the sources number their points from 1 + the largest id any rank was ever handed
+        s->vel_ok = false;
+        for (int64_t i = 0; i < n; ++i) d->max_id = std::max(d->max_id, (long long)ids[i]);
+    }
     return FLUID_OK;
 }
 
@@ -1881,6 +2075,147 @@ int fluid_dist_get_cuts(fluid_sim_t* s, int32_t* cuts_x, int32_t* cuts_y, int32_
     for (int a = 0; a < 3; ++a)
         if (c[a]) for (size_t i = 0; i < s->ds->cuts[a].size(); ++i) c[a][i] = s->ds->cuts[a][i];
     if (n_rebalanced) *n_rebalanced = s->ds->n_rebalanced;
+    return FLUID_OK;
+}
+
+// ---- particle sources and sinks of a decomposed run ----
+#define DSRC_GUARD(s)                                                    \
+    if (!(s)) return fail(FLUID_ERR_ARG, "null handle");                 \
+    if (!(s)->ds)                                                        \
+    return fail(FLUID_ERR_STATE, "not a decomposed handle: a fluid_create handle uses the one-GPU entry points (fluid_set_source, fluid_set_sink, fluid_get_source_stats, fluid_add_particles)")
+
+static bool dsrc_box(const fluid_sim* s, const int32_t lo[3], const int32_t hi[3], Box& b)
+{
+    const int N = s->g.N;
+    for (int a = 0; a < 3; ++a)
+        if (lo[a] < 0 || hi[a] > N - 1 || lo[a] > hi[a]) return false;
+    b = Box{lo[0], lo[1], lo[2], hi[0], hi[1], hi[2]};
+    return true;
+}
+// what the first slot needs: the scans' block sums (any count up to INT32_MAX) and the two agreed numbers
+static int dsrc_scratch(fluid_sim* s)
+{
+    DistState* d = s->ds;
+    if (!s->src_sums) HIPCHK(hipMalloc((void**)&s->src_sums, ((size_t)INT32_MAX / 2048 + 16) * sizeof(int)));
+    if (!d->src_d) HIPCHK(hipMalloc((void**)&d->src_d, 8 * sizeof(long long)));
+    if (!d->src_h) HIPCHK(hipHostMalloc((void**)&d->src_h, 8 * sizeof(long long)));
+    return FLUID_OK;
+}
+
+int fluid_dist_set_source(fluid_sim_t* s, int32_t slot, const fluid_source_t* src)
+{
+    DSRC_GUARD(s);
+    if (slot < 0 || slot >= FLUID_MAX_SOURCES) return fail(FLUID_ERR_ARG, "source slot out of range");
+    auto& q = s->ds->src[slot];
+    HIPCHK(hipSetDevice(s->prm.device));
+    if (!src) {
+        HIPCHK(hipStreamSynchronize(s->st));
+        if (q.buf) hipFree(q.buf);
+        q = DistState::SrcSlot{};
+        return FLUID_OK;
+    }
+    Box b;
+    if (!dsrc_box(s, src->lo, src->hi, b)) return fail(FLUID_ERR_ARG, "source box empty or off the grid");
+    if (src->per_cell < 1 || src->per_cell > 64) return fail(FLUID_ERR_ARG, "per_cell must be in 1..64");
+    if (src->mode != FLUID_SOURCE_ADD && src->mode != FLUID_SOURCE_FILL) return fail(FLUID_ERR_ARG, "bad source mode");
+    if (src->vel_mode != FLUID_SOURCE_VEL_FIXED && src->vel_mode != FLUID_SOURCE_VEL_GRID) return fail(FLUID_ERR_ARG, "bad source vel_mode");
+    if (src->every < 1) return fail(FLUID_ERR_ARG, "every must be >= 1");
+    if ((double)b.cells() * src->per_cell > (double)INT32_MAX) return fail(FLUID_ERR_ARG, "source box x per_cell exceeds INT32_MAX points");
+    int rc = dsrc_scratch(s);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(s->st));
+    if (q.buf) hipFree(q.buf);
+    q = DistState::SrcSlot{};
+    const size_t B = (size_t)b.cells();
+    HIPCHK(hipMalloc((void**)&q.buf, 5 * B * sizeof(int) + B + 16));
+    q.src = *src;
+    q.box = b;
+    if ((rc = src_mask_upload(s, q))) {
+        hipFree(q.buf);
+        q = DistState::SrcSlot{};
+        return rc;
+    }
+    q.on = true;
+    return FLUID_OK;
+}
+
+int fluid_dist_set_sink(fluid_sim_t* s, int32_t slot, const int32_t lo[3], const int32_t hi[3])
+{
+    DSRC_GUARD(s);
+    if (slot < 0 || slot >= FLUID_MAX_SINKS) return fail(FLUID_ERR_ARG, "sink slot out of range");
+    if (!lo) {
+        s->ds->sink_on[slot] = false;
+        return FLUID_OK;
+    }
+    Box b;
+    if (!hi || !dsrc_box(s, lo, hi, b)) return fail(FLUID_ERR_ARG, "sink box empty or off the grid");
+    HIPCHK(hipSetDevice(s->prm.device));
+    int rc = dsrc_scratch(s);
+    if (rc) return rc;
+    s->ds->sink[slot] = b;
+    s->ds->sink_on[slot] = true;
+    return FLUID_OK;
+}
+
+int fluid_dist_get_source_stats(fluid_sim_t* s, int64_t* emitted_last, int64_t* removed_last, int64_t* emitted_total, int64_t* removed_total)
+{
+    DSRC_GUARD(s);
+    if (emitted_last) *emitted_last = s->src_emit_last;
+    if (removed_last) *removed_last = s->src_rm_last;
+    if (emitted_total) *emitted_total = s->src_emit_total;
+    if (removed_total) *removed_total = s->src_rm_total;
+    return FLUID_OK;
+}
+
+int fluid_dist_add_particles(fluid_sim_t* s, int64_t n, const double* pos, const double* vel, const uint32_t* ids)
+{
+    DSRC_GUARD(s);
+    DistState* d = s->ds;
+    if (n < 0 || (n > 0 && (!pos || !ids))) return fail(FLUID_ERR_ARG, "bad particle arguments");
+    if (!vel && !s->vel_ok) return fail(FLUID_ERR_STATE, "add_particles with vel == NULL needs the grid velocities of a completed step on this window");
+    HIPCHK(hipSetDevice(s->prm.device));
+    const Grid g = s->g;
+    auto append = [&]() -> int {
+        // host check: every base cell in the owned block (the outer sides of an edge block reach to infinity, as for an upload)
+        for (int64_t i = 0; i < n; ++i) {
+            if (ids[i] == PID_DEAD) return fail(FLUID_ERR_ARG, "id 0xFFFFFFFF marks a dead particle");
+            for (int a = 0; a < 3; ++a) {
+                const double c = std::round(pos[3 * i + a]) - (double)g.lo;
+                if (!((c >= d->ob.lo[a] || !d->ob.has_lo[a]) && (c < d->ob.hi[a] || !d->ob.has_hi[a])))
+                    return fail(FLUID_ERR_ARG, "a particle's base cell lies outside this rank's block: nothing was appended");
+            }
+        }
+        if (s->np + (long)n > (long)INT32_MAX) return fail(FLUID_ERR_STATE, "more than INT32_MAX particles");
+        if (n == 0) return FLUID_OK;
+        int rc = grow_particles(s, s->p_off + s->np + (long)n);
+        if (rc) return rc;
+        uint32_t* dids = (uint32_t*)s->order;   // staging: order[] is free between steps
+        HIPCHK(hipMemcpyAsync(s->stage_pos, pos, 3 * n * sizeof(double), hipMemcpyHostToDevice, s->st));
+        if (vel) HIPCHK(hipMemcpyAsync(s->stage_vel, vel, 3 * n * sizeof(double), hipMemcpyHostToDevice, s->st));
+        HIPCHK(hipMemcpyAsync(dids, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, s->st));
+        launch_unpack_ids(s->st, (long)n, s->stage_pos, vel ? s->stage_vel : nullptr, dids, s->pa.shifted(s->p_off + s->np));
+        HIPCHK(hipGetLastError());
+        return FLUID_OK;
+    };
+    int rc = append();
+    const Particles p = s->pa.shifted(s->p_off + s->np);
+    if (!vel && d->repl) {
+        if (rc) return rc;
+        launch_interp_from_grid(s->st, g, (long)n, p, s->u, s->v, s->w);
+    } else if (!vel) {   // collective (the centres' halo): a rank that failed above tells the others before they wait for it
+        if ((rc = dist_agree(s, rc))) return rc;
+        const IBox all{{0, 0, 0}, {g.N, g.N, g.N}};
+        if ((rc = centre_halo(s, all))) return rc;
+        launch_interp_from_centres(s->st, g, (long)n, p, s->dcx, s->dcy, s->dcz);
+    } else if (rc) {
+        return rc;
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s->st));
+    s->np += (long)n;
+    for (int64_t i = 0; i < n; ++i) d->max_id = std::max(d->max_id, (long long)ids[i]);
+    s->sorted = s->have_p2g = s->have_flags = false;
+    s->sort_hint = false;   // (the warm start, have_guess, stays: the same scene a little fuller)
     return FLUID_OK;
 }
 

@@ -17,7 +17,7 @@ static uint64_t sm64_host(uint64_t x)
 
 #define SRC_GUARD(s)                                                                                                     \
     if (!(s)) return fail(FLUID_ERR_ARG, "null handle");                                                                 \
-    if ((s)->dist) return fail(FLUID_ERR_STATE, "particle sources and sinks are single-GPU only: a decomposed run has no global ids for new particles")
+    if ((s)->dist) return fail(FLUID_ERR_STATE, "these entry points are single-GPU only (they renumber the pids): a decomposed handle uses fluid_dist_set_source, fluid_dist_set_sink, fluid_dist_get_source_stats, fluid_dist_add_particles")
 
 // a box of the index space [0, N-1]^3, not empty
 static bool box_from(const fluid_sim* s, const int32_t lo[3], const int32_t hi[3], Box& b)

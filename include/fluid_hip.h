@@ -204,8 +204,8 @@ int fluid_resample(fluid_sim_t* s, int32_t per_cell, int64_t* n_parked);
  * pos.interpFromGrid(vels, 60, containerGrid) after it, commented out after FLIPadvect (fluid.cc:1495-1497; also under
  * `if (i%5 == 0)` at :1379-1382).  fluid_add_particles is that call; persistent sources and sinks are its general form, applied
  * by fluid_step itself at the end of every step, after FLIPadvect: first every sink, then every source in slot order.
- * A decomposed handle (fluid_create_dist) returns FLUID_ERR_STATE from every entry point of this block: global particle ids
- * across ranks are not provided for appended particles.
+ * A decomposed handle (fluid_create_dist) returns FLUID_ERR_STATE from every entry point of this block: it uses the
+ * fluid_dist_* entry points of the next block, which keep global particle ids across the ranks.
  *
  * Where a source puts its points (a fixed function of seed, t, cell and k; SplitMix64):
  *   sm(x):  z = x + 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB;
@@ -246,6 +246,49 @@ int fluid_set_sink(fluid_sim_t* s, int32_t slot, const int32_t lo[3], const int3
 /* Particles added by the sources / removed by the sinks in the last step, and in all steps since the handle was created
  * (fluid_add_particles is not counted).  Any pointer may be NULL. */
 int fluid_get_source_stats(fluid_sim_t* s, int64_t* emitted_last, int64_t* removed_last, int64_t* emitted_total, int64_t* removed_total);
+
+/* ---- particle sources and sinks of a decomposed run (handles of fluid_create_dist, both pressure modes) ------------------
+ * The same slots, limits, modes, argument checks and point formula as above, for every rank of a block-decomposed run.  A
+ * fluid_create handle gets FLUID_ERR_STATE from these four (it uses the entry points above), as a decomposed handle does there.
+ * Boxes are GLOBAL index boxes, `linear` is the global linear index (x*N + y)*N + z, solid is the global mask.  The set calls
+ * are collective in the sense of fluid_dist_set_rebalance: every rank of the run sets the same slots before the same step.
+ *
+ * When.     Inside fluid_step, after FLIPadvect and before the automatic output snapshot and the re-balancing (new particles
+ *           are counted and routed like any others), with t = the handle's count of completed steps, which re-balancing keeps.
+ *           First every sink, then the sources in slot order.
+ * Sinks.    A live particle whose base cell round(p) lies in a sink box is removed on whichever rank holds it at the end of
+ *           the step (after advect that may be one cell outside its holder's block).  It is marked dead where it is; nothing is
+ *           compacted.  THE SURVIVORS KEEP THEIR IDS: ids are never renumbered on a decomposed run.  This is the one deliberate
+ *           difference from the one-GPU step, whose sinks renumber the pids 0 .. np'-1.
+ * Sources.  Eligible cells, tries per cell and kept points are those of the one-GPU definition.  FILL counts the live
+ *           particles per cell over ALL ranks after the sinks (one SUM all-reduce of the box-sized histogram per FILL source
+ *           that is due).  A kept point is created on the rank that owns its cell, with id next_id + j, j = its rank in ascending
+ *           (linear, k) order over the whole box; then next_id += m.  Every rank plans and scans the whole box (it keeps a copy
+ *           of the global solid mask over the box for that), so the ids need no exchange.  next_id starts as 1 + the largest id
+ *           any rank was ever handed (fluid_upload_particles_ids, fluid_dist_add_particles; tracked per handle, agreed by one
+ *           MAX all-reduce in each step where a source is due) and only grows.  If next_id + m would reach 0xFFFFFFFF (the mark of
+ *           a dead particle) every rank returns FLUID_ERR_STATE before that source writes anything.
+ *           So: the particles of all ranks sorted by id are the sequence fluid_download_particles gives on one GPU with the
+ *           same slots, as long as the uploaded ids were 0 .. np-1 (survivors in pid order, then the new points by slot, linear, k).
+ * Velocity. FLUID_SOURCE_VEL_GRID and fluid_dist_add_particles(vel == NULL) give interpFromGrid's velocity, bit for bit the
+ *           one-GPU value: the ranks exchange a 1-wide halo of the cell-centre averages (decomposed mode), so the latter call is
+ *           collective there — every rank calls it, n = 0 is fine.  Velocities outside the step's box are zero, as on one GPU.
+ * Cost.     A step with no sink set and no source due adds no launch, no transport call and no wait.  Otherwise: one SUM
+ *           all-reduce of the removed count (sinks set), one MAX all-reduce of next_id (a source due), per due FILL source the
+ *           histogram's all-reduce, per emitting source one agreement (below) and, with FLUID_SOURCE_VEL_GRID in decomposed mode,
+ *           one halo exchange.
+ * Failure.  Growing the particle arrays for emitted points can fail on one rank alone: every rank then leaves the step, that one
+ *           with its own error, the others with FLUID_ERR_PEER (agreed before the next transport call).
+ * Re-balancing carries the slots, the counters and next_id into the new windows. */
+int fluid_dist_set_source(fluid_sim_t* s, int32_t slot, const fluid_source_t* src);   /* NULL clears */
+int fluid_dist_set_sink(fluid_sim_t* s, int32_t slot, const int32_t lo[3], const int32_t hi[3]);   /* lo == NULL clears */
+/* Global numbers, the same on every rank; FLUID_PATH_SOURCES is set on every rank when the global particle set changed. */
+int fluid_dist_get_source_stats(fluid_sim_t* s, int64_t* emitted_last, int64_t* removed_last, int64_t* emitted_total, int64_t* removed_total);
+/* Appends the caller's points with the caller's ids (unique ids are the caller's job; 0xFFFFFFFF is not an id).  Every point's
+ * base cell must lie in this rank's block (an edge block reaches to infinity on its outer sides), else FLUID_ERR_ARG and nothing
+ * is appended (checked on the host).  vel == NULL needs a step completed on this window (FLUID_ERR_STATE otherwise, also right
+ * after a step that moved the cut planes). */
+int fluid_dist_add_particles(fluid_sim_t* s, int64_t n, const double* pos, const double* vel, const uint32_t* ids);
 
 /* The closed pockets of the last step's pressure system that were solved apart from the global solve (FLUID_PATH_DROPLETS;
  * kernels_droplets.hip): n_components of them; cells (may be NULL) receives 64 entries per component — the window-array cell
