@@ -52,6 +52,17 @@ class LeafGridC(C.Structure):
     _fields_ = [("n", C.c_int32), ("n_leaves", C.c_int32), ("origin", C.c_void_p), ("values", C.c_void_p)]
 
 
+class SdfParams(C.Structure):
+    """fluid_sdf_params_t: sphere radius and half width of the band, in voxels (include/fluid_hip.h, "liquid surface")."""
+    _fields_ = [("radius", C.c_double), ("half_width", C.c_double)]
+
+
+class SdfGridC(C.Structure):
+    """fluid_sdf_grid_t: the narrow-band level set of the particles as the list of its 8^3 leaves."""
+    _fields_ = [("n", C.c_int32), ("n_leaves", C.c_int32), ("background", C.c_float), ("radius", C.c_float),
+                ("half_width", C.c_float), ("origin", C.c_void_p), ("values", C.c_void_p), ("active", C.c_void_p)]
+
+
 class MpmParams(C.Structure):
     """mpm_params_t (include/mpm_hip.h); defaults = the literals of mpm.cc."""
     _fields_ = [("B", C.c_int32), ("W", C.c_int32), ("device", C.c_int32), ("cg_max_iters", C.c_int32),
@@ -147,6 +158,11 @@ SYMBOLS = [
     ("fluid_dist_output_stats", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("fluid_dist_output_every", C.c_int, [_P, C.c_int32]),
     ("fluid_leaf_grids_merge", C.c_int64, [C.POINTER(LeafGridC), C.c_int32, C.c_int64, _P, _P]),
+    ("fluid_sdf_snapshot", C.c_int, [_P, C.POINTER(SdfParams)]),
+    ("fluid_sdf_wait", C.c_int, [_P, C.POINTER(SdfGridC)]),
+    ("fluid_sdf_stats", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("fluid_sdf_to_dense", C.c_int, [C.POINTER(SdfGridC), _P, _P]),
+    ("fluid_write_vdb_sdf", C.c_int, [C.c_char_p, C.POINTER(SdfGridC), C.c_int32]),
     # the snow-MPM step (include/mpm_hip.h)
     ("mpm_default_params", C.c_int, [C.POINTER(MpmParams)]),
     ("mpm_create", C.c_int, [C.POINTER(MpmParams), C.POINTER(_P)]),

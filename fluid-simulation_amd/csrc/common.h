@@ -277,6 +277,24 @@ struct OutWin {
 };
 void launch_out_mark_win(hipStream_t st, const float* f, const OutWin& w, int* flags);
 void launch_out_pack_win(hipStream_t st, const float* f, const OutWin& w, const int* flags, const int* slot, float* values, int* origin);
+// narrow-band level set of the particles (kernels_sdf.hip); coordinates are index-space coordinates, not array indices
+struct SdfGeom {
+    int lo, hi;                          // the grid
+    int bx0, by0, bz0, bnx, bny, bnz;    // bounding box of the counted particles' base cells: first cell and cells per axis
+    int L0;                              // origin of the grid's first leaf, lo & ~7
+    int l0[3], nl[3];                    // leaves of the box dilated by 4 cells and clipped to the grid: first (counted from L0) and how many
+    float R, w, dxf, bg, max2, min2;
+    __host__ __device__ inline long leaves() const { return (long)nl[0] * nl[1] * nl[2]; }
+    __host__ __device__ inline long cells() const { return (long)bnx * bny * bnz; }
+};
+void launch_sdf_bbox(hipStream_t st, long n, Particles p, int lo, int hi, int* box);   // box[6]: min, max of the counted base cells
+void launch_sdf_count(hipStream_t st, long n, Particles p, const SdfGeom& g, int* cnt, int* place);
+void launch_sdf_scatter(hipStream_t st, long n, Particles p, const SdfGeom& g, const int* start, const int* place, double* sx, double* sy,
+                        double* sz);
+void launch_sdf_search(hipStream_t st, const SdfGeom& g, const int* start, const double* sx, const double* sy, const double* sz, float* tv,
+                       uint64_t* tm, int* flags, unsigned* visits);   // visits: nullptr, or cells looked at per leaf of the range
+void launch_sdf_pack(hipStream_t st, const SdfGeom& g, const int* flags, const int* slot, const float* tv, const uint64_t* tm, float* values,
+                     uint64_t* active, int* origin);
 void launch_exclusive_scan(hipStream_t st, const int* in, int* out, long n, int* block_sums, int* total);
 void launch_sort_tail(hipStream_t st, const int* cell_count, int* cell_start, long c1, long ncell);
 void launch_index_scan(hipStream_t st, Grid g, const uint8_t* flags, int* indices, int* block_sums, int* total);

@@ -11,6 +11,10 @@
 // Output by default: after step i fluid_output_snapshot lists the grid's non-zero 8^3 leaves on the device and starts their copy
 // to pinned memory; the main thread goes on with step i + 1, waits for the copy (long over by then) and hands the leaf list to
 // a writer thread that zips the listed leaves once and appends the grid to both files while step i + 2 runs.
+//   FLUID_OUT_SURFACE=R,W (unset: off) — additionally simulation/surface<i>.vdb per step: the liquid surface as the narrow-band level
+// set of spheres of radius R voxels around the particles, band half width W voxels (fluid_sdf_snapshot after the density snapshot,
+// fluid_sdf_wait beside fluid_output_wait, fluid_write_vdb_sdf on the writer thread).  One GPU and the leaf output only: refused
+// with FLUID_BLOCKS, with FLUID_OUT_DENSE=1, with an empty FLUID_OUT and with FLUID_STEPS=0.  Stdout and every other file are what they are without it.
 // Initial particles: with the defaults (N = 121, 10 per voxel) exactly the reference's — fill(CoordBBox(-20, 20)) scattered by
 // UniformPointScatter with std::mt19937(FLUID_SEED) (fluid_scene_uniform_scatter: 689210 points); any other N / PPC takes the
 // scaled synthetic cube (fluid_scene_water_cube_drop).
@@ -66,6 +70,8 @@ struct LeafWriter {
     std::mutex m;
     std::condition_variable cv;
     fluid_leaf_grid_t job{};
+    fluid_sdf_grid_t sjob{};  // FLUID_OUT_SURFACE: the same step's surface
+    bool has_sjob = false;
     int job_step = -1;        // step whose grid is waiting (-1: none)
     int done = 0;             // grids written
     bool quit = false;
@@ -81,6 +87,8 @@ struct LeafWriter {
             cv.wait(lk, [&] { return job_step >= 0 || quit; });
             if (job_step < 0) return;
             const fluid_leaf_grid_t g = job;
+            const fluid_sdf_grid_t sg = sjob;
+            const bool has_sg = has_sjob;
             const int i = job_step;
             lk.unlock();
             std::string bad;
@@ -91,6 +99,10 @@ struct LeafWriter {
             else {
                 if (fluid_vdb_append_leaves(ws, 2, &g) != FLUID_OK) bad = fn + " / " + fin;
                 if (fluid_vdb_close(ws[0]) != FLUID_OK && bad.empty()) bad = fn;
+            }
+            if (has_sg && bad.empty()) {
+                const std::string fs = outdir + "/surface" + std::to_string(i) + ".vdb";
+                if (fluid_write_vdb_sdf(fs.c_str(), &sg, FLUID_VDB_ZIP_ACTIVE_MASK) != FLUID_OK) bad = fs;
             }
             if (raw_f32 && bad.empty()) {
                 const size_t ncell = (size_t)g.n * g.n * g.n;
@@ -112,11 +124,13 @@ struct LeafWriter {
         cv.wait(lk, [&] { return done >= n; });
         return error.empty();
     }
-    void submit(int step, const fluid_leaf_grid_t& g)
+    void submit(int step, const fluid_leaf_grid_t& g, const fluid_sdf_grid_t* surface = nullptr)
     {
         std::unique_lock<std::mutex> lk(m);
         cv.wait(lk, [&] { return job_step < 0; });
         job = g;
+        has_sjob = surface != nullptr;
+        if (surface) sjob = *surface;
         job_step = step;
         cv.notify_all();
     }
@@ -345,6 +359,24 @@ int main(int, char**)
     const long src_every = env_long("FLUID_SOURCE_EVERY", 0);
     const bool out_dense = env_long("FLUID_OUT_DENSE", 0) != 0;
     const char* blocks = getenv("FLUID_BLOCKS");
+    const char* surf = getenv("FLUID_OUT_SURFACE");
+    const bool surface = surf && *surf;
+    fluid_sdf_params_t sp{};
+    if (surface) {
+        char tail = 0;
+        if (sscanf(surf, "%lf,%lf%c", &sp.radius, &sp.half_width, &tail) != 2) {
+            std::cerr << "FLUID_OUT_SURFACE must be R,W (sphere radius and band half width in voxels), e.g. 1.5,2.5" << std::endl;
+            return 1;
+        }
+        if ((blocks && *blocks) || out_dense) {
+            std::cerr << "FLUID_OUT_SURFACE cannot be combined with " << (out_dense ? "FLUID_OUT_DENSE=1" : "FLUID_BLOCKS (the surface needs one GPU)") << std::endl;
+            return 1;
+        }
+        if (outdir.empty() || steps <= 0) {
+            std::cerr << "FLUID_OUT_SURFACE needs an output directory and at least one step (FLUID_OUT is empty or FLUID_STEPS is 0)" << std::endl;
+            return 1;
+        }
+    }
     BlockCfg bc;
     if (blocks && *blocks) {
         char tail = 0;
@@ -421,7 +453,12 @@ int main(int, char**)
             std::cerr << "fluid_output_wait: " << fluid_last_error() << std::endl;
             return false;
         }
-        lw.submit(step, g);
+        fluid_sdf_grid_t sg;
+        if (surface && fluid_sdf_wait(sim, &sg) != FLUID_OK) {
+            std::cerr << "fluid_sdf_wait: " << fluid_last_error() << std::endl;
+            return false;
+        }
+        lw.submit(step, g, surface ? &sg : nullptr);
         return true;
     };
 
@@ -459,6 +496,11 @@ int main(int, char**)
             if (!lw.wait_done(i - 1)) { std::cerr << "cannot write " << lw.error << std::endl; lw.stop(); return 1; }
             if (fluid_output_snapshot(sim) != FLUID_OK) {
                 std::cerr << "fluid_output_snapshot: " << fluid_last_error() << std::endl;
+                lw.stop();
+                return 1;
+            }
+            if (surface && fluid_sdf_snapshot(sim, &sp) != FLUID_OK) {
+                std::cerr << "fluid_sdf_snapshot: " << fluid_last_error() << std::endl;
                 lw.stop();
                 return 1;
             }

@@ -1,0 +1,257 @@
+// Level-set snapshots of the particles (include/fluid_hip.h, "liquid surface"): the narrow-band signed distance to the spheres
+// around the particles leaves the device as the list of OpenVDB's 8^3 leaves that hold anything but inactive +bg.  Kernels in
+// kernels_sdf.hip.
+//
+// fluid_sdf_snapshot, all on the handle's stream: bounding box of the counted particles' base cells (24 bytes read back: it sizes
+// everything that follows) -> count per cell of the box, exclusive scan, scatter of the positions into cell order -> search over
+// the leaves of the box dilated by 4 cells (values, masks and a listed flag per leaf of that range) -> exclusive scan of the
+// flags (count read back: 4 bytes) -> pack into the slot's device staging; the records then travel to pinned host memory on a
+// second stream behind an event.  Two slots ([n x 2048 B of values | n x 64 B of masks | n x 12 B of origins], one copy each): a
+// slot is written by snapshot q, q + 2, ..., so what fluid_sdf_wait handed out stays valid until the second following snapshot.
+// The particle arrays are only read; key, slot, cell_count, cell_start, the second particle buffer and every field stay as they
+// are, and `binned` keeps holding: the next step's sort starts from what FLIPadvect left, as if no snapshot had been taken.
+#include "sim.h"
+
+using namespace fl;
+#define fail fluid_fail
+
+constexpr size_t SDF_REC = FLUID_SDF_LEAF_BYTES;
+struct SdfSlot {
+    char* dev = nullptr;       // device staging
+    char* host = nullptr;      // pinned
+    size_t cap = 0;            // leaves either buffer holds
+    int n_leaves = 0;
+    float bg = 0, R = 0, w = 0;
+    hipEvent_t done = nullptr;   // recorded on the copy stream behind the slot's copy
+};
+struct SdfState {
+    // scratch: cells of the particles' box, particles, leaves of the dilated box
+    long cell_cap = 0, part_cap = 0, leaf_cap = 0;
+    int *cnt = nullptr, *start = nullptr, *cell_sums = nullptr;
+    int* place = nullptr;
+    double* spos = nullptr;    // sorted x | y | z, part_cap each
+    float* tv = nullptr;
+    uint64_t* tm = nullptr;
+    int *flags = nullptr, *slot = nullptr, *leaf_sums = nullptr;
+    unsigned* visits = nullptr;   // FLUID_SDF_VISITS=1 only
+    bool count_visits = false;
+    int *d_small = nullptr, *h_small = nullptr;   // box[6], cell total, listed count
+    hipStream_t copy = nullptr;
+    hipEvent_t packed = nullptr;
+    SdfSlot s[2];
+    long n_snap = 0, n_wait = 0;   // snapshots taken / waited for: snapshot q lives in slot q & 1
+    long last_leaves = 0, last_bytes = 0;
+};
+
+#define SDF_GUARD(s)                                                     \
+    if (!(s)) return fail(FLUID_ERR_ARG, "null handle");                 \
+    if ((s)->dist) return fail(FLUID_ERR_STATE, "level-set snapshots are single-GPU only: a decomposed handle holds a block of the particles")
+
+static int sdf_init(fluid_sim* s)
+{
+    if (s->sdf) return FLUID_OK;
+    SdfState* o = new SdfState();
+    s->sdf = o;   // from here on sdf_free releases whatever the lines below got
+    if (const char* e = getenv("FLUID_SDF_VISITS")) o->count_visits = atoi(e) != 0;   // developer knob (tools/sdf_cost.py)
+    HIPCHK(hipMalloc((void**)&o->d_small, 8 * sizeof(int)));
+    HIPCHK(hipHostMalloc((void**)&o->h_small, 8 * sizeof(int)));
+    HIPCHK(hipStreamCreateWithFlags(&o->copy, hipStreamNonBlocking));
+    HIPCHK(hipEventCreateWithFlags(&o->packed, hipEventDisableTiming));
+    for (auto& q : o->s) HIPCHK(hipEventCreateWithFlags(&q.done, hipEventDisableTiming));
+    return FLUID_OK;
+}
+
+void fl::sdf_free(fluid_sim* s)
+{
+    SdfState* o = s->sdf;
+    if (!o) return;
+    if (o->copy) hipStreamSynchronize(o->copy);
+    for (auto& q : o->s) {
+        if (q.dev) hipFree(q.dev);
+        if (q.host) hipHostFree(q.host);
+        if (q.done) hipEventDestroy(q.done);
+    }
+    for (void* p : {(void*)o->cnt, (void*)o->start, (void*)o->cell_sums, (void*)o->place, (void*)o->spos, (void*)o->tv, (void*)o->tm, (void*)o->flags,
+                    (void*)o->slot, (void*)o->leaf_sums, (void*)o->visits, (void*)o->d_small})
+        if (p) hipFree(p);
+    if (o->h_small) hipHostFree(o->h_small);
+    if (o->packed) hipEventDestroy(o->packed);
+    if (o->copy) hipStreamDestroy(o->copy);
+    delete o;
+    s->sdf = nullptr;
+}
+
+// (the handle's stream is idle here: every caller has just waited for a read-back on it)
+template <typename T>
+static hipError_t regrow(T*& p, size_t n)
+{
+    if (p) hipFree(p);
+    p = nullptr;
+    return hipMalloc((void**)&p, n * sizeof(T));
+}
+
+static int sdf_scratch(SdfState* o, long cells, long parts, long leaves)
+{
+    if (cells > o->cell_cap) {
+        o->cell_cap = 0;
+        const long cap = cells + cells / 4 + 64;
+        HIPCHK(regrow(o->cnt, (size_t)cap + 8));
+        HIPCHK(regrow(o->start, (size_t)cap + 8));
+        HIPCHK(regrow(o->cell_sums, (size_t)cap / 2048 + 16));
+        o->cell_cap = cap;
+    }
+    if (parts > o->part_cap) {
+        o->part_cap = 0;
+        const long cap = parts + parts / 8 + 64;
+        HIPCHK(regrow(o->place, (size_t)cap));
+        HIPCHK(regrow(o->spos, (size_t)3 * cap));
+        o->part_cap = cap;
+    }
+    if (leaves > o->leaf_cap) {
+        o->leaf_cap = 0;
+        const long cap = leaves + leaves / 4 + 64;
+        HIPCHK(regrow(o->tv, (size_t)cap * 512));
+        HIPCHK(regrow(o->tm, (size_t)cap * 8));
+        HIPCHK(regrow(o->flags, (size_t)cap));
+        HIPCHK(regrow(o->slot, (size_t)cap));
+        HIPCHK(regrow(o->leaf_sums, (size_t)cap / 2048 + 16));
+        if (o->count_visits) HIPCHK(regrow(o->visits, (size_t)cap));
+        o->leaf_cap = cap;
+    }
+    return FLUID_OK;
+}
+
+// room for n leaves in the slot (its earlier contents were handed out two snapshots ago: no longer promised)
+static int sdf_grow(SdfSlot& q, size_t n)
+{
+    if (n <= q.cap) return FLUID_OK;
+    if (q.dev) hipFree(q.dev);
+    if (q.host) hipHostFree(q.host);
+    q.dev = q.host = nullptr;
+    q.cap = 0;
+    const size_t cap = n + n / 2 + 64;
+    HIPCHK(hipMalloc((void**)&q.dev, cap * SDF_REC));
+    HIPCHK(hipHostMalloc((void**)&q.host, cap * SDF_REC));
+    q.cap = cap;
+    return FLUID_OK;
+}
+
+extern "C" {
+
+int fluid_sdf_snapshot(fluid_sim_t* s, const fluid_sdf_params_t* p)
+{
+    SDF_GUARD(s);
+    if (!p) return fail(FLUID_ERR_ARG, "null argument");
+    const float R = (float)p->radius, w = (float)p->half_width;
+    const float mx = R + w;
+    if (!(p->radius > 0) || !(R > 0.0f) || !(w >= 1.0f) || !(mx <= 4.0f))
+        return fail(FLUID_ERR_ARG, "level set: radius > 0, half_width >= 1 and radius + half_width <= 4 (voxels) are required");
+    HIPCHK(hipSetDevice(s->prm.device));
+    int rc = sdf_init(s);
+    if (rc) return rc;
+    SdfState* o = s->sdf;
+    if (o->n_snap - o->n_wait >= 2) return fail(FLUID_ERR_STATE, "two level-set snapshots are waiting for fluid_sdf_wait");
+    SdfSlot& q = o->s[o->n_snap & 1];
+    SdfGeom g{};
+    g.lo = s->g.lo, g.hi = s->g.hi, g.L0 = g.lo & ~7;
+    g.R = R, g.w = w, g.dxf = (float)s->prm.dx;
+    g.bg = g.dxf * w;
+    g.max2 = mx * mx;
+    const float mn = std::fmax(0.0f, R - w);
+    g.min2 = mn * mn;
+    const Particles live = s->pa.shifted(s->p_off);
+    int n = 0;
+    int* box = o->h_small;
+    if (s->np > 0) {
+        launch_sdf_bbox(s->st, s->np, live, g.lo, g.hi, o->d_small);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(o->h_small, o->d_small, 6 * sizeof(int), hipMemcpyDeviceToHost, s->st));
+        HIPCHK(hipStreamSynchronize(s->st));
+    }
+    if (s->np > 0 && box[3] >= box[0]) {
+        for (int a = 0; a < 3; ++a)
+            if (box[a] < g.lo || box[3 + a] > g.hi || box[3 + a] < box[a]) return fail(FLUID_ERR_HIP, "level set: particle box out of range");
+        g.bx0 = box[0], g.by0 = box[1], g.bz0 = box[2];
+        g.bnx = box[3] - box[0] + 1, g.bny = box[4] - box[1] + 1, g.bnz = box[5] - box[2] + 1;
+        for (int a = 0; a < 3; ++a) {
+            const int c0 = std::max(box[a] - 4, g.lo), c1 = std::min(box[3 + a] + 4, g.hi);
+            g.l0[a] = (c0 - g.L0) >> 3;
+            g.nl[a] = ((c1 - g.L0) >> 3) - g.l0[a] + 1;
+        }
+        const long cells = g.cells(), leaves = g.leaves();
+        if (cells + 1 > 0x7fffffffL || leaves > 0x7fffffffL) return fail(FLUID_ERR_ARG, "level set: the particles' box is too large");
+        if ((rc = sdf_scratch(o, cells + 1, s->np, leaves))) return rc;
+        double *sx = o->spos, *sy = o->spos + o->part_cap, *sz = o->spos + 2 * o->part_cap;
+        HIPCHK(hipMemsetAsync(o->cnt, 0, (size_t)(cells + 1) * sizeof(int), s->st));
+        launch_sdf_count(s->st, s->np, live, g, o->cnt, o->place);
+        launch_exclusive_scan(s->st, o->cnt, o->start, cells + 1, o->cell_sums, o->d_small + 6);   // start[cells] = the counted particles
+        launch_sdf_scatter(s->st, s->np, live, g, o->start, o->place, sx, sy, sz);
+        launch_sdf_search(s->st, g, o->start, sx, sy, sz, o->tv, o->tm, o->flags, o->count_visits ? o->visits : nullptr);
+        launch_exclusive_scan(s->st, o->flags, o->slot, leaves, o->leaf_sums, o->d_small + 7);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(o->h_small + 7, o->d_small + 7, sizeof(int), hipMemcpyDeviceToHost, s->st));
+        HIPCHK(hipStreamSynchronize(s->st));
+        n = o->h_small[7];
+        if (n < 0 || (long)n > leaves) return fail(FLUID_ERR_HIP, "level set: leaf count out of range");
+        if (o->count_visits) {   // cells looked at and voxels computed, for tools/sdf_cost.py
+            std::vector<unsigned> v((size_t)leaves);
+            HIPCHK(hipMemcpy(v.data(), o->visits, (size_t)leaves * sizeof(unsigned), hipMemcpyDeviceToHost));
+            double cv = 0;
+            long searched = 0;
+            for (long j = 0; j < leaves; ++j) cv += v[(size_t)j], searched += v[(size_t)j] > 0;
+            fprintf(stderr, "sdf visits: cells %.0f leaves_searched %ld leaves_in_range %ld\n", cv, searched, leaves);
+        }
+    }
+    if ((rc = sdf_grow(q, (size_t)n))) return rc;
+    q.n_leaves = n;
+    q.bg = g.bg, q.R = R, q.w = w;
+    if (n > 0) {
+        float* values = (float*)q.dev;
+        uint64_t* active = (uint64_t*)(q.dev + (size_t)n * 2048);
+        int* origin = (int*)(q.dev + (size_t)n * (2048 + 64));
+        launch_sdf_pack(s->st, g, o->flags, o->slot, o->tv, o->tm, values, active, origin);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(o->packed, s->st));
+        HIPCHK(hipStreamWaitEvent(o->copy, o->packed, 0));
+        HIPCHK(hipMemcpyAsync(q.host, q.dev, (size_t)n * SDF_REC, hipMemcpyDeviceToHost, o->copy));
+    }
+    HIPCHK(hipEventRecord(q.done, o->copy));
+    o->n_snap++;
+    o->last_leaves = n;
+    o->last_bytes = (long)((size_t)n * SDF_REC) + 4;
+    return FLUID_OK;
+}
+
+int fluid_sdf_wait(fluid_sim_t* s, fluid_sdf_grid_t* out)
+{
+    SDF_GUARD(s);
+    if (!out) return fail(FLUID_ERR_ARG, "null argument");
+    SdfState* o = s->sdf;
+    if (!o || o->n_wait >= o->n_snap) return fail(FLUID_ERR_STATE, "no level-set snapshot is outstanding");
+    SdfSlot& q = o->s[o->n_wait & 1];
+    HIPCHK(hipEventSynchronize(q.done));
+    const size_t n = (size_t)q.n_leaves;
+    out->n = s->g.N;
+    out->n_leaves = q.n_leaves;
+    out->background = q.bg;
+    out->radius = q.R;
+    out->half_width = q.w;
+    out->values = n ? (const float*)q.host : nullptr;
+    out->active = n ? (const uint64_t*)(q.host + n * 2048) : nullptr;
+    out->origin = n ? (const int32_t*)(q.host + n * (2048 + 64)) : nullptr;
+    o->n_wait++;
+    return FLUID_OK;
+}
+
+int fluid_sdf_stats(fluid_sim_t* s, int64_t* leaves_in_grid, int64_t* leaves_listed, int64_t* bytes_to_host)
+{
+    SDF_GUARD(s);
+    const int lo = s->g.lo, hi = s->g.hi;
+    const int64_t nl = ((hi & ~7) - (lo & ~7)) / 8 + 1;
+    if (leaves_in_grid) *leaves_in_grid = nl * nl * nl;
+    if (leaves_listed) *leaves_listed = s->sdf ? s->sdf->last_leaves : 0;
+    if (bytes_to_host) *bytes_to_host = s->sdf ? s->sdf->last_bytes : 0;
+    return FLUID_OK;
+}
+
+}  // extern "C"

@@ -202,6 +202,7 @@ struct fluid_sim {
     long src_emit_last = 0, src_rm_last = 0, src_emit_total = 0, src_rm_total = 0;
     struct OutState* out = nullptr;   // leaf snapshots of the output grid (fluid_output.hip), made by the first fluid_output_snapshot
     int out_every = 0;                // fluid_dist_output_every: fluid_step snapshots the owned block at the end of step t iff t % every == 0
+    struct SdfState* sdf = nullptr;   // level-set snapshots of the particles (fluid_sdf.hip): slots, streams and scratch of their own
     // profiling
     int prof_every = 0;
     ProfClass prof[FLUID_PROF_COUNT];
@@ -246,6 +247,9 @@ void output_free(fluid_sim* s);      // waits for the copies in flight, frees th
 int output_auto_check(fluid_sim* s); // entry of fluid_step: FLUID_ERR_STATE when this step's own snapshot would be the third outstanding
 int output_auto(fluid_sim* s);       // after FLIPadvect of step t = n_steps: the snapshot of fluid_dist_output_every, when due
 void output_move(fluid_sim* from, fluid_sim* to);   // re-balance: slots, counters, `every` and the step count go to the new window's handle
+
+// fluid_sdf.hip
+void sdf_free(fluid_sim* s);         // waits for the copies in flight, frees the scratch, the staging and the pinned buffers
 
 // fluid_dist.hip
 int dist_step(fluid_sim* s, fluid_step_stats_t* stats);

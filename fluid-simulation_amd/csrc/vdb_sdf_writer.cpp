@@ -1,0 +1,296 @@
+// .vdb writer for the liquid surface (include/fluid_hip.h, "liquid surface") and the dense form of its leaf list — host only, no
+// GPU, no OpenVDB.  Stands alone: it shares no code with vdb_writer.cpp, whose constants describe a tree with every leaf of
+// [lo,hi]^3 present and background 0.
+//
+// One FloatGrid named "surface", class "level set", in OpenVDB's file format 224 (the serialisation vdb_writer.cpp restates:
+// io/Archive.cc:939-971,1243-1328, tree/RootNode.h:2257-2288, tree/InternalNode.h:2175-2195, tree/LeafNode.h:1321-1324,1444-1453,
+// io/Compression.h:462-639).  What differs from the density grid:
+//   topology   only the listed leaves exist.  A root child (4096^3) and a 128^3 node exist where a listed leaf lies; every other
+//              slot of an internal node is an inactive background tile, so its value mask is all off and writeCompressedValues
+//              finds one inactive value equal to the background (child slots are skipped, Compression.h:506): metadata byte 0 and
+//              an empty value array.  The root has no tiles.  A grid with no listed leaf has no root child.
+//   leaves     value mask = the active mask; only the active values are stored (COMPRESS_ACTIVE_MASK).  The inactive ones are
+//              coded by the metadata byte (Compression.h:519-562): 0 = none, or all +background; 1 = all -background; 3 = both,
+//              followed by a selection mask whose on bits mark the inactive voxels that hold +background.
+//   metadata   "class" = "level set" and "name" = "surface" beside the file_* statistics (bounding box and count of the ACTIVE
+//              voxels; std::map order = by name).  A grid with a unique non-empty name keeps it in the descriptor
+//              (io/Archive.cc:1203-1206).
+//   transform  UniformScaleMap(voxel size), voxel size = background / half_width.
+// Parity with the library is unpinned, as for the density files; tests/test_sdf_host.py re-reads the files with tests/vdb_reader.py.
+#include <zlib.h>
+
+#include <climits>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <ctime>
+#include <map>
+#include <random>
+#include <string>
+#include <vector>
+
+#include "fluid_hip.h"
+
+namespace {
+
+struct Out {
+    FILE* f = nullptr;
+    size_t at = 0;
+    bool ok = true;
+    std::vector<char> buf;
+    std::vector<unsigned char> zbuf;
+    void flush()
+    {
+        if (!buf.empty() && fwrite(buf.data(), 1, buf.size(), f) != buf.size()) ok = false;
+        buf.clear();
+    }
+    void raw(const void* p, size_t n)
+    {
+        const char* c = (const char*)p;
+        if (n) buf.insert(buf.end(), c, c + n);
+        at += n;
+        if (buf.size() >= (size_t)1 << 20) flush();
+    }
+    template <typename T> void put(T v) { raw(&v, sizeof(T)); }
+    void str(const std::string& s) { put<uint32_t>((uint32_t)s.size()); raw(s.data(), s.size()); }
+    void zeros(size_t n) { const std::vector<char> z(n, 0); raw(z.data(), n); }
+    void patch64(size_t where, int64_t v)
+    {
+        flush();
+        if (fseeko(f, (off_t)where, SEEK_SET) != 0 || fwrite(&v, 1, 8, f) != 8 || fseeko(f, 0, SEEK_END) != 0) ok = false;
+    }
+    // writeData (io/Compression.h:253-264): zipToStream with COMPRESS_ZIP (io/Compression.cc:70-100), the raw bytes otherwise
+    void data(const void* p, size_t n, uint32_t compression)
+    {
+        if (!(compression & 0x1)) { raw(p, n); return; }
+        static const unsigned char none = 0;
+        const Bytef* src = n ? (const Bytef*)p : &none;
+        uLongf zn = compressBound((uLong)n);
+        zbuf.resize(zn);
+        const int st = compress2(zbuf.data(), &zn, src, (uLong)n, Z_DEFAULT_COMPRESSION);
+        if (st == Z_OK && zn < n) {
+            put<int64_t>((int64_t)zn);
+            raw(zbuf.data(), zn);
+        } else {
+            put<int64_t>(-(int64_t)n);
+            raw(p, n);
+        }
+    }
+};
+
+constexpr int LEAF = 8, INT1 = 128, INT2 = 4096;
+inline int floor_to(int v, int m) { return v & ~(m - 1); }
+
+template <typename T> void meta(Out& o, const char* name, const char* type, const T* v, uint32_t bytes)
+{
+    o.str(name); o.str(type); o.put<uint32_t>(bytes); o.raw(v, bytes);
+}
+
+inline bool bit(const uint64_t* m, int off) { return (m[off >> 6] >> (off & 63)) & 1; }
+inline bool same_bits(float a, float b) { return memcmp(&a, &b, 4) == 0; }
+
+// FLUID_OK, or FLUID_ERR_ARG: no arrays behind a non-empty list, an origin off the 8-grid, outside the leaves of [lo,hi]^3, or
+// not strictly ascending in (x, y, z)
+int check_list(const fluid_sdf_grid_t* g)
+{
+    if (!g || g->n < 1 || g->n > 4096 || g->n_leaves < 0) return FLUID_ERR_ARG;
+    if (g->n_leaves > 0 && (!g->origin || !g->values || !g->active)) return FLUID_ERR_ARG;
+    const int lo = -(g->n / 2), hi = lo + g->n - 1, L0 = floor_to(lo, LEAF), L1 = floor_to(hi, LEAF);
+    for (int i = 0; i < g->n_leaves; ++i) {
+        const int32_t* o = g->origin + 3 * (size_t)i;
+        for (int a = 0; a < 3; ++a)
+            if ((o[a] & (LEAF - 1)) != 0 || o[a] < L0 || o[a] > L1) return FLUID_ERR_ARG;
+        if (i > 0) {
+            const int32_t* p = o - 3;
+            const bool after = o[0] != p[0] ? o[0] > p[0] : o[1] != p[1] ? o[1] > p[1] : o[2] > p[2];
+            if (!after) return FLUID_ERR_ARG;
+        }
+    }
+    return FLUID_OK;
+}
+
+// the per-node metadata byte of a leaf, or -1: an inactive value that is neither +bg nor -bg
+int leaf_code(const float* v, const uint64_t* m, float bg)
+{
+    bool neg = false, pos = false;
+    for (int off = 0; off < 512; ++off) {
+        if (bit(m, off)) continue;
+        if (same_bits(v[off], bg)) pos = true;
+        else if (same_bits(v[off], -bg)) neg = true;
+        else return -1;
+    }
+    return !neg ? 0 : (!pos ? 1 : 3);   // NO_MASK_OR_INACTIVE_VALS, NO_MASK_AND_MINUS_BG, MASK_AND_NO_INACTIVE_VALS (io/Compression.h:94-100)
+}
+
+using Mid = std::map<int, std::vector<std::pair<int, int>>>;   // slot of a 128^3 node in its root child -> (slot of the leaf, index in the list)
+struct Key {
+    int x, y, z;
+    bool operator<(const Key& b) const { return x != b.x ? x < b.x : y != b.y ? y < b.y : z < b.z; }   // math/Coord.h:180-185
+};
+
+}  // namespace
+
+extern "C" {
+
+int fluid_sdf_to_dense(const fluid_sdf_grid_t* g, float* values, uint8_t* active)
+{
+    if (!values) return FLUID_ERR_ARG;
+    const int rc = check_list(g);
+    if (rc) return rc;
+    const int n = g->n, lo = -(n / 2);
+    const size_t nc = (size_t)n * n * n;
+    for (size_t i = 0; i < nc; ++i) values[i] = g->background;
+    if (active) memset(active, 0, nc);
+    for (int l = 0; l < g->n_leaves; ++l) {
+        const int32_t* o = g->origin + 3 * (size_t)l;
+        const float* v = g->values + 512 * (size_t)l;
+        const uint64_t* m = g->active + 8 * (size_t)l;
+        for (int x = 0; x < 8; ++x)
+            for (int y = 0; y < 8; ++y)
+                for (int z = 0; z < 8; ++z) {
+                    const int ax = o[0] + x - lo, ay = o[1] + y - lo, az = o[2] + z - lo;
+                    if (ax < 0 || ax >= n || ay < 0 || ay >= n || az < 0 || az >= n) continue;
+                    const int off = (x * 8 + y) * 8 + z;
+                    const size_t c = ((size_t)ax * n + ay) * n + az;
+                    values[c] = v[off];
+                    if (active) active[c] = bit(m, off) ? 1 : 0;
+                }
+    }
+    return FLUID_OK;
+}
+
+int fluid_write_vdb_sdf(const char* path, const fluid_sdf_grid_t* g, int32_t compression)
+{
+    if (!path || (compression != FLUID_VDB_ACTIVE_MASK && compression != FLUID_VDB_ZIP_ACTIVE_MASK)) return FLUID_ERR_ARG;
+    int rc = check_list(g);
+    if (rc) return rc;
+    const float bg = g->background;
+    if (!(bg > 0.0f) || !(g->half_width > 0.0f)) return FLUID_ERR_ARG;
+    const size_t nl = (size_t)g->n_leaves;
+    // per leaf: metadata byte; the tree the list spans; statistics of the active voxels
+    std::vector<int8_t> code(nl);
+    std::map<Key, Mid> roots;
+    int32_t bmin[3] = {INT_MAX, INT_MAX, INT_MAX}, bmax[3] = {INT_MIN, INT_MIN, INT_MIN};
+    int64_t voxels = 0, n_int1 = 0;
+    for (size_t l = 0; l < nl; ++l) {
+        const int32_t* o = g->origin + 3 * l;
+        const float* v = g->values + 512 * l;
+        const uint64_t* m = g->active + 8 * l;
+        const int c = leaf_code(v, m, bg);
+        if (c < 0) return FLUID_ERR_ARG;
+        code[l] = (int8_t)c;
+        const Key r{floor_to(o[0], INT2), floor_to(o[1], INT2), floor_to(o[2], INT2)};
+        const int a[3] = {(o[0] - r.x) / INT1, (o[1] - r.y) / INT1, (o[2] - r.z) / INT1};
+        const int q[3] = {((o[0] - r.x) % INT1) / LEAF, ((o[1] - r.y) % INT1) / LEAF, ((o[2] - r.z) % INT1) / LEAF};
+        roots[r][(a[0] << 10) + (a[1] << 5) + a[2]].push_back({(q[0] << 8) + (q[1] << 4) + q[2], (int)l});
+        for (int off = 0; off < 512; ++off)
+            if (bit(m, off)) {
+                const int p[3] = {o[0] + (off >> 6), o[1] + ((off >> 3) & 7), o[2] + (off & 7)};
+                for (int k = 0; k < 3; ++k) {
+                    bmin[k] = p[k] < bmin[k] ? p[k] : bmin[k];
+                    bmax[k] = p[k] > bmax[k] ? p[k] : bmax[k];
+                }
+                ++voxels;
+            }
+    }
+    for (auto& r : roots) n_int1 += (int64_t)r.second.size();   // (the list ascends in (x, y, z): so do the leaves of every 128^3 node)
+
+    Out o;
+    o.f = fopen(path, "wb");
+    if (!o.f) return FLUID_ERR_ARG;
+    const uint32_t comp = (uint32_t)compression;
+    // ---- header (io/Archive.cc:939-971) ----
+    o.put<int64_t>(0x56444220);
+    o.put<uint32_t>(224);
+    o.put<uint32_t>(4); o.put<uint32_t>(0);
+    o.put<char>(1);
+    {
+        std::mt19937 ran((unsigned)(std::random_device()() + (unsigned)std::time(nullptr)));
+        char u[37];
+        const uint32_t a = ran(), b = ran(), c = ran(), d = ran();
+        snprintf(u, sizeof(u), "%08x-%04x-4%03x-%04x-%04x%08x", a, b >> 16, b & 0xfff, 0x8000 | (c >> 18), c & 0xffff, d);
+        o.raw(u, 36);
+    }
+    o.put<uint32_t>(0);   // file-level metadata: empty map
+    o.put<int32_t>(1);    // one grid
+    // ---- descriptor ----
+    o.str("surface");
+    o.str("Tree_float_5_4_3");
+    o.str("");
+    const size_t off = o.at;
+    o.put<int64_t>(0); o.put<int64_t>(0); o.put<int64_t>(0);
+    o.patch64(off, (int64_t)o.at);
+    o.put<uint32_t>(comp);
+    // ---- grid metadata ----
+    // memUsage as vdb_writer.cpp's tree_mem_bytes counts it, for the nodes this tree has
+    const int64_t mem = (8 + 56 + 2 * 568) + 56 + (int64_t)roots.size() * (32768 * 8 + 4096 + 4096 + 12) + n_int1 * (4096 * 8 + 512 + 512 + 12) +
+                        (int64_t)nl * (96 + 2048);
+    const std::string cs = (comp & 0x1) ? "zip + active values" : "active values";
+    const std::string cls = "level set", name = "surface";
+    o.put<uint32_t>(7);
+    meta(o, "class", "string", cls.data(), (uint32_t)cls.size());
+    meta(o, "file_bbox_max", "vec3i", bmax, 12);
+    meta(o, "file_bbox_min", "vec3i", bmin, 12);
+    meta(o, "file_compression", "string", cs.data(), (uint32_t)cs.size());
+    meta(o, "file_mem_bytes", "int64", &mem, 8);
+    meta(o, "file_voxel_count", "int64", &voxels, 8);
+    meta(o, "name", "string", name.data(), (uint32_t)name.size());
+    // ---- transform: UniformScaleMap(dx) = scale, voxel size, 1/scale, 1/scale^2, 1/(2 scale) (math/Maps.h ScaleMap::write) ----
+    o.str("UniformScaleMap");
+    const double dx = (double)(bg / g->half_width);
+    const double sc[3] = {dx, dx, dx}, inv[3] = {1 / dx, 1 / dx, 1 / dx}, inv2[3] = {1 / (dx * dx), 1 / (dx * dx), 1 / (dx * dx)},
+                 invt[3] = {1 / (2 * dx), 1 / (2 * dx), 1 / (2 * dx)};
+    o.raw(sc, 24); o.raw(sc, 24); o.raw(inv, 24); o.raw(inv2, 24); o.raw(invt, 24);
+    // ---- topology ----
+    o.put<int32_t>(1);    // buffer count
+    o.put<float>(bg);
+    o.put<uint32_t>(0);   // root tiles
+    o.put<uint32_t>((uint32_t)roots.size());
+    for (auto& r : roots) {
+        const int32_t org[3] = {r.first.x, r.first.y, r.first.z};
+        o.raw(org, sizeof(org));
+        std::vector<uint64_t> cm(32 * 32 * 32 / 64, 0);
+        for (auto& mid : r.second) cm[(size_t)mid.first >> 6] |= 1ull << (mid.first & 63);
+        o.raw(cm.data(), cm.size() * 8);
+        o.zeros(cm.size() * 8);      // value mask: no active tile
+        o.put<int8_t>(0);            // every tile holds the background
+        o.data(nullptr, 0, comp);    // no active value
+        for (auto& mid : r.second) {
+            uint64_t lm[64] = {};
+            for (auto& lf : mid.second) lm[lf.first >> 6] |= 1ull << (lf.first & 63);
+            o.raw(lm, sizeof(lm));
+            o.zeros(sizeof(lm));
+            o.put<int8_t>(0);
+            o.data(nullptr, 0, comp);
+            for (auto& lf : mid.second) o.raw(g->active + 8 * (size_t)lf.second, 64);
+        }
+    }
+    o.patch64(off + 8, (int64_t)o.at);    // block position
+    // ---- buffers, in the order of the topology ----
+    for (auto& r : roots)
+        for (auto& mid : r.second)
+            for (auto& lf : mid.second) {
+                const size_t l = (size_t)lf.second;
+                const float* v = g->values + 512 * l;
+                const uint64_t* m = g->active + 8 * l;
+                o.raw(m, 64);
+                o.put<int8_t>(code[l]);
+                float act[512];
+                int na = 0;
+                uint64_t sel[8] = {};
+                for (int k = 0; k < 512; ++k) {
+                    if (bit(m, k)) act[na++] = v[k];
+                    else if (same_bits(v[k], bg)) sel[k >> 6] |= 1ull << (k & 63);
+                }
+                if (code[l] == 3) o.raw(sel, sizeof(sel));
+                o.data(act, (size_t)na * sizeof(float), comp);
+            }
+    o.patch64(off + 16, (int64_t)o.at);   // end position
+    o.flush();
+    const int frc = fclose(o.f);
+    if (o.ok && frc == 0) return FLUID_OK;
+    remove(path);   // a short write leaves no partial file behind
+    return FLUID_ERR_ARG;   // (the ABI has no code of its own for I/O: an unwritable path is a bad argument, as in vdb_writer.cpp)
+}
+
+}  // extern "C"

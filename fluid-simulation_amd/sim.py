@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 
-from ._lib import lib, check, FluidError, Params, StepStats, FIELD, Source, LeafGridC
+from ._lib import lib, check, FluidError, Params, StepStats, FIELD, Source, LeafGridC, SdfParams, SdfGridC
 
 _FIELD_DTYPE = {
     FIELD.CONTAINER: (np.float32, 1), FIELD.WEIGHTS: (np.float32, 1), FIELD.OUTPUT: (np.float32, 1),
@@ -113,6 +113,47 @@ def merge_leaf_grids(parts):
     if k and lib.fluid_leaf_grids_merge(arr, len(parts), k, org.ctypes.data_as(C.c_void_p), val.ctypes.data_as(C.c_void_p)) != k:
         raise FluidError(1, "fluid_leaf_grids_merge: the second call disagrees with the count")
     return LeafGrid(parts[0].n, org, val)
+
+
+class SdfGrid:
+    """fluid_sdf_grid_t on the host: the narrow-band level set of the particles as the list of its 8^3 leaves.  origin (k, 3)
+    int32, ascending (x, y, z); values (k, 512) float32, ((x&7)*8 + (y&7))*8 + (z&7); active (k, 512) bool in the same order;
+    background = (float)dx * half_width; radius and half_width as floats, as used."""
+
+    def __init__(self, n, origin, values, active, background, radius, half_width):
+        self.n = int(n)
+        self.origin = np.ascontiguousarray(origin, dtype=np.int32).reshape(-1, 3)
+        self.values = np.ascontiguousarray(values, dtype=np.float32).reshape(-1, 512)
+        self.active = np.ascontiguousarray(active, dtype=bool).reshape(-1, 512)
+        assert self.origin.shape[0] == self.values.shape[0] == self.active.shape[0]
+        self.background, self.radius, self.half_width = np.float32(background), np.float32(radius), np.float32(half_width)
+
+    @property
+    def n_leaves(self):
+        return self.origin.shape[0]
+
+    def _c(self):
+        """(struct, the arrays it points into): bit off & 63 of word off >> 6 (OpenVDB's NodeMask order)."""
+        words = np.packbits(self.active, axis=1, bitorder="little").view("<u8").reshape(-1, 8)
+        words = np.ascontiguousarray(words)
+        return SdfGridC(self.n, self.n_leaves, self.background, self.radius, self.half_width, self.origin.ctypes.data,
+                        self.values.ctypes.data, words.ctypes.data), words
+
+
+def sdf_to_dense(grid):
+    """(values float32 (n, n, n), active bool (n, n, n)) of an SdfGrid: +background / inactive outside the listed leaves
+    (fluid_sdf_to_dense: host only)."""
+    val = np.empty((grid.n,) * 3, dtype=np.float32)
+    act = np.empty((grid.n,) * 3, dtype=np.uint8)
+    c, _keep = grid._c()
+    check(lib.fluid_sdf_to_dense(C.byref(c), val.ctypes.data_as(C.c_void_p), act.ctypes.data_as(C.c_void_p)))
+    return val, act.astype(bool)
+
+
+def write_vdb_sdf(path, grid, compression="zip"):
+    """One FloatGrid "surface" of class "level set" whose leaves are the listed ones (fluid_write_vdb_sdf: host only)."""
+    c, _keep = grid._c()
+    check(lib.fluid_write_vdb_sdf(str(path).encode(), C.byref(c), _VDB_COMPRESSION[compression]))
 
 
 def water_cube_drop(n, ppc, seed=0):
@@ -345,6 +386,32 @@ class FluidSim:
     def output_stats(self):
         v = [C.c_int64() for _ in range(3)]
         check(lib.fluid_output_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("leaves_in_grid", "leaves_listed", "bytes_to_host"), (x.value for x in v)))
+
+    # ---- liquid surface: narrow-band level set of the particles (single GPU; include/fluid_hip.h) ----
+    def sdf_snapshot(self, radius, half_width):
+        """Enqueue the level set of the particles as they are now (spheres of `radius`, band of `half_width`, both in voxels);
+        a step() called next overlaps the copy to the host."""
+        p = SdfParams(float(radius), float(half_width))
+        check(lib.fluid_sdf_snapshot(self._h, C.byref(p)))
+
+    def sdf_wait(self):
+        """The oldest level-set snapshot not yet waited for, as an SdfGrid (copied out of the handle's pinned buffer)."""
+        g = SdfGridC()
+        check(lib.fluid_sdf_wait(self._h, C.byref(g)))
+        k = g.n_leaves
+        if k == 0:
+            return SdfGrid(g.n, np.empty((0, 3), np.int32), np.empty((0, 512), np.float32), np.empty((0, 512), bool),
+                           g.background, g.radius, g.half_width)
+        org = np.ctypeslib.as_array(C.cast(g.origin, C.POINTER(C.c_int32)), shape=(k, 3)).copy()
+        val = np.ctypeslib.as_array(C.cast(g.values, C.POINTER(C.c_float)), shape=(k, 512)).copy()
+        words = np.ctypeslib.as_array(C.cast(g.active, C.POINTER(C.c_uint64)), shape=(k, 8)).copy()
+        act = np.unpackbits(words.view(np.uint8), axis=1, bitorder="little").astype(bool)
+        return SdfGrid(g.n, org, val, act, g.background, g.radius, g.half_width)
+
+    def sdf_stats(self):
+        v = [C.c_int64() for _ in range(3)]
+        check(lib.fluid_sdf_stats(self._h, *[C.byref(x) for x in v]))
         return dict(zip(("leaves_in_grid", "leaves_listed", "bytes_to_host"), (x.value for x in v)))
 
     def extrapolate(self):

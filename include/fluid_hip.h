@@ -532,6 +532,62 @@ int fluid_dist_output_every(fluid_sim_t* s, int32_t every);
  * rules of fluid_vdb_append_leaves, two parts hold a non-zero bit pattern for the same voxel, cap_leaves is too small. */
 int64_t fluid_leaf_grids_merge(const fluid_leaf_grid_t* parts, int32_t n_parts, int64_t cap_leaves, int32_t* origin, float* values);
 
+/* ---- liquid surface: narrow-band level set of the particles, as leaves (single GPU) ------------------------------------------
+ * The density grid above is a one-cell blur of the particle set; this is the signed distance to the union of spheres of a fixed
+ * radius around the particles, as OpenVDB's ParticlesToLevelSet::rasterizeSpheres leaves it (tools/ParticlesToLevelSet.h:591-643,
+ * fixed radius; no prune, no renormalisation, Rmin not applied), restated as a function of the particle SET — a minimum, so no
+ * particle order is involved.  All quantities in index space: voxel c is the integer point c, a particle's coordinates are the
+ * handle's.
+ *   R = (float)radius, w = (float)half_width, dxf = (float)params.dx; every operation below rounded to float:
+ *   bg = dxf * w, mx = R + w, max2 = mx * mx, mn = max(0.0f, R - w), min2 = mn * mn.
+ *   A live particle counts iff its base cell round(p) (half away from zero) lies in [lo,hi]^3.
+ *   Squared distance of voxel c and particle P (differences and squares in double, narrowed to float after each axis, no FMA):
+ *     x2 = (float)((cx - Px) * (cx - Px));  x2y2 = (float)((double)x2 + (cy - Py) * (cy - Py));
+ *     x2y2z2 = (float)((double)x2y2 + (cz - Pz) * (cz - Pz))
+ *   m = the minimum of x2y2z2 over the counted particles.  The voxel is inactive +bg if there is no particle or m >= max2;
+ *   inactive -bg if m <= min2; otherwise d = dxf * (sqrtf(m) - R) (sqrtf correctly rounded): active with value d if d < bg, else
+ *   inactive +bg.
+ * Only voxels of [lo,hi]^3 are computed.  Leaves are OpenVDB's (origins at multiples of 8); a leaf is listed iff one of its in-grid
+ * voxels is anything but inactive +bg; voxels of a listed leaf outside the grid are inactive +bg, as is every voxel of an unlisted
+ * leaf.  The list is ascending in (x, y, z) origin.
+ * Limits: radius > 0, half_width >= 1, R + w <= 4 (float sum), else FLUID_ERR_ARG: a particle within mx of a voxel then has its
+ * base cell at Chebyshev distance <= 4 from it, so the search stays inside a 9^3 neighbourhood of cells.  One GPU only: a
+ * decomposed handle returns FLUID_ERR_STATE from the three handle entry points.  Parity of the file with the library is unpinned
+ * (as for the density files); the tests re-read it with their own reader. */
+typedef struct fluid_sdf_params { double radius, half_width; } fluid_sdf_params_t;   /* voxels */
+typedef struct fluid_sdf_grid {
+    int32_t n, n_leaves;
+    float background;            /* bg                                                                               */
+    float radius, half_width;    /* R, w as used                                                                     */
+    const int32_t* origin;       /* 3 per leaf                                                                       */
+    const float* values;         /* 512 per leaf, ((x&7)*8 + (y&7))*8 + (z&7)                                        */
+    const uint64_t* active;      /* 8 words per leaf: voxel off -> word off>>6, bit off&63 (OpenVDB NodeMask order)   */
+} fluid_sdf_grid_t;
+#define FLUID_SDF_LEAF_BYTES (2048 + 64 + 12)   /* a listed leaf on the way to the host: values, mask, origin            */
+/* Captures the particles as they are at the call (after a step: after FLIPadvect and the sources / sinks; also right after an
+ * upload).  Lifetime rules of the density snapshot above: kernels on the handle's stream, the 4-byte count of listed leaves read back,
+ * the records copied to pinned host memory on a second stream and not waited for; two snapshots may be outstanding, a third returns
+ * FLUID_ERR_STATE; buffers grow here, never inside a step, and are freed by the destroy call after the copies in flight have ended.
+ * Before the kernels are sized the particles' base-cell box is read back as well (24 bytes; not part of bytes_to_host).
+ * The slots and the count of outstanding snapshots are the surface's own: a caller can take this and a density snapshot per step.
+ * Nothing a later step reads is written: the snapshot bins the particles into scratch of its own. */
+int fluid_sdf_snapshot(fluid_sim_t* s, const fluid_sdf_params_t* p);
+/* The oldest snapshot not yet waited for (FLUID_ERR_STATE when there is none); with no listed leaf n_leaves = 0 and the pointers
+ * are NULL.  The pointers stay valid until the SECOND following surface snapshot on the handle. */
+int fluid_sdf_wait(fluid_sim_t* s, fluid_sdf_grid_t* out);
+/* Of the last snapshot (any pointer may be NULL): bytes_to_host = leaves_listed * FLUID_SDF_LEAF_BYTES + 4. */
+int fluid_sdf_stats(fluid_sim_t* s, int64_t* leaves_in_grid, int64_t* leaves_listed, int64_t* bytes_to_host);
+/* Host only: values[n^3] (z fastest) = +bg and active[n^3] (may be NULL) = 0 everywhere, then the in-grid voxels of every listed
+ * leaf.  FLUID_ERR_ARG on an origin that is not a multiple of 8, lies outside the leaves of [lo,hi]^3 or is not strictly ascending. */
+int fluid_sdf_to_dense(const fluid_sdf_grid_t* g, float* values, uint8_t* active);
+/* Host only: one FloatGrid named "surface" (Tree_float_5_4_3, background bg, grid class "level set", file format 224) whose
+ * topology is the listed leaves only — background tiles elsewhere — with the active masks as leaf value masks and the inactive
+ * values coded by the per-node metadata byte of io/Compression.h.  Voxel size = background / half_width (float division: params.dx
+ * whenever dxf * w is exact).  compression: FLUID_VDB_ACTIVE_MASK or FLUID_VDB_ZIP_ACTIVE_MASK.  Bad lists as above; an inactive
+ * value that is neither +bg nor -bg is FLUID_ERR_ARG too, and so is a path that cannot be opened or written in full (the
+ * partial file is removed). */
+int fluid_write_vdb_sdf(const char* path, const fluid_sdf_grid_t* g, int32_t compression);
+
 #ifdef __cplusplus
 }
 #endif

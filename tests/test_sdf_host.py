@@ -1,0 +1,171 @@
+"""CPU (-m "not gpu"): the host half of the liquid surface — fluid_sdf_to_dense and fluid_write_vdb_sdf on hand-made leaf
+lists (no GPU): the dense form against numpy, the file re-read with tests/vdb_reader.py (background, class, name, voxel size,
+leaf origins, values and masks bit for bit, both compressions), refused lists, and the writer under ASan + UBSan as a
+stand-alone program."""
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import sdf_ref
+import vdb_reader
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "fluid-simulation_amd", "csrc")
+ERR_ARG = 1
+
+
+def u32(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def hand_made(fs, n, bg=np.float32(2.5)):
+    """A dense level-set-like grid with every kind of leaf: mixed, all -bg, both inactive signs, all active; partial leaves at
+    both ends when n = 25.  Returns (SdfGrid, values, active)."""
+    lo, hi, l0, nl = sdf_ref.geometry(n)
+    rng = np.random.default_rng(n)
+    val = np.full((n, n, n), bg, np.float32)
+    act = np.zeros((n, n, n), bool)
+
+    def box(o):   # array slices of the in-grid part of the leaf with origin o
+        return tuple(slice(max(c, lo) - lo, min(c + 7, hi) - lo + 1) for c in o)
+    first, last = (l0,) * 3, (hi & ~7,) * 3
+    mid = (l0 + 8,) * 3 if nl > 2 else (l0 + 8, l0 + 8, l0)   # lies wholly inside the grid
+    b = box(first)                                       # first leaf: active values and both inactive signs
+    shape = val[b].shape
+    val[b] = rng.uniform(-bg, bg, shape).astype(np.float32)
+    act[b] = True
+    k = rng.random(shape)
+    act[b] &= k > 0.4
+    val[b] = np.where(k <= 0.2, -bg, np.where(k <= 0.4, bg, val[b]))
+    val[box(last)] = -bg                                 # last leaf: all -bg, nothing active
+    b = box(mid)                                         # a whole leaf, every voxel active
+    val[b] = rng.uniform(-1, 1, val[b].shape).astype(np.float32)
+    act[b] = True
+    b = box((l0 + 8, l0, hi & ~7))                       # active values, the rest +bg
+    k = rng.random(val[b].shape)
+    act[b] = k > 0.5
+    val[b] = np.where(act[b], np.float32(0.125) * k.astype(np.float32), bg)
+    org, v, a = sdf_ref.leaf_list(val, act, bg)
+    return fs.SdfGrid(n, org, v, a, bg, 1.5, 2.5), val, act
+
+
+@pytest.mark.parametrize("n", [16, 25])
+def test_to_dense(fs, n):
+    g, val, act = hand_made(fs, n)
+    assert g.n_leaves == 4
+    dv, da = fs.sdf_to_dense(g)
+    assert np.array_equal(u32(dv), u32(val)) and np.array_equal(da, act)
+    empty = fs.SdfGrid(n, np.empty((0, 3)), np.empty((0, 512)), np.empty((0, 512)), 2.5, 1.5, 2.5)
+    dv, da = fs.sdf_to_dense(empty)
+    assert (dv == np.float32(2.5)).all() and not da.any()
+
+
+@pytest.mark.parametrize("compression", ["zip", "active_mask"])
+@pytest.mark.parametrize("n", [16, 25])
+def test_file_rereads(fs, tmp_path, n, compression):
+    g, val, act = hand_made(fs, n)
+    lo, hi, _, _ = sdf_ref.geometry(n)
+    path = tmp_path / "surface.vdb"
+    fs.write_vdb_sdf(path, g, compression)
+    info, grids = vdb_reader.read(path)
+    assert info["version"] == 224 and len(grids) == 1
+    r = grids[0]
+    assert r.unique_name == "surface" and r.metadata["name"] == "surface" and r.metadata["class"] == "level set"
+    assert np.float32(r.background) == g.background and r.compression == {"zip": 3, "active_mask": 2}[compression]
+    assert np.array_equal(r.voxel_size, [1.0] * 3) and np.array_equal(r.scale, [1.0] * 3)
+    assert sorted(r.leaves) == [tuple(o) for o in g.origin.tolist()] and not r.tiles
+    assert r.metadata["file_voxel_count"] == int(act.sum())
+    ii = np.argwhere(act) + lo
+    assert r.metadata["file_bbox_min"] == tuple(ii.min(axis=0)) and r.metadata["file_bbox_max"] == tuple(ii.max(axis=0))
+    rv, ra = r.dense(lo, hi)
+    dv, da = fs.sdf_to_dense(g)
+    assert np.array_equal(u32(rv), u32(dv)) and np.array_equal(ra, da)
+    for o, v, a in zip(g.origin.tolist(), g.values, g.active):      # the leaves' own voxels, those outside the grid included
+        lv, lm = r.leaves[tuple(o)]
+        assert np.array_equal(u32(lv), u32(v)) and np.array_equal(lm, a)
+
+
+def test_voxel_size_and_empty_grid(fs, tmp_path):
+    g, _, _ = hand_made(fs, 16, bg=np.float32(1.0))
+    g.half_width = np.float32(2.0)                                   # dx = 0.5
+    fs.write_vdb_sdf(tmp_path / "h.vdb", g)
+    r = vdb_reader.read(tmp_path / "h.vdb")[1][0]
+    assert np.array_equal(r.voxel_size, [0.5] * 3) and np.array_equal(r.inv_scale, [2.0] * 3) and r.background == 1.0
+    empty = fs.SdfGrid(16, np.empty((0, 3)), np.empty((0, 512)), np.empty((0, 512)), 2.5, 1.5, 2.5)
+    fs.write_vdb_sdf(tmp_path / "e.vdb", empty, "active_mask")
+    r = vdb_reader.read(tmp_path / "e.vdb")[1][0]
+    assert not r.leaves and not r.tiles and r.root_children == [] and r.metadata["file_voxel_count"] == 0
+    assert (r.dense(-8, 7)[0] == np.float32(2.5)).all()
+
+
+def test_bad_lists_are_refused(fs, tmp_path):
+    import ctypes as C
+    n = 25
+    g, _, _ = hand_made(fs, n)
+    _, _, l0, _ = sdf_ref.geometry(n)
+    out = np.empty((n,) * 3, np.float32)
+
+    def both(grid):
+        c, _keep = grid._c()
+        assert fs.lib.fluid_sdf_to_dense(C.byref(c), out.ctypes.data_as(C.c_void_p), None) == ERR_ARG
+        assert fs.lib.fluid_write_vdb_sdf(str(tmp_path / "bad.vdb").encode(), C.byref(c), 3) == ERR_ARG
+        assert not (tmp_path / "bad.vdb").exists()
+    o = g.origin.copy(); o[1, 2] += 4
+    both(fs.SdfGrid(n, o, g.values, g.active, g.background, 1.5, 2.5))           # unaligned
+    o = g.origin.copy(); o[[1, 2]] = o[[2, 1]]
+    both(fs.SdfGrid(n, o, g.values, g.active, g.background, 1.5, 2.5))           # not ascending
+    o = g.origin.copy(); o[1] = o[0]
+    both(fs.SdfGrid(n, o, g.values, g.active, g.background, 1.5, 2.5))           # twice the same
+    o = g.origin.copy(); o[0, 0] = l0 - 8
+    both(fs.SdfGrid(n, o, g.values, g.active, g.background, 1.5, 2.5))           # outside the grid's leaves
+    o = g.origin.copy(); o[3, 1] = (sdf_ref.geometry(n)[1] & ~7) + 8
+    both(fs.SdfGrid(n, o, g.values, g.active, g.background, 1.5, 2.5))
+    c, _keep = g._c()
+    assert fs.lib.fluid_sdf_to_dense(C.byref(c), None, None) == ERR_ARG
+    assert fs.lib.fluid_write_vdb_sdf(str(tmp_path / "bad.vdb").encode(), C.byref(c), 1) == ERR_ARG     # ZIP alone: not offered
+    v = g.values.copy()
+    v[0, np.flatnonzero(~g.active[0])[0]] = 0.75                                   # an inactive value that is neither +bg nor -bg
+    c, _keep = fs.SdfGrid(n, g.origin, v, g.active, g.background, 1.5, 2.5)._c()
+    assert fs.lib.fluid_write_vdb_sdf(str(tmp_path / "bad.vdb").encode(), C.byref(c), 3) == ERR_ARG
+    assert not (tmp_path / "bad.vdb").exists()
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_sdf_writer_under_asan_ubsan(tmp_path):
+    exe = tmp_path / "host_san_sdf"
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
+           "-I", os.path.join(ROOT, "include"), os.path.join(CSRC, "vdb_sdf_writer.cpp"),
+           os.path.join(ROOT, "tests", "host_san_sdf_main.cpp"), "-o", str(exe), "-lz"]
+    b = subprocess.run(cmd, capture_output=True, text=True)
+    if b.returncode != 0 and "asan" in (b.stderr or "").lower() and "cannot find" in b.stderr.lower():
+        pytest.skip("sanitizer runtime not installed")
+    assert b.returncode == 0, b.stderr[-3000:]
+    r = subprocess.run([str(exe), str(tmp_path)], capture_output=True, text=True, timeout=600,
+                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
+    assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
+    assert "host sanitizer run (sdf): ok" in r.stdout
+    _, grids = vdb_reader.read(tmp_path / "san_zip.vdb")                           # what the sanitized build wrote re-reads too
+    assert grids[0].metadata["class"] == "level set" and len(grids[0].leaves) > 64
+
+
+def test_unwritable_path_is_refused(fs, tmp_path):
+    import ctypes as C
+    g, _, _ = hand_made(fs, 16)
+    c, _keep = g._c()
+    assert fs.lib.fluid_write_vdb_sdf(str(tmp_path / "no_such_dir" / "s.vdb").encode(), C.byref(c), 3) == ERR_ARG
+    assert not (tmp_path / "no_such_dir").exists()
+
+
+@pytest.mark.parametrize("extra", [{"FLUID_OUT": ""}, {"FLUID_STEPS": "0"}, {"FLUID_OUT_DENSE": "1"}, {"FLUID_BLOCKS": "2x1x1"}])
+def test_driver_refuses_a_surface_it_would_not_write(tmp_path, extra):
+    """FLUID_OUT_SURFACE with nothing to write it beside is an error, not ignored (decided before any handle is created)."""
+    env = dict(os.environ, FLUID_N="16", FLUID_PPC="1", FLUID_STEPS="1", FLUID_OUT=str(tmp_path / "simulation"), FLUID_OUT_SURFACE="1.5,2.5")
+    for k in ("FLUID_OUT_DENSE", "FLUID_BLOCKS", "FLUID_SOURCE_EVERY", "FLUID_RAW"):
+        env.pop(k, None)
+    env.update(extra)
+    r = subprocess.run([os.path.join(ROOT, "fluid-simulation_amd", "fluid")], capture_output=True, text=True, env=env, cwd=tmp_path, timeout=60)
+    assert r.returncode == 1 and "FLUID_OUT_SURFACE" in r.stderr, (r.returncode, r.stderr[-500:])
+    assert not list(tmp_path.rglob("*.vdb"))
