@@ -200,14 +200,59 @@ __device__ __forceinline__ int xcd_remap(int b, int nb)
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
 }
 
-// Sum three partial arrays in one pass; results broadcast to all threads.  sm: 12 doubles.
-__device__ __forceinline__ void block_sum3(const double* __restrict__ a, int na, const double* __restrict__ b, int nb,
-                                           const double* __restrict__ c, int nc, double* sm, double& ra, double& rb, double& rc)
+// A load of a device scalar that another launch wrote (PcgState fields), kept in the VECTOR memory queue: issued in front of a
+// kernel's first tile loads it counts on vmcnt with them and returns first.  (The plain form of a uniform address is a scalar
+// load: its wait is the LDS queue's, and the compiler puts it, and a branch on it, in front of everything else.)
+template <typename X>
+__device__ __forceinline__ X vload(const X* p)
 {
-    double va = 0, vb = 0, vc = 0;
-    for (int i = threadIdx.x; i < na; i += 256) va += a[i];
-    for (int i = threadIdx.x; i < nb; i += 256) vb += b[i];
-    for (int i = threadIdx.x; i < nc; i += 256) vc += c[i];
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Sum three partial arrays in one pass; results broadcast to all threads.  sm: 12 doubles.
+// Two halves, so that a kernel can issue the loads next to its own first loads and sum behind its first barrier: one round trip
+// for all of them instead of one per 256 values and array.
+constexpr int SUM3_PRE = 4;   // rounds of 256 values per array that the load half takes into registers (the PCG kernels' counts are <= 1024; k_sum2 folds more)
+struct Sum3Loads {
+    double a[SUM3_PRE], b[SUM3_PRE], c[SUM3_PRE];
+};
+// Branch-free: SUM3_PRE loads per array whatever the counts, the index clamped into the array and the value dropped by the sum half
+// (behind a test of n the compiler pulls the first add up to the load and waits there).  An array with n = 0 is never read, a[0] is
+// read in its place: `a` must be readable even with na = 0.
+__device__ __forceinline__ void sum3_load1(const double* __restrict__ a, int n, double* v)
+{
+    const int last = n > 0 ? n - 1 : 0;
+#pragma unroll
+    for (int k = 0; k < SUM3_PRE; ++k) {
+        const int i = (int)threadIdx.x + 256 * k;
+        v[k] = a[i < last ? i : last];
+    }
+}
+// LATE_C: the load half leaves the third array to the sum half (a second round trip; for a kernel short of registers)
+template <bool LATE_C = false>
+__device__ __forceinline__ void block_sum3_load(const double* __restrict__ a, int na, const double* __restrict__ b, int nb,
+                                                const double* __restrict__ c, int nc, Sum3Loads& v)
+{
+    sum3_load1(a, na, v.a);
+    sum3_load1(nb > 0 ? b : a, nb, v.b);
+    if (!LATE_C) sum3_load1(nc > 0 ? c : a, nc, v.c);
+}
+// per thread i = tid, tid + 256, ... ascending onto +0, only where i < n: the order of the rolled loop this replaces
+__device__ __forceinline__ double sum3_thread(const double* __restrict__ a, int n, const double* v)
+{
+    double s = 0;
+#pragma unroll
+    for (int k = 0; k < SUM3_PRE; ++k)
+        if ((int)threadIdx.x + 256 * k < n) s += v[k];
+    for (int i = (int)threadIdx.x + 256 * SUM3_PRE; i < n; i += 256) s += a[i];   // n > 1024: k_sum2 folding the r.z partials of a level-0 up leg of more than 1024 blocks (solve_mg)
+    return s;
+}
+template <bool LATE_C = false>
+__device__ __forceinline__ void block_sum3_sum(Sum3Loads& v, const double* __restrict__ a, int na, const double* __restrict__ b, int nb,
+                                               const double* __restrict__ c, int nc, double* sm, double& ra, double& rb, double& rc)
+{
+    if (LATE_C) sum3_load1(nc > 0 ? c : a, nc, v.c);
+    double va = sum3_thread(a, na, v.a), vb = sum3_thread(b, nb, v.b), vc = sum3_thread(c, nc, v.c);
     va = wave_sum(va); vb = wave_sum(vb); vc = wave_sum(vc);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     if (lane == 0) { sm[w] = va; sm[4 + w] = vb; sm[8 + w] = vc; }
@@ -215,6 +260,13 @@ __device__ __forceinline__ void block_sum3(const double* __restrict__ a, int na,
     ra = ((sm[0] + sm[1]) + sm[2]) + sm[3];
     rb = ((sm[4] + sm[5]) + sm[6]) + sm[7];
     rc = ((sm[8] + sm[9]) + sm[10]) + sm[11];
+}
+__device__ __forceinline__ void block_sum3(const double* __restrict__ a, int na, const double* __restrict__ b, int nb,
+                                           const double* __restrict__ c, int nc, double* sm, double& ra, double& rb, double& rc)
+{
+    Sum3Loads v;
+    block_sum3_load(a, na, b, nb, c, nc, v);
+    block_sum3_sum(v, a, na, b, nb, c, nc, sm, ra, rb, rc);
 }
 
 // ---- launchers (defined in kernels_*.hip) --------------------------------------------------

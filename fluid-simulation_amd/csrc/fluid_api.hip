@@ -900,7 +900,8 @@ static int solve_mg(fluid_sim* s, bool with_tail)
     // Batching of the convergence poll.  Iteration counts barely change from one solve to the next (Eigen's count i means
     // i + 1 bodies ran), so the first batch runs exactly the bodies the previous solve needed without looking — one poll
     // (head-only launch + 40-byte copy + stream sync, ~50 us) per solve when the count repeats; after that every body is
-    // polled.  Kernels of a finished solve exit at their first instruction, but each still costs a launch.
+    // polled.  Kernels of a finished solve store nothing, but each still costs a launch: SQ, XR and the level-0 legs exit behind
+    // their first barrier (the flag travels with the first tile's loads), the other V-cycle kernels at their first instruction.
     const int pclass = s->pass_class();
     long batch = s->mg_last_iters_k[pclass] > 5 ? s->mg_last_iters_k[pclass] + 1 : 4;
     bool done = false;

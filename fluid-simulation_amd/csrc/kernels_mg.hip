@@ -240,11 +240,13 @@ struct UpTile {
 // a barrier.  `live` = false: a group without a tile of its own walks a valid one for the barriers' sake and stores nothing.
 // rhs(q): the right-hand side at array index q (the plain form loads f[q]; the fused XR + down leg of level 0 forms r - alpha q there);
 // core(q): called once for every unknown of the tile itself, by the thread that forms its residual (the fused leg updates x and r there).
+// dn: the solve's done flag (block-uniform), loaded by the kernel in front of the tile's loads and looked at behind the body's first
+// barrier only: a finished solve costs the block one round of loads and stores nothing, a running one no round trip of its own.
 template <typename T, typename F, int TX, int TY, int TZ, bool RESTRICT, typename IO, int NG, typename RhsFn, typename CoreFn>
 __device__ __forceinline__ void mg_down_body_fn(const MLevel& m, const uint8_t* __restrict__ cnt, T* __restrict__ u,
                                                 T* __restrict__ r, const MLevel& mc, const uint8_t* __restrict__ cnt_c, T* __restrict__ fc,
                                                 const MgCoef<T>* cf, T off, int tile, int gx, int gy, bool live, int col, char* lds, T* sd, T* si,
-                                                int grp, RhsFn rhs, CoreFn core)
+                                                int grp, int dn, RhsFn rhs, CoreFn core)
 {
     typedef DownTile<T, TX, TY, TZ, RESTRICT> D;
     constexpr int H = D::H, AX = D::AX, AY = D::AY, AZ = D::AZ, BX = D::BX, BY = D::BY, BZ = D::BZ, CX = D::CX, CY = D::CY, CZ = D::CZ;
@@ -303,6 +305,7 @@ __device__ __forceinline__ void mg_down_body_fn(const MLevel& m, const uint8_t* 
         }
     }
     __syncthreads();
+    if (dn) return;
     // ---- u2 on region B (branch-free: a non-unknown has n = 0, si[0] = sd[0] = 0 and u1 = 0, so 0 falls out) ----
     if (actB && xb0 < BX) {
         const int a0 = (yb + 1) * AZ + zb + 1 + xb0 * AY * AZ;
@@ -405,9 +408,9 @@ template <typename T, typename F, int TX, int TY, int TZ, bool RESTRICT, typenam
 __device__ __forceinline__ void mg_down_body(const MLevel& m, const uint8_t* __restrict__ cnt, const F* __restrict__ f, T* __restrict__ u,
                                              T* __restrict__ r, const MLevel& mc, const uint8_t* __restrict__ cnt_c, T* __restrict__ fc,
                                              const MgCoef<T>* cf, T off, int tile, int gx, int gy, bool live, int col, char* lds, T* sd, T* si,
-                                             int grp = 0)
+                                             int grp, int dn)
 {
-    mg_down_body_fn<T, F, TX, TY, TZ, RESTRICT, IO, NG>(m, cnt, u, r, mc, cnt_c, fc, cf, off, tile, gx, gy, live, col, lds, sd, si, grp,
+    mg_down_body_fn<T, F, TX, TY, TZ, RESTRICT, IO, NG>(m, cnt, u, r, mc, cnt_c, fc, cf, off, tile, gx, gy, live, col, lds, sd, si, grp, dn,
                                                         [&](size_t q) { return IO::ld(f + q); }, [](size_t) {});
 }
 
@@ -418,12 +421,19 @@ __global__ __launch_bounds__(256 * NG) void k_mg_down(MLevel m, const uint8_t* _
 {
     __shared__ __attribute__((aligned(16))) char lds[DownTile<T, TX, TY, TZ, RESTRICT>::bytes];
     __shared__ T sd[8], si[8];
-    if (ps && ps->done) return;
+    // The leg without the restriction (level 0) takes the flag in the round of its tile's loads; the small legs below it (RESTRICT)
+    // measured no gain from that (profiles/r06/NOTES.md) and keep the exit in front of everything
+    int dn = 0;
+    if constexpr (RESTRICT) {
+        if (ps && ps->done) return;
+    } else {
+        dn = vload(&ps->done);   // (ps: the handle's, always valid)
+    }
     // 1-D launch: virtual tile ids are dealt so that each XCD (own L2) gets a contiguous run of tiles, z fastest;
     // tlist (mostly-air box): only the tiles that hold an unknown are launched, in ascending order (k_mg_tile_flags)
     const int tile = tlist ? tlist[xcd_remap(blockIdx.x, gridDim.x)] : xcd_remap(blockIdx.x, gridDim.x);
     mg_down_body<T, F, TX, TY, TZ, RESTRICT, IoPlain, NG>(m, cnt, f, u, r, mc, cnt_c, fc, &cf, cf.off, tile, gx, gy, true, NG > 1 ? (int)(threadIdx.x & 255) : (int)threadIdx.x,
-                                                          lds, sd, si, NG > 1 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 8) : 0);
+                                                          lds, sd, si, NG > 1 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 8) : 0, dn);
 }
 
 // One tile of the up leg; see mg_down_body for col / grp / lds / sd / si / cf / live.  red: 4 doubles (part_dot only, NG = 1).
@@ -431,7 +441,7 @@ template <typename T, typename F, typename O, int TX, int TY, int TZ, typename I
 __device__ __forceinline__ void mg_up_body(const MLevel& m, const uint8_t* __restrict__ cnt, const F* __restrict__ f, const T* __restrict__ u,
                                            O* __restrict__ out, const MLevel& mc, const T* __restrict__ ec, const MgCoef<T>* cf, T off,
                                            double* __restrict__ part_dot, int tile, int gx, int gy, T wc, const uint8_t* __restrict__ own, bool live,
-                                           int col, char* lds, T* sd, T* si, double* red, int grp = 0, bool pconst = false)
+                                           int col, char* lds, T* sd, T* si, double* red, int grp, bool pconst, int dn)
 {
     // pconst: the correction of a fine cell is its PARENT's value (piecewise-constant prolongation: the Galerkin coarse levels of kernels_gal.hip)
     // own (decomposed run, level 0): the PCG's count bytes — the partial f.out counts the rank's owned unknowns only
@@ -500,6 +510,7 @@ __device__ __forceinline__ void mg_up_body(const MLevel& m, const uint8_t* __res
         if (t < EX * EY * EZ) sE[t] = ee[it];
     }
     __syncthreads();
+    if (dn) return;   // see mg_down_body_fn
     // ---- v0 = u + P e on region A: bilinear in (y,z) once per coarse plane, then linear in x (region A starts at
     //      the even cell i0 - 2 and sE two coarse cells before i0 / 2: fine plane x sits over coarse plane (x>>1)+1) ----
     if (actA) {
@@ -589,10 +600,10 @@ __global__ __launch_bounds__(256, 5) void k_mg_up(MLevel m, const uint8_t* __res
     __shared__ __attribute__((aligned(16))) char lds[UpTile<T, TX, TY, TZ>::bytes];
     __shared__ T sd[8], si[8];
     __shared__ double red[4];
-    if (ps && ps->done) return;
+    const int dn = vload(&ps->done);
     const int tile = tlist ? tlist[xcd_remap(blockIdx.x, gridDim.x)] : xcd_remap(blockIdx.x, gridDim.x);  // see k_mg_down
     mg_up_body<T, F, O, TX, TY, TZ, IoPlain, 1>(m, cnt, f, u, out, mc, ec, &cf, cf.off, part_dot, tile, gx, gy, wc, own, true, (int)threadIdx.x, lds, sd, si, red, 0,
-                                                pconst != 0);
+                                                pconst != 0, dn);
 }
 
 // ---- restriction of the level-0 residual (its down kernel has no room for a halo of 3) -----------------

@@ -171,8 +171,26 @@ __global__ __launch_bounds__(256) void k_pcg_init_guess_l(Grid g, LBox L, const 
 // Start of a CG body (ConjugateGradient.h:45-60 for the first, :75-85 for the others): sums the
 // previous launch's partials (or reads the all-reduced scalars when n_prev == 1), decides
 // convergence identically in every block, returns beta.  false = this block must exit.
-template <typename T>
-__device__ __forceinline__ bool pcg_head(const double* __restrict__ part_rr, const double* __restrict__ part_rz_new,
+// The loads come in two halves: pcg_head_load in front of the kernel's first barrier, next to its tile loads (the partials and
+// ps->thr, which only the first SQ launch of a solve writes), pcg_head behind it.
+struct HeadLoads {
+    Sum3Loads p;
+    double thr;
+};
+// LATE_C: the third array is loaded behind the barrier, in a round of its own (the float SQ kernel: holding all three across the
+// barrier would cost it a wave per SIMD)
+template <bool LATE_C>
+__device__ __forceinline__ void pcg_head_load(const double* __restrict__ part_rr, const double* __restrict__ part_rz_new,
+                                              const double* __restrict__ part_rz_old, int n_prev, int n_rz, const PcgState* ps, int first, HeadLoads& h)
+{
+    h.thr = vload(&ps->thr);   // (first launch: unused)
+    // one sequence of loads for both kinds of launch (pointers and counts chosen first): behind an if / else the compiler waits
+    // for the flag and thr before it issues the partials' loads
+    const double* pb = first ? part_rz_old : part_rz_new;
+    block_sum3_load<LATE_C>(part_rr, n_prev, pb, first ? (first == 2 ? n_prev : 0) : n_rz, part_rz_old, first ? 0 : n_rz, h.p);
+}
+template <typename T, bool LATE_C>
+__device__ __forceinline__ bool pcg_head(HeadLoads& h, const double* __restrict__ part_rr, const double* __restrict__ part_rz_new,
                                          const double* __restrict__ part_rz_old, int n_prev, int n_rz, PcgState* ps, int first, double tol,
                                          double* red, T& beta)
 {
@@ -182,7 +200,7 @@ __device__ __forceinline__ bool pcg_head(const double* __restrict__ part_rr, con
         // b == 0 -> x = 0, done.  first == 2 (started from a guess): part_rz_old holds the partials of r0.r0, and a guess
         // that already meets the threshold ends the solve with 0 iterations (ConjugateGradient.h:51-56)
         double bb, rr0, d2;
-        block_sum3(part_rr, n_prev, part_rz_old, first == 2 ? n_prev : 0, part_rr, 0, red, bb, rr0, d2);
+        block_sum3_sum<LATE_C>(h.p, part_rr, n_prev, part_rz_old, first == 2 ? n_prev : 0, part_rr, 0, red, bb, rr0, d2);
         if (first != 2) rr0 = bb;
         const bool go = bb > 0 && !(rr0 < tol * tol * bb);
         if (blockIdx.x == 0 && tid == 0) {
@@ -194,8 +212,8 @@ __device__ __forceinline__ bool pcg_head(const double* __restrict__ part_rr, con
         return go;
     }
     double rr, rzn, rzo;
-    block_sum3(part_rr, n_prev, part_rz_new, n_rz, part_rz_old, n_rz, red, rr, rzn, rzo);
-    if (rr < ps->thr) {  // break before i++
+    block_sum3_sum<LATE_C>(h.p, part_rr, n_prev, part_rz_new, n_rz, part_rz_old, n_rz, red, rr, rzn, rzo);
+    if (rr < h.thr) {  // break before i++
         if (blockIdx.x == 0 && tid == 0) { ps->rr = rr; ps->done = 1; }
         return false;
     }
@@ -206,8 +224,10 @@ __device__ __forceinline__ bool pcg_head(const double* __restrict__ part_rr, con
 
 // SQ: s' = invdiag r + beta s ; q = A s' ; partial s'.q
 // Thread (ly = tid>>5, kz = tid&31) owns the x-column lx = -1..TX of its (y,z): the x
-// neighbours stay in registers, y/z neighbours go through LDS.  All global loads of the tile
-// are issued BEFORE the partial-sum reduction that yields beta, so both latencies overlap.
+// neighbours stay in registers, y/z neighbours go through LDS.  The head is ONE round of loads: the done flag, the previous
+// launch's partials with ps->thr (pcg_head_load) and the first tile are all issued in front of the first barrier, in that
+// order (the vector queue returns them in order: the reduction that yields beta needs the partials only, the tile's tail may
+// still be in flight); no branch on the flag before the barrier, behind which every wave reads the block's one copy.
 // DIST (decomposed run): the local box is the rank's owned cells + a halo; the count byte carries bit 7 on the one ring
 // of halo cells next to the owned ones (z and s are valid there, so s' is formed there too and no exchange of s' is
 // needed) and is 0 beyond; q and the partial s'.q are formed on the owned cells only.  The scalars are single
@@ -231,9 +251,11 @@ __global__ __launch_bounds__(256) void k_pcg_sq_l(LBox L, const uint8_t* __restr
     __shared__ int s_done;
     __shared__ T sdiag[8], sinv[8];
     const int tid = threadIdx.x;
+    const int dn = vload(&ps->done);
+    HeadLoads hl;
+    constexpr bool LATE_C = sizeof(T) == 4;
+    if constexpr (!AZ) pcg_head_load<LATE_C>(part_rr, part_rz_new, part_rz_old, n_prev, n_rz, ps, first, hl);
     load_coef(sdiag, sinv, cf);
-    // one read per block, broadcast: block 0 of THIS launch may set done while we start
-    if (tid == 0) s_done = ps->done;
 
     const int nty = (L.ny + TY - 1) / TY, ntz = (L.nz + TZ - 1) / TZ;
     const int ntiles = ((L.nx + TX - 1) / TX) * nty * ntz;
@@ -276,6 +298,8 @@ __global__ __launch_bounds__(256) void k_pcg_sq_l(LBox L, const uint8_t* __restr
         }
     };
     if (!sparse && tile < ntiles) issue(tile, true, true);
+    // one copy of the flag per block, broadcast: block 0 of THIS launch may set done while we start
+    if (tid == 0) s_done = dn;
 
     // ---- scalars ------------------------------------------------------------------------------
     T beta = 0;
@@ -283,7 +307,9 @@ __global__ __launch_bounds__(256) void k_pcg_sq_l(LBox L, const uint8_t* __restr
     if (s_done) return;
     // AZ (Chronopoulos-Gear form of the decomposed solve): q = A r and the partials of r.q only — no scalars to derive, s_in unread
     // (the caller passes first = 1), s_out unwritten
-    if (!AZ && !pcg_head<T>(part_rr, part_rz_new, part_rz_old, n_prev, n_rz, ps, first, tol, red, beta)) return;
+    if constexpr (!AZ) {
+        if (!pcg_head<T, LATE_C>(hl, part_rr, part_rz_new, part_rz_old, n_prev, n_rz, ps, first, tol, red, beta)) return;
+    }
 
     double acc = 0;
     while (tile < ntiles) {
@@ -502,8 +528,11 @@ __global__ __launch_bounds__(256) void k_pcg_xr_l(long n2, const uint8_t* __rest
     __shared__ double red[16];
     __shared__ int s_done;
     __shared__ T sdiag[8], sinv[8];
+    // the head's loads in one round, see k_pcg_sq_l: the flag, the partials, then the first loads of the sweep
+    const int dn = vload(&ps->done);
+    Sum3Loads pl;
+    block_sum3_load(part_rz_cur, n_xr, part_pq, n_sq, part_pq, 0, pl);
     load_coef(sdiag, sinv, cf);
-    if (threadIdx.x == 0) s_done = ps->done;
     typedef Vec2<T> V2;
     const V2* x2 = (const V2*)x;
     const V2* r2 = (const V2*)r;
@@ -536,10 +565,11 @@ __global__ __launch_bounds__(256) void k_pcg_xr_l(long n2, const uint8_t* __rest
         }
     };
     issue(i);
+    if (threadIdx.x == 0) s_done = dn;
     __syncthreads();
     if (s_done) return;
     double rz, pq, d3;
-    block_sum3(part_rz_cur, n_xr, part_pq, n_sq, part_pq, 0, red, rz, pq, d3);
+    block_sum3_sum(pl, part_rz_cur, n_xr, part_pq, n_sq, part_pq, 0, red, rz, pq, d3);
     if (!(pq > 0) || !(rz == rz)) {  // not SPD / NaN: stop instead of spreading NaNs
         if (blockIdx.x == 0 && threadIdx.x == 0) { ps->breakdown = 1; ps->done = 1; }
         return;
@@ -599,8 +629,11 @@ __global__ __launch_bounds__(256) void k_pcg_xr_t(LBox L, const uint8_t* __restr
     __shared__ double red[16];
     __shared__ int s_done;
     __shared__ T sdiag[8], sinv[8];
+    // the head's loads in one round, see k_pcg_sq_l: the flag, the partials, then the first loads of the sweep
+    const int dn = vload(&ps->done);
+    Sum3Loads pl;
+    block_sum3_load(part_rz_cur, n_xr, part_pq, n_sq, part_pq, 0, pl);
     load_coef(sdiag, sinv, cf);
-    if (threadIdx.x == 0) s_done = ps->done;
     const int nty = (L.ny + TY - 1) / TY, ntz = (L.nz + TZ - 1) / TZ;
     const long sx = (long)L.Ly * L.Lz;
     const int ly = threadIdx.x >> 5, kz = threadIdx.x & 31;
@@ -619,10 +652,11 @@ __global__ __launch_bounds__(256) void k_pcg_xr_t(LBox L, const uint8_t* __restr
     };
     int lidx = xcd_remap(blockIdx.x, gridDim.x);
     if (lidx < nlist) issue(tlist[lidx]);
+    if (threadIdx.x == 0) s_done = dn;
     __syncthreads();
     if (s_done) return;
     double rz, pq, d3;
-    block_sum3(part_rz_cur, n_xr, part_pq, n_sq, part_pq, 0, red, rz, pq, d3);
+    block_sum3_sum(pl, part_rz_cur, n_xr, part_pq, n_sq, part_pq, 0, red, rz, pq, d3);
     if (!(pq > 0) || !(rz == rz)) {  // not SPD / NaN: stop instead of spreading NaNs
         if (blockIdx.x == 0 && threadIdx.x == 0) { ps->breakdown = 1; ps->done = 1; }
         return;
@@ -672,8 +706,11 @@ __global__ __launch_bounds__(256) void k_pcg_xr_rows(LBox L, const uint8_t* __re
     __shared__ double red[16];
     __shared__ int s_done;
     __shared__ T sdiag[8], sinv[8];
+    // the head's loads in one round, see k_pcg_sq_l: the flag, the partials, then the first loads of the sweep
+    const int dn = vload(&ps->done);
+    Sum3Loads pl;
+    block_sum3_load(part_rz_cur, n_xr, part_pq, n_sq, part_pq, 0, pl);
     load_coef(sdiag, sinv, cf);
-    if (threadIdx.x == 0) s_done = ps->done;
     const int ntz = (L.nz + 31) / 32;
     const int sub = threadIdx.x >> 5, kz = threadIdx.x & 31;
     // U rows in flight per thread.  Every load is unconditional (a list index past the end is clamped to the last row and the
@@ -703,10 +740,11 @@ __global__ __launch_bounds__(256) void k_pcg_xr_rows(LBox L, const uint8_t* __re
         issue(u, rown[u]);
         rown[u] = row_at(ri + (U + u) * stride);
     }
+    if (threadIdx.x == 0) s_done = dn;
     __syncthreads();
     if (s_done) return;
     double rz, pq, d3;
-    block_sum3(part_rz_cur, n_xr, part_pq, n_sq, part_pq, 0, red, rz, pq, d3);
+    block_sum3_sum(pl, part_rz_cur, n_xr, part_pq, n_sq, part_pq, 0, red, rz, pq, d3);
     if (!(pq > 0) || !(rz == rz)) {  // not SPD / NaN: stop instead of spreading NaNs
         if (blockIdx.x == 0 && threadIdx.x == 0) { ps->breakdown = 1; ps->done = 1; }
         return;
