@@ -163,6 +163,10 @@ SYMBOLS = [
     ("fluid_sdf_stats", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("fluid_sdf_to_dense", C.c_int, [C.POINTER(SdfGridC), _P, _P]),
     ("fluid_write_vdb_sdf", C.c_int, [C.c_char_p, C.POINTER(SdfGridC), C.c_int32]),
+    ("fluid_dist_sdf_snapshot", C.c_int, [_P, C.POINTER(SdfParams)]),
+    ("fluid_dist_sdf_wait", C.c_int, [_P, C.POINTER(SdfGridC)]),
+    ("fluid_dist_sdf_stats", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("fluid_sdf_grids_merge", C.c_int64, [C.POINTER(SdfGridC), C.c_int32, C.c_int64, _P, _P, _P]),
     # the snow-MPM step (include/mpm_hip.h)
     ("mpm_default_params", C.c_int, [C.POINTER(MpmParams)]),
     ("mpm_create", C.c_int, [C.POINTER(MpmParams), C.POINTER(_P)]),

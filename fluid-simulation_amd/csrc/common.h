@@ -339,8 +339,9 @@ struct SdfGeom {
     __host__ __device__ inline long leaves() const { return (long)nl[0] * nl[1] * nl[2]; }
     __host__ __device__ inline long cells() const { return (long)bnx * bny * bnz; }
 };
-void launch_sdf_bbox(hipStream_t st, long n, Particles p, int lo, int hi, int* box);   // box[6]: min, max of the counted base cells
-void launch_sdf_count(hipStream_t st, long n, Particles p, const SdfGeom& g, int* cnt, int* place);
+// live: entries with pid == PID_DEAD (a decomposed handle's served ghosts and removed particles) are in no cell
+void launch_sdf_bbox(hipStream_t st, long n, Particles p, int lo, int hi, int* box, bool live = false);   // box[6]: min, max of the counted base cells
+void launch_sdf_count(hipStream_t st, long n, Particles p, const SdfGeom& g, int* cnt, int* place, bool live = false);
 void launch_sdf_scatter(hipStream_t st, long n, Particles p, const SdfGeom& g, const int* start, const int* place, double* sx, double* sy,
                         double* sz);
 void launch_sdf_search(hipStream_t st, const SdfGeom& g, const int* start, const double* sx, const double* sy, const double* sz, float* tv,

@@ -1744,6 +1744,7 @@ int dist_rebalance(fluid_sim* s)
     t->prof_every = s->prof_every;
     for (int c = 0; c < FLUID_PROF_COUNT; ++c) std::swap(t->prof[c], s->prof[c]);
     output_move(s, t);      // snapshots handed out or in flight stay valid: their buffers are the state's, not the window's
+    sdf_move(s, t);         // ... and so do the level-set lists (fluid_dist_sdf_wait)
     std::swap(*s, *t);      // the caller's handle now holds the new window
     fluid_destroy(t);       // ... and this one the old
     return FLUID_OK;

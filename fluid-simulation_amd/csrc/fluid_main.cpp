@@ -32,6 +32,11 @@
 // non-zero leaves of the block it owned — the main thread waits for all blocks, releases the next step, merges the lists
 // (fluid_leaf_grids_merge, two merge buffers in turn) and hands the grid to the same writer thread: the same files.  The stdout
 // lines are rank 0's numbers.  FLUID_SOURCE_EVERY and FLUID_OUT_DENSE=1 are refused with FLUID_BLOCKS.
+//   FLUID_BLOCKS_SURFACE=R,W (unset: off; with FLUID_BLOCKS only) — additionally simulation/surface<i>.vdb per step, the file
+// FLUID_OUT_SURFACE writes on one GPU: every block thread takes fluid_dist_sdf_snapshot of its live particles after its step and
+// waits for it, the main thread merges the blocks' lists (fluid_sdf_grids_merge, two merge buffers in turn) and hands the grid to
+// the writer thread beside the density job.  Refused without FLUID_BLOCKS, malformed, with an empty FLUID_OUT and with
+// FLUID_STEPS=0, before any handle is created.  Stdout and every other file are what they are without it.
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -153,6 +158,8 @@ struct BlockCfg {
     double rb_ratio = 1.5;
     std::string outdir;
     bool raw_f32 = false;
+    bool surface = false;     // FLUID_BLOCKS_SURFACE
+    fluid_sdf_params_t sp{};
 };
 
 // What the main thread and the block threads share: `go` = steps released so far, done[i & 1] = blocks that finished step i.
@@ -210,6 +217,8 @@ static int run_blocks(const BlockCfg& cfg, const std::vector<double>& pos, int64
     }
     const bool output = !cfg.outdir.empty() && steps > 0;
     std::vector<fluid_leaf_grid_t> part[2] = {std::vector<fluid_leaf_grid_t>(R), std::vector<fluid_leaf_grid_t>(R)};
+    const bool surface = output && cfg.surface;
+    std::vector<fluid_sdf_grid_t> spart[2] = {std::vector<fluid_sdf_grid_t>(R), std::vector<fluid_sdf_grid_t>(R)};
     std::vector<fluid_step_stats_t> st0(2);   // rank 0's stats of step i in st0[i & 1]
     auto block = [&](int r) {
         fluid_sim_t* sim = nullptr;
@@ -240,6 +249,9 @@ static int run_blocks(const BlockCfg& cfg, const std::vector<double>& pos, int64
             if (fluid_step(sim, &st) != FLUID_OK) { err("fluid_step"); break; }
             // (the copy of this step's list is the only thing waited for here: the next step starts when the main thread says so)
             if (output && fluid_dist_output_wait(sim, &part[i & 1][r]) != FLUID_OK) { err("fluid_dist_output_wait"); break; }
+            // the surface of this block's live particles as the step left them (exact whether or not the step moved the planes)
+            if (surface && fluid_dist_sdf_snapshot(sim, &cfg.sp) != FLUID_OK) { err("fluid_dist_sdf_snapshot"); break; }
+            if (surface && fluid_dist_sdf_wait(sim, &spart[i & 1][r]) != FLUID_OK) { err("fluid_dist_sdf_wait"); break; }
             {
                 std::lock_guard<std::mutex> lk(sy.m);
                 if (r == 0) st0[i & 1] = st;
@@ -290,6 +302,9 @@ static int run_blocks(const BlockCfg& cfg, const std::vector<double>& pos, int64
     // the merged grid of step i lives in buffer i & 1 until the writer thread has put grid i on disk
     std::vector<int32_t> m_org[2];
     std::vector<float> m_val[2];
+    std::vector<int32_t> s_org[2];
+    std::vector<float> s_val[2];
+    std::vector<uint64_t> s_act[2];
     double dt = cfg.prm.max_dt, simulationTime = 0;
     auto release = [&](int upto) {
         {
@@ -327,7 +342,20 @@ static int run_blocks(const BlockCfg& cfg, const std::vector<double>& pos, int64
         auto& val = m_val[i & 1];
         if (org.size() < 3 * (size_t)k) { org.resize(3 * (size_t)k + 3 * 64); val.resize(512 * ((size_t)k + 64)); }
         if (fluid_leaf_grids_merge(part[i & 1].data(), R, k, org.data(), val.data()) != k) { sy.fail("fluid_leaf_grids_merge: the blocks' leaf lists do not merge"); break; }
-        lw.submit(i, fluid_leaf_grid_t{n, (int32_t)k, k ? org.data() : nullptr, k ? val.data() : nullptr});
+        fluid_sdf_grid_t sg{};
+        if (surface) {
+            const auto& sp = spart[i & 1];
+            const int64_t ks = fluid_sdf_grids_merge(sp.data(), R, 0, nullptr, nullptr, nullptr);
+            if (ks < 0) { sy.fail("fluid_sdf_grids_merge: the blocks' surface lists do not merge"); break; }
+            auto& so = s_org[i & 1];
+            auto& sv = s_val[i & 1];
+            auto& sa = s_act[i & 1];
+            if (so.size() < 3 * (size_t)ks) { so.resize(3 * ((size_t)ks + 64)); sv.resize(512 * ((size_t)ks + 64)); sa.resize(8 * ((size_t)ks + 64)); }
+            if (ks && fluid_sdf_grids_merge(sp.data(), R, ks, so.data(), sv.data(), sa.data()) != ks) { sy.fail("fluid_sdf_grids_merge: the blocks' surface lists do not merge"); break; }
+            sg = fluid_sdf_grid_t{n, (int32_t)ks, sp[0].background, sp[0].radius, sp[0].half_width, ks ? so.data() : nullptr, ks ? sv.data() : nullptr,
+                                  ks ? sa.data() : nullptr};
+        }
+        lw.submit(i, fluid_leaf_grid_t{n, (int32_t)k, k ? org.data() : nullptr, k ? val.data() : nullptr}, surface ? &sg : nullptr);
     }
     bool ok = !sy.failed;
     if (output) {
@@ -369,7 +397,7 @@ int main(int, char**)
             return 1;
         }
         if ((blocks && *blocks) || out_dense) {
-            std::cerr << "FLUID_OUT_SURFACE cannot be combined with " << (out_dense ? "FLUID_OUT_DENSE=1" : "FLUID_BLOCKS (the surface needs one GPU)") << std::endl;
+            std::cerr << "FLUID_OUT_SURFACE cannot be combined with " << (out_dense ? "FLUID_OUT_DENSE=1" : "FLUID_BLOCKS (a block run takes FLUID_BLOCKS_SURFACE=R,W)") << std::endl;
             return 1;
         }
         if (outdir.empty() || steps <= 0) {
@@ -378,6 +406,22 @@ int main(int, char**)
         }
     }
     BlockCfg bc;
+    if (const char* bs = getenv("FLUID_BLOCKS_SURFACE"); bs && *bs) {
+        char tail = 0;
+        if (sscanf(bs, "%lf,%lf%c", &bc.sp.radius, &bc.sp.half_width, &tail) != 2) {
+            std::cerr << "FLUID_BLOCKS_SURFACE must be R,W (sphere radius and band half width in voxels), e.g. 1.5,2.5" << std::endl;
+            return 1;
+        }
+        if (!(blocks && *blocks)) {
+            std::cerr << "FLUID_BLOCKS_SURFACE needs FLUID_BLOCKS=AxBxC (one GPU takes FLUID_OUT_SURFACE=R,W)" << std::endl;
+            return 1;
+        }
+        if (outdir.empty() || steps <= 0) {
+            std::cerr << "FLUID_BLOCKS_SURFACE needs an output directory and at least one step (FLUID_OUT is empty or FLUID_STEPS is 0)" << std::endl;
+            return 1;
+        }
+        bc.surface = true;
+    }
     if (blocks && *blocks) {
         char tail = 0;
         if (sscanf(blocks, "%dx%dx%d%c", &bc.dims[0], &bc.dims[1], &bc.dims[2], &tail) != 3 || bc.dims[0] < 1 || bc.dims[1] < 1 || bc.dims[2] < 1 ||

@@ -10,6 +10,12 @@
 // slot is written by snapshot q, q + 2, ..., so what fluid_sdf_wait handed out stays valid until the second following snapshot.
 // The particle arrays are only read; key, slot, cell_count, cell_start, the second particle buffer and every field stay as they
 // are, and `binned` keeps holding: the next step's sort starts from what FLIPadvect left, as if no snapshot had been taken.
+//
+// fluid_dist_sdf_snapshot is the same sequence on a decomposed handle ("liquid surface (decomposed runs)"): the rank's LIVE
+// particles (k_sdf_bbox<true> / k_sdf_count<true> pass over the entries marked PID_DEAD), global coordinates, every leaf they reach
+// whether the rank owns it or not.  Rank-local: no transport call; the ranks' lists merge on the host (fluid_sdf_grids_merge,
+// vdb_sdf_writer.cpp).  The state is one per handle and shared by both forms; when the cut planes move it is handed to the new
+// window's handle (sdf_move), so lists handed out or in flight stay valid.
 #include "sim.h"
 
 using namespace fl;
@@ -45,7 +51,7 @@ struct SdfState {
 
 #define SDF_GUARD(s)                                                     \
     if (!(s)) return fail(FLUID_ERR_ARG, "null handle");                 \
-    if ((s)->dist) return fail(FLUID_ERR_STATE, "level-set snapshots are single-GPU only: a decomposed handle holds a block of the particles")
+    if ((s)->dist) return fail(FLUID_ERR_STATE, "level-set snapshots are single-GPU only: a decomposed handle holds a block of the particles (fluid_dist_sdf_*)")
 
 static int sdf_init(fluid_sim* s)
 {
@@ -136,11 +142,9 @@ static int sdf_grow(SdfSlot& q, size_t n)
     return FLUID_OK;
 }
 
-extern "C" {
-
-int fluid_sdf_snapshot(fluid_sim_t* s, const fluid_sdf_params_t* p)
+// bbox -> count, scan, scatter -> search -> scan -> pack -> copy; a decomposed handle (s->dist) bins its live entries only
+static int sdf_capture(fluid_sim* s, const fluid_sdf_params_t* p)
 {
-    SDF_GUARD(s);
     if (!p) return fail(FLUID_ERR_ARG, "null argument");
     const float R = (float)p->radius, w = (float)p->half_width;
     const float mx = R + w;
@@ -163,7 +167,7 @@ int fluid_sdf_snapshot(fluid_sim_t* s, const fluid_sdf_params_t* p)
     int n = 0;
     int* box = o->h_small;
     if (s->np > 0) {
-        launch_sdf_bbox(s->st, s->np, live, g.lo, g.hi, o->d_small);
+        launch_sdf_bbox(s->st, s->np, live, g.lo, g.hi, o->d_small, s->dist);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(o->h_small, o->d_small, 6 * sizeof(int), hipMemcpyDeviceToHost, s->st));
         HIPCHK(hipStreamSynchronize(s->st));
@@ -183,7 +187,7 @@ int fluid_sdf_snapshot(fluid_sim_t* s, const fluid_sdf_params_t* p)
         if ((rc = sdf_scratch(o, cells + 1, s->np, leaves))) return rc;
         double *sx = o->spos, *sy = o->spos + o->part_cap, *sz = o->spos + 2 * o->part_cap;
         HIPCHK(hipMemsetAsync(o->cnt, 0, (size_t)(cells + 1) * sizeof(int), s->st));
-        launch_sdf_count(s->st, s->np, live, g, o->cnt, o->place);
+        launch_sdf_count(s->st, s->np, live, g, o->cnt, o->place, s->dist);
         launch_exclusive_scan(s->st, o->cnt, o->start, cells + 1, o->cell_sums, o->d_small + 6);   // start[cells] = the counted particles
         launch_sdf_scatter(s->st, s->np, live, g, o->start, o->place, sx, sy, sz);
         launch_sdf_search(s->st, g, o->start, sx, sy, sz, o->tv, o->tm, o->flags, o->count_visits ? o->visits : nullptr);
@@ -222,9 +226,8 @@ int fluid_sdf_snapshot(fluid_sim_t* s, const fluid_sdf_params_t* p)
     return FLUID_OK;
 }
 
-int fluid_sdf_wait(fluid_sim_t* s, fluid_sdf_grid_t* out)
+static int sdf_wait(fluid_sim* s, fluid_sdf_grid_t* out)
 {
-    SDF_GUARD(s);
     if (!out) return fail(FLUID_ERR_ARG, "null argument");
     SdfState* o = s->sdf;
     if (!o || o->n_wait >= o->n_snap) return fail(FLUID_ERR_STATE, "no level-set snapshot is outstanding");
@@ -243,15 +246,59 @@ int fluid_sdf_wait(fluid_sim_t* s, fluid_sdf_grid_t* out)
     return FLUID_OK;
 }
 
-int fluid_sdf_stats(fluid_sim_t* s, int64_t* leaves_in_grid, int64_t* leaves_listed, int64_t* bytes_to_host)
+static int sdf_stats(fluid_sim* s, int64_t* leaves_in_grid, int64_t* leaves_listed, int64_t* bytes_to_host)
 {
-    SDF_GUARD(s);
     const int lo = s->g.lo, hi = s->g.hi;
     const int64_t nl = ((hi & ~7) - (lo & ~7)) / 8 + 1;
     if (leaves_in_grid) *leaves_in_grid = nl * nl * nl;
     if (leaves_listed) *leaves_listed = s->sdf ? s->sdf->last_leaves : 0;
     if (bytes_to_host) *bytes_to_host = s->sdf ? s->sdf->last_bytes : 0;
     return FLUID_OK;
+}
+
+void fl::sdf_move(fluid_sim* from, fluid_sim* to)
+{
+    sdf_free(to);
+    to->sdf = from->sdf;
+    from->sdf = nullptr;
+}
+
+extern "C" {
+
+int fluid_sdf_snapshot(fluid_sim_t* s, const fluid_sdf_params_t* p)
+{
+    SDF_GUARD(s);
+    return sdf_capture(s, p);
+}
+
+int fluid_sdf_wait(fluid_sim_t* s, fluid_sdf_grid_t* out)
+{
+    SDF_GUARD(s);
+    return sdf_wait(s, out);
+}
+
+int fluid_sdf_stats(fluid_sim_t* s, int64_t* leaves_in_grid, int64_t* leaves_listed, int64_t* bytes_to_host)
+{
+    SDF_GUARD(s);
+    return sdf_stats(s, leaves_in_grid, leaves_listed, bytes_to_host);
+}
+
+int fluid_dist_sdf_snapshot(fluid_sim_t* s, const fluid_sdf_params_t* p)
+{
+    if (!s) return fail(FLUID_ERR_ARG, "null handle");
+    return sdf_capture(s, p);
+}
+
+int fluid_dist_sdf_wait(fluid_sim_t* s, fluid_sdf_grid_t* out)
+{
+    if (!s) return fail(FLUID_ERR_ARG, "null handle");
+    return sdf_wait(s, out);
+}
+
+int fluid_dist_sdf_stats(fluid_sim_t* s, int64_t* leaves_in_grid, int64_t* leaves_listed, int64_t* bytes_to_host)
+{
+    if (!s) return fail(FLUID_ERR_ARG, "null handle");
+    return sdf_stats(s, leaves_in_grid, leaves_listed, bytes_to_host);
 }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
 // Narrow-band level set of the particles for gfx950 (wave64): the signed distance to the union of spheres of radius R around the
 // particles, clipped to a band of half width w, as the leaves of OpenVDB's tree (include/fluid_hip.h, "liquid surface";
 // fluid_sdf.hip).  The value of a voxel is a function of the MINIMUM squared distance over the particles, so no order is involved:
-//   bin      the particles whose base cell round(p) lies in the grid are counted per cell of their bounding box (integer atomics
+//   bin      the particles (of a decomposed handle: the live ones, k_sdf_bbox<true> / k_sdf_count<true>) whose base cell round(p)
+//            lies in the grid are counted per cell of their bounding box (integer atomics
 //            hand out a place inside the cell: which place does not matter to a minimum), the counts are scanned, the positions
 //            are scattered into cell order (z fastest), all in scratch of the snapshot's own;
 //   search   one 512-thread block per leaf of the box dilated by 4 cells: the cell starts of the leaf's 16^3 neighbourhood go to
@@ -37,12 +38,17 @@ __global__ void k_sdf_box_init(int* __restrict__ box)
 }
 
 // box[0..2] = min, box[3..5] = max of the counted particles' base cells (integer min / max: order-free)
+// LIVE (here and in k_sdf_count): the arrays of a decomposed handle, where an entry with pid == PID_DEAD is a ghost that was served
+// or a particle a sink removed, with a stale position: it is in no cell.  The one-GPU form never reads pid.
+template <bool LIVE>
 __global__ __launch_bounds__(256) void k_sdf_bbox(long n, const double* __restrict__ px, const double* __restrict__ py,
-                                                  const double* __restrict__ pz, int lo, int hi, int* __restrict__ box)
+                                                  const double* __restrict__ pz, int lo, int hi, int* __restrict__ box,
+                                                  const uint32_t* __restrict__ pid)
 {
     int mn[3] = {INT_MAX, INT_MAX, INT_MAX}, mx[3] = {INT_MIN, INT_MIN, INT_MIN};
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         int c[3];
+        if (LIVE && pid[i] == PID_DEAD) continue;
         if (!sdf_cell(px[i], py[i], pz[i], lo, hi, c[0], c[1], c[2])) continue;
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
@@ -73,12 +79,19 @@ __device__ __forceinline__ long sdf_box_index(const SdfGeom& g, int cx, int cy, 
     return ((long)(cx - g.bx0) * g.bny + (cy - g.by0)) * g.bnz + (cz - g.bz0);
 }
 
-// cnt[cell]++ over the box; place[i] = the particle's place inside its cell (-1: not counted)
+// cnt[cell]++ over the box; place[i] = the particle's place inside its cell (-1: not counted, and k_sdf_scatter passes it over:
+// a dead entry is never scattered)
+template <bool LIVE>
 __global__ __launch_bounds__(256) void k_sdf_count(long n, const double* __restrict__ px, const double* __restrict__ py,
-                                                   const double* __restrict__ pz, SdfGeom g, int* __restrict__ cnt, int* __restrict__ place)
+                                                   const double* __restrict__ pz, SdfGeom g, int* __restrict__ cnt, int* __restrict__ place,
+                                                   const uint32_t* __restrict__ pid)
 {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
+    if (LIVE && pid[i] == PID_DEAD) {
+        place[i] = -1;
+        return;
+    }
     int cx, cy, cz;
     place[i] = sdf_cell(px[i], py[i], pz[i], g.lo, g.hi, cx, cy, cz) ? atomicAdd(&cnt[sdf_box_index(g, cx, cy, cz)], 1) : -1;
 }
@@ -208,17 +221,21 @@ __global__ __launch_bounds__(256) void k_sdf_pack(SdfGeom g, long nrange, const 
     if (lane < 3) origin[s * 3 + lane] = g.L0 + 8 * (g.l0[lane] + (lane == 0 ? jx : lane == 1 ? jy : jz));
 }
 
-void launch_sdf_bbox(hipStream_t st, long n, Particles p, int lo, int hi, int* box)
+void launch_sdf_bbox(hipStream_t st, long n, Particles p, int lo, int hi, int* box, bool live)
 {
     hipLaunchKernelGGL(k_sdf_box_init, dim3(1), dim3(64), 0, st, box);
     if (n <= 0) return;
     const long nb = (n + 255) / 256;
-    hipLaunchKernelGGL(k_sdf_bbox, dim3((unsigned)(nb < 2048 ? nb : 2048)), dim3(256), 0, st, n, p.px, p.py, p.pz, lo, hi, box);
+    const dim3 grid((unsigned)(nb < 2048 ? nb : 2048));
+    if (live) hipLaunchKernelGGL(k_sdf_bbox<true>, grid, dim3(256), 0, st, n, p.px, p.py, p.pz, lo, hi, box, p.pid);
+    else hipLaunchKernelGGL(k_sdf_bbox<false>, grid, dim3(256), 0, st, n, p.px, p.py, p.pz, lo, hi, box, (const uint32_t*)nullptr);
 }
 
-void launch_sdf_count(hipStream_t st, long n, Particles p, const SdfGeom& g, int* cnt, int* place)
+void launch_sdf_count(hipStream_t st, long n, Particles p, const SdfGeom& g, int* cnt, int* place, bool live)
 {
-    hipLaunchKernelGGL(k_sdf_count, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, p.px, p.py, p.pz, g, cnt, place);
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (live) hipLaunchKernelGGL(k_sdf_count<true>, grid, dim3(256), 0, st, n, p.px, p.py, p.pz, g, cnt, place, p.pid);
+    else hipLaunchKernelGGL(k_sdf_count<false>, grid, dim3(256), 0, st, n, p.px, p.py, p.pz, g, cnt, place, (const uint32_t*)nullptr);
 }
 
 void launch_sdf_scatter(hipStream_t st, long n, Particles p, const SdfGeom& g, const int* start, const int* place, double* sx, double* sy,

@@ -250,6 +250,7 @@ void output_move(fluid_sim* from, fluid_sim* to);   // re-balance: slots, counte
 
 // fluid_sdf.hip
 void sdf_free(fluid_sim* s);         // waits for the copies in flight, frees the scratch, the staging and the pinned buffers
+void sdf_move(fluid_sim* from, fluid_sim* to);      // re-balance: slots, streams, scratch and counters go to the new window's handle
 
 // fluid_dist.hip
 int dist_step(fluid_sim* s, fluid_step_stats_t* stats);

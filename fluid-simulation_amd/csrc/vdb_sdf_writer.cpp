@@ -19,6 +19,7 @@
 // Parity with the library is unpinned, as for the density files; tests/test_sdf_host.py re-reads the files with tests/vdb_reader.py.
 #include <zlib.h>
 
+#include <algorithm>
 #include <climits>
 #include <cstdint>
 #include <cstdio>
@@ -157,6 +158,75 @@ int fluid_sdf_to_dense(const fluid_sdf_grid_t* g, float* values, uint8_t* active
                 }
     }
     return FLUID_OK;
+}
+
+// Host only ("liquid surface (decomposed runs)").  A k-way merge of ascending lists: the smallest origin at the parts' cursors
+// is the next merged leaf, every part that lists it is folded in, in part order.  Per voxel the three states are ordered
+// inactive -bg < active (by value) < inactive +bg: the state decides first, the float value only among active voxels (a plain
+// minimum of the values with the masks ORed would leave a -bg voxel active).
+int64_t fluid_sdf_grids_merge(const fluid_sdf_grid_t* parts, int32_t n_parts, int64_t cap_leaves, int32_t* origin, float* values, uint64_t* active)
+{
+    const bool count_only = !origin && !values && !active;
+    if (!parts || n_parts < 1 || (!count_only && (!origin || !values || !active))) return -FLUID_ERR_ARG;
+    const float bg = parts[0].background;
+    for (int p = 0; p < n_parts; ++p) {
+        const fluid_sdf_grid_t& g = parts[p];
+        if (check_list(&g) != FLUID_OK || g.n != parts[0].n || !same_bits(g.background, bg) || !same_bits(g.radius, parts[0].radius) ||
+            !same_bits(g.half_width, parts[0].half_width))
+            return -FLUID_ERR_ARG;
+        for (int l = 0; l < g.n_leaves; ++l)
+            if (leaf_code(g.values + 512 * (size_t)l, g.active + 8 * (size_t)l, bg) < 0) return -FLUID_ERR_ARG;
+    }
+    auto before = [](const int32_t* a, const int32_t* b) { return a[0] != b[0] ? a[0] < b[0] : a[1] != b[1] ? a[1] < b[1] : a[2] < b[2]; };
+    std::vector<int32_t> cur((size_t)n_parts);
+    int64_t count = 0;
+    for (int pass = 0; pass < (count_only ? 1 : 2); ++pass) {
+        if (pass == 1 && count > cap_leaves) return -FLUID_ERR_ARG;
+        std::fill(cur.begin(), cur.end(), 0);
+        count = 0;
+        for (;;) {
+            const int32_t* o = nullptr;   // the smallest origin at the parts' cursors
+            for (int p = 0; p < n_parts; ++p) {
+                if (cur[p] >= parts[p].n_leaves) continue;
+                const int32_t* c = parts[p].origin + 3 * (size_t)cur[p];
+                if (!o || before(c, o)) o = c;
+            }
+            if (!o) break;
+            const int32_t o3[3] = {o[0], o[1], o[2]};
+            float* acc = pass == 1 ? values + 512 * (size_t)count : nullptr;
+            uint64_t* am = pass == 1 ? active + 8 * (size_t)count : nullptr;
+            int n_in = 0;
+            for (int p = 0; p < n_parts; ++p) {
+                if (cur[p] >= parts[p].n_leaves) continue;
+                const int32_t* c = parts[p].origin + 3 * (size_t)cur[p];
+                if (c[0] != o3[0] || c[1] != o3[1] || c[2] != o3[2]) continue;
+                const float* v = parts[p].values + 512 * (size_t)cur[p];
+                const uint64_t* m = parts[p].active + 8 * (size_t)cur[p];
+                cur[p]++;
+                if (pass == 0) continue;
+                if (n_in++ == 0) {
+                    memcpy(acc, v, 512 * sizeof(float));
+                    memcpy(am, m, 8 * sizeof(uint64_t));
+                    continue;
+                }
+                for (int i = 0; i < 512; ++i) {
+                    const bool a_in = bit(m, i), a_acc = bit(am, i);
+                    if (!a_acc && !same_bits(acc[i], bg)) continue;    // inactive -bg so far: it stays
+                    if (!a_in) {
+                        if (same_bits(v[i], bg)) continue;             // this part has nothing to say
+                        acc[i] = v[i];                                 // inactive -bg beats whatever was there
+                        am[i >> 6] &= ~(1ull << (i & 63));
+                    } else if (!a_acc || v[i] < acc[i]) {              // active: the smallest value, the first part's bits on a tie
+                        acc[i] = v[i];
+                        am[i >> 6] |= 1ull << (i & 63);
+                    }
+                }
+            }
+            if (pass == 1) memcpy(origin + 3 * (size_t)count, o3, sizeof o3);
+            count++;
+        }
+    }
+    return count;
 }
 
 int fluid_write_vdb_sdf(const char* path, const fluid_sdf_grid_t* g, int32_t compression)

@@ -15,8 +15,8 @@ import threading
 
 import numpy as np
 
-from ._lib import lib, check, Params, StepStats, LeafGridC, Source
-from .sim import FluidSim, grid_bounds, merge_leaf_grids, _leaf_grid_copy  # noqa: F401
+from ._lib import lib, check, Params, StepStats, LeafGridC, Source, SdfParams, SdfGridC
+from .sim import FluidSim, grid_bounds, merge_leaf_grids, _leaf_grid_copy, merge_sdf_grids, _sdf_grid_copy  # noqa: F401
 
 EXCHANGE_T = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                          C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p)
@@ -408,6 +408,23 @@ class DistFluidSim(FluidSim):
         """step() itself snapshots the owned block at the end of every step t with t % k == 0 (0 = off), before a re-balancing
         moves the planes; the same k on every rank, and every rank waits alike."""
         check(lib.fluid_dist_output_every(self._h, int(k)))
+
+    # ---- liquid surface of this rank's live particles (include/fluid_hip.h, "liquid surface (decomposed runs)"); rank-local ----
+    def sdf_snapshot(self, radius, half_width):
+        """Enqueue the level set of this rank's live particles as they are now (global origins; every leaf they reach)."""
+        p = SdfParams(float(radius), float(half_width))
+        check(lib.fluid_dist_sdf_snapshot(self._h, C.byref(p)))
+
+    def sdf_wait(self):
+        """The oldest level-set snapshot not yet waited for, as an SdfGrid (merge_sdf_grids joins the ranks')."""
+        g = SdfGridC()
+        check(lib.fluid_dist_sdf_wait(self._h, C.byref(g)))
+        return _sdf_grid_copy(g)
+
+    def sdf_stats(self):
+        v = [C.c_int64() for _ in range(3)]
+        check(lib.fluid_dist_sdf_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("leaves_in_grid", "leaves_listed", "bytes_to_host"), (x.value for x in v)))
 
     # ---- particle sources and sinks (include/fluid_hip.h, "of a decomposed run"): FluidSim's signatures, global boxes; the set
     # calls are collective (the same slots on every rank before the same step), ids are never renumbered ----

@@ -140,6 +140,39 @@ class SdfGrid:
                         self.values.ctypes.data, words.ctypes.data), words
 
 
+def _sdf_grid_copy(g):
+    """SdfGrid copied out of the buffers a fluid_sdf_grid_t points into."""
+    k = g.n_leaves
+    if k == 0:
+        return SdfGrid(g.n, np.empty((0, 3), np.int32), np.empty((0, 512), np.float32), np.empty((0, 512), bool),
+                       g.background, g.radius, g.half_width)
+    org = np.ctypeslib.as_array(C.cast(g.origin, C.POINTER(C.c_int32)), shape=(k, 3)).copy()
+    val = np.ctypeslib.as_array(C.cast(g.values, C.POINTER(C.c_float)), shape=(k, 512)).copy()
+    words = np.ctypeslib.as_array(C.cast(g.active, C.POINTER(C.c_uint64)), shape=(k, 8)).copy()
+    act = np.unpackbits(words.view(np.uint8), axis=1, bitorder="little").astype(bool)
+    return SdfGrid(g.n, org, val, act, g.background, g.radius, g.half_width)
+
+
+def merge_sdf_grids(parts):
+    """The SdfGrid of the whole particle set from the ranks' SdfGrids (DistFluidSim.sdf_wait of every rank): the union of their
+    leaves, ascending; per voxel inactive -background wins, then the smallest active value, else inactive +background
+    (fluid_sdf_grids_merge: host only)."""
+    parts = list(parts)
+    cs = [p._c() for p in parts]           # (struct, mask words): the words must outlive the calls
+    arr = (SdfGridC * len(parts))(*[c for c, _ in cs])
+    k = lib.fluid_sdf_grids_merge(arr, len(parts), 0, None, None, None)
+    if k < 0:
+        raise FluidError(-k, "fluid_sdf_grids_merge: the parts do not merge (different n or parameters, a bad list, or an inactive "
+                             "value that is neither +background nor -background)")
+    org, val, words = np.empty((k, 3), np.int32), np.empty((k, 512), np.float32), np.zeros((k, 8), np.uint64)
+    if k and lib.fluid_sdf_grids_merge(arr, len(parts), k, org.ctypes.data_as(C.c_void_p), val.ctypes.data_as(C.c_void_p),
+                                       words.ctypes.data_as(C.c_void_p)) != k:
+        raise FluidError(1, "fluid_sdf_grids_merge: the second call disagrees with the count")
+    act = np.unpackbits(words.view(np.uint8), axis=1, bitorder="little").astype(bool).reshape(k, 512)
+    p0 = parts[0]
+    return SdfGrid(p0.n, org, val, act, p0.background, p0.radius, p0.half_width)
+
+
 def sdf_to_dense(grid):
     """(values float32 (n, n, n), active bool (n, n, n)) of an SdfGrid: +background / inactive outside the listed leaves
     (fluid_sdf_to_dense: host only)."""
@@ -399,15 +432,7 @@ class FluidSim:
         """The oldest level-set snapshot not yet waited for, as an SdfGrid (copied out of the handle's pinned buffer)."""
         g = SdfGridC()
         check(lib.fluid_sdf_wait(self._h, C.byref(g)))
-        k = g.n_leaves
-        if k == 0:
-            return SdfGrid(g.n, np.empty((0, 3), np.int32), np.empty((0, 512), np.float32), np.empty((0, 512), bool),
-                           g.background, g.radius, g.half_width)
-        org = np.ctypeslib.as_array(C.cast(g.origin, C.POINTER(C.c_int32)), shape=(k, 3)).copy()
-        val = np.ctypeslib.as_array(C.cast(g.values, C.POINTER(C.c_float)), shape=(k, 512)).copy()
-        words = np.ctypeslib.as_array(C.cast(g.active, C.POINTER(C.c_uint64)), shape=(k, 8)).copy()
-        act = np.unpackbits(words.view(np.uint8), axis=1, bitorder="little").astype(bool)
-        return SdfGrid(g.n, org, val, act, g.background, g.radius, g.half_width)
+        return _sdf_grid_copy(g)
 
     def sdf_stats(self):
         v = [C.c_int64() for _ in range(3)]

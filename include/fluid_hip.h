@@ -551,8 +551,9 @@ int64_t fluid_leaf_grids_merge(const fluid_leaf_grid_t* parts, int32_t n_parts, 
  * voxels is anything but inactive +bg; voxels of a listed leaf outside the grid are inactive +bg, as is every voxel of an unlisted
  * leaf.  The list is ascending in (x, y, z) origin.
  * Limits: radius > 0, half_width >= 1, R + w <= 4 (float sum), else FLUID_ERR_ARG: a particle within mx of a voxel then has its
- * base cell at Chebyshev distance <= 4 from it, so the search stays inside a 9^3 neighbourhood of cells.  One GPU only: a
- * decomposed handle returns FLUID_ERR_STATE from the three handle entry points.  Parity of the file with the library is unpinned
+ * base cell at Chebyshev distance <= 4 from it, so the search stays inside a 9^3 neighbourhood of cells.  A decomposed handle
+ * returns FLUID_ERR_STATE from the three handle entry points below and takes its surface rank by rank with the next section
+ * ("liquid surface (decomposed runs)").  Parity of the file with the library is unpinned
  * (as for the density files); the tests re-read it with their own reader. */
 typedef struct fluid_sdf_params { double radius, half_width; } fluid_sdf_params_t;   /* voxels */
 typedef struct fluid_sdf_grid {
@@ -587,6 +588,55 @@ int fluid_sdf_to_dense(const fluid_sdf_grid_t* g, float* values, uint8_t* active
  * value that is neither +bg nor -bg is FLUID_ERR_ARG too, and so is a path that cannot be opened or written in full (the
  * partial file is removed). */
 int fluid_write_vdb_sdf(const char* path, const fluid_sdf_grid_t* g, int32_t compression);
+
+/* ---- liquid surface (decomposed runs) --------------------------------------------------------------------------------------
+ * A voxel's value is a monotone function of the MINIMUM of x2y2z2 over the particles, and a minimum over a union of sets is the
+ * minimum of the per-set minima: every rank takes the surface of its own particles, and a host merge joins the lists exactly.  No
+ * ghost particles, no halo, no transport call; the rule is the same in decomposed and in replicated mode (both shard the particles).
+ *
+ * Rank-local list.  fluid_dist_sdf_snapshot on a decomposed handle gives exactly the list fluid_sdf_snapshot would give on a one-GPU
+ * handle of the same N that holds this rank's LIVE particles and nothing else.  Live: the particles fluid_download_particles_ids
+ * returns — after a step the arrays still hold the ghosts that were served and the particles a sink removed, marked dead and with
+ * stale positions: they do not count.  The base cell must lie in [lo,hi]^3 as above.  Coordinates on a decomposed handle are global
+ * index-space coordinates, so origins are global.  The list covers every leaf this rank's particles reach (their base-cell box dilated
+ * by 4 cells, clipped to the grid), NOT the owned block: after FLIPadvect a rank's particles may sit outside its block, and a voxel
+ * near a cut plane is reached from both sides.
+ *
+ * Merge.  The merged list is the union of the parts' leaves, ascending (x, y, z); a part that does not list a leaf contributes
+ * inactive +bg in all of its voxels.  Per voxel, over the parts:
+ *   1. some part holds it inactive with value -bg: the result is inactive -bg;
+ *   2. otherwise, some part holds it active: active with the smallest active value (equal values: the first such part's bits);
+ *   3. otherwise inactive +bg.
+ * Exact: d = dxf * (sqrtf(m) - R) is a composition of correctly rounded monotone operations, so the smallest m gives the smallest d,
+ * and m <= min2 on any part holds for the union too.  The three states are ordered by this rule, not by their float values: a plain
+ * minimum of the values is not the merge.  For the lists the ranks of a run give, the merge is the list fluid_sdf_snapshot gives for
+ * the union of their live particles.
+ *
+ *   per step, every rank:    fluid_step(s, &st);  fluid_dist_sdf_snapshot(s, &sp);  fluid_dist_sdf_wait(s, &part[rank]);
+ *   one place:               k = fluid_sdf_grids_merge(part, R, cap, origin, values, active);
+ *                            g = {n, k, bg, radius, half_width, origin, values, active};  fluid_write_vdb_sdf(path, &g, ...);
+ * The particles survive a re-balancing of the cut planes (unlike the fields), so a snapshot the caller takes after fluid_step is exact
+ * whether or not the step moved the planes: there is no `every` form.
+ */
+/* fluid_sdf_snapshot in every respect but the particles that count (above): kernels on the handle's stream, the 24-byte box and the
+ * 4-byte count read back, the records copied on a second stream and not waited for, two snapshots may be outstanding (a third:
+ * FLUID_ERR_STATE), buffers grow here and never inside a step.  A plain fluid_create handle is accepted: the list is
+ * fluid_sdf_snapshot's, and both forms share the handle's two slots and its count of outstanding snapshots. */
+int fluid_dist_sdf_snapshot(fluid_sim_t* s, const fluid_sdf_params_t* p);
+/* The oldest snapshot not yet waited for, as fluid_sdf_wait; out->n is the global N; a rank with no counted particle gets
+ * n_leaves = 0 and NULL pointers.  The pointers stay valid until the SECOND following surface snapshot on the handle — also across a
+ * step that moves the cut planes (FLUID_PATH_DIST_REBALANCED). */
+int fluid_dist_sdf_wait(fluid_sim_t* s, fluid_sdf_grid_t* out);
+/* leaves_in_grid = the leaves of the GLOBAL grid, as fluid_sdf_stats; the other two of this handle's last snapshot:
+ * bytes_to_host = leaves_listed * FLUID_SDF_LEAF_BYTES + 4.  Any pointer may be NULL. */
+int fluid_dist_sdf_stats(fluid_sim_t* s, int64_t* leaves_in_grid, int64_t* leaves_listed, int64_t* bytes_to_host);
+/* Host only.  The merge defined above into origin[3 * cap_leaves] / values[512 * cap_leaves] / active[8 * cap_leaves].  Returns the
+ * merged leaf count (origin == values == active == NULL: the count only, cap_leaves is ignored), or -FLUID_ERR_ARG with nothing
+ * written: n_parts < 1; the parts' n, background, radius or half_width differ as bit patterns; a part breaks the list rules of
+ * fluid_sdf_to_dense; an inactive voxel of a part holds neither +bg nor -bg; cap_leaves is too small.  Parts with n_leaves == 0 and
+ * NULL pointers are valid. */
+int64_t fluid_sdf_grids_merge(const fluid_sdf_grid_t* parts, int32_t n_parts, int64_t cap_leaves, int32_t* origin, float* values,
+                              uint64_t* active);
 
 #ifdef __cplusplus
 }

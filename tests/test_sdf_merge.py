@@ -1,0 +1,235 @@
+"""Host only: fluid_sdf_grids_merge (include/fluid_hip.h, "liquid surface (decomposed runs)") against tests/sdf_ref.py.  The parts
+are closed() of subsets of a particle set, the expected merge is closed() of the whole set; origins, masks and values (as bit
+patterns) must be equal exactly.  The input must reach every branch of the per-voxel rule, which the test counts for itself."""
+import ctypes as C
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import sdf_ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "fluid-simulation_amd", "csrc")
+SETS = [(1.5, 2.5, 1.0), (3.0, 1.0, 1.0), (1.0, 2.0, 0.5), (2.0, 2.0, 1.0)]      # (R, w, dx): those of test_gpu_sdf.py
+ERR_ARG = 1
+
+
+def u32(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def particles(n):
+    """A filled block of 8 per cell over the cells -2..1 (it straddles the three centre planes) and 150 scattered points, some of
+    them outside the grid."""
+    lo, hi, _, _ = sdf_ref.geometry(n)
+    rng = np.random.default_rng(100 + n)
+    c = np.stack(np.meshgrid(*[np.arange(-2, 2)] * 3, indexing="ij"), axis=-1).reshape(-1, 3)
+    block = np.repeat(c, 8, axis=0) + rng.uniform(-0.49, 0.49, (8 * len(c), 3))
+    return np.vstack([block, rng.uniform(lo - 1.0, hi + 1.0, (150, 3))])
+
+
+def grid_of(fs, pos, n, R, w, dx):
+    """(SdfGrid, dense values, dense mask) of closed() on `pos`."""
+    val, act = sdf_ref.closed(pos, n, R, w, dx)
+    fR, fw, _, bg, _, _ = sdf_ref.constants(R, w, dx)
+    org, v, a = sdf_ref.leaf_list(val, act, bg)
+    return fs.SdfGrid(n, org, v, a, bg, fR, fw), val, act
+
+
+def splits(pos, n):
+    rng = np.random.default_rng(7 + n)
+    k = rng.integers(0, 5, len(pos))
+    if n == 25:
+        k[k == 3] = 0                                                     # one part of the five is empty
+    by_cell = ((sdf_ref.base_cell(pos) >= 0) * np.array([4, 2, 1])).sum(axis=1)
+    return {"random5": [pos[k == i] for i in range(5)], "octants": [pos[by_cell == i] for i in range(8)]}
+
+
+_CASES = {}
+
+
+def case(fs, n, si):
+    """Whole grid and the parts of both splits, computed once per (n, set)."""
+    if (n, si) not in _CASES:
+        R, w, dx = SETS[si]
+        pos = particles(n)
+        whole = grid_of(fs, pos, n, R, w, dx)
+        parts = {name: [grid_of(fs, p, n, R, w, dx) for p in ps] for name, ps in splits(pos, n).items()}
+        _CASES[(n, si)] = (whole, parts)
+    return _CASES[(n, si)]
+
+
+def same(a, b):
+    return (a.n == b.n and np.array_equal(a.origin, b.origin) and np.array_equal(a.active, b.active) and
+            np.array_equal(u32(a.values), u32(b.values)) and
+            (u32(a.background), u32(a.radius), u32(a.half_width)) == (u32(b.background), u32(b.radius), u32(b.half_width)))
+
+
+@pytest.mark.parametrize("split", ["random5", "octants"])
+@pytest.mark.parametrize("si", range(4))
+@pytest.mark.parametrize("n", [16, 25])
+def test_merge_equals_the_whole_set(fs, n, si, split):
+    R, w, dx = SETS[si]
+    (whole, wval, wact), parts = case(fs, n, si)
+    ps = parts[split]
+    if n == 25 and split == "random5":
+        assert ps[3][0].n_leaves == 0
+    merged = fs.merge_sdf_grids([p[0] for p in ps])
+    assert merged.n_leaves == whole.n_leaves > 0
+    assert same(merged, whole)
+    # the input reaches every branch of the rule
+    bg = whole.background
+    keys = {}
+    for g, _, _ in ps:
+        for o, v, a in zip(map(tuple, g.origin.tolist()), g.values, g.active):
+            keys.setdefault(o, []).append((v.tobytes(), a.tobytes()))
+    shared_differing = sum(len(set(r)) > 1 for r in keys.values())
+    n_active = sum(a.astype(int) for _, _, a in ps)
+    neg_after = ~wact & (u32(wval) == u32(-bg))
+    active_then_neg = int((neg_after & (n_active > 0)).sum())
+    vals = np.stack([np.where(a, v, np.nan) for _, v, a in ps])
+    with np.errstate(invalid="ignore"):
+        two_differing = int(((n_active >= 2) & (np.nanmax(np.where(np.isnan(vals), -np.inf, vals), axis=0) >
+                                                np.nanmin(np.where(np.isnan(vals), np.inf, vals), axis=0))).sum())
+    print(f"n={n} set={si} {split}: leaves={whole.n_leaves} sum of parts={sum(p[0].n_leaves for p in ps)} "
+          f"shared_differing={shared_differing} active_then_neg={active_then_neg} two_differing={two_differing}")
+    assert shared_differing > 0
+    assert two_differing > 0
+    assert sum(p[0].n_leaves for p in ps) > whole.n_leaves
+    if R > w:
+        assert active_then_neg > 0                                        # a plain minimum of the values leaves these active
+    else:
+        assert not neg_after.any()
+
+
+def c_parts(grids):
+    cs = [g._c() for g in grids]
+    return (type(cs[0][0]) * len(cs))(*[c for c, _ in cs]), cs
+
+
+def raw_merge(fs, grids, cap, count_only=False, fill=0x5A):
+    """(return value, origin, values, active) with the output arrays pre-filled."""
+    arr, _keep = c_parts(grids)
+    if count_only:
+        return fs.lib.fluid_sdf_grids_merge(arr, len(grids), cap, None, None, None), None, None, None
+    room = max(cap, 1)
+    org = np.full((room, 3), fill, np.int32)
+    val = np.full((room, 512), fill, np.float32)
+    act = np.full((room, 8), fill, np.uint64)
+    k = fs.lib.fluid_sdf_grids_merge(arr, len(grids), cap, org.ctypes.data_as(C.c_void_p), val.ctypes.data_as(C.c_void_p),
+                                     act.ctypes.data_as(C.c_void_p))
+    return k, org, val, act
+
+
+def untouched(org, val, act, fill=0x5A):
+    return (org == fill).all() and (val == np.float32(fill)).all() and (act == fill).all()
+
+
+def test_counts_capacity_single_and_empty(fs):
+    n = 16
+    (whole, _, _), parts = case(fs, n, 1)
+    gs = [p[0] for p in parts["octants"]]
+    k = whole.n_leaves
+    assert raw_merge(fs, gs, 0, count_only=True)[0] == k
+    assert raw_merge(fs, gs, 123456, count_only=True)[0] == k              # cap_leaves is ignored
+    r, org, val, act = raw_merge(fs, gs, k - 1)
+    assert r == -ERR_ARG and untouched(org, val, act)
+    r, org, val, act = raw_merge(fs, gs, k)
+    assert r == k and np.array_equal(org, whole.origin) and np.array_equal(u32(val), u32(whole.values))
+    assert same(fs.merge_sdf_grids([gs[5]]), gs[5])                        # one part alone: that part
+    empty = fs.SdfGrid(n, np.empty((0, 3), np.int32), np.empty((0, 512), np.float32), np.empty((0, 512), bool),
+                       whole.background, whole.radius, whole.half_width)
+    assert fs.merge_sdf_grids([empty, empty, empty]).n_leaves == 0
+    assert same(fs.merge_sdf_grids([empty, gs[5], empty]), gs[5])
+    c = fs.SdfGridC(n, 0, whole.background, whole.radius, whole.half_width, None, None, None)      # NULL pointers
+    assert fs.lib.fluid_sdf_grids_merge((fs.SdfGridC * 2)(c, c), 2, 0, None, None, None) == 0
+    # a tie: the same part twice is that part
+    assert same(fs.merge_sdf_grids([gs[5], gs[5]]), gs[5])
+
+
+def test_refusals_leave_the_output_alone(fs):
+    n = 16
+    (whole, _, _), parts = case(fs, n, 1)
+    a, b = parts["octants"][0][0], parts["octants"][7][0]
+    cap = whole.n_leaves + 8
+    S = fs.SdfGrid
+
+    def refused(grids):
+        assert raw_merge(fs, grids, 0, count_only=True)[0] == -ERR_ARG
+        r, org, val, act = raw_merge(fs, grids, cap)
+        assert r == -ERR_ARG and untouched(org, val, act)
+
+    assert raw_merge(fs, [a, b], cap)[0] > 0                               # the pair merges as it is
+    arr, _keep = c_parts([a, b])
+    assert fs.lib.fluid_sdf_grids_merge(arr, 0, cap, None, None, None) == -ERR_ARG          # n_parts < 1
+    assert fs.lib.fluid_sdf_grids_merge(None, 2, cap, None, None, None) == -ERR_ARG
+    org = np.zeros((cap, 3), np.int32)
+    assert fs.lib.fluid_sdf_grids_merge(arr, 2, cap, org.ctypes.data_as(C.c_void_p), None, None) == -ERR_ARG   # some arrays only
+    assert not org.any()
+    refused([a, S(n + 1, b.origin, b.values, b.active, b.background, b.radius, b.half_width)])
+    nxt = lambda x: np.nextafter(np.float32(x), np.float32(np.inf))
+    refused([a, S(n, b.origin, np.where(b.active, b.values, np.where(b.values > 0, nxt(b.background), -nxt(b.background))), b.active,
+                  nxt(b.background), b.radius, b.half_width)])             # a consistent part with another background
+    refused([a, S(n, b.origin, b.values, b.active, b.background, nxt(b.radius), b.half_width)])
+    refused([a, S(n, b.origin, b.values, b.active, b.background, b.radius, nxt(b.half_width))])
+    o = b.origin.copy(); o[0, 2] += 4
+    refused([a, S(n, o, b.values, b.active, b.background, b.radius, b.half_width)])          # off the 8-grid
+    o = b.origin.copy(); o[[0, 1]] = o[[1, 0]]
+    refused([a, S(n, o, b.values, b.active, b.background, b.radius, b.half_width)])          # not ascending
+    o = b.origin.copy(); o[1] = o[0]
+    refused([a, S(n, o, b.values, b.active, b.background, b.radius, b.half_width)])          # a leaf twice
+    o = b.origin.copy(); o[-1, 0] = (sdf_ref.geometry(n)[1] & ~7) + 8
+    refused([a, S(n, o, b.values, b.active, b.background, b.radius, b.half_width)])          # outside the grid's leaves
+    v = b.values.copy()
+    v[0, np.flatnonzero(~b.active[0])[0]] = 0.75                           # an inactive value that is neither +bg nor -bg
+    refused([a, S(n, b.origin, v, b.active, b.background, b.radius, b.half_width)])
+    c, _k = b._c()
+    nul = fs.SdfGridC(c.n, c.n_leaves, c.background, c.radius, c.half_width, c.origin, c.values, None)   # no mask array behind leaves
+    assert fs.lib.fluid_sdf_grids_merge((fs.SdfGridC * 1)(nul), 1, 0, None, None, None) == -ERR_ARG
+
+
+def test_a_plain_minimum_is_not_the_merge(fs):
+    """What the -bg branch guards: min over the values with the masks ORed differs from the merge on a set with R > w."""
+    n = 16
+    (whole, wval, wact), parts = case(fs, n, 1)
+    ps = parts["octants"]
+    vmin = np.minimum.reduce([v for _, v, _ in ps])
+    aor = np.logical_or.reduce([a for _, _, a in ps])
+    assert np.array_equal(u32(vmin), u32(wval))                            # the values alone would pass ...
+    assert (aor & ~wact).any()                                             # ... the ORed masks would not
+    dv, da = fs.sdf_to_dense(fs.merge_sdf_grids([p[0] for p in ps]))
+    assert np.array_equal(da, wact) and np.array_equal(u32(dv), u32(wval))
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_sdf_merge_under_asan_ubsan(tmp_path):
+    exe = tmp_path / "host_san_sdf_merge"
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
+           "-I", os.path.join(ROOT, "include"), os.path.join(CSRC, "vdb_sdf_writer.cpp"),
+           os.path.join(ROOT, "tests", "host_san_sdf_merge_main.cpp"), "-o", str(exe), "-lz"]
+    b = subprocess.run(cmd, capture_output=True, text=True)
+    if b.returncode != 0 and "asan" in (b.stderr or "").lower() and "cannot find" in b.stderr.lower():
+        pytest.skip("sanitizer runtime not installed")
+    assert b.returncode == 0, b.stderr[-3000:]
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600,
+                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
+    assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
+    assert "host sanitizer run (sdf merge): ok" in r.stdout
+
+
+@pytest.mark.parametrize("extra", [{"FLUID_BLOCKS": ""}, {"FLUID_BLOCKS_SURFACE": "1.5"}, {"FLUID_BLOCKS_SURFACE": "1.5;2.5"},
+                                   {"FLUID_OUT": ""}, {"FLUID_STEPS": "0"}])
+def test_driver_refuses_a_block_surface_it_would_not_write(tmp_path, extra):
+    """FLUID_BLOCKS_SURFACE without blocks, malformed or with nothing to write it beside is an error, decided before any handle is
+    created (so this runs without a GPU)."""
+    env = dict(os.environ, FLUID_N="16", FLUID_PPC="1", FLUID_STEPS="1", FLUID_OUT=str(tmp_path / "simulation"), FLUID_BLOCKS="2x1x1",
+               FLUID_BLOCKS_SURFACE="1.5,2.5")
+    for k in ("FLUID_OUT_DENSE", "FLUID_OUT_SURFACE", "FLUID_SOURCE_EVERY", "FLUID_RAW"):
+        env.pop(k, None)
+    env.update(extra)
+    r = subprocess.run([os.path.join(ROOT, "fluid-simulation_amd", "fluid")], capture_output=True, text=True, env=env, cwd=tmp_path, timeout=60)
+    assert r.returncode == 1 and "FLUID_BLOCKS_SURFACE" in r.stderr, (r.returncode, r.stderr[-500:])
+    assert not list(tmp_path.rglob("*.vdb"))
