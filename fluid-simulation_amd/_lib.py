@@ -63,6 +63,12 @@ class SdfGridC(C.Structure):
                 ("half_width", C.c_float), ("origin", C.c_void_p), ("values", C.c_void_p), ("active", C.c_void_p)]
 
 
+class MeshC(C.Structure):
+    """fluid_mesh_t: the surface nets of the level set (include/fluid_hip.h, "liquid surface as a mesh")."""
+    _fields_ = [("n", C.c_int32), ("n_vertices", C.c_int64), ("n_quads", C.c_int64), ("radius", C.c_float),
+                ("half_width", C.c_float), ("background", C.c_float), ("vertices", C.c_void_p), ("quads", C.c_void_p)]
+
+
 class MpmParams(C.Structure):
     """mpm_params_t (include/mpm_hip.h); defaults = the literals of mpm.cc."""
     _fields_ = [("B", C.c_int32), ("W", C.c_int32), ("device", C.c_int32), ("cg_max_iters", C.c_int32),
@@ -167,6 +173,11 @@ SYMBOLS = [
     ("fluid_dist_sdf_wait", C.c_int, [_P, C.POINTER(SdfGridC)]),
     ("fluid_dist_sdf_stats", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("fluid_sdf_grids_merge", C.c_int64, [C.POINTER(SdfGridC), C.c_int32, C.c_int64, _P, _P, _P]),
+    ("fluid_mesh_snapshot", C.c_int, [_P, C.POINTER(SdfParams)]),
+    ("fluid_mesh_wait", C.c_int, [_P, C.POINTER(MeshC)]),
+    ("fluid_mesh_stats", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("fluid_sdf_mesh", C.c_int64, [C.POINTER(SdfGridC), C.c_int64, C.c_int64, _P, _P, C.POINTER(C.c_int64)]),
+    ("fluid_write_ply_mesh", C.c_int, [C.c_char_p, C.POINTER(MeshC), C.c_float]),
     # the snow-MPM step (include/mpm_hip.h)
     ("mpm_default_params", C.c_int, [C.POINTER(MpmParams)]),
     ("mpm_create", C.c_int, [C.POINTER(MpmParams), C.POINTER(_P)]),

@@ -348,6 +348,12 @@ void launch_sdf_search(hipStream_t st, const SdfGeom& g, const int* start, const
                        uint64_t* tm, int* flags, unsigned* visits);   // visits: nullptr, or cells looked at per leaf of the range
 void launch_sdf_pack(hipStream_t st, const SdfGeom& g, const int* flags, const int* slot, const float* tv, const uint64_t* tm, float* values,
                      uint64_t* active, int* origin);
+// surface nets of that level set (kernels_mesh.hip): per leaf of the range the mixed-cell mask (8 words), the exclusive prefix of the
+// words' popcounts, the vertex and the quad count; tot[2] = the two totals, saturating at 2^31 (a one-block sum of the counts)
+void launch_mesh_mark(hipStream_t st, const SdfGeom& g, const float* tv, const int* flags, uint64_t* cmask, int* cpre, int* vcnt, int* qcnt,
+                      unsigned* tot);
+void launch_mesh_emit(hipStream_t st, const SdfGeom& g, const float* tv, const int* flags, const uint64_t* cmask, const int* cpre, const int* vcnt,
+                      const int* qcnt, const int* vbase, const int* qbase, float* vertices, uint32_t* quads);
 void launch_exclusive_scan(hipStream_t st, const int* in, int* out, long n, int* block_sums, int* total);
 void launch_sort_tail(hipStream_t st, const int* cell_count, int* cell_start, long c1, long ncell);
 void launch_index_scan(hipStream_t st, Grid g, const uint8_t* flags, int* indices, int* block_sums, int* total);

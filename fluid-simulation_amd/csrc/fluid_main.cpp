@@ -15,6 +15,10 @@
 // set of spheres of radius R voxels around the particles, band half width W voxels (fluid_sdf_snapshot after the density snapshot,
 // fluid_sdf_wait beside fluid_output_wait, fluid_write_vdb_sdf on the writer thread).  One GPU and the leaf output only: refused
 // with FLUID_BLOCKS, with FLUID_OUT_DENSE=1, with an empty FLUID_OUT and with FLUID_STEPS=0.  Stdout and every other file are what they are without it.
+//   FLUID_OUT_MESH=R,W (unset: off) — additionally simulation/mesh<i>.ply per step: the same surface as polygons, the surface nets of
+// that level set (fluid_mesh_snapshot after the other snapshots, fluid_mesh_wait beside theirs, fluid_write_ply_mesh with voxel size
+// dx on the writer thread).  With or without FLUID_OUT_SURFACE; refused where that one is.  Stdout and every other file are what
+// they are without it.
 // Initial particles: with the defaults (N = 121, 10 per voxel) exactly the reference's — fill(CoordBBox(-20, 20)) scattered by
 // UniformPointScatter with std::mt19937(FLUID_SEED) (fluid_scene_uniform_scatter: 689210 points); any other N / PPC takes the
 // scaled synthetic cube (fluid_scene_water_cube_drop).
@@ -77,6 +81,9 @@ struct LeafWriter {
     fluid_leaf_grid_t job{};
     fluid_sdf_grid_t sjob{};  // FLUID_OUT_SURFACE: the same step's surface
     bool has_sjob = false;
+    fluid_mesh_t mjob{};      // FLUID_OUT_MESH: the same step's mesh
+    bool has_mjob = false;
+    float voxel = 1.0f;
     int job_step = -1;        // step whose grid is waiting (-1: none)
     int done = 0;             // grids written
     bool quit = false;
@@ -94,6 +101,8 @@ struct LeafWriter {
             const fluid_leaf_grid_t g = job;
             const fluid_sdf_grid_t sg = sjob;
             const bool has_sg = has_sjob;
+            const fluid_mesh_t mg = mjob;
+            const bool has_mg = has_mjob;
             const int i = job_step;
             lk.unlock();
             std::string bad;
@@ -108,6 +117,10 @@ struct LeafWriter {
             if (has_sg && bad.empty()) {
                 const std::string fs = outdir + "/surface" + std::to_string(i) + ".vdb";
                 if (fluid_write_vdb_sdf(fs.c_str(), &sg, FLUID_VDB_ZIP_ACTIVE_MASK) != FLUID_OK) bad = fs;
+            }
+            if (has_mg && bad.empty()) {
+                const std::string fm = outdir + "/mesh" + std::to_string(i) + ".ply";
+                if (fluid_write_ply_mesh(fm.c_str(), &mg, voxel) != FLUID_OK) bad = fm;
             }
             if (raw_f32 && bad.empty()) {
                 const size_t ncell = (size_t)g.n * g.n * g.n;
@@ -129,13 +142,15 @@ struct LeafWriter {
         cv.wait(lk, [&] { return done >= n; });
         return error.empty();
     }
-    void submit(int step, const fluid_leaf_grid_t& g, const fluid_sdf_grid_t* surface = nullptr)
+    void submit(int step, const fluid_leaf_grid_t& g, const fluid_sdf_grid_t* surface = nullptr, const fluid_mesh_t* mesh = nullptr)
     {
         std::unique_lock<std::mutex> lk(m);
         cv.wait(lk, [&] { return job_step < 0; });
         job = g;
         has_sjob = surface != nullptr;
         if (surface) sjob = *surface;
+        has_mjob = mesh != nullptr;
+        if (mesh) mjob = *mesh;
         job_step = step;
         cv.notify_all();
     }
@@ -405,6 +420,24 @@ int main(int, char**)
             return 1;
         }
     }
+    const char* menv = getenv("FLUID_OUT_MESH");
+    const bool mesh = menv && *menv;
+    fluid_sdf_params_t mp{};
+    if (mesh) {
+        char tail = 0;
+        if (sscanf(menv, "%lf,%lf%c", &mp.radius, &mp.half_width, &tail) != 2) {
+            std::cerr << "FLUID_OUT_MESH must be R,W (sphere radius and band half width in voxels), e.g. 1.5,2.5" << std::endl;
+            return 1;
+        }
+        if ((blocks && *blocks) || out_dense) {
+            std::cerr << "FLUID_OUT_MESH cannot be combined with " << (out_dense ? "FLUID_OUT_DENSE=1" : "FLUID_BLOCKS (a block run meshes its merged surface on the host: fluid_sdf_mesh)") << std::endl;
+            return 1;
+        }
+        if (outdir.empty() || steps <= 0) {
+            std::cerr << "FLUID_OUT_MESH needs an output directory and at least one step (FLUID_OUT is empty or FLUID_STEPS is 0)" << std::endl;
+            return 1;
+        }
+    }
     BlockCfg bc;
     if (const char* bs = getenv("FLUID_BLOCKS_SURFACE"); bs && *bs) {
         char tail = 0;
@@ -488,6 +521,7 @@ int main(int, char**)
     const bool leaves = !outdir.empty() && steps > 0 && !out_dense;
     if (leaves) {
         lw.outdir = outdir, lw.fin = fin, lw.all = all, lw.raw_f32 = raw_f32;
+        lw.voxel = (float)prm.dx;
         lw.start();
     }
     // hands the oldest snapshot to the writer thread
@@ -502,7 +536,12 @@ int main(int, char**)
             std::cerr << "fluid_sdf_wait: " << fluid_last_error() << std::endl;
             return false;
         }
-        lw.submit(step, g, surface ? &sg : nullptr);
+        fluid_mesh_t mg;
+        if (mesh && fluid_mesh_wait(sim, &mg) != FLUID_OK) {
+            std::cerr << "fluid_mesh_wait: " << fluid_last_error() << std::endl;
+            return false;
+        }
+        lw.submit(step, g, surface ? &sg : nullptr, mesh ? &mg : nullptr);
         return true;
     };
 
@@ -545,6 +584,11 @@ int main(int, char**)
             }
             if (surface && fluid_sdf_snapshot(sim, &sp) != FLUID_OK) {
                 std::cerr << "fluid_sdf_snapshot: " << fluid_last_error() << std::endl;
+                lw.stop();
+                return 1;
+            }
+            if (mesh && fluid_mesh_snapshot(sim, &mp) != FLUID_OK) {
+                std::cerr << "fluid_mesh_snapshot: " << fluid_last_error() << std::endl;
                 lw.stop();
                 return 1;
             }

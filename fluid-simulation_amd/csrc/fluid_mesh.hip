@@ -1,0 +1,194 @@
+// Mesh snapshots of the liquid surface (include/fluid_hip.h, "liquid surface as a mesh"): the surface nets of the particles' level
+// set leave the device as vertices and quads.  Kernels in kernels_mesh.hip.
+//
+// fluid_mesh_snapshot, all on the handle's stream: the front half of a level-set snapshot (fluid_sdf.hip: bbox, 24 bytes read back,
+// count, scan, scatter, search — the search scratch is the surface's own, shared in stream order) -> mark (mask, vertex and quad
+// count per leaf of the range) and the two totals (read back: 8 bytes, they size the slot) -> two exclusive scans of the counts ->
+// emit into the slot's device staging; the records then travel to pinned host memory on a second stream behind an event.  No leaf
+// is packed.  Two slots ([nq x 16 B of quads | nv x 12 B of vertices], one copy each): a slot is written by snapshot q, q + 2, ...,
+// so what fluid_mesh_wait handed out stays valid until the second following mesh snapshot.  Slots and the count of outstanding
+// snapshots are the mesh's own: density, surface and mesh can all be taken in one step.  The particle arrays are only read and
+// `binned` keeps holding, as for the surface.
+#include "sim.h"
+
+using namespace fl;
+#define fail fluid_fail
+
+struct MeshSlot {
+    char* dev = nullptr;       // device staging
+    char* host = nullptr;      // pinned
+    size_t cap = 0;            // bytes either buffer holds
+    long nv = 0, nq = 0;
+    float bg = 0, R = 0, w = 0;
+    hipEvent_t done = nullptr;   // recorded on the copy stream behind the slot's copy
+};
+struct MeshState {
+    long leaf_cap = 0;            // leaves of the range the per-leaf scratch holds
+    uint64_t* cmask = nullptr;    // 8 words per leaf
+    int *cpre = nullptr, *vcnt = nullptr, *qcnt = nullptr, *vbase = nullptr, *qbase = nullptr, *sums = nullptr;
+    int* d_scan_tot = nullptr;    // where launch_exclusive_scan puts its 32-bit totals (it always writes one; d_tot is what is read)
+    unsigned *d_tot = nullptr, *h_tot = nullptr;   // vertices, quads: saturating at 2^31
+    hipStream_t copy = nullptr;
+    hipEvent_t emitted = nullptr;
+    MeshSlot s[2];
+    long n_snap = 0, n_wait = 0;   // snapshots taken / waited for: snapshot q lives in slot q & 1
+    long last_v = 0, last_q = 0;
+};
+
+#define MESH_GUARD(s)                                                    \
+    if (!(s)) return fail(FLUID_ERR_ARG, "null handle");                 \
+    if ((s)->dist) return fail(FLUID_ERR_STATE, "mesh snapshots are single-GPU only: a decomposed run merges its blocks' level-set lists (fluid_sdf_grids_merge) and meshes the result on the host (fluid_sdf_mesh)")
+
+static int mesh_init(fluid_sim* s)
+{
+    if (s->mesh) return FLUID_OK;
+    MeshState* o = new MeshState();
+    s->mesh = o;   // from here on mesh_free releases whatever the lines below got
+    HIPCHK(hipMalloc((void**)&o->d_tot, 2 * sizeof(unsigned)));
+    HIPCHK(hipMalloc((void**)&o->d_scan_tot, 2 * sizeof(int)));
+    HIPCHK(hipHostMalloc((void**)&o->h_tot, 2 * sizeof(unsigned)));
+    HIPCHK(hipStreamCreateWithFlags(&o->copy, hipStreamNonBlocking));
+    HIPCHK(hipEventCreateWithFlags(&o->emitted, hipEventDisableTiming));
+    for (auto& q : o->s) HIPCHK(hipEventCreateWithFlags(&q.done, hipEventDisableTiming));
+    return FLUID_OK;
+}
+
+void fl::mesh_free(fluid_sim* s)
+{
+    MeshState* o = s->mesh;
+    if (!o) return;
+    if (o->copy) hipStreamSynchronize(o->copy);
+    for (auto& q : o->s) {
+        if (q.dev) hipFree(q.dev);
+        if (q.host) hipHostFree(q.host);
+        if (q.done) hipEventDestroy(q.done);
+    }
+    for (void* p : {(void*)o->cmask, (void*)o->cpre, (void*)o->vcnt, (void*)o->qcnt, (void*)o->vbase, (void*)o->qbase, (void*)o->sums,
+                    (void*)o->d_scan_tot, (void*)o->d_tot})
+        if (p) hipFree(p);
+    if (o->h_tot) hipHostFree(o->h_tot);
+    if (o->emitted) hipEventDestroy(o->emitted);
+    if (o->copy) hipStreamDestroy(o->copy);
+    delete o;
+    s->mesh = nullptr;
+}
+
+// (the front half's kernels are still queued on the handle's stream here; none of them touches these buffers, the mesh kernels
+// of the snapshot before have ended — the front half waited for the box behind them — and hipFree waits for the device anyway)
+template <typename T>
+static hipError_t regrow(T*& p, size_t n)
+{
+    if (p) hipFree(p);
+    p = nullptr;
+    return hipMalloc((void**)&p, n * sizeof(T));
+}
+
+static int mesh_scratch(MeshState* o, long leaves)
+{
+    if (leaves <= o->leaf_cap) return FLUID_OK;
+    o->leaf_cap = 0;
+    const long cap = leaves + leaves / 4 + 64;
+    HIPCHK(regrow(o->cmask, (size_t)cap * 8));
+    HIPCHK(regrow(o->cpre, (size_t)cap * 8));
+    HIPCHK(regrow(o->vcnt, (size_t)cap));
+    HIPCHK(regrow(o->qcnt, (size_t)cap));
+    HIPCHK(regrow(o->vbase, (size_t)cap));
+    HIPCHK(regrow(o->qbase, (size_t)cap));
+    HIPCHK(regrow(o->sums, (size_t)cap / 2048 + 16));
+    o->leaf_cap = cap;
+    return FLUID_OK;
+}
+
+// room for `bytes` in the slot (its earlier contents were handed out two snapshots ago: no longer promised)
+static int mesh_grow(MeshSlot& q, size_t bytes)
+{
+    if (bytes <= q.cap) return FLUID_OK;
+    if (q.dev) hipFree(q.dev);
+    if (q.host) hipHostFree(q.host);
+    q.dev = q.host = nullptr;
+    q.cap = 0;
+    const size_t cap = bytes + bytes / 2 + 4096;
+    HIPCHK(hipMalloc((void**)&q.dev, cap));
+    HIPCHK(hipHostMalloc((void**)&q.host, cap));
+    q.cap = cap;
+    return FLUID_OK;
+}
+
+extern "C" {
+
+int fluid_mesh_snapshot(fluid_sim_t* s, const fluid_sdf_params_t* p)
+{
+    MESH_GUARD(s);
+    SdfFront f;
+    int rc = sdf_begin(s, p, &f);
+    if (rc) return rc;
+    if ((rc = mesh_init(s))) return rc;
+    MeshState* o = s->mesh;
+    if (o->n_snap - o->n_wait >= 2) return fail(FLUID_ERR_STATE, "two mesh snapshots are waiting for fluid_mesh_wait");
+    MeshSlot& q = o->s[o->n_snap & 1];
+    if ((rc = sdf_front(s, &f))) return rc;
+    const SdfGeom& g = f.g;
+    long nv = 0, nq = 0;
+    if (f.any) {
+        const long leaves = g.leaves();
+        if ((rc = mesh_scratch(o, leaves))) return rc;
+        launch_mesh_mark(s->st, g, f.tv, f.flags, o->cmask, o->cpre, o->vcnt, o->qcnt, o->d_tot);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(o->h_tot, o->d_tot, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, s->st));
+        launch_exclusive_scan(s->st, o->vcnt, o->vbase, leaves, o->sums, o->d_scan_tot);
+        launch_exclusive_scan(s->st, o->qcnt, o->qbase, leaves, o->sums, o->d_scan_tot + 1);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(s->st));
+        if (o->h_tot[0] > 0x7fffffffu || o->h_tot[1] > 0x7fffffffu)
+            return fail(FLUID_ERR_ARG, "mesh: more than 2^31 - 1 vertices or quads");
+        nv = (long)o->h_tot[0], nq = (long)o->h_tot[1];
+    }
+    const size_t bytes = (size_t)nq * 16 + (size_t)nv * 12;
+    if ((rc = mesh_grow(q, bytes))) return rc;
+    q.nv = nv, q.nq = nq;
+    q.bg = g.bg, q.R = g.R, q.w = g.w;
+    if (nv > 0) {
+        launch_mesh_emit(s->st, g, f.tv, f.flags, o->cmask, o->cpre, o->vcnt, o->qcnt, o->vbase, o->qbase, (float*)(q.dev + (size_t)nq * 16),
+                         (uint32_t*)q.dev);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(o->emitted, s->st));
+        HIPCHK(hipStreamWaitEvent(o->copy, o->emitted, 0));
+        HIPCHK(hipMemcpyAsync(q.host, q.dev, bytes, hipMemcpyDeviceToHost, o->copy));
+    }
+    HIPCHK(hipEventRecord(q.done, o->copy));
+    o->n_snap++;
+    o->last_v = nv, o->last_q = nq;
+    return FLUID_OK;
+}
+
+int fluid_mesh_wait(fluid_sim_t* s, fluid_mesh_t* out)
+{
+    MESH_GUARD(s);
+    if (!out) return fail(FLUID_ERR_ARG, "null argument");
+    MeshState* o = s->mesh;
+    if (!o || o->n_wait >= o->n_snap) return fail(FLUID_ERR_STATE, "no mesh snapshot is outstanding");
+    MeshSlot& q = o->s[o->n_wait & 1];
+    HIPCHK(hipEventSynchronize(q.done));
+    out->n = s->g.N;
+    out->n_vertices = q.nv;
+    out->n_quads = q.nq;
+    out->radius = q.R;
+    out->half_width = q.w;
+    out->background = q.bg;
+    out->quads = q.nq ? (const uint32_t*)q.host : nullptr;
+    out->vertices = q.nv ? (const float*)(q.host + (size_t)q.nq * 16) : nullptr;
+    o->n_wait++;
+    return FLUID_OK;
+}
+
+int fluid_mesh_stats(fluid_sim_t* s, int64_t* vertices, int64_t* quads, int64_t* bytes_to_host)
+{
+    MESH_GUARD(s);
+    const int64_t nv = s->mesh ? s->mesh->last_v : 0, nq = s->mesh ? s->mesh->last_q : 0;
+    if (vertices) *vertices = nv;
+    if (quads) *quads = nq;
+    if (bytes_to_host) *bytes_to_host = s->mesh ? 12 * nv + 16 * nq + 8 : 0;
+    return FLUID_OK;
+}
+
+}  // extern "C"

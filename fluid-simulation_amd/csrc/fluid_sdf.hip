@@ -16,6 +16,9 @@
 // whether the rank owns it or not.  Rank-local: no transport call; the ranks' lists merge on the host (fluid_sdf_grids_merge,
 // vdb_sdf_writer.cpp).  The state is one per handle and shared by both forms; when the cut planes move it is handed to the new
 // window's handle (sdf_move), so lists handed out or in flight stay valid.
+//
+// The front half (sdf_begin, sdf_front: everything up to and including the search) is also the front half of fluid_mesh_snapshot
+// (fluid_mesh.hip), which works on the search's scratch in place of the pack.
 #include "sim.h"
 
 using namespace fl;
@@ -142,8 +145,12 @@ static int sdf_grow(SdfSlot& q, size_t n)
     return FLUID_OK;
 }
 
-// bbox -> count, scan, scatter -> search -> scan -> pack -> copy; a decomposed handle (s->dist) bins its live entries only
-static int sdf_capture(fluid_sim* s, const fluid_sdf_params_t* p)
+// The front half of a snapshot, shared with the mesh (fluid_mesh.hip).  sdf_begin: the parameters' limits, the state, the constants
+// of the level set.  sdf_front: bbox (24 bytes read back: the handle's stream is waited for) -> count, scan, scatter -> search, all
+// on the handle's stream; a decomposed handle (s->dist) bins its live entries only.  f->any = some particle counts; then f->g holds
+// the box and the range, and tv / flags are the search's: 512 values and a listed flag per leaf of the range (the values of a leaf
+// whose flag is 0 may be stale: kernels_sdf.hip).  The scratch is one per handle: whoever calls next overwrites it, in stream order.
+int fl::sdf_begin(fluid_sim* s, const fluid_sdf_params_t* p, SdfFront* f)
 {
     if (!p) return fail(FLUID_ERR_ARG, "null argument");
     const float R = (float)p->radius, w = (float)p->half_width;
@@ -153,18 +160,25 @@ static int sdf_capture(fluid_sim* s, const fluid_sdf_params_t* p)
     HIPCHK(hipSetDevice(s->prm.device));
     int rc = sdf_init(s);
     if (rc) return rc;
-    SdfState* o = s->sdf;
-    if (o->n_snap - o->n_wait >= 2) return fail(FLUID_ERR_STATE, "two level-set snapshots are waiting for fluid_sdf_wait");
-    SdfSlot& q = o->s[o->n_snap & 1];
-    SdfGeom g{};
+    SdfGeom& g = f->g;
+    g = SdfGeom{};
     g.lo = s->g.lo, g.hi = s->g.hi, g.L0 = g.lo & ~7;
     g.R = R, g.w = w, g.dxf = (float)s->prm.dx;
     g.bg = g.dxf * w;
     g.max2 = mx * mx;
     const float mn = std::fmax(0.0f, R - w);
     g.min2 = mn * mn;
+    f->any = false;
+    f->tv = nullptr, f->flags = nullptr;
+    return FLUID_OK;
+}
+
+int fl::sdf_front(fluid_sim* s, SdfFront* f)
+{
+    SdfState* o = s->sdf;
+    SdfGeom& g = f->g;
+    int rc;
     const Particles live = s->pa.shifted(s->p_off);
-    int n = 0;
     int* box = o->h_small;
     if (s->np > 0) {
         launch_sdf_bbox(s->st, s->np, live, g.lo, g.hi, o->d_small, s->dist);
@@ -191,6 +205,27 @@ static int sdf_capture(fluid_sim* s, const fluid_sdf_params_t* p)
         launch_exclusive_scan(s->st, o->cnt, o->start, cells + 1, o->cell_sums, o->d_small + 6);   // start[cells] = the counted particles
         launch_sdf_scatter(s->st, s->np, live, g, o->start, o->place, sx, sy, sz);
         launch_sdf_search(s->st, g, o->start, sx, sy, sz, o->tv, o->tm, o->flags, o->count_visits ? o->visits : nullptr);
+        f->any = true;
+        f->tv = o->tv, f->flags = o->flags;
+    }
+    return FLUID_OK;
+}
+
+// front half -> scan of the flags -> pack -> copy
+static int sdf_capture(fluid_sim* s, const fluid_sdf_params_t* p)
+{
+    SdfFront f;
+    int rc = sdf_begin(s, p, &f);
+    if (rc) return rc;
+    SdfState* o = s->sdf;
+    if (o->n_snap - o->n_wait >= 2) return fail(FLUID_ERR_STATE, "two level-set snapshots are waiting for fluid_sdf_wait");
+    SdfSlot& q = o->s[o->n_snap & 1];
+    if ((rc = sdf_front(s, &f))) return rc;
+    const SdfGeom& g = f.g;
+    const float R = g.R, w = g.w;
+    int n = 0;
+    if (f.any) {
+        const long leaves = g.leaves();
         launch_exclusive_scan(s->st, o->flags, o->slot, leaves, o->leaf_sums, o->d_small + 7);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(o->h_small + 7, o->d_small + 7, sizeof(int), hipMemcpyDeviceToHost, s->st));

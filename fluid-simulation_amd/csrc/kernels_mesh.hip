@@ -1,0 +1,245 @@
+// Surface nets of the particles' level set for gfx950 (wave64): one vertex per grid cell whose eight corners disagree in sign, one
+// quad per grid edge whose two ends disagree in sign, no case table (include/fluid_hip.h, "liquid surface as a mesh";
+// fluid_mesh.hip).  The kernels work on what k_sdf_search (kernels_sdf.hip) leaves on the device: tv (512 values) and a listed
+// flag per leaf j = (jx * nl[1] + jy) * nl[2] + jz of the range, the particles' base-cell box dilated by 4 cells and clipped to the
+// grid.  A leaf whose flag is 0 is +bg everywhere WHATEVER its tv holds (the search leaves early and writes the flag alone, so the
+// values may be those of an earlier snapshot), and so is every leaf outside the range: only flagged leaves' tv is ever read.
+//
+// Every leaf of the range is processed, not only the listed ones, and no leaf outside it needs to be.  A voxel is inside (< 0)
+// only if it is less than R <= 3 from a counted particle (w >= 1 and R + w <= 4), so within 3 cells (Chebyshev) of that particle's
+// base cell (|p - round(p)| <= 0.5).  A mixed cell has an inside corner, and its min corner is that corner minus {0,1}^3: within
+// [-4, +3] cells of the base cell.  The range holds the base cells' box dilated by 4, clipped to the grid, and a cell exists only
+// inside the grid: every mixed cell's min corner lies in a leaf of the range.  The same holds for the four cells round an edge
+// with a sign change (each has that edge's inside end as a corner), so a quad's vertex numbers are looked up inside the range.
+//
+//   mark   one 512-thread block per leaf of the range, thread t = the voxel ((x&7)*8 + (y&7))*8 + (z&7) = the cell with that min
+//          corner = the owner of the three edges that leave the voxel towards +x, +y, +z.  The leaf's 9^3 values go to LDS, the
+//          +1 faces from up to seven neighbour leaves (index arithmetic on j).  Out: the mixed-cell mask (8 words by ballot,
+//          wave = x plane), the exclusive prefix of the words' popcounts, the vertex and the quad count of the leaf.  A leaf
+//          with no listed leaf among itself and the seven leaves at +1 has neither and leaves at once.
+//   totals one block sums the leaves' counts in 64 bits and writes min(sum, 2^31) for either: what the host reads back to size the
+//          slot, and to refuse a mesh whose 32-bit bases would wrap.  (A first form added the counts to two words by
+//          compare-and-swap from k_mesh_mark: the blocks queued on them, 1.9 ms at 256^3 against 14 us for k_mesh_emit.)
+//   (two exclusive scans of the counts on the host side give the leaves' bases)
+//   emit   same tiling.  A mixed cell's vertex goes to vbase[leaf] + its rank in the mask; a quad to qbase[leaf] + the quads of
+//          lower voxels (ballots of the three edge bits) — position alone decides the place, there is no ordering by arrival.  The
+//          number of a vertex in a neighbour leaf at -1 is vbase[leaf'] + the popcount of that leaf's stored mask below the cell.
+// Arithmetic of a vertex: include/fluid_hip.h; float, no FMA (-ffp-contract=off), the division correctly rounded
+// (-fhip-fp32-correctly-rounded-divide-sqrt).
+#include "common.h"
+
+namespace fl {
+
+constexpr int MESH_V = 9 * 9 * 9;
+
+struct MeshLeaf {
+    long j;
+    int jx, jy, jz;   // leaf of the range
+    int ox, oy, oz;   // its origin
+};
+
+__device__ __forceinline__ MeshLeaf mesh_leaf(const SdfGeom& g)
+{
+    MeshLeaf l;
+    l.j = blockIdx.x;
+    l.jz = (int)(l.j % g.nl[2]), l.jy = (int)((l.j / g.nl[2]) % g.nl[1]), l.jx = (int)(l.j / ((long)g.nl[1] * g.nl[2]));
+    l.ox = g.L0 + 8 * (g.l0[0] + l.jx), l.oy = g.L0 + 8 * (g.l0[1] + l.jy), l.oz = g.L0 + 8 * (g.l0[2] + l.jz);
+    return l;
+}
+
+// index of the leaf (jx, jy, jz) of the range, or -1: outside the range
+__device__ __forceinline__ long mesh_range_index(const SdfGeom& g, int jx, int jy, int jz)
+{
+    if (jx < 0 || jx >= g.nl[0] || jy < 0 || jy >= g.nl[1] || jz < 0 || jz >= g.nl[2]) return -1;
+    return ((long)jx * g.nl[1] + jy) * g.nl[2] + jz;
+}
+
+// V[(lx * 9 + ly) * 9 + lz] = val(origin + (lx, ly, lz)), lx, ly, lz in 0..8: +bg wherever the leaf is unlisted or outside the range
+__device__ __forceinline__ void mesh_load(const SdfGeom& g, const MeshLeaf& l, const float* __restrict__ tv, const int* __restrict__ flags,
+                                          float* V)
+{
+    for (int i = threadIdx.x; i < MESH_V; i += 512) {
+        const int lz = i % 9, ly = (i / 9) % 9, lx = i / 81;
+        const long q = mesh_range_index(g, l.jx + (lx >> 3), l.jy + (ly >> 3), l.jz + (lz >> 3));
+        float v = g.bg;
+        if (q >= 0 && flags[q]) v = tv[q * 512 + (((lx & 7) * 8 + (ly & 7)) * 8 + (lz & 7))];
+        V[i] = v;
+    }
+}
+
+// The thread's cell and edges.  Returns the inside mask of the 8 corners (bit dx*4 + dy*2 + dz); mixed = the cell exists and its
+// corners disagree; edges bit a = the owned edge along axis a gives a quad (its ends disagree and the four cells round it exist).
+__device__ __forceinline__ unsigned mesh_cell(const SdfGeom& g, const float* c, int px, int py, int pz, bool& mixed, unsigned& edges)
+{
+    unsigned m = 0;
+#pragma unroll
+    for (int d = 0; d < 8; ++d) m |= (c[(d >> 2) * 81 + ((d >> 1) & 1) * 9 + (d & 1)] < 0.0f ? 1u : 0u) << d;
+    const bool cx = px >= g.lo && px <= g.hi - 1, cy = py >= g.lo && py <= g.hi - 1, cz = pz >= g.lo && pz <= g.hi - 1;        // the cell's axis range
+    const bool qx = px >= g.lo + 1 && cx, qy = py >= g.lo + 1 && cy, qz = pz >= g.lo + 1 && cz;                                // ... and the cell at -1 too
+    mixed = cx && cy && cz && m != 0 && m != 255;
+    const unsigned in0 = m & 1;
+    edges = 0;
+    if (cx && qy && qz && ((m >> 4) & 1) != in0) edges |= 1;
+    if (cy && qz && qx && ((m >> 2) & 1) != in0) edges |= 2;
+    if (cz && qx && qy && ((m >> 1) & 1) != in0) edges |= 4;
+    return m;
+}
+
+__global__ __launch_bounds__(512) void k_mesh_mark(SdfGeom g, const float* __restrict__ tv, const int* __restrict__ flags,
+                                                   unsigned long long* __restrict__ cmask, int* __restrict__ cpre, int* __restrict__ vcnt,
+                                                   int* __restrict__ qcnt)
+{
+    __shared__ float V[MESH_V];
+    __shared__ int wv[8], wq[8];
+    const int t = threadIdx.x;
+    const MeshLeaf l = mesh_leaf(g);
+    bool listed = false;
+    if (t < 8) {
+        const long q = mesh_range_index(g, l.jx + (t >> 2), l.jy + ((t >> 1) & 1), l.jz + (t & 1));
+        listed = q >= 0 && flags[q] != 0;
+    }
+    if (!__syncthreads_or(listed)) {   // +bg in all 9^3: no mixed cell, no edge with a sign change
+        if (t < 8) cmask[l.j * 8 + t] = 0, cpre[l.j * 8 + t] = 0;
+        if (t == 0) vcnt[l.j] = 0, qcnt[l.j] = 0;
+        return;
+    }
+    mesh_load(g, l, tv, flags, V);
+    __syncthreads();
+    const int x = t >> 6, y = (t >> 3) & 7, z = t & 7;
+    bool mixed;
+    unsigned edges;
+    mesh_cell(g, V + (x * 9 + y) * 9 + z, l.ox + x, l.oy + y, l.oz + z, mixed, edges);
+    const unsigned long long b = __ballot(mixed);
+    const int nq = __popcll(__ballot(edges & 1)) + __popcll(__ballot(edges & 2)) + __popcll(__ballot(edges & 4));
+    if ((t & 63) == 0) {
+        cmask[l.j * 8 + x] = b;
+        wv[x] = __popcll(b);
+        wq[x] = nq;
+    }
+    __syncthreads();
+    if (t < 8) {
+        int pre = 0;
+        for (int k = 0; k < t; ++k) pre += wv[k];
+        cpre[l.j * 8 + t] = pre;
+    }
+    if (t == 0) {
+        int nv = 0, nqs = 0;
+        for (int k = 0; k < 8; ++k) nv += wv[k], nqs += wq[k];
+        vcnt[l.j] = nv;
+        qcnt[l.j] = nqs;
+    }
+}
+
+// tot[0] = min(sum of vcnt, 2^31), tot[1] = the same of qcnt; one block, sums in 64 bits (a leaf gives at most 512 and 1536)
+__global__ __launch_bounds__(1024) void k_mesh_totals(long n, const int* __restrict__ vcnt, const int* __restrict__ qcnt, unsigned* __restrict__ tot)
+{
+    __shared__ unsigned long long sv[16], sq[16];
+    unsigned long long v = 0, q = 0;
+    for (long i = threadIdx.x; i < n; i += 1024) v += (unsigned)vcnt[i], q += (unsigned)qcnt[i];
+    v = wave_sum(v);
+    q = wave_sum(q);
+    if ((threadIdx.x & 63) == 0) sv[threadIdx.x >> 6] = v, sq[threadIdx.x >> 6] = q;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        v = q = 0;
+        for (int k = 0; k < 16; ++k) v += sv[k], q += sq[k];
+        tot[0] = v > 0x80000000ull ? 0x80000000u : (unsigned)v;
+        tot[1] = q > 0x80000000ull ? 0x80000000u : (unsigned)q;
+    }
+}
+
+// number of the vertex of the (mixed) cell with min corner (cx, cy, cz); 0xffffffff if its leaf lay outside the range (header: it cannot)
+__device__ __forceinline__ unsigned mesh_vertex_number(const SdfGeom& g, int cx, int cy, int cz, const unsigned long long* __restrict__ cmask,
+                                                       const int* __restrict__ cpre, const int* __restrict__ vbase)
+{
+    const long q = mesh_range_index(g, ((cx - g.L0) >> 3) - g.l0[0], ((cy - g.L0) >> 3) - g.l0[1], ((cz - g.L0) >> 3) - g.l0[2]);
+    if (q < 0) return 0xffffffffu;
+    const int off = ((cx & 7) * 8 + (cy & 7)) * 8 + (cz & 7);
+    const unsigned long long below = cmask[q * 8 + (off >> 6)] & ((1ull << (off & 63)) - 1ull);
+    return (unsigned)(vbase[q] + cpre[q * 8 + (off >> 6)] + __popcll(below));
+}
+
+__global__ __launch_bounds__(512) void k_mesh_emit(SdfGeom g, const float* __restrict__ tv, const int* __restrict__ flags,
+                                                   const unsigned long long* __restrict__ cmask, const int* __restrict__ cpre,
+                                                   const int* __restrict__ vcnt, const int* __restrict__ qcnt, const int* __restrict__ vbase,
+                                                   const int* __restrict__ qbase, float* __restrict__ vertices, uint4* __restrict__ quads)
+{
+    __shared__ float V[MESH_V];
+    __shared__ int wq[8];
+    const int t = threadIdx.x;
+    const MeshLeaf l = mesh_leaf(g);
+    if (vcnt[l.j] == 0 && qcnt[l.j] == 0) return;   // (the whole block alike)
+    mesh_load(g, l, tv, flags, V);
+    __syncthreads();
+    const int x = t >> 6, y = (t >> 3) & 7, z = t & 7;
+    const int px = l.ox + x, py = l.oy + y, pz = l.oz + z;
+    const float* c = V + (x * 9 + y) * 9 + z;
+    bool mixed;
+    unsigned edges;
+    const unsigned m = mesh_cell(g, c, px, py, pz, mixed, edges);
+    const unsigned long long lt = (1ull << (t & 63)) - 1ull;
+    const unsigned long long b = __ballot(mixed), bx = __ballot(edges & 1), by = __ballot(edges & 2), bz = __ballot(edges & 4);
+    if ((t & 63) == 0) wq[x] = __popcll(bx) + __popcll(by) + __popcll(bz);
+    __syncthreads();
+    if (mixed) {
+        // the 12 edges: axis x, y, z; the two other axes, in ascending order, at (0,0), (0,1), (1,0), (1,1)
+        float sx = 0.0f, sy = 0.0f, sz = 0.0f;
+        int k = 0;
+#pragma unroll
+        for (int o = 0; o < 4; ++o) {
+            const int d1 = o >> 1, d2 = o & 1;
+            const float v0 = c[d1 * 9 + d2], v1 = c[81 + d1 * 9 + d2];
+            if ((v0 < 0.0f) != (v1 < 0.0f)) sx += v0 / (v0 - v1), sy += (float)d1, sz += (float)d2, ++k;
+        }
+#pragma unroll
+        for (int o = 0; o < 4; ++o) {
+            const int d1 = o >> 1, d2 = o & 1;
+            const float v0 = c[d1 * 81 + d2], v1 = c[d1 * 81 + 9 + d2];
+            if ((v0 < 0.0f) != (v1 < 0.0f)) sx += (float)d1, sy += v0 / (v0 - v1), sz += (float)d2, ++k;
+        }
+#pragma unroll
+        for (int o = 0; o < 4; ++o) {
+            const int d1 = o >> 1, d2 = o & 1;
+            const float v0 = c[d1 * 81 + d2 * 9], v1 = c[d1 * 81 + d2 * 9 + 1];
+            if ((v0 < 0.0f) != (v1 < 0.0f)) sx += (float)d1, sy += (float)d2, sz += v0 / (v0 - v1), ++k;
+        }
+        const float kf = (float)k;
+        float* out = vertices + 3 * (size_t)(vbase[l.j] + cpre[l.j * 8 + x] + __popcll(b & lt));
+        out[0] = (float)px + sx / kf;
+        out[1] = (float)py + sy / kf;
+        out[2] = (float)pz + sz / kf;
+    }
+    if (edges) {
+        size_t at = (size_t)qbase[l.j] + __popcll(bx & lt) + __popcll(by & lt) + __popcll(bz & lt);
+        for (int k = 0; k < x; ++k) at += wq[k];
+        const bool inside = m & 1;
+        const unsigned q2 = mesh_vertex_number(g, px, py, pz, cmask, cpre, vbase);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            if (!((edges >> a) & 1)) continue;
+            // (b, c) = the two other axes in cyclic order; Q0 = p - e_b - e_c, Q1 = p - e_c, Q3 = p - e_b
+            const int bxs = a == 2, bys = a == 0, bzs = a == 1;
+            const int cxs = a == 1, cys = a == 2, czs = a == 0;
+            const unsigned q0 = mesh_vertex_number(g, px - bxs - cxs, py - bys - cys, pz - bzs - czs, cmask, cpre, vbase);
+            const unsigned q1 = mesh_vertex_number(g, px - cxs, py - cys, pz - czs, cmask, cpre, vbase);
+            const unsigned q3 = mesh_vertex_number(g, px - bxs, py - bys, pz - bzs, cmask, cpre, vbase);
+            quads[at++] = inside ? make_uint4(q0, q1, q2, q3) : make_uint4(q0, q3, q2, q1);
+        }
+    }
+}
+
+void launch_mesh_mark(hipStream_t st, const SdfGeom& g, const float* tv, const int* flags, uint64_t* cmask, int* cpre, int* vcnt, int* qcnt,
+                      unsigned* tot)
+{
+    hipLaunchKernelGGL(k_mesh_mark, dim3((unsigned)g.leaves()), dim3(512), 0, st, g, tv, flags, (unsigned long long*)cmask, cpre, vcnt, qcnt);
+    hipLaunchKernelGGL(k_mesh_totals, dim3(1), dim3(1024), 0, st, g.leaves(), (const int*)vcnt, (const int*)qcnt, tot);
+}
+
+void launch_mesh_emit(hipStream_t st, const SdfGeom& g, const float* tv, const int* flags, const uint64_t* cmask, const int* cpre, const int* vcnt,
+                      const int* qcnt, const int* vbase, const int* qbase, float* vertices, uint32_t* quads)
+{
+    hipLaunchKernelGGL(k_mesh_emit, dim3((unsigned)g.leaves()), dim3(512), 0, st, g, tv, flags, (const unsigned long long*)cmask, cpre, vcnt, qcnt,
+                       vbase, qbase, vertices, (uint4*)quads);
+}
+
+}  // namespace fl

@@ -203,6 +203,7 @@ struct fluid_sim {
     struct OutState* out = nullptr;   // leaf snapshots of the output grid (fluid_output.hip), made by the first fluid_output_snapshot
     int out_every = 0;                // fluid_dist_output_every: fluid_step snapshots the owned block at the end of step t iff t % every == 0
     struct SdfState* sdf = nullptr;   // level-set snapshots of the particles (fluid_sdf.hip): slots, streams and scratch of their own
+    struct MeshState* mesh = nullptr; // surface-net snapshots of that level set (fluid_mesh.hip): slots, stream and per-leaf scratch of their own
     // profiling
     int prof_every = 0;
     ProfClass prof[FLUID_PROF_COUNT];
@@ -251,6 +252,18 @@ void output_move(fluid_sim* from, fluid_sim* to);   // re-balance: slots, counte
 // fluid_sdf.hip
 void sdf_free(fluid_sim* s);         // waits for the copies in flight, frees the scratch, the staging and the pinned buffers
 void sdf_move(fluid_sim* from, fluid_sim* to);      // re-balance: slots, streams, scratch and counters go to the new window's handle
+// the front half of a level-set snapshot, for fluid_sdf_snapshot and fluid_mesh_snapshot alike
+struct SdfFront {
+    SdfGeom g;
+    bool any;             // some particle counts: g holds the box and the range, tv / flags are filled for every leaf of the range
+    const float* tv;      // 512 values per leaf of the range (stale where flags[j] == 0)
+    const int* flags;     // the leaf is listed
+};
+int sdf_begin(fluid_sim* s, const fluid_sdf_params_t* p, SdfFront* f);   // limits of the parameters, the state, the constants of g
+int sdf_front(fluid_sim* s, SdfFront* f);                                // bbox (waits for the stream) -> count, scan, scatter -> search
+
+// fluid_mesh.hip
+void mesh_free(fluid_sim* s);        // waits for the copies in flight, frees the scratch, the staging and the pinned buffers
 
 // fluid_dist.hip
 int dist_step(fluid_sim* s, fluid_step_stats_t* stats);

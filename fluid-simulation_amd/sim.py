@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 
-from ._lib import lib, check, FluidError, Params, StepStats, FIELD, Source, LeafGridC, SdfParams, SdfGridC
+from ._lib import lib, check, FluidError, Params, StepStats, FIELD, Source, LeafGridC, SdfParams, SdfGridC, MeshC
 
 _FIELD_DTYPE = {
     FIELD.CONTAINER: (np.float32, 1), FIELD.WEIGHTS: (np.float32, 1), FIELD.OUTPUT: (np.float32, 1),
@@ -187,6 +187,49 @@ def write_vdb_sdf(path, grid, compression="zip"):
     """One FloatGrid "surface" of class "level set" whose leaves are the listed ones (fluid_write_vdb_sdf: host only)."""
     c, _keep = grid._c()
     check(lib.fluid_write_vdb_sdf(str(path).encode(), C.byref(c), _VDB_COMPRESSION[compression]))
+
+
+class Mesh:
+    """fluid_mesh_t on the host: the surface nets of the level set (include/fluid_hip.h, "liquid surface as a mesh").  vertices
+    (nv, 3) float32 in index space, quads (nq, 4) uint32 vertex numbers, counter-clockwise seen from outside the liquid."""
+
+    def __init__(self, n, vertices, quads, background=0.0, radius=0.0, half_width=0.0):
+        self.n = int(n)
+        self.vertices = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+        self.quads = np.ascontiguousarray(quads, dtype=np.uint32).reshape(-1, 4)
+        self.background, self.radius, self.half_width = np.float32(background), np.float32(radius), np.float32(half_width)
+
+    def _c(self):
+        nv, nq = len(self.vertices), len(self.quads)
+        return MeshC(self.n, nv, nq, self.radius, self.half_width, self.background, self.vertices.ctypes.data if nv else None,
+                     self.quads.ctypes.data if nq else None)
+
+
+def sdf_mesh(grid):
+    """The Mesh of an SdfGrid, every unlisted leaf being +background (fluid_sdf_mesh: host only).  A decomposed run gets its mesh
+    as sdf_mesh(merge_sdf_grids(parts))."""
+    c, _keep = grid._c()
+    nq = C.c_int64()
+    nv = lib.fluid_sdf_mesh(C.byref(c), 0, 0, None, None, C.byref(nq))
+    if nv < 0:
+        raise FluidError(-nv, "fluid_sdf_mesh: a bad leaf list, or more than 2^31 - 1 vertices or quads")
+    v, q = np.empty((nv, 3), np.float32), np.empty((nq.value, 4), np.uint32)
+    if nv:
+        nq2 = C.c_int64(-1)
+        nv2 = lib.fluid_sdf_mesh(C.byref(c), nv, len(q), v.ctypes.data_as(C.c_void_p), q.ctypes.data_as(C.c_void_p), C.byref(nq2))
+        if nv2 < 0:
+            raise FluidError(-nv2, "fluid_sdf_mesh: the second call was refused")
+        if (nv2, nq2.value) != (nv, len(q)):
+            raise RuntimeError(f"fluid_sdf_mesh: the second call gives {nv2} vertices and {nq2.value} quads, the first gave {nv} and {len(q)}")
+    return Mesh(grid.n, v, q, grid.background, grid.radius, grid.half_width)
+
+
+def write_ply_mesh(path, mesh, voxel_size):
+    """Binary little-endian PLY of a Mesh (or of a (vertices, quads) pair); positions are index space times voxel_size
+    (fluid_write_ply_mesh: host only)."""
+    if not isinstance(mesh, Mesh):
+        mesh = Mesh(0, mesh[0], mesh[1])
+    check(lib.fluid_write_ply_mesh(str(path).encode(), C.byref(mesh._c()), float(voxel_size)))
 
 
 def water_cube_drop(n, ppc, seed=0):
@@ -438,6 +481,30 @@ class FluidSim:
         v = [C.c_int64() for _ in range(3)]
         check(lib.fluid_sdf_stats(self._h, *[C.byref(x) for x in v]))
         return dict(zip(("leaves_in_grid", "leaves_listed", "bytes_to_host"), (x.value for x in v)))
+
+    # ---- liquid surface as a mesh: surface nets of the level set (single GPU; include/fluid_hip.h) ----
+    def mesh_snapshot(self, radius, half_width):
+        """Enqueue the surface nets of the level set of the particles as they are now (parameters as sdf_snapshot); a step()
+        called next overlaps the copy to the host."""
+        p = SdfParams(float(radius), float(half_width))
+        check(lib.fluid_mesh_snapshot(self._h, C.byref(p)))
+
+    def mesh_wait(self):
+        """The oldest mesh snapshot not yet waited for: (vertices (nv, 3) float32 in index space, quads (nq, 4) uint32), copied
+        out of the handle's pinned buffer."""
+        m = MeshC()
+        check(lib.fluid_mesh_wait(self._h, C.byref(m)))
+        v, q = np.empty((m.n_vertices, 3), np.float32), np.empty((m.n_quads, 4), np.uint32)
+        if m.n_vertices:
+            v[:] = np.ctypeslib.as_array(C.cast(m.vertices, C.POINTER(C.c_float)), shape=(m.n_vertices, 3))
+        if m.n_quads:
+            q[:] = np.ctypeslib.as_array(C.cast(m.quads, C.POINTER(C.c_uint32)), shape=(m.n_quads, 4))
+        return v, q
+
+    def mesh_stats(self):
+        v = [C.c_int64() for _ in range(3)]
+        check(lib.fluid_mesh_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("vertices", "quads", "bytes_to_host"), (x.value for x in v)))
 
     def extrapolate(self):
         """fluid.cc:705-802 after p2g(): velocities for every cell inside W (dead code in the reference; optional here).  Returns the passes run."""

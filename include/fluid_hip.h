@@ -638,6 +638,73 @@ int fluid_dist_sdf_stats(fluid_sim_t* s, int64_t* leaves_in_grid, int64_t* leave
 int64_t fluid_sdf_grids_merge(const fluid_sdf_grid_t* parts, int32_t n_parts, int64_t cap_leaves, int32_t* origin, float* values,
                               uint64_t* active);
 
+/* ---- liquid surface as a mesh: surface nets of the level set ----------------------------------------------------------------
+ * Polygons for everyone who is no volume renderer.  The reference names tools/VolumeToMesh.h, whose output depends on the library's
+ * tree traversal; like the level set itself the mesh gets an exact, order-free definition of its own — naive surface nets on the
+ * voxel grid, no case table — and every implementation (the kernels, fluid_sdf_mesh below, the tests' numpy form) gives the same
+ * bytes.
+ *
+ * Input.  The level set of "liquid surface" for the same fluid_sdf_params_t, with the same limits.  val(c), c in [lo,hi]^3, is the
+ * value of every voxel, inactive ones included (+bg or -bg); the active mask plays no part.  A voxel is INSIDE iff val(c) < 0.0f.
+ *
+ * Cells.  Cell c has the corners c + {0,1}^3 and exists iff lo <= c_a <= hi - 1 on every axis: nothing outside the grid is read or
+ * assumed.  A cell is MIXED iff its corners are not all inside or all outside.
+ *
+ * Vertex of a mixed cell (float throughout, no FMA).  Walk the 12 edges in this order: axis a = x, y, z; for each axis the two
+ * other axes, in ascending axis order, take the offsets (0,0), (0,1), (1,0), (1,1).  An edge runs from corner c0 (offset 0 on axis
+ * a) to c1 = c0 + e_a and COUNTS iff exactly one end is inside.  For a counting edge t = v0 / (v0 - v1) (float subtraction, then the
+ * correctly rounded float division); the point's offset from c is t on axis a and the corner's 0.0f / 1.0f on the other two.  One
+ * end is < 0 and the other >= 0, so v0 - v1 is never zero and t lies in (0, 1].  Per axis s_axis starts at 0.0f and receives the
+ * offsets in edge order; k counts the counting edges.  The vertex is (float)c_axis + s_axis / (float)k, in index space.
+ *
+ * Quads.  Voxel p owns the edges p -> p + e_a, a = x, y, z.  An edge gives a quad iff its ends differ in sign and the four cells
+ * round it exist.  With (b, c) the two other axes in cyclic order (x -> (y,z), y -> (z,x), z -> (x,y)) the cells are Q0 = p - e_b - e_c,
+ * Q1 = p - e_c, Q2 = p, Q3 = p - e_b; they exist iff lo <= p_a <= hi - 1 and lo + 1 <= p_b, p_c <= hi - 1, and all four are mixed by
+ * construction.  The quad is (Q0, Q1, Q2, Q3) if p is inside — counter-clockwise seen from +a, the normal points out of the liquid —
+ * and (Q0, Q3, Q2, Q1) if p is outside; its entries are the cells' vertex numbers (uint32).  Edges that lack a cell (on the outermost
+ * voxel layer) give no quad: the mesh is open where the surface meets the grid face.  Degenerate quads are kept.
+ *
+ * Order.  Vertices ascend by the origin (x, y, z) of the OpenVDB leaf that holds the cell's min corner c, then by c's offset in the
+ * leaf ((x&7)*8 + (y&7))*8 + (z&7).  Quads ascend by the leaf origin of p, then p's offset, then a.  Leaf origins are multiples of 8
+ * from lo & ~7, as everywhere else.
+ *
+ * A decomposed run merges its blocks' lists (fluid_sdf_grids_merge) and meshes the result on the host:
+ *   k = fluid_sdf_grids_merge(...);  g = {n, k, ...};  nv = fluid_sdf_mesh(&g, 0, 0, NULL, NULL, &nq);  (allocate)  fluid_sdf_mesh(&g, nv, nq, v, q, &nq);
+ */
+typedef struct fluid_mesh {
+    int32_t n;
+    int64_t n_vertices, n_quads;
+    float radius, half_width, background;   /* R, w, bg as used                                                  */
+    const float* vertices;                  /* 3 per vertex, index space                                         */
+    const uint32_t* quads;                  /* 4 per quad                                                        */
+} fluid_mesh_t;
+/* The front half of fluid_sdf_snapshot (box, 24 bytes read back; bins; search) and then the mesh kernels; no leaf is packed.  The
+ * search scratch is the surface's: both kinds of snapshot run in order on the handle's stream.  Lifetime rules of the surface
+ * snapshot: kernels on the handle's stream, the two totals read back (8 bytes), the records copied to pinned host memory on a second
+ * stream and not waited for; two mesh snapshots may be outstanding, a third returns FLUID_ERR_STATE; buffers grow here, never inside
+ * a step, and are freed by the destroy call after the copies in flight have ended.  The slots and the count of outstanding snapshots
+ * are the mesh's own: density, surface and mesh can all be taken in one step.  Nothing a later step reads is written.
+ * FLUID_ERR_ARG: bad parameters (as fluid_sdf_snapshot), or more than 2^31 - 1 vertices or quads.  FLUID_ERR_STATE on a decomposed
+ * handle (all three entry points): see fluid_sdf_mesh. */
+int fluid_mesh_snapshot(fluid_sim_t* s, const fluid_sdf_params_t* p);
+/* The oldest snapshot not yet waited for (FLUID_ERR_STATE when there is none).  No counted particle or no mixed cell: counts 0 and
+ * NULL pointers (quads is NULL whenever n_quads is 0).  The pointers stay valid until the SECOND following mesh snapshot. */
+int fluid_mesh_wait(fluid_sim_t* s, fluid_mesh_t* out);
+/* Of the last snapshot (any pointer may be NULL): bytes_to_host = 12 * vertices + 16 * quads + 8. */
+int fluid_mesh_stats(fluid_sim_t* s, int64_t* vertices, int64_t* quads, int64_t* bytes_to_host);
+/* Host only: the definition above applied to a leaf list, every unlisted leaf being +bg.  Returns the vertex count and *n_quads (may
+ * be NULL).  vertices == quads == NULL: the counts only, the caps are ignored; otherwise both arrays are required, 3 * cap_vertices
+ * floats and 4 * cap_quads uint32.  -FLUID_ERR_ARG with nothing written: a list fluid_sdf_to_dense refuses, one array without the
+ * other, a cap too small, more than 2^31 - 1 vertices or quads.  Works leaf by leaf over the listed leaves and their neighbours at
+ * -1; no dense grid is made. */
+int64_t fluid_sdf_mesh(const fluid_sdf_grid_t* g, int64_t cap_vertices, int64_t cap_quads, float* vertices, uint32_t* quads, int64_t* n_quads);
+/* Host only: binary little-endian PLY, no compression.  Header, line by line: ply / format binary_little_endian 1.0 /
+ * element vertex <nv> / property float x / property float y / property float z / element face <nq> /
+ * property list uchar uint vertex_indices / end_header.  A vertex is its three index-space components times voxel_size, in float;
+ * a face is the byte 4 and the quad's four uint32.  FLUID_ERR_ARG: voxel_size not > 0, a count without its array, a quad entry
+ * >= n_vertices, a path that cannot be opened or written in full (the partial file is removed). */
+int fluid_write_ply_mesh(const char* path, const fluid_mesh_t* m, float voxel_size);
+
 #ifdef __cplusplus
 }
 #endif

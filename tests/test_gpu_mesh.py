@@ -1,0 +1,255 @@
+"""GPU (-m gpu): the liquid surface as a mesh (fluid_mesh_snapshot / _wait / _stats, kernels_mesh.hip).  In every comparison the
+device mesh equals tests/mesh_ref.py of tests/sdf_ref.py closed() AND fluid_sdf_mesh of the fluid_sdf_snapshot list taken from
+the same particles: vertices as bit patterns, quads exactly."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import mesh_ref
+import sdf_ref
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SETS = mesh_ref.SETS
+ERR_ARG, ERR_STATE = 1, 3
+
+
+def u32(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def same(got, vert, quads, what=""):
+    v, q = got
+    assert v.shape == vert.shape and q.shape == quads.shape, (what, v.shape, vert.shape, q.shape, quads.shape)
+    assert v.dtype == np.float32 and q.dtype == np.uint32
+    assert np.array_equal(u32(v), u32(vert)), what
+    assert np.array_equal(q, quads), what
+
+
+def check(fs, sim, ref, R, w, what=""):
+    """The handle's mesh of its particles is `ref` = mesh_ref.mesh(...)[:2], and so is the host mesher's of the handle's surface list."""
+    sim.mesh_snapshot(R, w)
+    got = sim.mesh_wait()
+    same(got, ref[0], ref[1], what)
+    st = sim.mesh_stats()
+    assert st == {"vertices": len(ref[0]), "quads": len(ref[1]), "bytes_to_host": 12 * len(ref[0]) + 16 * len(ref[1]) + 8}, what
+    sim.sdf_snapshot(R, w)
+    h = fs.sdf_mesh(sim.sdf_wait())
+    same((h.vertices, h.quads), ref[0], ref[1], what + " (host mesher)")
+    return got
+
+
+def ref_of(pos, n, R, w, dx):
+    return mesh_ref.mesh(sdf_ref.closed(pos, n, R, w, dx)[0])
+
+
+@pytest.mark.parametrize("R,w,dx", SETS)
+@pytest.mark.parametrize("n", [16, 25])
+def test_one_particle(fs, n, R, w, dx):
+    pos, _, _, ref = mesh_ref.scene("one", n, R, w, dx)
+    sim = fs.FluidSim(n=n, dx=dx)
+    sim.upload_particles(pos)
+    v, q = check(fs, sim, ref, R, w)
+    assert len(v) > 0 and mesh_ref.is_closed(q)
+    sim.close()
+
+
+@pytest.mark.parametrize("R,w,dx", [SETS[0], SETS[1]])
+def test_eight_leaf_corner(fs, R, w, dx):
+    """Vertex numbers in the neighbours at -1 on every axis."""
+    n = 16
+    pos, _, _, ref = mesh_ref.scene("corner", n, R, w, dx)
+    sim = fs.FluidSim(n=n, dx=dx)
+    sim.upload_particles(pos)
+    check(fs, sim, ref, R, w)
+    cells = ref[2]
+    assert len({tuple(o) for o in (cells & ~7).tolist()}) == 8
+    sim.close()
+
+
+@pytest.mark.parametrize("name,n,prm", [("lo", 16, SETS[1]), ("lo", 25, SETS[0]), ("hi", 16, SETS[1]), ("hi", 25, SETS[3])])
+def test_grid_faces(fs, name, n, prm):
+    """Cells clipped at the grid faces; the mesh is open there."""
+    R, w, dx = prm
+    pos, _, _, ref = mesh_ref.scene(name, n, R, w, dx)
+    sim = fs.FluidSim(n=n, dx=dx)
+    sim.upload_particles(pos)
+    v, q = check(fs, sim, ref, R, w)
+    assert len(q) > 0 and not mesh_ref.is_closed(q)
+    sim.close()
+
+
+def test_cloud_and_stale_scratch(fs):
+    """The 300-particle cloud; then, on the same handle, one particle far from where the cloud's listed leaves were, and two in
+    opposite corners: the search leaves the leaves of the new range that no particle reaches at once, their values in the
+    scratch are the cloud's — the mesh must not read them."""
+    n, (R, w, dx) = 25, (1.0, 1.0, 1.0)
+    pos, _, _, ref = mesh_ref.scene("cloud", n, R, w, dx)
+    sim = fs.FluidSim(n=n, dx=dx)
+    sim.upload_particles(pos)
+    sim.mesh_snapshot(R, w)
+    same(sim.mesh_wait(), ref[0], ref[1], "cloud")
+    # (two particles in opposite corners: their range is the whole grid, and every leaf in between is left at once)
+    for p in ([[10.3, 10.2, -9.6]], [[-10.4, 9.7, 10.1]], [[0.3, -0.2, 0.41]], [[10.3, 10.2, -9.6], [-10.4, -9.7, 10.1]]):
+        one = np.array(p)
+        sim.upload_particles(one)
+        sim.mesh_snapshot(R, w)                                                # (no surface snapshot in between: the scratch is the cloud's)
+        r1 = ref_of(one, n, R, w, dx)
+        assert 0 < len(r1[0]) < 100
+        same(sim.mesh_wait(), r1[0], r1[1], f"particles {p} after the cloud")
+        sim.upload_particles(pos)
+        check(fs, sim, ref, R, w, "cloud again")
+    sim.close()
+
+
+def test_drop_scene_after_upload_and_steps(fs):
+    n, (R, w, dx) = 32, SETS[0]
+    pos = fs.water_cube_drop(n, 8, seed=0)
+    sim = fs.FluidSim(n=n)
+    sim.upload_particles(pos)
+    check(fs, sim, ref_of(pos, n, R, w, dx), R, w, "after upload")
+    for _ in range(3):
+        sim.step()
+    p, _ = sim.download_particles()
+    v, q = check(fs, sim, ref_of(p, n, R, w, dx), R, w, "after 3 steps")
+    assert len(q) > 100
+    sim.close()
+
+
+def test_slots_and_refusals(fs):
+    n, (R, w, dx) = 32, SETS[0]
+    sim = fs.FluidSim(n=n)
+    h = sim._h
+    m = fs.MeshC()
+    assert fs.lib.fluid_mesh_wait(h, C.byref(m)) == ERR_STATE                   # nothing outstanding
+    assert sim.mesh_stats() == {"vertices": 0, "quads": 0, "bytes_to_host": 0}
+    for bad in ((2.0, 2.5), (1.5, 0.5), (0.0, 2.0), (float("nan"), 2.0)):
+        assert fs.lib.fluid_mesh_snapshot(h, C.byref(fs.SdfParams(*bad))) == ERR_ARG, bad
+    assert fs.lib.fluid_mesh_snapshot(h, None) == ERR_ARG and fs.lib.fluid_mesh_wait(h, None) == ERR_ARG
+    sim.mesh_snapshot(R, w)                                                    # no particles at all: an empty mesh
+    assert fs.lib.fluid_mesh_wait(h, C.byref(m)) == 0
+    assert (m.n, m.n_vertices, m.n_quads, m.vertices, m.quads) == (n, 0, 0, None, None)
+    assert sim.mesh_stats() == {"vertices": 0, "quads": 0, "bytes_to_host": 8}
+    p1 = fs.water_cube_drop(n, 4, seed=0)
+    sim.upload_particles(p1)
+    sim.mesh_snapshot(R, w)
+    sim.step()
+    p2, _ = sim.download_particles()
+    sim.mesh_snapshot(2.0, 2.0)
+    assert fs.lib.fluid_mesh_snapshot(h, C.byref(fs.SdfParams(R, w))) == ERR_STATE      # a third
+    assert "two mesh snapshots" in fs.lib.fluid_last_error().decode()
+    m1, m2 = fs.MeshC(), fs.MeshC()
+    assert fs.lib.fluid_mesh_wait(h, C.byref(m1)) == 0 and fs.lib.fluid_mesh_wait(h, C.byref(m2)) == 0
+    assert fs.lib.fluid_mesh_wait(h, C.byref(m)) == ERR_STATE
+
+    def view(mc):
+        v = np.ctypeslib.as_array(C.cast(mc.vertices, C.POINTER(C.c_float)), shape=(mc.n_vertices, 3))
+        q = np.ctypeslib.as_array(C.cast(mc.quads, C.POINTER(C.c_uint32)), shape=(mc.n_quads, 4))
+        return v, q
+    # the first one's pointers are intact after the second snapshot and both waits
+    r1, r2 = ref_of(p1, n, R, w, dx), ref_of(p2, n, 2.0, 2.0, 1.0)
+    same(view(m1), r1[0], r1[1], "first")
+    same(view(m2), r2[0], r2[1], "second")
+    fR, fw, _, bg, _, _ = sdf_ref.constants(2.0, 2.0, 1.0)
+    assert (m2.radius, m2.half_width, m2.background, m2.n) == (fR, fw, bg, n)
+    assert sim.mesh_stats() == {"vertices": len(r2[0]), "quads": len(r2[1]), "bytes_to_host": 12 * len(r2[0]) + 16 * len(r2[1]) + 8}
+    for _ in range(3):                                                          # the slots are reused
+        sim.step()
+        check(fs, sim, ref_of(sim.download_particles()[0], n, R, w, dx), R, w)
+    sim.close()
+
+
+def test_decomposed_handle_refuses(fs):
+    fd = fs.load_dist()
+    n = 16
+    grp = fd.LocalGroup(1)
+    sim = fd.DistFluidSim(n, (1, 1, 1), fd.uniform_cuts(n, (1, 1, 1)), grp.comms[0])
+    h = sim._h
+    m, x = fs.MeshC(), C.c_int64()
+    assert fs.lib.fluid_mesh_snapshot(h, C.byref(fs.SdfParams(1.5, 2.5))) == ERR_STATE
+    assert "fluid_sdf_mesh" in fs.lib.fluid_last_error().decode()
+    assert fs.lib.fluid_mesh_wait(h, C.byref(m)) == ERR_STATE
+    assert fs.lib.fluid_mesh_stats(h, C.byref(x), None, None) == ERR_STATE
+    sim.close()
+
+
+def test_snapshots_do_not_disturb_the_steps_or_each_other(fs):
+    """The same input on three handles: B takes density, surface and mesh snapshots after every step, C the surface alone, A
+    nothing.  Particles bit for bit and every field of the step stats as on A; B's surface lists are C's."""
+    n, (R, w, _) = 32, SETS[0]
+    pos = fs.water_cube_drop(n, 8, seed=3)
+    a, b, c = fs.FluidSim(n=n), fs.FluidSim(n=n), fs.FluidSim(n=n)
+    for s in (a, b, c):
+        s.upload_particles(pos)
+    sa, sb = [], []
+    for k in range(5):
+        sa.append(a.step())
+        sb.append(b.step())
+        c.step()
+        b.output_snapshot()
+        b.mesh_snapshot(R, w)
+        b.sdf_snapshot(R, w)
+        c.sdf_snapshot(R, w)
+        assert b.output_wait().n_leaves > 0
+        gb, gc = b.sdf_wait(), c.sdf_wait()
+        v, q = b.mesh_wait()
+        assert len(v) > 0 and len(q) > 0 and q.max() < len(v)
+        assert gb.n_leaves == gc.n_leaves > 0 and np.array_equal(gb.origin, gc.origin)
+        assert np.array_equal(u32(gb.values), u32(gc.values)) and np.array_equal(gb.active, gc.active)
+    assert sa == sb
+    (pa, va), (pb, vb) = a.download_particles(), b.download_particles()
+    assert pa.tobytes() == pb.tobytes() and va.tobytes() == vb.tobytes()
+    for s in (a, b, c):
+        s.close()
+
+
+def read_ply(path):
+    raw = open(path, "rb").read()
+    end = raw.index(b"end_header\n") + len(b"end_header\n")
+    head = raw[:end].decode("ascii")
+    nv = int(head.split("element vertex ")[1].split("\n")[0])
+    nq = int(head.split("element face ")[1].split("\n")[0])
+    v = np.frombuffer(raw, "<f4", 3 * nv, end).reshape(nv, 3)
+    f = np.frombuffer(raw, np.dtype([("k", "u1"), ("i", "<u4", 4)]), nq, end + 12 * nv)
+    assert end + 12 * nv + 17 * nq == len(raw)
+    return v, f
+
+
+def test_driver_writes_the_mesh(fs, tmp_path):
+    """The `fluid` program with FLUID_OUT_MESH=R,W: mesh<i>.ply holds the handle's mesh of the particles of step i (taken from a
+    handle that runs the same scene here) times the voxel size, and stdout and the other files are what they are without it."""
+    import leaf_ref
+    n, ppc, steps, (R, w, dx) = 24, 4, 3, SETS[0]
+    exe = os.path.join(ROOT, "fluid-simulation_amd", "fluid")
+    outs = {}
+    for mode in ("plain", "mesh"):
+        d = tmp_path / mode
+        d.mkdir()
+        env = dict(os.environ, FLUID_N=str(n), FLUID_PPC=str(ppc), FLUID_STEPS=str(steps), FLUID_OUT=str(d / "simulation"))
+        for k in ("FLUID_OUT_MESH", "FLUID_OUT_SURFACE", "FLUID_OUT_DENSE", "FLUID_BLOCKS", "FLUID_BLOCKS_SURFACE", "FLUID_SOURCE_EVERY", "FLUID_RAW"):
+            env.pop(k, None)
+        if mode == "mesh":
+            env["FLUID_OUT_MESH"] = f"{R},{w}"
+        r = subprocess.run([exe], capture_output=True, text=True, env=env, cwd=d, timeout=300)
+        assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
+        outs[mode] = [ln for ln in r.stdout.splitlines() if not ln.startswith("Time Taken")]
+    assert outs["plain"] == outs["mesh"]
+    names = lambda m: sorted(str(p.relative_to(tmp_path / m)) for p in (tmp_path / m).rglob("*") if p.is_file())   # noqa: E731
+    assert names("mesh") == sorted(names("plain") + [f"simulation/mesh{i}.ply" for i in range(steps)])
+    for nm in names("plain"):
+        assert leaf_ref.same_file(tmp_path / "plain" / nm, tmp_path / "mesh" / nm), nm
+    sim = fs.FluidSim(n=n)
+    sim.upload_particles(fs.water_cube_drop(n, ppc, seed=0))
+    for i in range(steps):
+        sim.step()
+        sim.mesh_snapshot(R, w)
+        v, q = sim.mesh_wait()
+        fv, ff = read_ply(tmp_path / "mesh" / f"simulation/mesh{i}.ply")
+        assert len(q) > 0 and np.array_equal(u32(fv), u32(v * np.float32(dx))) and np.array_equal(ff["i"], q) and (ff["k"] == 4).all(), i
+    ref = ref_of(sim.download_particles()[0], n, R, w, dx)                      # ... and the last one is the reference's
+    same((v, q), ref[0], ref[1])
+    sim.close()

@@ -1,0 +1,154 @@
+"""CPU (-m "not gpu"): the host half of the liquid surface as a mesh — fluid_sdf_mesh on tests/sdf_ref.py leaf lists against
+tests/mesh_ref.py (vertices as bit patterns, quads exactly), its refusals, the PLY writer re-read with numpy, and both under
+ASan + UBSan as a stand-alone program."""
+import ctypes as C
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import mesh_ref
+import sdf_ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "fluid-simulation_amd", "csrc")
+ERR_ARG = 1
+SETS = mesh_ref.SETS
+HEADER = ("ply\nformat binary_little_endian 1.0\nelement vertex {nv}\nproperty float x\nproperty float y\nproperty float z\n"
+          "element face {nq}\nproperty list uchar uint vertex_indices\nend_header\n")
+
+
+def u32(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def grid_of(fs, name, n, R, w, dx):
+    _, val, act, ref = mesh_ref.scene(name, n, R, w, dx)
+    fR, fw, _, bg, _, _ = sdf_ref.constants(R, w, dx)
+    org, v, a = sdf_ref.leaf_list(val, act, bg)
+    return fs.SdfGrid(n, org, v, a, bg, fR, fw), ref
+
+
+def same(m, ref):
+    vert, quads = ref[0], ref[1]
+    assert m.vertices.shape == vert.shape and m.quads.shape == quads.shape, (m.vertices.shape, vert.shape, m.quads.shape, quads.shape)
+    assert np.array_equal(u32(m.vertices), u32(vert))
+    assert m.quads.dtype == np.uint32 and np.array_equal(m.quads, quads)
+
+
+CASES = ([("one", n, s) for n in (16, 25) for s in SETS] +
+         [("corner", 16, SETS[0]), ("corner", 16, SETS[1]), ("lo", 16, SETS[1]), ("lo", 25, SETS[0]), ("hi", 25, SETS[3]), ("hi", 16, SETS[1]),
+          ("cloud", 25, (1.0, 1.0, 1.0))])
+
+
+@pytest.mark.parametrize("name,n,prm", CASES)
+def test_sdf_mesh_is_the_reference(fs, name, n, prm):
+    g, ref = grid_of(fs, name, n, *prm)
+    assert g.n_leaves > 0 and len(ref[0]) > 0
+    same(fs.sdf_mesh(g), ref)
+
+
+def test_empty_list(fs):
+    m = fs.sdf_mesh(fs.SdfGrid(16, np.empty((0, 3)), np.empty((0, 512)), np.empty((0, 512)), 2.5, 1.5, 2.5))
+    assert m.vertices.shape == (0, 3) and m.quads.shape == (0, 4)
+
+
+def test_refusals_and_counts_only(fs):
+    g, (vert, quads, _, _) = grid_of(fs, "corner", 16, *SETS[1])
+    nv, nq = len(vert), len(quads)
+    c, _keep = g._c()
+    got = C.c_int64(-1)
+    assert fs.lib.fluid_sdf_mesh(C.byref(c), 0, 0, None, None, C.byref(got)) == nv and got.value == nq     # counts only: caps ignored
+    assert fs.lib.fluid_sdf_mesh(C.byref(c), 0, 0, None, None, None) == nv
+    v, q = np.full((nv, 3), 7, np.float32), np.full((nq, 4), 7, np.uint32)
+    pv, pq = v.ctypes.data_as(C.c_void_p), q.ctypes.data_as(C.c_void_p)
+    assert fs.lib.fluid_sdf_mesh(C.byref(c), nv - 1, nq, pv, pq, None) == -ERR_ARG
+    assert fs.lib.fluid_sdf_mesh(C.byref(c), nv, nq - 1, pv, pq, None) == -ERR_ARG
+    assert fs.lib.fluid_sdf_mesh(C.byref(c), nv, nq, pv, None, None) == -ERR_ARG
+    assert fs.lib.fluid_sdf_mesh(C.byref(c), nv, nq, None, pq, None) == -ERR_ARG
+    assert (v == 7).all() and (q == 7).all()                                     # nothing written
+    assert fs.lib.fluid_sdf_mesh(C.byref(c), nv + 5, nq + 5, pv, pq, C.byref(got)) == nv and got.value == nq
+    assert np.array_equal(u32(v), u32(vert)) and np.array_equal(q, quads)
+    o = g.origin.copy(); o[[1, 2]] = o[[2, 1]]                                   # unsorted origins
+    with pytest.raises(fs.FluidError):
+        fs.sdf_mesh(fs.SdfGrid(16, o, g.values, g.active, g.background, g.radius, g.half_width))
+    o = g.origin.copy(); o[0, 1] += 4                                            # off the 8-grid
+    with pytest.raises(fs.FluidError):
+        fs.sdf_mesh(fs.SdfGrid(16, o, g.values, g.active, g.background, g.radius, g.half_width))
+    assert fs.lib.fluid_sdf_mesh(None, 0, 0, None, None, None) == -ERR_ARG
+
+
+def read_ply(path):
+    raw = open(path, "rb").read()
+    end = raw.index(b"end_header\n") + len(b"end_header\n")
+    head = raw[:end].decode("ascii")
+    nv = int(head.split("element vertex ")[1].split("\n")[0])
+    nq = int(head.split("element face ")[1].split("\n")[0])
+    v = np.frombuffer(raw, "<f4", 3 * nv, end).reshape(nv, 3)
+    f = np.frombuffer(raw, np.dtype([("k", "u1"), ("i", "<u4", 4)]), nq, end + 12 * nv)
+    assert end + 12 * nv + 17 * nq == len(raw)
+    return head, v, f
+
+
+@pytest.mark.parametrize("voxel_size", [1.0, 0.3])
+def test_ply_rereads(fs, tmp_path, voxel_size):
+    g, (vert, quads, _, _) = grid_of(fs, "cloud", 25, 1.0, 1.0, 1.0)
+    m = fs.sdf_mesh(g)
+    path = tmp_path / "m.ply"
+    fs.write_ply_mesh(path, m, voxel_size)
+    head, v, f = read_ply(path)
+    assert head == HEADER.format(nv=len(vert), nq=len(quads))
+    assert np.array_equal(u32(v), u32(vert * np.float32(voxel_size)))
+    assert (f["k"] == 4).all() and np.array_equal(f["i"], quads)
+    fs.write_ply_mesh(tmp_path / "pair.ply", (vert, quads), voxel_size)           # a plain (vertices, quads) pair writes the same file
+    assert open(tmp_path / "pair.ply", "rb").read() == open(path, "rb").read()
+    fs.write_ply_mesh(tmp_path / "e.ply", fs.Mesh(16, np.empty((0, 3)), np.empty((0, 4))), voxel_size)
+    assert open(tmp_path / "e.ply", "rb").read().decode() == HEADER.format(nv=0, nq=0)
+
+
+def test_ply_refusals(fs, tmp_path):
+    g, (vert, quads, _, _) = grid_of(fs, "one", 16, *SETS[0])
+    m = fs.Mesh(16, vert, quads)
+    c = m._c()
+    bad = tmp_path / "no_such_dir" / "m.ply"
+    assert fs.lib.fluid_write_ply_mesh(str(bad).encode(), C.byref(c), 1.0) == ERR_ARG                    # unwritable path
+    assert not (tmp_path / "no_such_dir").exists()
+    p = str(tmp_path / "m.ply").encode()
+    for vs in (0.0, -1.0, float("nan")):
+        assert fs.lib.fluid_write_ply_mesh(p, C.byref(c), vs) == ERR_ARG
+    q = quads.copy(); q[3, 2] = len(vert)                                        # an index past the vertices
+    assert fs.lib.fluid_write_ply_mesh(p, C.byref(fs.Mesh(16, vert, q)._c()), 1.0) == ERR_ARG
+    assert fs.lib.fluid_write_ply_mesh(p, None, 1.0) == ERR_ARG and fs.lib.fluid_write_ply_mesh(None, C.byref(c), 1.0) == ERR_ARG
+    assert not (tmp_path / "m.ply").exists()
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_mesher_and_ply_writer_under_asan_ubsan(tmp_path):
+    exe = tmp_path / "host_san_mesh"
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off",
+           "-fno-omit-frame-pointer", "-I", os.path.join(ROOT, "include"), os.path.join(CSRC, "mesh_host.cpp"),
+           os.path.join(ROOT, "tests", "host_san_mesh_main.cpp"), "-o", str(exe)]
+    b = subprocess.run(cmd, capture_output=True, text=True)
+    if b.returncode != 0 and "asan" in (b.stderr or "").lower() and "cannot find" in b.stderr.lower():
+        pytest.skip("sanitizer runtime not installed")
+    assert b.returncode == 0, b.stderr[-3000:]
+    r = subprocess.run([str(exe), str(tmp_path)], capture_output=True, text=True, timeout=600,
+                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
+    assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
+    assert "host sanitizer run (mesh): ok" in r.stdout
+    nv, nq = (int(x) for x in r.stdout.split("ok")[1].split())
+    head, v, f = read_ply(tmp_path / "san_mesh.ply")                            # what the sanitized build wrote re-reads too
+    assert head == HEADER.format(nv=nv, nq=nq) and (f["k"] == 4).all() and f["i"].max() < nv
+
+
+@pytest.mark.parametrize("extra", [{"FLUID_OUT": ""}, {"FLUID_STEPS": "0"}, {"FLUID_OUT_DENSE": "1"}, {"FLUID_BLOCKS": "2x1x1"}, {"FLUID_OUT_MESH": "1.5"}])
+def test_driver_refuses_a_mesh_it_would_not_write(fs, tmp_path, extra):
+    env = dict(os.environ, FLUID_N="16", FLUID_PPC="1", FLUID_STEPS="1", FLUID_OUT=str(tmp_path / "simulation"), FLUID_OUT_MESH="1.5,2.5")
+    for k in ("FLUID_OUT_DENSE", "FLUID_BLOCKS", "FLUID_SOURCE_EVERY", "FLUID_RAW", "FLUID_OUT_SURFACE", "FLUID_BLOCKS_SURFACE"):
+        env.pop(k, None)
+    env.update(extra)
+    r = subprocess.run([os.path.join(ROOT, "fluid-simulation_amd", "fluid")], capture_output=True, text=True, env=env, cwd=tmp_path, timeout=60)
+    assert r.returncode == 1 and "FLUID_OUT_MESH" in r.stderr, (r.returncode, r.stderr[-500:])
+    assert not list(tmp_path.rglob("*.ply")) and not list(tmp_path.rglob("*.vdb"))
