@@ -63,6 +63,11 @@ class SdfGridC(C.Structure):
                 ("half_width", C.c_float), ("origin", C.c_void_p), ("values", C.c_void_p), ("active", C.c_void_p)]
 
 
+class SdfFilter(C.Structure):
+    """fluid_sdf_filter_t: box filter width, iterations and offset (include/fluid_hip.h, "liquid surface, smoothed")."""
+    _fields_ = [("width", C.c_int32), ("iterations", C.c_int32), ("offset", C.c_double)]
+
+
 class MeshC(C.Structure):
     """fluid_mesh_t: the surface nets of the level set (include/fluid_hip.h, "liquid surface as a mesh")."""
     _fields_ = [("n", C.c_int32), ("n_vertices", C.c_int64), ("n_quads", C.c_int64), ("radius", C.c_float),
@@ -173,6 +178,9 @@ SYMBOLS = [
     ("fluid_dist_sdf_wait", C.c_int, [_P, C.POINTER(SdfGridC)]),
     ("fluid_dist_sdf_stats", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("fluid_sdf_grids_merge", C.c_int64, [C.POINTER(SdfGridC), C.c_int32, C.c_int64, _P, _P, _P]),
+    ("fluid_sdf_snapshot_filtered", C.c_int, [_P, C.POINTER(SdfParams), C.POINTER(SdfFilter)]),
+    ("fluid_mesh_snapshot_filtered", C.c_int, [_P, C.POINTER(SdfParams), C.POINTER(SdfFilter)]),
+    ("fluid_sdf_filter", C.c_int, [C.POINTER(SdfGridC), C.POINTER(SdfFilter), _P]),
     ("fluid_mesh_snapshot", C.c_int, [_P, C.POINTER(SdfParams)]),
     ("fluid_mesh_wait", C.c_int, [_P, C.POINTER(MeshC)]),
     ("fluid_mesh_stats", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

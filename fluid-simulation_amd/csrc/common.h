@@ -334,7 +334,7 @@ struct SdfGeom {
     int lo, hi;                          // the grid
     int bx0, by0, bz0, bnx, bny, bnz;    // bounding box of the counted particles' base cells: first cell and cells per axis
     int L0;                              // origin of the grid's first leaf, lo & ~7
-    int l0[3], nl[3];                    // leaves of the box dilated by 4 cells and clipped to the grid: first (counted from L0) and how many
+    int l0[3], nl[3];                    // leaves of the box dilated by 4 cells (a filtered mesh: 5) and clipped to the grid: first (counted from L0) and how many
     float R, w, dxf, bg, max2, min2;
     __host__ __device__ inline long leaves() const { return (long)nl[0] * nl[1] * nl[2]; }
     __host__ __device__ inline long cells() const { return (long)bnx * bny * bnz; }
@@ -348,6 +348,11 @@ void launch_sdf_search(hipStream_t st, const SdfGeom& g, const int* start, const
                        uint64_t* tm, int* flags, unsigned* visits);   // visits: nullptr, or cells looked at per leaf of the range
 void launch_sdf_pack(hipStream_t st, const SdfGeom& g, const int* flags, const int* slot, const float* tv, const uint64_t* tm, float* values,
                      uint64_t* active, int* origin);
+// box filter of that level set (kernels_sdf_filter.hip): one pass of width W along `axis` from src to dst (both 512 values per leaf of
+// the range; only flagged leaves are read or written), `off` added to the active voxels' results (0.0f: none); and the offset alone
+void launch_sdf_box(hipStream_t st, const SdfGeom& g, int axis, int W, float off, const int* flags, const uint64_t* tm, const float* src,
+                    float* dst);
+void launch_sdf_offset(hipStream_t st, const SdfGeom& g, float off, const int* flags, const uint64_t* tm, float* tv);
 // surface nets of that level set (kernels_mesh.hip): per leaf of the range the mixed-cell mask (8 words), the exclusive prefix of the
 // words' popcounts, the vertex and the quad count; tot[2] = the two totals, saturating at 2^31 (a one-block sum of the counts)
 void launch_mesh_mark(hipStream_t st, const SdfGeom& g, const float* tv, const int* flags, uint64_t* cmask, int* cpre, int* vcnt, int* qcnt,

@@ -41,6 +41,11 @@
 // waits for it, the main thread merges the blocks' lists (fluid_sdf_grids_merge, two merge buffers in turn) and hands the grid to
 // the writer thread beside the density job.  Refused without FLUID_BLOCKS, malformed, with an empty FLUID_OUT and with
 // FLUID_STEPS=0, before any handle is created.  Stdout and every other file are what they are without it.
+//   FLUID_OUT_SMOOTH=W,K[,OFFSET] (unset: off) — what FLUID_OUT_SURFACE, FLUID_OUT_MESH and FLUID_BLOCKS_SURFACE write is the level set
+// after K box filters of width W voxels and the offset (include/fluid_hip.h, "liquid surface, smoothed"): on one GPU the snapshots
+// are fluid_sdf_snapshot_filtered / fluid_mesh_snapshot_filtered; a block run filters the merged list on the main thread
+// (fluid_sdf_filter, two buffers in turn) before it goes to the writer thread.  Refused malformed, outside the filter's limits, or
+// with none of the three set, before any handle is created.  Without it stdout and every file are what they were.
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -175,6 +180,8 @@ struct BlockCfg {
     bool raw_f32 = false;
     bool surface = false;     // FLUID_BLOCKS_SURFACE
     fluid_sdf_params_t sp{};
+    bool smooth = false;      // FLUID_OUT_SMOOTH
+    fluid_sdf_filter_t sf{};
 };
 
 // What the main thread and the block threads share: `go` = steps released so far, done[i & 1] = blocks that finished step i.
@@ -320,6 +327,7 @@ static int run_blocks(const BlockCfg& cfg, const std::vector<double>& pos, int64
     std::vector<int32_t> s_org[2];
     std::vector<float> s_val[2];
     std::vector<uint64_t> s_act[2];
+    std::vector<float> s_smooth[2];   // FLUID_OUT_SMOOTH: the filtered values of the merged list
     double dt = cfg.prm.max_dt, simulationTime = 0;
     auto release = [&](int upto) {
         {
@@ -369,6 +377,12 @@ static int run_blocks(const BlockCfg& cfg, const std::vector<double>& pos, int64
             if (ks && fluid_sdf_grids_merge(sp.data(), R, ks, so.data(), sv.data(), sa.data()) != ks) { sy.fail("fluid_sdf_grids_merge: the blocks' surface lists do not merge"); break; }
             sg = fluid_sdf_grid_t{n, (int32_t)ks, sp[0].background, sp[0].radius, sp[0].half_width, ks ? so.data() : nullptr, ks ? sv.data() : nullptr,
                                   ks ? sa.data() : nullptr};
+            if (cfg.smooth && ks) {
+                auto& sm = s_smooth[i & 1];
+                if (sm.size() < sv.size()) sm.resize(sv.size());
+                if (fluid_sdf_filter(&sg, &cfg.sf, sm.data()) != FLUID_OK) { sy.fail("fluid_sdf_filter: the merged surface list was refused"); break; }
+                sg.values = sm.data();
+            }
         }
         lw.submit(i, fluid_leaf_grid_t{n, (int32_t)k, k ? org.data() : nullptr, k ? val.data() : nullptr}, surface ? &sg : nullptr);
     }
@@ -454,6 +468,28 @@ int main(int, char**)
             return 1;
         }
         bc.surface = true;
+    }
+    const char* smenv = getenv("FLUID_OUT_SMOOTH");
+    const bool smooth = smenv && *smenv;
+    fluid_sdf_filter_t sf{};
+    if (smooth) {
+        char tail = 0;
+        const int got = sscanf(smenv, "%d,%d,%lf%c", &sf.width, &sf.iterations, &sf.offset, &tail);
+        if (got == 2) {   // "W,K" alone: nothing may follow K
+            int used = 0;
+            if (sscanf(smenv, "%d,%d%n", &sf.width, &sf.iterations, &used) != 2 || smenv[used] != 0) sf.width = 0;
+            sf.offset = 0;
+        }
+        if ((got != 2 && got != 3) || sf.width < 1 || sf.width > 4 || sf.iterations < 0 || sf.iterations > 16 || !std::isfinite(sf.offset) ||
+            !std::isfinite((float)sf.offset)) {
+            std::cerr << "FLUID_OUT_SMOOTH must be W,K[,OFFSET] (box width 1..4 voxels, iterations 0..16, a finite offset), e.g. 1,4,-0.5" << std::endl;
+            return 1;
+        }
+        if (!surface && !mesh && !bc.surface) {
+            std::cerr << "FLUID_OUT_SMOOTH smooths what FLUID_OUT_SURFACE, FLUID_OUT_MESH or FLUID_BLOCKS_SURFACE write: none of them is set" << std::endl;
+            return 1;
+        }
+        bc.smooth = true, bc.sf = sf;
     }
     if (blocks && *blocks) {
         char tail = 0;
@@ -582,12 +618,12 @@ int main(int, char**)
                 lw.stop();
                 return 1;
             }
-            if (surface && fluid_sdf_snapshot(sim, &sp) != FLUID_OK) {
+            if (surface && (smooth ? fluid_sdf_snapshot_filtered(sim, &sp, &sf) : fluid_sdf_snapshot(sim, &sp)) != FLUID_OK) {
                 std::cerr << "fluid_sdf_snapshot: " << fluid_last_error() << std::endl;
                 lw.stop();
                 return 1;
             }
-            if (mesh && fluid_mesh_snapshot(sim, &mp) != FLUID_OK) {
+            if (mesh && (smooth ? fluid_mesh_snapshot_filtered(sim, &mp, &sf) : fluid_mesh_snapshot(sim, &mp)) != FLUID_OK) {
                 std::cerr << "fluid_mesh_snapshot: " << fluid_last_error() << std::endl;
                 lw.stop();
                 return 1;

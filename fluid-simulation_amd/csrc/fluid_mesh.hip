@@ -9,6 +9,11 @@
 // so what fluid_mesh_wait handed out stays valid until the second following mesh snapshot.  Slots and the count of outstanding
 // snapshots are the mesh's own: density, surface and mesh can all be taken in one step.  The particle arrays are only read and
 // `binned` keeps holding, as for the surface.
+//
+// fluid_mesh_snapshot_filtered ("liquid surface, smoothed"): the front half runs over the box dilated by 5 cells and ends with the
+// filter's box passes (fluid_sdf.hip); the mesh kernels read the buffer the last pass wrote.  After the filter an inside voxel is
+// only known to be active or -bg, so within 4 cells of a base cell, and a mixed cell's min corner within [-5, +4]: kernels_mesh.hip's
+// range argument with every distance one larger.
 #include "sim.h"
 
 using namespace fl;
@@ -114,14 +119,12 @@ static int mesh_grow(MeshSlot& q, size_t bytes)
     return FLUID_OK;
 }
 
-extern "C" {
-
-int fluid_mesh_snapshot(fluid_sim_t* s, const fluid_sdf_params_t* p)
+static int mesh_capture(fluid_sim* s, const fluid_sdf_params_t* p, const fluid_sdf_filter_t* filt)
 {
-    MESH_GUARD(s);
     SdfFront f;
-    int rc = sdf_begin(s, p, &f);
+    int rc = sdf_begin(s, p, &f, filt);
     if (rc) return rc;
+    if (filt) f.dilate = 5;
     if ((rc = mesh_init(s))) return rc;
     MeshState* o = s->mesh;
     if (o->n_snap - o->n_wait >= 2) return fail(FLUID_ERR_STATE, "two mesh snapshots are waiting for fluid_mesh_wait");
@@ -159,6 +162,22 @@ int fluid_mesh_snapshot(fluid_sim_t* s, const fluid_sdf_params_t* p)
     o->n_snap++;
     o->last_v = nv, o->last_q = nq;
     return FLUID_OK;
+}
+
+extern "C" {
+
+int fluid_mesh_snapshot(fluid_sim_t* s, const fluid_sdf_params_t* p)
+{
+    MESH_GUARD(s);
+    return mesh_capture(s, p, nullptr);
+}
+
+int fluid_mesh_snapshot_filtered(fluid_sim_t* s, const fluid_sdf_params_t* p, const fluid_sdf_filter_t* f)
+{
+    if (!s) return fail(FLUID_ERR_ARG, "null handle");
+    if (s->dist) return fail(FLUID_ERR_STATE, "filtered mesh snapshots are single-GPU only: a decomposed run merges its blocks' level-set lists (fluid_sdf_grids_merge), filters the result (fluid_sdf_filter) and meshes it on the host (fluid_sdf_mesh)");
+    if (!f) return fail(FLUID_ERR_ARG, "null argument");
+    return mesh_capture(s, p, f);
 }
 
 int fluid_mesh_wait(fluid_sim_t* s, fluid_mesh_t* out)

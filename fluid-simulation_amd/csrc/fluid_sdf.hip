@@ -19,6 +19,10 @@
 //
 // The front half (sdf_begin, sdf_front: everything up to and including the search) is also the front half of fluid_mesh_snapshot
 // (fluid_mesh.hip), which works on the search's scratch in place of the pack.
+//
+// fluid_sdf_snapshot_filtered / fluid_mesh_snapshot_filtered ("liquid surface, smoothed"; kernels_sdf_filter.hip): the front half
+// ends with the filter's box passes, one launch each, 3 per iteration (x, z, y), from tv to tv2 and back; what follows reads
+// whichever buffer the last pass wrote.  tv2 exists from the handle's first filtered snapshot on.
 #include "sim.h"
 
 using namespace fl;
@@ -40,6 +44,8 @@ struct SdfState {
     int* place = nullptr;
     double* spos = nullptr;    // sorted x | y | z, part_cap each
     float* tv = nullptr;
+    float* tv2 = nullptr;      // the box passes' second buffer, leaf_cap x 512 like tv: allocated once a filtered snapshot was asked for
+    bool filtered = false;
     uint64_t* tm = nullptr;
     int *flags = nullptr, *slot = nullptr, *leaf_sums = nullptr;
     unsigned* visits = nullptr;   // FLUID_SDF_VISITS=1 only
@@ -80,7 +86,7 @@ void fl::sdf_free(fluid_sim* s)
         if (q.host) hipHostFree(q.host);
         if (q.done) hipEventDestroy(q.done);
     }
-    for (void* p : {(void*)o->cnt, (void*)o->start, (void*)o->cell_sums, (void*)o->place, (void*)o->spos, (void*)o->tv, (void*)o->tm, (void*)o->flags,
+    for (void* p : {(void*)o->cnt, (void*)o->start, (void*)o->cell_sums, (void*)o->place, (void*)o->spos, (void*)o->tv, (void*)o->tv2, (void*)o->tm, (void*)o->flags,
                     (void*)o->slot, (void*)o->leaf_sums, (void*)o->visits, (void*)o->d_small})
         if (p) hipFree(p);
     if (o->h_small) hipHostFree(o->h_small);
@@ -99,8 +105,12 @@ static hipError_t regrow(T*& p, size_t n)
     return hipMalloc((void**)&p, n * sizeof(T));
 }
 
-static int sdf_scratch(SdfState* o, long cells, long parts, long leaves)
+static int sdf_scratch(SdfState* o, long cells, long parts, long leaves, bool filtered)
 {
+    if (filtered && !o->filtered) {   // the first filtered snapshot of the handle: tv2 beside whatever tv there is
+        o->filtered = true;
+        if (o->leaf_cap > 0) HIPCHK(regrow(o->tv2, (size_t)o->leaf_cap * 512));
+    }
     if (cells > o->cell_cap) {
         o->cell_cap = 0;
         const long cap = cells + cells / 4 + 64;
@@ -120,6 +130,7 @@ static int sdf_scratch(SdfState* o, long cells, long parts, long leaves)
         o->leaf_cap = 0;
         const long cap = leaves + leaves / 4 + 64;
         HIPCHK(regrow(o->tv, (size_t)cap * 512));
+        if (o->filtered) HIPCHK(regrow(o->tv2, (size_t)cap * 512));
         HIPCHK(regrow(o->tm, (size_t)cap * 8));
         HIPCHK(regrow(o->flags, (size_t)cap));
         HIPCHK(regrow(o->slot, (size_t)cap));
@@ -150,9 +161,12 @@ static int sdf_grow(SdfSlot& q, size_t n)
 // on the handle's stream; a decomposed handle (s->dist) bins its live entries only.  f->any = some particle counts; then f->g holds
 // the box and the range, and tv / flags are the search's: 512 values and a listed flag per leaf of the range (the values of a leaf
 // whose flag is 0 may be stale: kernels_sdf.hip).  The scratch is one per handle: whoever calls next overwrites it, in stream order.
-int fl::sdf_begin(fluid_sim* s, const fluid_sdf_params_t* p, SdfFront* f)
+int fl::sdf_begin(fluid_sim* s, const fluid_sdf_params_t* p, SdfFront* f, const fluid_sdf_filter_t* filt)
 {
     if (!p) return fail(FLUID_ERR_ARG, "null argument");
+    if (filt && (filt->width < 1 || filt->width > 4 || filt->iterations < 0 || filt->iterations > 16 || !std::isfinite(filt->offset) ||
+                 !std::isfinite((float)filt->offset)))
+        return fail(FLUID_ERR_ARG, "level-set filter: width in 1..4, iterations in 0..16 and a finite offset are required");
     const float R = (float)p->radius, w = (float)p->half_width;
     const float mx = R + w;
     if (!(p->radius > 0) || !(R > 0.0f) || !(w >= 1.0f) || !(mx <= 4.0f))
@@ -170,6 +184,7 @@ int fl::sdf_begin(fluid_sim* s, const fluid_sdf_params_t* p, SdfFront* f)
     g.min2 = mn * mn;
     f->any = false;
     f->tv = nullptr, f->flags = nullptr;
+    f->filt = filt, f->dilate = 4;
     return FLUID_OK;
 }
 
@@ -192,13 +207,13 @@ int fl::sdf_front(fluid_sim* s, SdfFront* f)
         g.bx0 = box[0], g.by0 = box[1], g.bz0 = box[2];
         g.bnx = box[3] - box[0] + 1, g.bny = box[4] - box[1] + 1, g.bnz = box[5] - box[2] + 1;
         for (int a = 0; a < 3; ++a) {
-            const int c0 = std::max(box[a] - 4, g.lo), c1 = std::min(box[3 + a] + 4, g.hi);
+            const int c0 = std::max(box[a] - f->dilate, g.lo), c1 = std::min(box[3 + a] + f->dilate, g.hi);
             g.l0[a] = (c0 - g.L0) >> 3;
             g.nl[a] = ((c1 - g.L0) >> 3) - g.l0[a] + 1;
         }
         const long cells = g.cells(), leaves = g.leaves();
         if (cells + 1 > 0x7fffffffL || leaves > 0x7fffffffL) return fail(FLUID_ERR_ARG, "level set: the particles' box is too large");
-        if ((rc = sdf_scratch(o, cells + 1, s->np, leaves))) return rc;
+        if ((rc = sdf_scratch(o, cells + 1, s->np, leaves, f->filt != nullptr))) return rc;
         double *sx = o->spos, *sy = o->spos + o->part_cap, *sz = o->spos + 2 * o->part_cap;
         HIPCHK(hipMemsetAsync(o->cnt, 0, (size_t)(cells + 1) * sizeof(int), s->st));
         launch_sdf_count(s->st, s->np, live, g, o->cnt, o->place, s->dist);
@@ -207,15 +222,28 @@ int fl::sdf_front(fluid_sim* s, SdfFront* f)
         launch_sdf_search(s->st, g, o->start, sx, sy, sz, o->tv, o->tm, o->flags, o->count_visits ? o->visits : nullptr);
         f->any = true;
         f->tv = o->tv, f->flags = o->flags;
+        if (f->filt) {
+            // iteration = x, z, y (the library's order); the offset rides on the last pass, or is a pass of its own without one
+            static const int axes[3] = {0, 2, 1};
+            const int W = f->filt->width, passes = 3 * f->filt->iterations;
+            const float off = (float)f->filt->offset;
+            float *src = o->tv, *dst = o->tv2;
+            for (int k = 0; k < passes; ++k) {
+                launch_sdf_box(s->st, g, axes[k % 3], W, k == passes - 1 ? off : 0.0f, o->flags, o->tm, src, dst);
+                std::swap(src, dst);
+            }
+            if (passes == 0 && off != 0.0f) launch_sdf_offset(s->st, g, off, o->flags, o->tm, src);
+            f->tv = src;
+        }
     }
     return FLUID_OK;
 }
 
 // front half -> scan of the flags -> pack -> copy
-static int sdf_capture(fluid_sim* s, const fluid_sdf_params_t* p)
+static int sdf_capture(fluid_sim* s, const fluid_sdf_params_t* p, const fluid_sdf_filter_t* filt = nullptr)
 {
     SdfFront f;
-    int rc = sdf_begin(s, p, &f);
+    int rc = sdf_begin(s, p, &f, filt);
     if (rc) return rc;
     SdfState* o = s->sdf;
     if (o->n_snap - o->n_wait >= 2) return fail(FLUID_ERR_STATE, "two level-set snapshots are waiting for fluid_sdf_wait");
@@ -248,7 +276,7 @@ static int sdf_capture(fluid_sim* s, const fluid_sdf_params_t* p)
         float* values = (float*)q.dev;
         uint64_t* active = (uint64_t*)(q.dev + (size_t)n * 2048);
         int* origin = (int*)(q.dev + (size_t)n * (2048 + 64));
-        launch_sdf_pack(s->st, g, o->flags, o->slot, o->tv, o->tm, values, active, origin);
+        launch_sdf_pack(s->st, g, o->flags, o->slot, f.tv, o->tm, values, active, origin);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(o->packed, s->st));
         HIPCHK(hipStreamWaitEvent(o->copy, o->packed, 0));
@@ -304,6 +332,14 @@ int fluid_sdf_snapshot(fluid_sim_t* s, const fluid_sdf_params_t* p)
 {
     SDF_GUARD(s);
     return sdf_capture(s, p);
+}
+
+int fluid_sdf_snapshot_filtered(fluid_sim_t* s, const fluid_sdf_params_t* p, const fluid_sdf_filter_t* f)
+{
+    if (!s) return fail(FLUID_ERR_ARG, "null handle");
+    if (s->dist) return fail(FLUID_ERR_STATE, "filtered level-set snapshots are single-GPU only: a mean of per-block minima is not the mean of the minimum; filter the merged list on the host (fluid_sdf_filter)");
+    if (!f) return fail(FLUID_ERR_ARG, "null argument");
+    return sdf_capture(s, p, f);
 }
 
 int fluid_sdf_wait(fluid_sim_t* s, fluid_sdf_grid_t* out)

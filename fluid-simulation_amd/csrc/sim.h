@@ -256,11 +256,14 @@ void sdf_move(fluid_sim* from, fluid_sim* to);      // re-balance: slots, stream
 struct SdfFront {
     SdfGeom g;
     bool any;             // some particle counts: g holds the box and the range, tv / flags are filled for every leaf of the range
-    const float* tv;      // 512 values per leaf of the range (stale where flags[j] == 0)
+    const float* tv;      // 512 values per leaf of the range (stale where flags[j] == 0): the filter's last buffer when filt is set
     const int* flags;     // the leaf is listed
+    const fluid_sdf_filter_t* filt;   // nullptr: unfiltered.  Set by sdf_begin from its argument (limits checked there)
+    int dilate;           // cells the base-cell box is dilated by for the range: 4; 5 for a filtered mesh (set by the caller after sdf_begin)
 };
-int sdf_begin(fluid_sim* s, const fluid_sdf_params_t* p, SdfFront* f);   // limits of the parameters, the state, the constants of g
-int sdf_front(fluid_sim* s, SdfFront* f);                                // bbox (waits for the stream) -> count, scan, scatter -> search
+// limits of the parameters (and of the filter, when one is given), the state, the constants of g
+int sdf_begin(fluid_sim* s, const fluid_sdf_params_t* p, SdfFront* f, const fluid_sdf_filter_t* filt = nullptr);
+int sdf_front(fluid_sim* s, SdfFront* f);   // bbox (waits for the stream) -> count, scan, scatter -> search -> the filter's passes
 
 // fluid_mesh.hip
 void mesh_free(fluid_sim* s);        // waits for the copies in flight, frees the scratch, the staging and the pinned buffers

@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 
-from ._lib import lib, check, FluidError, Params, StepStats, FIELD, Source, LeafGridC, SdfParams, SdfGridC, MeshC
+from ._lib import lib, check, FluidError, Params, StepStats, FIELD, Source, LeafGridC, SdfParams, SdfGridC, SdfFilter, MeshC
 
 _FIELD_DTYPE = {
     FIELD.CONTAINER: (np.float32, 1), FIELD.WEIGHTS: (np.float32, 1), FIELD.OUTPUT: (np.float32, 1),
@@ -187,6 +187,25 @@ def write_vdb_sdf(path, grid, compression="zip"):
     """One FloatGrid "surface" of class "level set" whose leaves are the listed ones (fluid_write_vdb_sdf: host only)."""
     c, _keep = grid._c()
     check(lib.fluid_write_vdb_sdf(str(path).encode(), C.byref(c), _VDB_COMPRESSION[compression]))
+
+
+def _sdf_filter_of(smooth):
+    """fluid_sdf_filter_t of a (width, iterations[, offset]) tuple."""
+    if len(smooth) not in (2, 3):
+        raise ValueError("smooth must be (width, iterations) or (width, iterations, offset)")
+    return SdfFilter(int(smooth[0]), int(smooth[1]), float(smooth[2]) if len(smooth) == 3 else 0.0)
+
+
+def sdf_filter(grid, width, iterations, offset=0.0):
+    """The SdfGrid with `iterations` box filters of `width` and then `offset` applied to its active voxels; masks, leaves and
+    inactive values stay (fluid_sdf_filter: host only).  A decomposed run smooths sdf_filter(merge_sdf_grids(parts), ...)."""
+    c, _keep = grid._c()
+    f = SdfFilter(int(width), int(iterations), float(offset))
+    val = np.empty((grid.n_leaves, 512), np.float32)
+    rc = lib.fluid_sdf_filter(C.byref(c), C.byref(f), val.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise FluidError(rc, "fluid_sdf_filter: a bad leaf list or filter (width 1..4, iterations 0..16, finite offset)")
+    return SdfGrid(grid.n, grid.origin, val, grid.active, grid.background, grid.radius, grid.half_width)
 
 
 class Mesh:
@@ -465,11 +484,15 @@ class FluidSim:
         return dict(zip(("leaves_in_grid", "leaves_listed", "bytes_to_host"), (x.value for x in v)))
 
     # ---- liquid surface: narrow-band level set of the particles (single GPU; include/fluid_hip.h) ----
-    def sdf_snapshot(self, radius, half_width):
+    def sdf_snapshot(self, radius, half_width, smooth=None):
         """Enqueue the level set of the particles as they are now (spheres of `radius`, band of `half_width`, both in voxels);
-        a step() called next overlaps the copy to the host."""
+        a step() called next overlaps the copy to the host.  smooth=(width, iterations[, offset]): box-filtered and offset on
+        the device first (include/fluid_hip.h, "liquid surface, smoothed")."""
         p = SdfParams(float(radius), float(half_width))
-        check(lib.fluid_sdf_snapshot(self._h, C.byref(p)))
+        if smooth is None:
+            check(lib.fluid_sdf_snapshot(self._h, C.byref(p)))
+        else:
+            check(lib.fluid_sdf_snapshot_filtered(self._h, C.byref(p), C.byref(_sdf_filter_of(smooth))))
 
     def sdf_wait(self):
         """The oldest level-set snapshot not yet waited for, as an SdfGrid (copied out of the handle's pinned buffer)."""
@@ -483,11 +506,14 @@ class FluidSim:
         return dict(zip(("leaves_in_grid", "leaves_listed", "bytes_to_host"), (x.value for x in v)))
 
     # ---- liquid surface as a mesh: surface nets of the level set (single GPU; include/fluid_hip.h) ----
-    def mesh_snapshot(self, radius, half_width):
-        """Enqueue the surface nets of the level set of the particles as they are now (parameters as sdf_snapshot); a step()
-        called next overlaps the copy to the host."""
+    def mesh_snapshot(self, radius, half_width, smooth=None):
+        """Enqueue the surface nets of the level set of the particles as they are now (parameters as sdf_snapshot, `smooth`
+        included); a step() called next overlaps the copy to the host."""
         p = SdfParams(float(radius), float(half_width))
-        check(lib.fluid_mesh_snapshot(self._h, C.byref(p)))
+        if smooth is None:
+            check(lib.fluid_mesh_snapshot(self._h, C.byref(p)))
+        else:
+            check(lib.fluid_mesh_snapshot_filtered(self._h, C.byref(p), C.byref(_sdf_filter_of(smooth))))
 
     def mesh_wait(self):
         """The oldest mesh snapshot not yet waited for: (vertices (nv, 3) float32 in index space, quads (nq, 4) uint32), copied

@@ -638,6 +638,52 @@ int fluid_dist_sdf_stats(fluid_sim_t* s, int64_t* leaves_in_grid, int64_t* leave
 int64_t fluid_sdf_grids_merge(const fluid_sdf_grid_t* parts, int32_t n_parts, int64_t cap_leaves, int32_t* origin, float* values,
                               uint64_t* active);
 
+/* ---- liquid surface, smoothed: box filter and offset of the level set ------------------------------------------------------
+ * The level set above is the raw union of spheres: a surface of bumps one particle wide.  OpenVDB pipelines put LevelSetFilter
+ * between ParticlesToLevelSet and VolumeToMesh (mean or gaussian flow, then an offset that gives back the volume the flow took);
+ * this is that stage, restated from the library's arithmetic (tools/LevelSetFilter.h:213-222, 231-233, 303-310, 471, 530-535) as
+ * an exact, order-free definition of its own: the kernels, fluid_sdf_filter below and the tests' numpy form give the same bytes.
+ *
+ * Input.  The level set of "liquid surface": val(c) and act(c), c in [lo,hi]^3; every voxel of an unlisted leaf is inactive +bg,
+ * and OUTSIDE THE GRID val is +bg (what the library's accessor returns outside the tree).  Float throughout, no FMA.
+ *
+ * One box pass of width W along axis a.  frac = 1.0f / (float)(2W + 1), one correctly rounded float division.  For every ACTIVE
+ * voxel c:  s = 0.0f;  for i = -W .. +W ascending: s = s + val_prev(c + i e_a);  val_new(c) = s * frac.  Inactive voxels keep
+ * their value (+bg or -bg).  val_prev is the complete result of the pass before (Jacobi, never in place); a voxel's sum has a
+ * fixed order and depends on nothing but its inputs, so no schedule can change the result.
+ * One iteration = three passes in the library's order: axis x, then axis Z, then axis Y (Filter::box binds boxX, boxY, boxZ in
+ * that order, and boxY is Avg<2>).  After K iterations the offset: off = (float)offset; if off != 0.0f every active voxel gets
+ * val = val + off (negative: the liquid grows); off == 0.0f skips the step, so K = 0 with offset 0 gives the unfiltered bytes.
+ * Topology does not change: the active masks, the set of listed leaves and their order stay, inactive values stay +-bg, only
+ * the values of active voxels differ.
+ *
+ * What this is not.  LevelSetTracker::track() is NOT run (the library's mean() / gaussian() run it after every box): there is no
+ * renormalisation and no rebuild of the band; mean(W) corresponds to K = 1, gaussian(W) to K = 4.  An offset of more than about
+ * bg - dx in magnitude pushes the surface into the band's edge, where the inactive +-bg plateau begins.
+ * Limits: width in 1..4, iterations in 0..16, offset finite; anything else is FLUID_ERR_ARG.
+ *
+ * fluid_dist_sdf_snapshot stays unfiltered: a mean of per-rank minima is not the mean of the minimum.  A decomposed run filters
+ * after the merge:  k = fluid_sdf_grids_merge(...);  g = {n, k, ...};  fluid_sdf_filter(&g, &f, smooth);  g.values = smooth;
+ * then fluid_write_vdb_sdf / fluid_sdf_mesh as before. */
+typedef struct fluid_sdf_filter { int32_t width; int32_t iterations; double offset; } fluid_sdf_filter_t;
+/* fluid_sdf_snapshot in every respect (same two slots, same count of outstanding snapshots — the third is FLUID_ERR_STATE —, same
+ * fluid_sdf_wait / fluid_sdf_stats), with 3 * iterations box passes (one more pass for an offset when iterations is 0) on the
+ * handle's stream between the search and the pack.  The passes ping-pong between the search's values and a second buffer of the
+ * same size, which the handle's first filtered snapshot allocates (never inside a step; an unfiltered caller never pays for it).
+ * FLUID_ERR_ARG: bad parameters or bad filter limits.  FLUID_ERR_STATE on a decomposed handle: filter the merged list
+ * (fluid_sdf_filter). */
+int fluid_sdf_snapshot_filtered(fluid_sim_t* s, const fluid_sdf_params_t* p, const fluid_sdf_filter_t* f);
+/* fluid_mesh_snapshot ("liquid surface as a mesh", below) of the filtered level set: same slots, count, fluid_mesh_wait /
+ * fluid_mesh_stats.  The front half runs over the particles' base-cell box dilated by 5 cells (unfiltered: 4): after the filter an
+ * inside voxel is only known to be active or -bg, hence within R + w <= 4 of a particle and within 4 cells of its base cell, and the
+ * min corner of a mixed cell lies in [-5, +4] of it.  Errors as above (FLUID_ERR_STATE names fluid_sdf_filter and fluid_sdf_mesh). */
+int fluid_mesh_snapshot_filtered(fluid_sim_t* s, const fluid_sdf_params_t* p, const fluid_sdf_filter_t* f);
+/* Host only: the definition above applied to a leaf list; values[512 * n_leaves] receives the filtered values in the list's order
+ * (g's own arrays are only read).  Voxels of listed leaves outside the grid are read as +bg and copied unchanged.  Works leaf by
+ * leaf, the two neighbours on the pass's axis found by bisection; no dense grid is made.  FLUID_ERR_ARG with nothing written: a
+ * list fluid_sdf_to_dense refuses, bad filter limits, values NULL with leaves, values overlapping g->values. */
+int fluid_sdf_filter(const fluid_sdf_grid_t* g, const fluid_sdf_filter_t* f, float* values);
+
 /* ---- liquid surface as a mesh: surface nets of the level set ----------------------------------------------------------------
  * Polygons for everyone who is no volume renderer.  The reference names tools/VolumeToMesh.h, whose output depends on the library's
  * tree traversal; like the level set itself the mesh gets an exact, order-free definition of its own — naive surface nets on the
