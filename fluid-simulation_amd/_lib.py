@@ -74,6 +74,16 @@ class MeshC(C.Structure):
                 ("half_width", C.c_float), ("background", C.c_float), ("vertices", C.c_void_p), ("quads", C.c_void_p)]
 
 
+class SdfAttrC(C.Structure):
+    """fluid_sdf_attr_t: the closest particle's id and velocity per voxel of a leaf list ("liquid surface, attributes")."""
+    _fields_ = [("n_leaves", C.c_int32), ("id", C.c_void_p), ("velocity", C.c_void_p)]
+
+
+class MeshAttrC(C.Structure):
+    """fluid_mesh_attr_t: a velocity per mesh vertex."""
+    _fields_ = [("n_vertices", C.c_int64), ("velocity", C.c_void_p)]
+
+
 class MpmParams(C.Structure):
     """mpm_params_t (include/mpm_hip.h); defaults = the literals of mpm.cc."""
     _fields_ = [("B", C.c_int32), ("W", C.c_int32), ("device", C.c_int32), ("cg_max_iters", C.c_int32),
@@ -186,6 +196,13 @@ SYMBOLS = [
     ("fluid_mesh_stats", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("fluid_sdf_mesh", C.c_int64, [C.POINTER(SdfGridC), C.c_int64, C.c_int64, _P, _P, C.POINTER(C.c_int64)]),
     ("fluid_write_ply_mesh", C.c_int, [C.c_char_p, C.POINTER(MeshC), C.c_float]),
+    ("fluid_sdf_snapshot_attr", C.c_int, [_P, C.POINTER(SdfParams), C.POINTER(SdfFilter)]),
+    ("fluid_sdf_wait_attr", C.c_int, [_P, C.POINTER(SdfGridC), C.POINTER(SdfAttrC)]),
+    ("fluid_mesh_snapshot_attr", C.c_int, [_P, C.POINTER(SdfParams), C.POINTER(SdfFilter)]),
+    ("fluid_mesh_wait_attr", C.c_int, [_P, C.POINTER(MeshC), C.POINTER(MeshAttrC)]),
+    ("fluid_sdf_mesh_attr", C.c_int64, [C.POINTER(SdfGridC), C.POINTER(SdfAttrC), C.c_int64, _P]),
+    ("fluid_sdf_attr_to_dense", C.c_int, [C.POINTER(SdfGridC), C.POINTER(SdfAttrC), _P, _P]),
+    ("fluid_write_ply_mesh_attr", C.c_int, [C.c_char_p, C.POINTER(MeshC), C.POINTER(MeshAttrC), C.c_float, C.c_float]),
     # the snow-MPM step (include/mpm_hip.h)
     ("mpm_default_params", C.c_int, [C.POINTER(MpmParams)]),
     ("mpm_create", C.c_int, [C.POINTER(MpmParams), C.POINTER(_P)]),

@@ -343,11 +343,21 @@ struct SdfGeom {
 void launch_sdf_bbox(hipStream_t st, long n, Particles p, int lo, int hi, int* box, bool live = false);   // box[6]: min, max of the counted base cells
 void launch_sdf_count(hipStream_t st, long n, Particles p, const SdfGeom& g, int* cnt, int* place, bool live = false);
 void launch_sdf_scatter(hipStream_t st, long n, Particles p, const SdfGeom& g, const int* start, const int* place, double* sx, double* sy,
-                        double* sz);
+                        double* sz, int* ssrc = nullptr);   // ssrc: nullptr, or where each sorted position's index in the live arrays goes
 void launch_sdf_search(hipStream_t st, const SdfGeom& g, const int* start, const double* sx, const double* sy, const double* sz, float* tv,
                        uint64_t* tm, int* flags, unsigned* visits);   // visits: nullptr, or cells looked at per leaf of the range
 void launch_sdf_pack(hipStream_t st, const SdfGeom& g, const int* flags, const int* slot, const float* tv, const uint64_t* tm, float* values,
                      uint64_t* active, int* origin);
+// "liquid surface, attributes": the search that also keeps the closest particle (smallest id among equals) and writes its id (tid: 512
+// per leaf of the range) and narrowed velocity (tvel: [leaf][axis][512]) for the active voxels; the pack that also lists them; the emit
+// that also writes a velocity per vertex.  p: the live arrays ssrc indexes (pid, vx, vy, vz are read)
+void launch_sdf_search_attr(hipStream_t st, const SdfGeom& g, const int* start, const double* sx, const double* sy, const double* sz, float* tv,
+                            uint64_t* tm, int* flags, const int* ssrc, Particles p, uint32_t* tid, float* tvel);
+void launch_sdf_pack_attr(hipStream_t st, const SdfGeom& g, const int* flags, const int* slot, const float* tv, const uint64_t* tm, float* values,
+                          uint64_t* active, int* origin, const uint32_t* tid, const float* tvel, uint32_t* ids, float* vel);
+void launch_mesh_emit_attr(hipStream_t st, const SdfGeom& g, const float* tv, const int* flags, const uint64_t* tm, const float* tvel,
+                           const uint64_t* cmask, const int* cpre, const int* vcnt, const int* qcnt, const int* vbase, const int* qbase,
+                           float* vertices, uint32_t* quads, float* vvel);
 // box filter of that level set (kernels_sdf_filter.hip): one pass of width W along `axis` from src to dst (both 512 values per leaf of
 // the range; only flagged leaves are read or written), `off` added to the active voxels' results (0.0f: none); and the offset alone
 void launch_sdf_box(hipStream_t st, const SdfGeom& g, int axis, int W, float off, const int* flags, const uint64_t* tm, const float* src,

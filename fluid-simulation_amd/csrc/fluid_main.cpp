@@ -19,6 +19,11 @@
 // that level set (fluid_mesh_snapshot after the other snapshots, fluid_mesh_wait beside theirs, fluid_write_ply_mesh with voxel size
 // dx on the writer thread).  With or without FLUID_OUT_SURFACE; refused where that one is.  Stdout and every other file are what
 // they are without it.
+//   FLUID_OUT_MESH_VEL=SCALE (unset: off; with FLUID_OUT_MESH only) — mesh<i>.ply carries vx / vy / vz per vertex, the velocity of the
+// closest particles interpolated onto the vertex (include/fluid_hip.h, "liquid surface, attributes": fluid_mesh_snapshot_attr,
+// fluid_mesh_wait_attr, fluid_write_ply_mesh_attr) times SCALE, a finite number.  Composes with FLUID_OUT_SMOOTH.  Refused without
+// FLUID_OUT_MESH or malformed, before any handle is created.  Positions and faces are those of the file without it; unset, every file
+// is byte for byte what it was.
 // Initial particles: with the defaults (N = 121, 10 per voxel) exactly the reference's — fill(CoordBBox(-20, 20)) scattered by
 // UniformPointScatter with std::mt19937(FLUID_SEED) (fluid_scene_uniform_scatter: 689210 points); any other N / PPC takes the
 // scaled synthetic cube (fluid_scene_water_cube_drop).
@@ -88,6 +93,9 @@ struct LeafWriter {
     bool has_sjob = false;
     fluid_mesh_t mjob{};      // FLUID_OUT_MESH: the same step's mesh
     bool has_mjob = false;
+    fluid_mesh_attr_t majob{};   // FLUID_OUT_MESH_VEL: its vertex velocities
+    bool has_majob = false;
+    float vel_scale = 1.0f;
     float voxel = 1.0f;
     int job_step = -1;        // step whose grid is waiting (-1: none)
     int done = 0;             // grids written
@@ -108,6 +116,8 @@ struct LeafWriter {
             const bool has_sg = has_sjob;
             const fluid_mesh_t mg = mjob;
             const bool has_mg = has_mjob;
+            const fluid_mesh_attr_t ma = majob;
+            const bool has_ma = has_majob;
             const int i = job_step;
             lk.unlock();
             std::string bad;
@@ -125,7 +135,7 @@ struct LeafWriter {
             }
             if (has_mg && bad.empty()) {
                 const std::string fm = outdir + "/mesh" + std::to_string(i) + ".ply";
-                if (fluid_write_ply_mesh(fm.c_str(), &mg, voxel) != FLUID_OK) bad = fm;
+                if ((has_ma ? fluid_write_ply_mesh_attr(fm.c_str(), &mg, &ma, voxel, vel_scale) : fluid_write_ply_mesh(fm.c_str(), &mg, voxel)) != FLUID_OK) bad = fm;
             }
             if (raw_f32 && bad.empty()) {
                 const size_t ncell = (size_t)g.n * g.n * g.n;
@@ -147,7 +157,8 @@ struct LeafWriter {
         cv.wait(lk, [&] { return done >= n; });
         return error.empty();
     }
-    void submit(int step, const fluid_leaf_grid_t& g, const fluid_sdf_grid_t* surface = nullptr, const fluid_mesh_t* mesh = nullptr)
+    void submit(int step, const fluid_leaf_grid_t& g, const fluid_sdf_grid_t* surface = nullptr, const fluid_mesh_t* mesh = nullptr,
+                const fluid_mesh_attr_t* mesh_attr = nullptr)
     {
         std::unique_lock<std::mutex> lk(m);
         cv.wait(lk, [&] { return job_step < 0; });
@@ -156,6 +167,8 @@ struct LeafWriter {
         if (surface) sjob = *surface;
         has_mjob = mesh != nullptr;
         if (mesh) mjob = *mesh;
+        has_majob = mesh && mesh_attr;
+        if (has_majob) majob = *mesh_attr;
         job_step = step;
         cv.notify_all();
     }
@@ -452,6 +465,20 @@ int main(int, char**)
             return 1;
         }
     }
+    const char* mvenv = getenv("FLUID_OUT_MESH_VEL");
+    const bool mesh_vel = mvenv && *mvenv;
+    double mesh_vel_scale = 1.0;
+    if (mesh_vel) {
+        char tail = 0;
+        if (sscanf(mvenv, "%lf%c", &mesh_vel_scale, &tail) != 1 || !std::isfinite(mesh_vel_scale) || !std::isfinite((float)mesh_vel_scale)) {
+            std::cerr << "FLUID_OUT_MESH_VEL must be SCALE, a finite number the vertex velocities are multiplied by, e.g. 1" << std::endl;
+            return 1;
+        }
+        if (!mesh) {
+            std::cerr << "FLUID_OUT_MESH_VEL adds velocities to what FLUID_OUT_MESH=R,W writes (one GPU): it is not set" << std::endl;
+            return 1;
+        }
+    }
     BlockCfg bc;
     if (const char* bs = getenv("FLUID_BLOCKS_SURFACE"); bs && *bs) {
         char tail = 0;
@@ -558,6 +585,7 @@ int main(int, char**)
     if (leaves) {
         lw.outdir = outdir, lw.fin = fin, lw.all = all, lw.raw_f32 = raw_f32;
         lw.voxel = (float)prm.dx;
+        lw.vel_scale = (float)mesh_vel_scale;
         lw.start();
     }
     // hands the oldest snapshot to the writer thread
@@ -573,11 +601,12 @@ int main(int, char**)
             return false;
         }
         fluid_mesh_t mg;
-        if (mesh && fluid_mesh_wait(sim, &mg) != FLUID_OK) {
+        fluid_mesh_attr_t ma;
+        if (mesh && (mesh_vel ? fluid_mesh_wait_attr(sim, &mg, &ma) : fluid_mesh_wait(sim, &mg)) != FLUID_OK) {
             std::cerr << "fluid_mesh_wait: " << fluid_last_error() << std::endl;
             return false;
         }
-        lw.submit(step, g, surface ? &sg : nullptr, mesh ? &mg : nullptr);
+        lw.submit(step, g, surface ? &sg : nullptr, mesh ? &mg : nullptr, mesh && mesh_vel ? &ma : nullptr);
         return true;
     };
 
@@ -623,7 +652,9 @@ int main(int, char**)
                 lw.stop();
                 return 1;
             }
-            if (mesh && (smooth ? fluid_mesh_snapshot_filtered(sim, &mp, &sf) : fluid_mesh_snapshot(sim, &mp)) != FLUID_OK) {
+            if (mesh && (mesh_vel ? fluid_mesh_snapshot_attr(sim, &mp, smooth ? &sf : nullptr)
+                         : smooth ? fluid_mesh_snapshot_filtered(sim, &mp, &sf)
+                                  : fluid_mesh_snapshot(sim, &mp)) != FLUID_OK) {
                 std::cerr << "fluid_mesh_snapshot: " << fluid_last_error() << std::endl;
                 lw.stop();
                 return 1;

@@ -14,6 +14,9 @@
 // filter's box passes (fluid_sdf.hip); the mesh kernels read the buffer the last pass wrote.  After the filter an inside voxel is
 // only known to be active or -bg, so within 4 cells of a base cell, and a mixed cell's min corner within [-5, +4]: kernels_mesh.hip's
 // range argument with every distance one larger.
+//
+// fluid_mesh_snapshot_attr ("liquid surface, attributes"): the front half's search also leaves the closest particle's velocity per
+// voxel, the emit kernel writes a velocity per vertex, and the slot's record is [quads | vertices | nv x 12 B of velocities].
 #include "sim.h"
 
 using namespace fl;
@@ -24,6 +27,7 @@ struct MeshSlot {
     char* host = nullptr;      // pinned
     size_t cap = 0;            // bytes either buffer holds
     long nv = 0, nq = 0;
+    bool attr = false;         // the snapshot in the slot carries vertex velocities
     float bg = 0, R = 0, w = 0;
     hipEvent_t done = nullptr;   // recorded on the copy stream behind the slot's copy
 };
@@ -38,6 +42,7 @@ struct MeshState {
     MeshSlot s[2];
     long n_snap = 0, n_wait = 0;   // snapshots taken / waited for: snapshot q lives in slot q & 1
     long last_v = 0, last_q = 0;
+    bool last_attr = false;
 };
 
 #define MESH_GUARD(s)                                                    \
@@ -119,12 +124,13 @@ static int mesh_grow(MeshSlot& q, size_t bytes)
     return FLUID_OK;
 }
 
-static int mesh_capture(fluid_sim* s, const fluid_sdf_params_t* p, const fluid_sdf_filter_t* filt)
+static int mesh_capture(fluid_sim* s, const fluid_sdf_params_t* p, const fluid_sdf_filter_t* filt, bool attr = false)
 {
     SdfFront f;
     int rc = sdf_begin(s, p, &f, filt);
     if (rc) return rc;
     if (filt) f.dilate = 5;
+    f.attr = attr;
     if ((rc = mesh_init(s))) return rc;
     MeshState* o = s->mesh;
     if (o->n_snap - o->n_wait >= 2) return fail(FLUID_ERR_STATE, "two mesh snapshots are waiting for fluid_mesh_wait");
@@ -146,13 +152,18 @@ static int mesh_capture(fluid_sim* s, const fluid_sdf_params_t* p, const fluid_s
             return fail(FLUID_ERR_ARG, "mesh: more than 2^31 - 1 vertices or quads");
         nv = (long)o->h_tot[0], nq = (long)o->h_tot[1];
     }
-    const size_t bytes = (size_t)nq * 16 + (size_t)nv * 12;
+    const size_t bytes = (size_t)nq * 16 + (size_t)nv * (attr ? 24 : 12);
     if ((rc = mesh_grow(q, bytes))) return rc;
     q.nv = nv, q.nq = nq;
+    q.attr = attr;
     q.bg = g.bg, q.R = g.R, q.w = g.w;
     if (nv > 0) {
-        launch_mesh_emit(s->st, g, f.tv, f.flags, o->cmask, o->cpre, o->vcnt, o->qcnt, o->vbase, o->qbase, (float*)(q.dev + (size_t)nq * 16),
-                         (uint32_t*)q.dev);
+        if (attr)
+            launch_mesh_emit_attr(s->st, g, f.tv, f.flags, f.tm, f.tvel, o->cmask, o->cpre, o->vcnt, o->qcnt, o->vbase, o->qbase,
+                                  (float*)(q.dev + (size_t)nq * 16), (uint32_t*)q.dev, (float*)(q.dev + (size_t)nq * 16 + (size_t)nv * 12));
+        else
+            launch_mesh_emit(s->st, g, f.tv, f.flags, o->cmask, o->cpre, o->vcnt, o->qcnt, o->vbase, o->qbase, (float*)(q.dev + (size_t)nq * 16),
+                             (uint32_t*)q.dev);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(o->emitted, s->st));
         HIPCHK(hipStreamWaitEvent(o->copy, o->emitted, 0));
@@ -161,6 +172,30 @@ static int mesh_capture(fluid_sim* s, const fluid_sdf_params_t* p, const fluid_s
     HIPCHK(hipEventRecord(q.done, o->copy));
     o->n_snap++;
     o->last_v = nv, o->last_q = nq;
+    o->last_attr = attr;
+    return FLUID_OK;
+}
+
+static int mesh_wait(fluid_sim* s, fluid_mesh_t* out, fluid_mesh_attr_t* at)
+{
+    if (!out) return fail(FLUID_ERR_ARG, "null argument");
+    MeshState* o = s->mesh;
+    if (!o || o->n_wait >= o->n_snap) return fail(FLUID_ERR_STATE, "no mesh snapshot is outstanding");
+    MeshSlot& q = o->s[o->n_wait & 1];
+    HIPCHK(hipEventSynchronize(q.done));
+    out->n = s->g.N;
+    out->n_vertices = q.nv;
+    out->n_quads = q.nq;
+    out->radius = q.R;
+    out->half_width = q.w;
+    out->background = q.bg;
+    out->quads = q.nq ? (const uint32_t*)q.host : nullptr;
+    out->vertices = q.nv ? (const float*)(q.host + (size_t)q.nq * 16) : nullptr;
+    if (at) {
+        at->n_vertices = q.nv;
+        at->velocity = q.nv && q.attr ? (const float*)(q.host + (size_t)q.nq * 16 + (size_t)q.nv * 12) : nullptr;
+    }
+    o->n_wait++;
     return FLUID_OK;
 }
 
@@ -183,21 +218,23 @@ int fluid_mesh_snapshot_filtered(fluid_sim_t* s, const fluid_sdf_params_t* p, co
 int fluid_mesh_wait(fluid_sim_t* s, fluid_mesh_t* out)
 {
     MESH_GUARD(s);
-    if (!out) return fail(FLUID_ERR_ARG, "null argument");
-    MeshState* o = s->mesh;
-    if (!o || o->n_wait >= o->n_snap) return fail(FLUID_ERR_STATE, "no mesh snapshot is outstanding");
-    MeshSlot& q = o->s[o->n_wait & 1];
-    HIPCHK(hipEventSynchronize(q.done));
-    out->n = s->g.N;
-    out->n_vertices = q.nv;
-    out->n_quads = q.nq;
-    out->radius = q.R;
-    out->half_width = q.w;
-    out->background = q.bg;
-    out->quads = q.nq ? (const uint32_t*)q.host : nullptr;
-    out->vertices = q.nv ? (const float*)(q.host + (size_t)q.nq * 16) : nullptr;
-    o->n_wait++;
-    return FLUID_OK;
+    return mesh_wait(s, out, nullptr);
+}
+
+#define MESH_ATTR_GUARD(s)                               \
+    if (!(s)) return fail(FLUID_ERR_ARG, "null handle"); \
+    if ((s)->dist) return fail(FLUID_ERR_STATE, "surface attributes are single-GPU only: the merge of the blocks' lists sees values, and equal values do not imply equal squared distances")
+
+int fluid_mesh_snapshot_attr(fluid_sim_t* s, const fluid_sdf_params_t* p, const fluid_sdf_filter_t* f)
+{
+    MESH_ATTR_GUARD(s);
+    return mesh_capture(s, p, f, true);
+}
+
+int fluid_mesh_wait_attr(fluid_sim_t* s, fluid_mesh_t* out, fluid_mesh_attr_t* attr)
+{
+    MESH_ATTR_GUARD(s);
+    return mesh_wait(s, out, attr);
 }
 
 int fluid_mesh_stats(fluid_sim_t* s, int64_t* vertices, int64_t* quads, int64_t* bytes_to_host)
@@ -206,7 +243,7 @@ int fluid_mesh_stats(fluid_sim_t* s, int64_t* vertices, int64_t* quads, int64_t*
     const int64_t nv = s->mesh ? s->mesh->last_v : 0, nq = s->mesh ? s->mesh->last_q : 0;
     if (vertices) *vertices = nv;
     if (quads) *quads = nq;
-    if (bytes_to_host) *bytes_to_host = s->mesh ? 12 * nv + 16 * nq + 8 : 0;
+    if (bytes_to_host) *bytes_to_host = s->mesh ? (s->mesh->last_attr ? 24 : 12) * nv + 16 * nq + 8 : 0;
     return FLUID_OK;
 }
 

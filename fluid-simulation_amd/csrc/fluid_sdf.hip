@@ -23,6 +23,13 @@
 // fluid_sdf_snapshot_filtered / fluid_mesh_snapshot_filtered ("liquid surface, smoothed"; kernels_sdf_filter.hip): the front half
 // ends with the filter's box passes, one launch each, 3 per iteration (x, z, y), from tv to tv2 and back; what follows reads
 // whichever buffer the last pass wrote.  tv2 exists from the handle's first filtered snapshot on.
+//
+// fluid_sdf_snapshot_attr / fluid_mesh_snapshot_attr ("liquid surface, attributes"): the scatter also writes each sorted position's
+// index in the live arrays (ssrc), the search keeps the closest particle beside the minimum and writes its id and velocity per voxel
+// (tid, tvel), and the pack lists them.  ssrc, tid and tvel exist from the handle's first attribute snapshot on.  An attribute
+// snapshot is one more kind of snapshot in the same two slots: its record is [n x 2048 B of values | n x 2048 B of ids |
+// n x 6144 B of velocities | n x 64 B of masks | n x 12 B of origins] (the 16-byte copies of the pack stay aligned for every n),
+// one copy behind the same event.
 #include "sim.h"
 
 using namespace fl;
@@ -33,6 +40,8 @@ struct SdfSlot {
     char* dev = nullptr;       // device staging
     char* host = nullptr;      // pinned
     size_t cap = 0;            // leaves either buffer holds
+    bool wide = false;         // ... each with room for the attributes (the slot has held an attribute snapshot)
+    bool attr = false;         // the snapshot in the slot carries attributes
     int n_leaves = 0;
     float bg = 0, R = 0, w = 0;
     hipEvent_t done = nullptr;   // recorded on the copy stream behind the slot's copy
@@ -46,6 +55,12 @@ struct SdfState {
     float* tv = nullptr;
     float* tv2 = nullptr;      // the box passes' second buffer, leaf_cap x 512 like tv: allocated once a filtered snapshot was asked for
     bool filtered = false;
+    // attributes: index in the live arrays per sorted position (part_cap), winner's id (leaf_cap x 512) and velocity (leaf_cap x 3 x 512)
+    // per voxel: allocated once an attribute snapshot was asked for
+    int* ssrc = nullptr;
+    uint32_t* tid = nullptr;
+    float* tvel = nullptr;
+    bool attr = false;
     uint64_t* tm = nullptr;
     int *flags = nullptr, *slot = nullptr, *leaf_sums = nullptr;
     unsigned* visits = nullptr;   // FLUID_SDF_VISITS=1 only
@@ -86,7 +101,7 @@ void fl::sdf_free(fluid_sim* s)
         if (q.host) hipHostFree(q.host);
         if (q.done) hipEventDestroy(q.done);
     }
-    for (void* p : {(void*)o->cnt, (void*)o->start, (void*)o->cell_sums, (void*)o->place, (void*)o->spos, (void*)o->tv, (void*)o->tv2, (void*)o->tm, (void*)o->flags,
+    for (void* p : {(void*)o->cnt, (void*)o->start, (void*)o->cell_sums, (void*)o->place, (void*)o->spos, (void*)o->tv, (void*)o->tv2, (void*)o->ssrc, (void*)o->tid, (void*)o->tvel, (void*)o->tm, (void*)o->flags,
                     (void*)o->slot, (void*)o->leaf_sums, (void*)o->visits, (void*)o->d_small})
         if (p) hipFree(p);
     if (o->h_small) hipHostFree(o->h_small);
@@ -105,8 +120,16 @@ static hipError_t regrow(T*& p, size_t n)
     return hipMalloc((void**)&p, n * sizeof(T));
 }
 
-static int sdf_scratch(SdfState* o, long cells, long parts, long leaves, bool filtered)
+static int sdf_scratch(SdfState* o, long cells, long parts, long leaves, bool filtered, bool attr)
 {
+    if (attr && !o->attr) {   // the first attribute snapshot of the handle: ssrc, tid and tvel beside whatever there is
+        o->attr = true;
+        if (o->part_cap > 0) HIPCHK(regrow(o->ssrc, (size_t)o->part_cap));
+        if (o->leaf_cap > 0) {
+            HIPCHK(regrow(o->tid, (size_t)o->leaf_cap * 512));
+            HIPCHK(regrow(o->tvel, (size_t)o->leaf_cap * 1536));
+        }
+    }
     if (filtered && !o->filtered) {   // the first filtered snapshot of the handle: tv2 beside whatever tv there is
         o->filtered = true;
         if (o->leaf_cap > 0) HIPCHK(regrow(o->tv2, (size_t)o->leaf_cap * 512));
@@ -124,6 +147,7 @@ static int sdf_scratch(SdfState* o, long cells, long parts, long leaves, bool fi
         const long cap = parts + parts / 8 + 64;
         HIPCHK(regrow(o->place, (size_t)cap));
         HIPCHK(regrow(o->spos, (size_t)3 * cap));
+        if (o->attr) HIPCHK(regrow(o->ssrc, (size_t)cap));
         o->part_cap = cap;
     }
     if (leaves > o->leaf_cap) {
@@ -131,6 +155,10 @@ static int sdf_scratch(SdfState* o, long cells, long parts, long leaves, bool fi
         const long cap = leaves + leaves / 4 + 64;
         HIPCHK(regrow(o->tv, (size_t)cap * 512));
         if (o->filtered) HIPCHK(regrow(o->tv2, (size_t)cap * 512));
+        if (o->attr) {
+            HIPCHK(regrow(o->tid, (size_t)cap * 512));
+            HIPCHK(regrow(o->tvel, (size_t)cap * 1536));
+        }
         HIPCHK(regrow(o->tm, (size_t)cap * 8));
         HIPCHK(regrow(o->flags, (size_t)cap));
         HIPCHK(regrow(o->slot, (size_t)cap));
@@ -142,16 +170,18 @@ static int sdf_scratch(SdfState* o, long cells, long parts, long leaves, bool fi
 }
 
 // room for n leaves in the slot (its earlier contents were handed out two snapshots ago: no longer promised)
-static int sdf_grow(SdfSlot& q, size_t n)
+static int sdf_grow(SdfSlot& q, size_t n, bool attr)
 {
-    if (n <= q.cap) return FLUID_OK;
+    if (n <= q.cap && (!attr || q.wide)) return FLUID_OK;
+    if (attr) q.wide = true;   // (and stays so: a plain snapshot in a wide slot uses the front of it)
+    const size_t rec = q.wide ? SDF_REC + FLUID_SDF_ATTR_LEAF_BYTES : SDF_REC;
     if (q.dev) hipFree(q.dev);
     if (q.host) hipHostFree(q.host);
     q.dev = q.host = nullptr;
     q.cap = 0;
     const size_t cap = n + n / 2 + 64;
-    HIPCHK(hipMalloc((void**)&q.dev, cap * SDF_REC));
-    HIPCHK(hipHostMalloc((void**)&q.host, cap * SDF_REC));
+    HIPCHK(hipMalloc((void**)&q.dev, cap * rec));
+    HIPCHK(hipHostMalloc((void**)&q.host, cap * rec));
     q.cap = cap;
     return FLUID_OK;
 }
@@ -185,6 +215,8 @@ int fl::sdf_begin(fluid_sim* s, const fluid_sdf_params_t* p, SdfFront* f, const 
     f->any = false;
     f->tv = nullptr, f->flags = nullptr;
     f->filt = filt, f->dilate = 4;
+    f->attr = false;
+    f->tm = nullptr, f->tid = nullptr, f->tvel = nullptr;
     return FLUID_OK;
 }
 
@@ -213,15 +245,18 @@ int fl::sdf_front(fluid_sim* s, SdfFront* f)
         }
         const long cells = g.cells(), leaves = g.leaves();
         if (cells + 1 > 0x7fffffffL || leaves > 0x7fffffffL) return fail(FLUID_ERR_ARG, "level set: the particles' box is too large");
-        if ((rc = sdf_scratch(o, cells + 1, s->np, leaves, f->filt != nullptr))) return rc;
+        if ((rc = sdf_scratch(o, cells + 1, s->np, leaves, f->filt != nullptr, f->attr))) return rc;
         double *sx = o->spos, *sy = o->spos + o->part_cap, *sz = o->spos + 2 * o->part_cap;
         HIPCHK(hipMemsetAsync(o->cnt, 0, (size_t)(cells + 1) * sizeof(int), s->st));
         launch_sdf_count(s->st, s->np, live, g, o->cnt, o->place, s->dist);
         launch_exclusive_scan(s->st, o->cnt, o->start, cells + 1, o->cell_sums, o->d_small + 6);   // start[cells] = the counted particles
-        launch_sdf_scatter(s->st, s->np, live, g, o->start, o->place, sx, sy, sz);
-        launch_sdf_search(s->st, g, o->start, sx, sy, sz, o->tv, o->tm, o->flags, o->count_visits ? o->visits : nullptr);
+        launch_sdf_scatter(s->st, s->np, live, g, o->start, o->place, sx, sy, sz, f->attr ? o->ssrc : nullptr);
+        if (f->attr) launch_sdf_search_attr(s->st, g, o->start, sx, sy, sz, o->tv, o->tm, o->flags, o->ssrc, live, o->tid, o->tvel);
+        else launch_sdf_search(s->st, g, o->start, sx, sy, sz, o->tv, o->tm, o->flags, o->count_visits ? o->visits : nullptr);
         f->any = true;
         f->tv = o->tv, f->flags = o->flags;
+        f->tm = o->tm;
+        if (f->attr) f->tid = o->tid, f->tvel = o->tvel;
         if (f->filt) {
             // iteration = x, z, y (the library's order); the offset rides on the last pass, or is a pass of its own without one
             static const int axes[3] = {0, 2, 1};
@@ -240,11 +275,12 @@ int fl::sdf_front(fluid_sim* s, SdfFront* f)
 }
 
 // front half -> scan of the flags -> pack -> copy
-static int sdf_capture(fluid_sim* s, const fluid_sdf_params_t* p, const fluid_sdf_filter_t* filt = nullptr)
+static int sdf_capture(fluid_sim* s, const fluid_sdf_params_t* p, const fluid_sdf_filter_t* filt = nullptr, bool attr = false)
 {
     SdfFront f;
     int rc = sdf_begin(s, p, &f, filt);
     if (rc) return rc;
+    f.attr = attr;
     SdfState* o = s->sdf;
     if (o->n_snap - o->n_wait >= 2) return fail(FLUID_ERR_STATE, "two level-set snapshots are waiting for fluid_sdf_wait");
     SdfSlot& q = o->s[o->n_snap & 1];
@@ -260,7 +296,7 @@ static int sdf_capture(fluid_sim* s, const fluid_sdf_params_t* p, const fluid_sd
         HIPCHK(hipStreamSynchronize(s->st));
         n = o->h_small[7];
         if (n < 0 || (long)n > leaves) return fail(FLUID_ERR_HIP, "level set: leaf count out of range");
-        if (o->count_visits) {   // cells looked at and voxels computed, for tools/sdf_cost.py
+        if (o->count_visits && !attr) {   // cells looked at and voxels computed, for tools/sdf_cost.py
             std::vector<unsigned> v((size_t)leaves);
             HIPCHK(hipMemcpy(v.data(), o->visits, (size_t)leaves * sizeof(unsigned), hipMemcpyDeviceToHost));
             double cv = 0;
@@ -269,27 +305,33 @@ static int sdf_capture(fluid_sim* s, const fluid_sdf_params_t* p, const fluid_sd
             fprintf(stderr, "sdf visits: cells %.0f leaves_searched %ld leaves_in_range %ld\n", cv, searched, leaves);
         }
     }
-    if ((rc = sdf_grow(q, (size_t)n))) return rc;
+    if ((rc = sdf_grow(q, (size_t)n, attr))) return rc;
     q.n_leaves = n;
+    q.attr = attr;
+    const size_t rec = attr ? SDF_REC + FLUID_SDF_ATTR_LEAF_BYTES : SDF_REC;
     q.bg = g.bg, q.R = R, q.w = w;
     if (n > 0) {
+        const size_t a = attr ? (size_t)n * FLUID_SDF_ATTR_LEAF_BYTES : 0;   // the attributes lie between the values and the masks
         float* values = (float*)q.dev;
-        uint64_t* active = (uint64_t*)(q.dev + (size_t)n * 2048);
-        int* origin = (int*)(q.dev + (size_t)n * (2048 + 64));
-        launch_sdf_pack(s->st, g, o->flags, o->slot, f.tv, o->tm, values, active, origin);
+        uint64_t* active = (uint64_t*)(q.dev + (size_t)n * 2048 + a);
+        int* origin = (int*)(q.dev + (size_t)n * (2048 + 64) + a);
+        if (attr)
+            launch_sdf_pack_attr(s->st, g, o->flags, o->slot, f.tv, o->tm, values, active, origin, f.tid, f.tvel, (uint32_t*)(q.dev + (size_t)n * 2048),
+                                 (float*)(q.dev + (size_t)n * 4096));
+        else launch_sdf_pack(s->st, g, o->flags, o->slot, f.tv, o->tm, values, active, origin);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(o->packed, s->st));
         HIPCHK(hipStreamWaitEvent(o->copy, o->packed, 0));
-        HIPCHK(hipMemcpyAsync(q.host, q.dev, (size_t)n * SDF_REC, hipMemcpyDeviceToHost, o->copy));
+        HIPCHK(hipMemcpyAsync(q.host, q.dev, (size_t)n * rec, hipMemcpyDeviceToHost, o->copy));
     }
     HIPCHK(hipEventRecord(q.done, o->copy));
     o->n_snap++;
     o->last_leaves = n;
-    o->last_bytes = (long)((size_t)n * SDF_REC) + 4;
+    o->last_bytes = (long)((size_t)n * rec) + 4;
     return FLUID_OK;
 }
 
-static int sdf_wait(fluid_sim* s, fluid_sdf_grid_t* out)
+static int sdf_wait(fluid_sim* s, fluid_sdf_grid_t* out, fluid_sdf_attr_t* at = nullptr)
 {
     if (!out) return fail(FLUID_ERR_ARG, "null argument");
     SdfState* o = s->sdf;
@@ -303,8 +345,14 @@ static int sdf_wait(fluid_sim* s, fluid_sdf_grid_t* out)
     out->radius = q.R;
     out->half_width = q.w;
     out->values = n ? (const float*)q.host : nullptr;
-    out->active = n ? (const uint64_t*)(q.host + n * 2048) : nullptr;
-    out->origin = n ? (const int32_t*)(q.host + n * (2048 + 64)) : nullptr;
+    const size_t a = q.attr ? n * FLUID_SDF_ATTR_LEAF_BYTES : 0;
+    out->active = n ? (const uint64_t*)(q.host + n * 2048 + a) : nullptr;
+    out->origin = n ? (const int32_t*)(q.host + n * (2048 + 64) + a) : nullptr;
+    if (at) {
+        at->n_leaves = q.n_leaves;
+        at->id = n && q.attr ? (const uint32_t*)(q.host + n * 2048) : nullptr;
+        at->velocity = n && q.attr ? (const float*)(q.host + n * 4096) : nullptr;
+    }
     o->n_wait++;
     return FLUID_OK;
 }
@@ -346,6 +394,22 @@ int fluid_sdf_wait(fluid_sim_t* s, fluid_sdf_grid_t* out)
 {
     SDF_GUARD(s);
     return sdf_wait(s, out);
+}
+
+#define SDF_ATTR_GUARD(s)                                \
+    if (!(s)) return fail(FLUID_ERR_ARG, "null handle"); \
+    if ((s)->dist) return fail(FLUID_ERR_STATE, "surface attributes are single-GPU only: the merge of the blocks' lists sees values, and equal values do not imply equal squared distances")
+
+int fluid_sdf_snapshot_attr(fluid_sim_t* s, const fluid_sdf_params_t* p, const fluid_sdf_filter_t* f)
+{
+    SDF_ATTR_GUARD(s);
+    return sdf_capture(s, p, f, true);
+}
+
+int fluid_sdf_wait_attr(fluid_sim_t* s, fluid_sdf_grid_t* out, fluid_sdf_attr_t* attr)
+{
+    SDF_ATTR_GUARD(s);
+    return sdf_wait(s, out, attr);
 }
 
 int fluid_sdf_stats(fluid_sim_t* s, int64_t* leaves_in_grid, int64_t* leaves_listed, int64_t* bytes_to_host)

@@ -24,6 +24,7 @@
 //   emit   same tiling.  A mixed cell's vertex goes to vbase[leaf] + its rank in the mask; a quad to qbase[leaf] + the quads of
 //          lower voxels (ballots of the three edge bits) — position alone decides the place, there is no ordering by arrival.  The
 //          number of a vertex in a neighbour leaf at -1 is vbase[leaf'] + the popcount of that leaf's stored mask below the cell.
+//   emit<true> ("liquid surface, attributes") also writes a velocity per vertex from the search's per-voxel velocities and masks.
 // Arithmetic of a vertex: include/fluid_hip.h; float, no FMA (-ffp-contract=off), the division correctly rounded
 // (-fhip-fp32-correctly-rounded-divide-sqrt).
 #include "common.h"
@@ -159,17 +160,60 @@ __device__ __forceinline__ unsigned mesh_vertex_number(const SdfGeom& g, int cx,
     return (unsigned)(vbase[q] + cpre[q * 8 + (off >> 6)] + __popcll(below));
 }
 
+// One counting edge's share of the vertex velocity ("liquid surface, attributes"): i0, i1 = the ends' places in the 9^3 tile
+__device__ __forceinline__ void mesh_edge_vel(const float* A, const unsigned char* B, int i0, int i1, float t, float* s, int& kv)
+{
+    const bool b0 = B[i0] != 0, b1 = B[i1] != 0;
+    if (!b0 && !b1) return;   // (cannot be on a device snapshot: include/fluid_hip.h)
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float a0 = A[a * MESH_V + i0], a1 = A[a * MESH_V + i1];
+        float e;
+        if (b0 && b1) {
+            const float d = a1 - a0;
+            const float td = t * d;
+            e = a0 + td;
+        } else e = b0 ? a0 : a1;
+        s[a] += e;
+    }
+    ++kv;
+}
+
+// ATTR: beside the values the block stages the velocities (3 x 9^3 floats) and the active bits (one byte each) of the same up to
+// eight leaves, not active wherever the leaf is unflagged or outside the range (the search's tm / tvel of such a leaf are stale or
+// do not exist); each mixed cell's thread writes its vertex velocity to the place its vertex goes.
+template <bool ATTR>
 __global__ __launch_bounds__(512) void k_mesh_emit(SdfGeom g, const float* __restrict__ tv, const int* __restrict__ flags,
                                                    const unsigned long long* __restrict__ cmask, const int* __restrict__ cpre,
                                                    const int* __restrict__ vcnt, const int* __restrict__ qcnt, const int* __restrict__ vbase,
-                                                   const int* __restrict__ qbase, float* __restrict__ vertices, uint4* __restrict__ quads)
+                                                   const int* __restrict__ qbase, float* __restrict__ vertices, uint4* __restrict__ quads,
+                                                   const unsigned long long* __restrict__ tm, const float* __restrict__ tvel,
+                                                   float* __restrict__ vvel)
 {
     __shared__ float V[MESH_V];
+    __shared__ float A[ATTR ? 3 * MESH_V : 1];
+    __shared__ unsigned char B[ATTR ? MESH_V : 1];
     __shared__ int wq[8];
     const int t = threadIdx.x;
     const MeshLeaf l = mesh_leaf(g);
     if (vcnt[l.j] == 0 && qcnt[l.j] == 0) return;   // (the whole block alike)
     mesh_load(g, l, tv, flags, V);
+    if (ATTR) {
+        for (int i = t; i < MESH_V; i += 512) {
+            const int lz = i % 9, ly = (i / 9) % 9, lx = i / 81;
+            const long q = mesh_range_index(g, l.jx + (lx >> 3), l.jy + (ly >> 3), l.jz + (lz >> 3));
+            float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f;
+            unsigned char b = 0;
+            if (q >= 0 && flags[q]) {
+                const int off = ((lx & 7) * 8 + (ly & 7)) * 8 + (lz & 7);
+                b = (unsigned char)((tm[q * 8 + (off >> 6)] >> (off & 63)) & 1ull);
+                const float* tw = tvel + q * 1536 + off;
+                a0 = tw[0], a1 = tw[512], a2 = tw[1024];
+            }
+            A[i] = a0, A[MESH_V + i] = a1, A[2 * MESH_V + i] = a2;
+            B[i] = b;
+        }
+    }
     __syncthreads();
     const int x = t >> 6, y = (t >> 3) & 7, z = t & 7;
     const int px = l.ox + x, py = l.oy + y, pz = l.oz + z;
@@ -184,30 +228,52 @@ __global__ __launch_bounds__(512) void k_mesh_emit(SdfGeom g, const float* __res
     if (mixed) {
         // the 12 edges: axis x, y, z; the two other axes, in ascending order, at (0,0), (0,1), (1,0), (1,1)
         float sx = 0.0f, sy = 0.0f, sz = 0.0f;
-        int k = 0;
+        float sv[3] = {0.0f, 0.0f, 0.0f};
+        int k = 0, kv = 0;
+        const int c0 = (x * 9 + y) * 9 + z;   // the cell's min corner in the tile
 #pragma unroll
         for (int o = 0; o < 4; ++o) {
             const int d1 = o >> 1, d2 = o & 1;
             const float v0 = c[d1 * 9 + d2], v1 = c[81 + d1 * 9 + d2];
-            if ((v0 < 0.0f) != (v1 < 0.0f)) sx += v0 / (v0 - v1), sy += (float)d1, sz += (float)d2, ++k;
+            if ((v0 < 0.0f) != (v1 < 0.0f)) {
+                const float tt = v0 / (v0 - v1);
+                sx += tt, sy += (float)d1, sz += (float)d2, ++k;
+                if (ATTR) mesh_edge_vel(A, B, c0 + d1 * 9 + d2, c0 + 81 + d1 * 9 + d2, tt, sv, kv);
+            }
         }
 #pragma unroll
         for (int o = 0; o < 4; ++o) {
             const int d1 = o >> 1, d2 = o & 1;
             const float v0 = c[d1 * 81 + d2], v1 = c[d1 * 81 + 9 + d2];
-            if ((v0 < 0.0f) != (v1 < 0.0f)) sx += (float)d1, sy += v0 / (v0 - v1), sz += (float)d2, ++k;
+            if ((v0 < 0.0f) != (v1 < 0.0f)) {
+                const float tt = v0 / (v0 - v1);
+                sx += (float)d1, sy += tt, sz += (float)d2, ++k;
+                if (ATTR) mesh_edge_vel(A, B, c0 + d1 * 81 + d2, c0 + d1 * 81 + 9 + d2, tt, sv, kv);
+            }
         }
 #pragma unroll
         for (int o = 0; o < 4; ++o) {
             const int d1 = o >> 1, d2 = o & 1;
             const float v0 = c[d1 * 81 + d2 * 9], v1 = c[d1 * 81 + d2 * 9 + 1];
-            if ((v0 < 0.0f) != (v1 < 0.0f)) sx += (float)d1, sy += (float)d2, sz += v0 / (v0 - v1), ++k;
+            if ((v0 < 0.0f) != (v1 < 0.0f)) {
+                const float tt = v0 / (v0 - v1);
+                sx += (float)d1, sy += (float)d2, sz += tt, ++k;
+                if (ATTR) mesh_edge_vel(A, B, c0 + d1 * 81 + d2 * 9, c0 + d1 * 81 + d2 * 9 + 1, tt, sv, kv);
+            }
         }
         const float kf = (float)k;
-        float* out = vertices + 3 * (size_t)(vbase[l.j] + cpre[l.j * 8 + x] + __popcll(b & lt));
+        const size_t vn = (size_t)(vbase[l.j] + cpre[l.j * 8 + x] + __popcll(b & lt));
+        float* out = vertices + 3 * vn;
         out[0] = (float)px + sx / kf;
         out[1] = (float)py + sy / kf;
         out[2] = (float)pz + sz / kf;
+        if (ATTR) {
+            const float kvf = (float)kv;
+            float* ov = vvel + 3 * vn;
+            ov[0] = kv ? sv[0] / kvf : 0.0f;
+            ov[1] = kv ? sv[1] / kvf : 0.0f;
+            ov[2] = kv ? sv[2] / kvf : 0.0f;
+        }
     }
     if (edges) {
         size_t at = (size_t)qbase[l.j] + __popcll(bx & lt) + __popcll(by & lt) + __popcll(bz & lt);
@@ -238,8 +304,16 @@ void launch_mesh_mark(hipStream_t st, const SdfGeom& g, const float* tv, const i
 void launch_mesh_emit(hipStream_t st, const SdfGeom& g, const float* tv, const int* flags, const uint64_t* cmask, const int* cpre, const int* vcnt,
                       const int* qcnt, const int* vbase, const int* qbase, float* vertices, uint32_t* quads)
 {
-    hipLaunchKernelGGL(k_mesh_emit, dim3((unsigned)g.leaves()), dim3(512), 0, st, g, tv, flags, (const unsigned long long*)cmask, cpre, vcnt, qcnt,
-                       vbase, qbase, vertices, (uint4*)quads);
+    hipLaunchKernelGGL(k_mesh_emit<false>, dim3((unsigned)g.leaves()), dim3(512), 0, st, g, tv, flags, (const unsigned long long*)cmask, cpre, vcnt, qcnt,
+                       vbase, qbase, vertices, (uint4*)quads, (const unsigned long long*)nullptr, (const float*)nullptr, (float*)nullptr);
+}
+
+void launch_mesh_emit_attr(hipStream_t st, const SdfGeom& g, const float* tv, const int* flags, const uint64_t* tm, const float* tvel,
+                           const uint64_t* cmask, const int* cpre, const int* vcnt, const int* qcnt, const int* vbase, const int* qbase,
+                           float* vertices, uint32_t* quads, float* vvel)
+{
+    hipLaunchKernelGGL(k_mesh_emit<true>, dim3((unsigned)g.leaves()), dim3(512), 0, st, g, tv, flags, (const unsigned long long*)cmask, cpre, vcnt, qcnt,
+                       vbase, qbase, vertices, (uint4*)quads, (const unsigned long long*)tm, tvel, vvel);
 }
 
 }  // namespace fl

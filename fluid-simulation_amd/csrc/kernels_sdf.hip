@@ -9,6 +9,8 @@
 //            LDS (17 per z row: 17 KB), a leaf with no particle in reach leaves at once, a thread owns one voxel and walks the
 //            Chebyshev rings of cells around it;
 //   pack     the listed leaves' values, masks and origins in ascending order (exclusive scan of the flags; masks by ballot).
+// Attributes (include/fluid_hip.h, "liquid surface, attributes"): template flags on scatter, search and pack carry the closest
+// particle's id and velocity along; the plain instantiations are the code they were.
 // Ring stop.  A particle whose base cell is k + 1 cells away on some axis has |c - p| >= k + 0.5 on that axis, exactly
 // (|p - round(p)| <= 0.5).  k + 0.5 and its square are floats, every rounding below is monotone and every addend non-negative, so
 // the particle's x2y2z2 AS COMPUTED is >= (k + 0.5)^2: once the minimum so far is <= that, no ring further out can lower it, and
@@ -96,10 +98,13 @@ __global__ __launch_bounds__(256) void k_sdf_count(long n, const double* __restr
     place[i] = sdf_cell(px[i], py[i], pz[i], g.lo, g.hi, cx, cy, cz) ? atomicAdd(&cnt[sdf_box_index(g, cx, cy, cz)], 1) : -1;
 }
 
+// ATTR: ssrc[d] = i as well, the index in the live arrays of the particle at sorted position d (after a step the live arrays are
+// in the step's sort order, not in id order: the attribute search goes through ssrc to pid and the velocities)
+template <bool ATTR>
 __global__ __launch_bounds__(256) void k_sdf_scatter(long n, const double* __restrict__ px, const double* __restrict__ py,
                                                      const double* __restrict__ pz, SdfGeom g, const int* __restrict__ start,
                                                      const int* __restrict__ place, double* __restrict__ sx, double* __restrict__ sy,
-                                                     double* __restrict__ sz)
+                                                     double* __restrict__ sz, int* __restrict__ ssrc)
 {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n || place[i] < 0) return;
@@ -108,6 +113,7 @@ __global__ __launch_bounds__(256) void k_sdf_scatter(long n, const double* __res
     sdf_cell(x, y, z, g.lo, g.hi, cx, cy, cz);
     const long d = (long)start[sdf_box_index(g, cx, cy, cz)] + place[i];
     sx[d] = x, sy[d] = y, sz[d] = z;
+    if (ATTR) ssrc[d] = (int)i;
 }
 
 __device__ __forceinline__ float sdf_dist2(int vx, int vy, int vz, double x, double y, double z)
@@ -123,10 +129,28 @@ __device__ __forceinline__ float sdf_dist2(int vx, int vy, int vz, double x, dou
 // sorted arrays, lz = 16 being the end of the row's last cell; rows and cells outside the particles' box are empty (equal starts).
 // tv / tm: 512 values and 8 mask words per leaf of the range; flags[j] = the leaf is listed.  VISITS: visits[j] = cells looked at
 // by the leaf's voxels (a figure for tools/sdf_cost.py; the plain kernel does not count).
-template <bool VISITS>
+// ARGMIN ("liquid surface, attributes"): the sorted position of the particle that gave m travels with m.  A strictly smaller x2
+// replaces it; an equal one (rare) loads both ids through ssrc -> pid and keeps the smaller, so the winner is the smallest id among
+// the particles at the minimum whatever order the walk meets them in.  The ring stop asks for m strictly below (k + 0.5)^2 <= every
+// x2 further out, so no particle tied with the minimum is left unvisited for a voxel that ends up active.  m itself is updated by
+// the same fminf: values and masks are those of the plain kernel.  Every thread of a flagged leaf writes tid (512 per leaf) and
+// tvel ([leaf][axis][512]): the winner's id and narrowed velocity where the voxel is active, NO_ID / +0 elsewhere.  A block that
+// leaves early writes the flag alone: its tid / tvel are stale and never read.
+__device__ __forceinline__ void sdf_visit(float& m, float x2) { m = fminf(m, x2); }
+__device__ __forceinline__ void sdf_visit_arg(float& m, int& best, float x2, int p, const int* __restrict__ ssrc, const uint32_t* __restrict__ pid)
+{
+    if (x2 < m) best = p;
+    else if (x2 == m && best >= 0 && pid[ssrc[p]] < pid[ssrc[best]]) best = p;
+    m = fminf(m, x2);
+}
+
+template <bool VISITS, bool ARGMIN>
 __global__ __launch_bounds__(512) void k_sdf_search(SdfGeom g, const int* __restrict__ start, const double* __restrict__ sx,
                                                     const double* __restrict__ sy, const double* __restrict__ sz, float* __restrict__ tv,
-                                                    unsigned long long* __restrict__ tm, int* __restrict__ flags, unsigned* __restrict__ visits)
+                                                    unsigned long long* __restrict__ tm, int* __restrict__ flags, unsigned* __restrict__ visits,
+                                                    const int* __restrict__ ssrc, const uint32_t* __restrict__ pid,
+                                                    const double* __restrict__ pvx, const double* __restrict__ pvy,
+                                                    const double* __restrict__ pvz, uint32_t* __restrict__ tid, float* __restrict__ tvel)
 {
     __shared__ int S[16 * 16 * 17];
     __shared__ unsigned vis[8];
@@ -158,6 +182,7 @@ __global__ __launch_bounds__(512) void k_sdf_search(SdfGeom g, const int* __rest
     const int vx = ox + x, vy = oy + y, vz = oz + z;
     const bool in = vx >= g.lo && vx <= g.hi && vy >= g.lo && vy <= g.hi && vz >= g.lo && vz <= g.hi;
     float m = INFINITY;
+    int best = -1;
     unsigned nvis = 0;
     if (in) {
         const int zc = z + 4;
@@ -168,10 +193,18 @@ __global__ __launch_bounds__(512) void k_sdf_search(SdfGeom g, const int* __rest
                     const bool shell = dx == -k || dx == k || dy == -k || dy == k;   // the whole z run belongs to ring k
                     // the cells of a z run are contiguous in the sorted arrays: one range; else the run's two end cells
                     const int b0 = S[row - k], e0 = shell ? S[row + k + 1] : S[row - k + 1];
-                    for (int p = b0; p < e0; ++p) m = fminf(m, sdf_dist2(vx, vy, vz, sx[p], sy[p], sz[p]));
+                    for (int p = b0; p < e0; ++p) {
+                        const float x2 = sdf_dist2(vx, vy, vz, sx[p], sy[p], sz[p]);
+                        if (ARGMIN) sdf_visit_arg(m, best, x2, p, ssrc, pid);
+                        else sdf_visit(m, x2);
+                    }
                     if (!shell) {
                         const int b1 = S[row + k], e1 = S[row + k + 1];
-                        for (int p = b1; p < e1; ++p) m = fminf(m, sdf_dist2(vx, vy, vz, sx[p], sy[p], sz[p]));
+                        for (int p = b1; p < e1; ++p) {
+                            const float x2 = sdf_dist2(vx, vy, vz, sx[p], sy[p], sz[p]);
+                            if (ARGMIN) sdf_visit_arg(m, best, x2, p, ssrc, pid);
+                            else sdf_visit(m, x2);
+                        }
                     }
                     if (VISITS) nvis += shell ? 2 * k + 1 : 2;
                 }
@@ -191,6 +224,18 @@ __global__ __launch_bounds__(512) void k_sdf_search(SdfGeom g, const int* __rest
         }
     }
     tv[j * 512 + t] = val;
+    if (ARGMIN) {
+        uint32_t id = 0xffffffffu;
+        float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f;
+        if (act && best >= 0) {   // (an active voxel has m < inf, so a winner)
+            const int src = ssrc[best];
+            id = pid[src];
+            a0 = (float)pvx[src], a1 = (float)pvy[src], a2 = (float)pvz[src];
+        }
+        tid[j * 512 + t] = id;
+        float* tw = tvel + j * 1536 + t;
+        tw[0] = a0, tw[512] = a1, tw[1024] = a2;
+    }
     const unsigned long long b = __ballot(act);
     if ((t & 63) == 0) tm[j * 8 + x] = b;
     const int listed = __syncthreads_or(in && (act || val != g.bg));
@@ -204,9 +249,13 @@ __global__ __launch_bounds__(512) void k_sdf_search(SdfGeom g, const int* __rest
 }
 
 // One wave per leaf of the range; the waves of unlisted leaves leave at once.  slot[j] = the record's place in the list.
+// ATTR: the leaf's 512 ids and 3 x 512 velocities as well, in 16-byte copies (every base is a multiple of 2048 bytes from hipMalloc's).
+template <bool ATTR>
 __global__ __launch_bounds__(256) void k_sdf_pack(SdfGeom g, long nrange, const int* __restrict__ flags, const int* __restrict__ slot,
                                                   const float* __restrict__ tv, const unsigned long long* __restrict__ tm,
-                                                  float* __restrict__ values, unsigned long long* __restrict__ active, int* __restrict__ origin)
+                                                  float* __restrict__ values, unsigned long long* __restrict__ active, int* __restrict__ origin,
+                                                  const uint32_t* __restrict__ tid, const float* __restrict__ tvel, uint32_t* __restrict__ ids,
+                                                  float* __restrict__ vel)
 {
     const long j = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (j >= nrange || !flags[j]) return;
@@ -219,6 +268,16 @@ __global__ __launch_bounds__(256) void k_sdf_pack(SdfGeom g, long nrange, const 
     dst[1] = src[1];
     if (lane < 8) active[s * 8 + lane] = tm[j * 8 + lane];
     if (lane < 3) origin[s * 3 + lane] = g.L0 + 8 * (g.l0[lane] + (lane == 0 ? jx : lane == 1 ? jy : jz));
+    if (ATTR) {
+        const uint4* is = (const uint4*)(tid + j * 512);
+        uint4* id = (uint4*)(ids + s * 512);
+        id[lane] = is[lane];
+        id[lane + 64] = is[lane + 64];
+        const float4* vs = (const float4*)(tvel + j * 1536);
+        float4* vd = (float4*)(vel + s * 1536);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) vd[lane + 64 * k] = vs[lane + 64 * k];
+    }
 }
 
 void launch_sdf_bbox(hipStream_t st, long n, Particles p, int lo, int hi, int* box, bool live)
@@ -239,25 +298,49 @@ void launch_sdf_count(hipStream_t st, long n, Particles p, const SdfGeom& g, int
 }
 
 void launch_sdf_scatter(hipStream_t st, long n, Particles p, const SdfGeom& g, const int* start, const int* place, double* sx, double* sy,
-                        double* sz)
+                        double* sz, int* ssrc)
 {
-    hipLaunchKernelGGL(k_sdf_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, p.px, p.py, p.pz, g, start, place, sx, sy, sz);
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (ssrc) hipLaunchKernelGGL(k_sdf_scatter<true>, grid, dim3(256), 0, st, n, p.px, p.py, p.pz, g, start, place, sx, sy, sz, ssrc);
+    else hipLaunchKernelGGL(k_sdf_scatter<false>, grid, dim3(256), 0, st, n, p.px, p.py, p.pz, g, start, place, sx, sy, sz, ssrc);
 }
 
 void launch_sdf_search(hipStream_t st, const SdfGeom& g, const int* start, const double* sx, const double* sy, const double* sz, float* tv,
                        uint64_t* tm, int* flags, unsigned* visits)
 {
     const unsigned nb = (unsigned)g.leaves();
-    if (visits) hipLaunchKernelGGL(k_sdf_search<true>, dim3(nb), dim3(512), 0, st, g, start, sx, sy, sz, tv, (unsigned long long*)tm, flags, visits);
-    else hipLaunchKernelGGL(k_sdf_search<false>, dim3(nb), dim3(512), 0, st, g, start, sx, sy, sz, tv, (unsigned long long*)tm, flags, visits);
+    const int* ns = nullptr;
+    const uint32_t* nu = nullptr;
+    const double* nd = nullptr;
+    if (visits)
+        hipLaunchKernelGGL((k_sdf_search<true, false>), dim3(nb), dim3(512), 0, st, g, start, sx, sy, sz, tv, (unsigned long long*)tm, flags, visits, ns,
+                           nu, nd, nd, nd, (uint32_t*)nullptr, (float*)nullptr);
+    else
+        hipLaunchKernelGGL((k_sdf_search<false, false>), dim3(nb), dim3(512), 0, st, g, start, sx, sy, sz, tv, (unsigned long long*)tm, flags, visits, ns,
+                           nu, nd, nd, nd, (uint32_t*)nullptr, (float*)nullptr);
+}
+
+void launch_sdf_search_attr(hipStream_t st, const SdfGeom& g, const int* start, const double* sx, const double* sy, const double* sz, float* tv,
+                            uint64_t* tm, int* flags, const int* ssrc, Particles p, uint32_t* tid, float* tvel)
+{
+    hipLaunchKernelGGL((k_sdf_search<false, true>), dim3((unsigned)g.leaves()), dim3(512), 0, st, g, start, sx, sy, sz, tv, (unsigned long long*)tm,
+                       flags, (unsigned*)nullptr, ssrc, (const uint32_t*)p.pid, (const double*)p.vx, (const double*)p.vy, (const double*)p.vz, tid, tvel);
 }
 
 void launch_sdf_pack(hipStream_t st, const SdfGeom& g, const int* flags, const int* slot, const float* tv, const uint64_t* tm, float* values,
                      uint64_t* active, int* origin)
 {
     const long nrange = g.leaves();
-    hipLaunchKernelGGL(k_sdf_pack, dim3((unsigned)((nrange + 3) / 4)), dim3(256), 0, st, g, nrange, flags, slot, tv, (const unsigned long long*)tm,
-                       values, (unsigned long long*)active, origin);
+    hipLaunchKernelGGL(k_sdf_pack<false>, dim3((unsigned)((nrange + 3) / 4)), dim3(256), 0, st, g, nrange, flags, slot, tv, (const unsigned long long*)tm,
+                       values, (unsigned long long*)active, origin, (const uint32_t*)nullptr, (const float*)nullptr, (uint32_t*)nullptr, (float*)nullptr);
+}
+
+void launch_sdf_pack_attr(hipStream_t st, const SdfGeom& g, const int* flags, const int* slot, const float* tv, const uint64_t* tm, float* values,
+                          uint64_t* active, int* origin, const uint32_t* tid, const float* tvel, uint32_t* ids, float* vel)
+{
+    const long nrange = g.leaves();
+    hipLaunchKernelGGL(k_sdf_pack<true>, dim3((unsigned)((nrange + 3) / 4)), dim3(256), 0, st, g, nrange, flags, slot, tv, (const unsigned long long*)tm,
+                       values, (unsigned long long*)active, origin, tid, tvel, ids, vel);
 }
 
 }  // namespace fl

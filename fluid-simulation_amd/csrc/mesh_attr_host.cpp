@@ -1,0 +1,243 @@
+// The liquid surface's attributes on the host (include/fluid_hip.h, "liquid surface, attributes") — no GPU, no HIP, no OpenVDB;
+// stands alone like mesh_host.cpp, whose walk it repeats.
+//   fluid_sdf_mesh_attr        the vertex velocities of fluid_sdf_mesh(grid) in its vertex order: the same leaves are worked on
+//                              (the listed ones and their neighbours at -1), in the same ascending order, each with its 9^3 values,
+//                              active bits and velocities (the +1 faces from up to seven neighbours, found by bisection).  One
+//                              pass: the order of the definition is the order of the walk.  No dense grid.  This is the second
+//                              implementation the kernel (kernels_mesh.hip, k_mesh_emit<true>) is compared with, and the only one
+//                              a hand-made list can drive into the rule for an edge with no active end.
+//   fluid_sdf_attr_to_dense    ids and velocities of a leaf list on the dense grid.
+//   fluid_write_ply_mesh_attr  binary little-endian PLY with vx / vy / vz per vertex.
+// Arithmetic: float, no contraction (the build states -ffp-contract=off).
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "fluid_hip.h"
+
+namespace {
+
+constexpr int LEAF = 8;
+constexpr int TILE = 9 * 9 * 9;
+inline int floor_to(int v, int m) { return v & ~(m - 1); }
+
+struct Org {
+    int32_t x, y, z;
+    bool operator<(const Org& b) const { return x != b.x ? x < b.x : y != b.y ? y < b.y : z < b.z; }
+    bool operator==(const Org& b) const { return x == b.x && y == b.y && z == b.z; }
+};
+
+// the list rules of fluid_sdf_to_dense
+int check_list(const fluid_sdf_grid_t* g)
+{
+    if (!g || g->n < 1 || g->n > 4096 || g->n_leaves < 0) return FLUID_ERR_ARG;
+    if (g->n_leaves > 0 && (!g->origin || !g->values || !g->active)) return FLUID_ERR_ARG;
+    const int lo = -(g->n / 2), hi = lo + g->n - 1, L0 = floor_to(lo, LEAF), L1 = floor_to(hi, LEAF);
+    for (int i = 0; i < g->n_leaves; ++i) {
+        const int32_t* o = g->origin + 3 * (size_t)i;
+        for (int a = 0; a < 3; ++a)
+            if ((o[a] & (LEAF - 1)) != 0 || o[a] < L0 || o[a] > L1) return FLUID_ERR_ARG;
+        if (i > 0 && !(Org{o[-3], o[-2], o[-1]} < Org{o[0], o[1], o[2]})) return FLUID_ERR_ARG;
+    }
+    return FLUID_OK;
+}
+
+int check_attr(const fluid_sdf_grid_t* g, const fluid_sdf_attr_t* a)
+{
+    if (check_list(g) != FLUID_OK || !a || a->n_leaves != g->n_leaves) return FLUID_ERR_ARG;
+    if (g->n_leaves > 0 && (!a->id || !a->velocity)) return FLUID_ERR_ARG;
+    return FLUID_OK;
+}
+
+struct Tile {
+    const fluid_sdf_grid_t* g;
+    const fluid_sdf_attr_t* at;
+    int lo, hi;
+    float V[TILE];        // values, +bg where no leaf is listed
+    float A[3][TILE];     // velocities
+    uint8_t B[TILE];      // active bits
+
+    long listed(const Org& o) const   // index in the list, or -1
+    {
+        long a = 0, b = g->n_leaves;
+        while (a < b) {
+            const long m = (a + b) / 2;
+            const int32_t* p = g->origin + 3 * (size_t)m;
+            if (Org{p[0], p[1], p[2]} < o) a = m + 1;
+            else b = m;
+        }
+        if (a == g->n_leaves) return -1;
+        const int32_t* p = g->origin + 3 * (size_t)a;
+        return Org{p[0], p[1], p[2]} == o ? a : -1;
+    }
+    // [(lx * 9 + ly) * 9 + lz] = the voxel o + (lx, ly, lz), 0 <= lx, ly, lz <= 8
+    void load(const Org& o)
+    {
+        for (int i = 0; i < TILE; ++i) V[i] = g->background, A[0][i] = A[1][i] = A[2][i] = 0.0f, B[i] = 0;
+        for (int d = 0; d < 8; ++d) {
+            const int dx = d >> 2, dy = (d >> 1) & 1, dz = d & 1;
+            const long l = listed(Org{o.x + 8 * dx, o.y + 8 * dy, o.z + 8 * dz});
+            if (l < 0) continue;
+            const float* v = g->values + 512 * (size_t)l;
+            const uint64_t* m = g->active + 8 * (size_t)l;
+            const float* vel = at->velocity + 1536 * (size_t)l;
+            for (int x = 0; x < (dx ? 1 : 8); ++x)
+                for (int y = 0; y < (dy ? 1 : 8); ++y)
+                    for (int z = 0; z < (dz ? 1 : 8); ++z) {
+                        const int off = (x * 8 + y) * 8 + z, i = ((x + 8 * dx) * 9 + (y + 8 * dy)) * 9 + z + 8 * dz;
+                        V[i] = v[off];
+                        B[i] = (uint8_t)((m[off >> 6] >> (off & 63)) & 1u);
+                        for (int a = 0; a < 3; ++a) A[a][i] = vel[512 * a + off];
+                    }
+        }
+    }
+    bool mixed(int i, int px, int py, int pz) const
+    {
+        unsigned m = 0;
+        for (int d = 0; d < 8; ++d) m |= (V[i + (d >> 2) * 81 + ((d >> 1) & 1) * 9 + (d & 1)] < 0.0f ? 1u : 0u) << d;
+        const bool cx = px >= lo && px <= hi - 1, cy = py >= lo && py <= hi - 1, cz = pz >= lo && pz <= hi - 1;
+        return cx && cy && cz && m != 0 && m != 255;
+    }
+    // the velocity of the vertex of the (mixed) cell whose min corner is place i of the tile
+    void vertex(int i, float* out) const
+    {
+        float s[3] = {0.0f, 0.0f, 0.0f};
+        int kv = 0;
+        static const int stride[3] = {81, 9, 1};
+        for (int a = 0; a < 3; ++a) {
+            const int b1 = a == 0 ? 1 : 0, b2 = a == 2 ? 1 : 2;   // the two other axes, ascending
+            for (int o = 0; o < 4; ++o) {
+                const int d1 = o >> 1, d2 = o & 1;
+                const int i0 = i + d1 * stride[b1] + d2 * stride[b2], i1 = i0 + stride[a];
+                const float v0 = V[i0], v1 = V[i1];
+                if ((v0 < 0.0f) == (v1 < 0.0f)) continue;
+                const bool a0 = B[i0] != 0, a1 = B[i1] != 0;
+                if (!a0 && !a1) continue;
+                const float den = v0 - v1;
+                const float t = v0 / den;
+                for (int c = 0; c < 3; ++c) {
+                    float e;
+                    if (a0 && a1) {
+                        const float d = A[c][i1] - A[c][i0];
+                        const float td = t * d;
+                        e = A[c][i0] + td;
+                    } else e = a0 ? A[c][i0] : A[c][i1];
+                    s[c] += e;
+                }
+                ++kv;
+            }
+        }
+        const float kf = (float)kv;
+        for (int c = 0; c < 3; ++c) out[c] = kv ? s[c] / kf : 0.0f;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int64_t fluid_sdf_mesh_attr(const fluid_sdf_grid_t* g, const fluid_sdf_attr_t* at, int64_t cap_vertices, float* velocity)
+{
+    if (check_attr(g, at) != FLUID_OK) return -FLUID_ERR_ARG;
+    std::vector<Tile> holder(1);   // (13 KB: not on the stack of whoever calls)
+    Tile& me = holder[0];
+    me.g = g, me.at = at;
+    me.lo = -(g->n / 2), me.hi = me.lo + g->n - 1;
+    const int L0 = floor_to(me.lo, LEAF);
+    std::vector<Org> work;
+    work.reserve((size_t)g->n_leaves * 2);
+    for (int l = 0; l < g->n_leaves; ++l) {
+        const int32_t* o = g->origin + 3 * (size_t)l;
+        for (int d = 0; d < 8; ++d) {
+            const Org c{o[0] - 8 * (d >> 2), o[1] - 8 * ((d >> 1) & 1), o[2] - 8 * (d & 1)};
+            if (c.x >= L0 && c.y >= L0 && c.z >= L0) work.push_back(c);
+        }
+    }
+    std::sort(work.begin(), work.end());
+    work.erase(std::unique(work.begin(), work.end()), work.end());
+    // pass 0 counts (nothing is written before the cap is known to hold), pass 1 writes
+    int64_t nv = 0;
+    for (int pass = 0; pass < (velocity ? 2 : 1); ++pass) {
+        if (pass == 1 && nv > cap_vertices) return -FLUID_ERR_ARG;
+        int64_t k = 0;
+        for (const Org& w : work) {
+            me.load(w);
+            for (int off = 0; off < 512; ++off) {
+                const int x = off >> 6, y = (off >> 3) & 7, z = off & 7;
+                const int i = (x * 9 + y) * 9 + z;
+                if (!me.mixed(i, w.x + x, w.y + y, w.z + z)) continue;
+                if (pass == 1) me.vertex(i, velocity + 3 * (size_t)k);
+                ++k;
+            }
+        }
+        nv = k;
+        if (nv > 0x7fffffffLL) return -FLUID_ERR_ARG;
+    }
+    return nv;
+}
+
+int fluid_sdf_attr_to_dense(const fluid_sdf_grid_t* g, const fluid_sdf_attr_t* at, uint32_t* id, float* velocity)
+{
+    if (check_attr(g, at) != FLUID_OK) return FLUID_ERR_ARG;
+    const int n = g->n, lo = -(n / 2), hi = lo + n - 1;
+    const size_t n3 = (size_t)n * n * n;
+    if (id) std::fill(id, id + n3, (uint32_t)FLUID_SDF_NO_ID);
+    if (velocity) std::fill(velocity, velocity + 3 * n3, 0.0f);
+    for (int l = 0; l < g->n_leaves; ++l) {
+        const int32_t* o = g->origin + 3 * (size_t)l;
+        for (int off = 0; off < 512; ++off) {
+            const int x = o[0] + (off >> 6), y = o[1] + ((off >> 3) & 7), z = o[2] + (off & 7);
+            if (x < lo || x > hi || y < lo || y > hi || z < lo || z > hi) continue;
+            const size_t c = ((size_t)(x - lo) * n + (size_t)(y - lo)) * n + (size_t)(z - lo);
+            if (id) id[c] = at->id[512 * (size_t)l + off];
+            if (velocity)
+                for (int a = 0; a < 3; ++a) velocity[a * n3 + c] = at->velocity[1536 * (size_t)l + 512 * a + off];
+        }
+    }
+    return FLUID_OK;
+}
+
+int fluid_write_ply_mesh_attr(const char* path, const fluid_mesh_t* m, const fluid_mesh_attr_t* at, float voxel_size, float velocity_scale)
+{
+    if (!path || !m || !at || m->n_vertices < 0 || m->n_quads < 0 || !(voxel_size > 0.0f) || !std::isfinite(velocity_scale)) return FLUID_ERR_ARG;
+    if (at->n_vertices != m->n_vertices) return FLUID_ERR_ARG;
+    if ((m->n_vertices > 0 && (!m->vertices || !at->velocity)) || (m->n_quads > 0 && !m->quads)) return FLUID_ERR_ARG;
+    for (int64_t i = 0; i < 4 * m->n_quads; ++i)
+        if ((int64_t)m->quads[i] >= m->n_vertices) return FLUID_ERR_ARG;
+    FILE* f = fopen(path, "wb");
+    if (!f) return FLUID_ERR_ARG;
+    bool ok = fprintf(f,
+                      "ply\nformat binary_little_endian 1.0\nelement vertex %lld\nproperty float x\nproperty float y\nproperty float z\n"
+                      "property float vx\nproperty float vy\nproperty float vz\n"
+                      "element face %lld\nproperty list uchar uint vertex_indices\nend_header\n",
+                      (long long)m->n_vertices, (long long)m->n_quads) > 0;
+    std::vector<char> buf;
+    buf.reserve((size_t)1 << 20);
+    auto flush = [&] {
+        if (!buf.empty() && fwrite(buf.data(), 1, buf.size(), f) != buf.size()) ok = false;
+        buf.clear();
+    };
+    for (int64_t i = 0; ok && i < m->n_vertices; ++i) {
+        float rec[6];
+        for (int a = 0; a < 3; ++a) rec[a] = m->vertices[3 * i + a] * voxel_size, rec[3 + a] = at->velocity[3 * i + a] * velocity_scale;
+        const char* c = (const char*)rec;
+        buf.insert(buf.end(), c, c + 24);
+        if (buf.size() >= ((size_t)1 << 20) - 32) flush();
+    }
+    for (int64_t i = 0; ok && i < m->n_quads; ++i) {
+        buf.push_back((char)4);
+        const char* c = (const char*)(m->quads + 4 * i);
+        buf.insert(buf.end(), c, c + 16);
+        if (buf.size() >= ((size_t)1 << 20) - 32) flush();
+    }
+    flush();
+    const int frc = fclose(f);
+    if (ok && frc == 0) return FLUID_OK;
+    remove(path);   // a short write leaves no partial file behind
+    return FLUID_ERR_ARG;
+}
+
+}  // extern "C"

@@ -260,6 +260,10 @@ struct SdfFront {
     const int* flags;     // the leaf is listed
     const fluid_sdf_filter_t* filt;   // nullptr: unfiltered.  Set by sdf_begin from its argument (limits checked there)
     int dilate;           // cells the base-cell box is dilated by for the range: 4; 5 for a filtered mesh (set by the caller after sdf_begin)
+    bool attr;            // "liquid surface, attributes": the search also keeps the closest particle (set by the caller after sdf_begin)
+    const uint64_t* tm;   // 8 mask words per leaf of the range (stale where flags[j] == 0)
+    const uint32_t* tid;  // attr: 512 ids per leaf of the range, and
+    const float* tvel;    // [leaf][axis][512] velocities (both stale where flags[j] == 0; nullptr without attr)
 };
 // limits of the parameters (and of the filter, when one is given), the state, the constants of g
 int sdf_begin(fluid_sim* s, const fluid_sdf_params_t* p, SdfFront* f, const fluid_sdf_filter_t* filt = nullptr);

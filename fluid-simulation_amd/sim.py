@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 
-from ._lib import lib, check, FluidError, Params, StepStats, FIELD, Source, LeafGridC, SdfParams, SdfGridC, SdfFilter, MeshC
+from ._lib import lib, check, FluidError, Params, StepStats, FIELD, Source, LeafGridC, SdfParams, SdfGridC, SdfFilter, MeshC, SdfAttrC, MeshAttrC
 
 _FIELD_DTYPE = {
     FIELD.CONTAINER: (np.float32, 1), FIELD.WEIGHTS: (np.float32, 1), FIELD.OUTPUT: (np.float32, 1),
@@ -243,12 +243,65 @@ def sdf_mesh(grid):
     return Mesh(grid.n, v, q, grid.background, grid.radius, grid.half_width)
 
 
-def write_ply_mesh(path, mesh, voxel_size):
+def write_ply_mesh(path, mesh, voxel_size, velocity=None, velocity_scale=1.0):
     """Binary little-endian PLY of a Mesh (or of a (vertices, quads) pair); positions are index space times voxel_size
-    (fluid_write_ply_mesh: host only)."""
+    (fluid_write_ply_mesh: host only).  velocity (nv, 3): vx / vy / vz per vertex as well, times velocity_scale
+    (fluid_write_ply_mesh_attr)."""
     if not isinstance(mesh, Mesh):
         mesh = Mesh(0, mesh[0], mesh[1])
-    check(lib.fluid_write_ply_mesh(str(path).encode(), C.byref(mesh._c()), float(voxel_size)))
+    if velocity is None:
+        check(lib.fluid_write_ply_mesh(str(path).encode(), C.byref(mesh._c()), float(voxel_size)))
+        return
+    vel = np.ascontiguousarray(velocity, dtype=np.float32).reshape(-1, 3)
+    at = MeshAttrC(len(vel), vel.ctypes.data if len(vel) else None)
+    rc = lib.fluid_write_ply_mesh_attr(str(path).encode(), C.byref(mesh._c()), C.byref(at), float(voxel_size), float(velocity_scale))
+    if rc != 0:
+        raise FluidError(rc, "fluid_write_ply_mesh_attr: a bad mesh, a velocity count that is not the vertex count, a bad scale or path")
+
+
+class SdfAttr:
+    """fluid_sdf_attr_t on the host ("liquid surface, attributes"): per voxel of an SdfGrid's leaves the closest particle's id
+    (k, 512) uint32 — 0xffffffff where the voxel is not active — and velocity (k, 3, 512) float32."""
+    NO_ID = 0xFFFFFFFF
+
+    def __init__(self, id, velocity):
+        self.id = np.ascontiguousarray(id, dtype=np.uint32).reshape(-1, 512)
+        self.velocity = np.ascontiguousarray(velocity, dtype=np.float32).reshape(-1, 3, 512)
+        assert self.id.shape[0] == self.velocity.shape[0]
+
+    @property
+    def n_leaves(self):
+        return self.id.shape[0]
+
+    def _c(self):
+        k = self.n_leaves
+        return SdfAttrC(k, self.id.ctypes.data if k else None, self.velocity.ctypes.data if k else None)
+
+
+def sdf_mesh_attr(grid, attr):
+    """velocity (nv, 3) float32: the vertex velocities of sdf_mesh(grid), in its vertex order (fluid_sdf_mesh_attr: host only)."""
+    c, _keep = grid._c()
+    a = attr._c()
+    nv = lib.fluid_sdf_mesh_attr(C.byref(c), C.byref(a), 0, None)
+    if nv < 0:
+        raise FluidError(-nv, "fluid_sdf_mesh_attr: a bad leaf list, or attributes of another list")
+    vel = np.empty((nv, 3), np.float32)
+    if nv and lib.fluid_sdf_mesh_attr(C.byref(c), C.byref(a), nv, vel.ctypes.data_as(C.c_void_p)) != nv:
+        raise FluidError(1, "fluid_sdf_mesh_attr: the second call disagrees with the count")
+    return vel
+
+
+def sdf_attr_to_dense(grid, attr):
+    """(id uint32 (n, n, n), velocity float32 (3, n, n, n)) of an SdfGrid's attributes: 0xffffffff / +0 outside the listed leaves
+    (fluid_sdf_attr_to_dense: host only)."""
+    ids = np.empty((grid.n,) * 3, dtype=np.uint32)
+    vel = np.empty((3,) + (grid.n,) * 3, dtype=np.float32)
+    c, _keep = grid._c()
+    a = attr._c()
+    check_rc = lib.fluid_sdf_attr_to_dense(C.byref(c), C.byref(a), ids.ctypes.data_as(C.c_void_p), vel.ctypes.data_as(C.c_void_p))
+    if check_rc != 0:
+        raise FluidError(check_rc, "fluid_sdf_attr_to_dense: a bad leaf list, or attributes of another list")
+    return ids, vel
 
 
 def water_cube_drop(n, ppc, seed=0):
@@ -484,12 +537,16 @@ class FluidSim:
         return dict(zip(("leaves_in_grid", "leaves_listed", "bytes_to_host"), (x.value for x in v)))
 
     # ---- liquid surface: narrow-band level set of the particles (single GPU; include/fluid_hip.h) ----
-    def sdf_snapshot(self, radius, half_width, smooth=None):
+    def sdf_snapshot(self, radius, half_width, smooth=None, attr=False):
         """Enqueue the level set of the particles as they are now (spheres of `radius`, band of `half_width`, both in voxels);
         a step() called next overlaps the copy to the host.  smooth=(width, iterations[, offset]): box-filtered and offset on
-        the device first (include/fluid_hip.h, "liquid surface, smoothed")."""
+        the device first (include/fluid_hip.h, "liquid surface, smoothed").  attr=True: with the closest particle's id and
+        velocity per voxel ("liquid surface, attributes"; sdf_wait_attr returns them)."""
         p = SdfParams(float(radius), float(half_width))
-        if smooth is None:
+        if attr:
+            f = None if smooth is None else C.byref(_sdf_filter_of(smooth))
+            check(lib.fluid_sdf_snapshot_attr(self._h, C.byref(p), f))
+        elif smooth is None:
             check(lib.fluid_sdf_snapshot(self._h, C.byref(p)))
         else:
             check(lib.fluid_sdf_snapshot_filtered(self._h, C.byref(p), C.byref(_sdf_filter_of(smooth))))
@@ -500,17 +557,33 @@ class FluidSim:
         check(lib.fluid_sdf_wait(self._h, C.byref(g)))
         return _sdf_grid_copy(g)
 
+    def sdf_wait_attr(self):
+        """(SdfGrid, SdfAttr) of the oldest level-set snapshot not yet waited for; the SdfAttr is None if that snapshot was
+        taken without attr=True (or lists no leaf)."""
+        g, a = SdfGridC(), SdfAttrC()
+        check(lib.fluid_sdf_wait_attr(self._h, C.byref(g), C.byref(a)))
+        grid = _sdf_grid_copy(g)
+        if not a.id:
+            return grid, None
+        k = a.n_leaves
+        ids = np.ctypeslib.as_array(C.cast(a.id, C.POINTER(C.c_uint32)), shape=(k, 512)).copy()
+        vel = np.ctypeslib.as_array(C.cast(a.velocity, C.POINTER(C.c_float)), shape=(k, 3, 512)).copy()
+        return grid, SdfAttr(ids, vel)
+
     def sdf_stats(self):
         v = [C.c_int64() for _ in range(3)]
         check(lib.fluid_sdf_stats(self._h, *[C.byref(x) for x in v]))
         return dict(zip(("leaves_in_grid", "leaves_listed", "bytes_to_host"), (x.value for x in v)))
 
     # ---- liquid surface as a mesh: surface nets of the level set (single GPU; include/fluid_hip.h) ----
-    def mesh_snapshot(self, radius, half_width, smooth=None):
+    def mesh_snapshot(self, radius, half_width, smooth=None, attr=False):
         """Enqueue the surface nets of the level set of the particles as they are now (parameters as sdf_snapshot, `smooth`
-        included); a step() called next overlaps the copy to the host."""
+        included); a step() called next overlaps the copy to the host.  attr=True: with a velocity per vertex (mesh_wait_attr)."""
         p = SdfParams(float(radius), float(half_width))
-        if smooth is None:
+        if attr:
+            f = None if smooth is None else C.byref(_sdf_filter_of(smooth))
+            check(lib.fluid_mesh_snapshot_attr(self._h, C.byref(p), f))
+        elif smooth is None:
             check(lib.fluid_mesh_snapshot(self._h, C.byref(p)))
         else:
             check(lib.fluid_mesh_snapshot_filtered(self._h, C.byref(p), C.byref(_sdf_filter_of(smooth))))
@@ -526,6 +599,21 @@ class FluidSim:
         if m.n_quads:
             q[:] = np.ctypeslib.as_array(C.cast(m.quads, C.POINTER(C.c_uint32)), shape=(m.n_quads, 4))
         return v, q
+
+    def mesh_wait_attr(self):
+        """(vertices, quads, velocity (nv, 3) float32) of the oldest mesh snapshot not yet waited for; velocity is None if that
+        snapshot was taken without attr=True (or has no vertex)."""
+        m, a = MeshC(), MeshAttrC()
+        check(lib.fluid_mesh_wait_attr(self._h, C.byref(m), C.byref(a)))
+        v, q = np.empty((m.n_vertices, 3), np.float32), np.empty((m.n_quads, 4), np.uint32)
+        if m.n_vertices:
+            v[:] = np.ctypeslib.as_array(C.cast(m.vertices, C.POINTER(C.c_float)), shape=(m.n_vertices, 3))
+        if m.n_quads:
+            q[:] = np.ctypeslib.as_array(C.cast(m.quads, C.POINTER(C.c_uint32)), shape=(m.n_quads, 4))
+        vel = None
+        if a.velocity:
+            vel = np.ctypeslib.as_array(C.cast(a.velocity, C.POINTER(C.c_float)), shape=(m.n_vertices, 3)).copy()
+        return v, q, vel
 
     def mesh_stats(self):
         v = [C.c_int64() for _ in range(3)]

@@ -751,6 +751,86 @@ int64_t fluid_sdf_mesh(const fluid_sdf_grid_t* g, int64_t cap_vertices, int64_t 
  * >= n_vertices, a path that cannot be opened or written in full (the partial file is removed). */
 int fluid_write_ply_mesh(const char* path, const fluid_mesh_t* m, float voxel_size);
 
+/* ---- liquid surface, attributes: the closest particle's id and velocity per voxel, a velocity per mesh vertex (single GPU) -------
+ * Geometry alone leaves the device above.  Motion blur needs a velocity per vertex; colour, age or foam need to know which
+ * particle a piece of surface belongs to.  OpenVDB's ParticlesToLevelSet has the second half (the AttributeT template argument,
+ * attributeGrid(), getAtt and Merge(d, att), tools/ParticlesToLevelSet.h:132-189, 603-637): every voxel the rasteriser sets also
+ * receives the attribute of the particle that set it.  Like the level set, the mesh and the filter this gets an exact, order-free
+ * definition of its own, and the kernels, the host functions below and the tests' numpy form give the same bytes.  Float unless
+ * stated, no FMA.
+ *
+ * Voxel attributes.  Input: the level set of "liquid surface" for the same fluid_sdf_params_t, the same counted particles, the
+ * same x2y2z2.  For an ACTIVE voxel c, m(c) is the minimum of x2y2z2 over the counted particles, as there.
+ *   The voxel's closest particle is the counted particle with x2y2z2 == m(c) that has the SMALLEST id.
+ *   id(c) is that particle's id: on a one-GPU handle the row of the particle in what fluid_download_particles returns at the time
+ *   of the snapshot (the ids given to fluid_upload_particles_ids, where that was the upload).
+ *   vel(c) = ((float)vx, (float)vy, (float)vz) of that particle: one narrowing of the handle's double velocity, no scaling.
+ *   A voxel that is not active (inactive +-bg, or outside the grid in a listed leaf) has id = FLUID_SDF_NO_ID and
+ *   vel = (+0.0f, +0.0f, +0.0f).
+ * No particle order is involved.  Every particle with the minimal x2y2z2 also has the minimal d, so this is the attribute grid the
+ * library leaves when it happens to visit that particle first (`if (d < v)` is strict, :637): it is ONE OF the library's possible
+ * outcomes, not "the" outcome — the library's depends on the order of its particle list.  The tie is broken on m, not on d: many
+ * distinct m share one d (up to 40 float steps of m for valid parameters), and a single pass cannot know the final class of d
+ * while it walks.
+ * A filter (fluid_sdf_filter_t) changes values, never topology: ids and velocities of a filtered snapshot are those of the
+ * unfiltered one, as in the library, where LevelSetFilter never touches the attribute grid.
+ *
+ * Vertex velocity.  Take a mixed cell's vertex and walk its 12 edges in the order of "liquid surface as a mesh".  For every
+ * COUNTING edge, with v0, v1, t as defined there, A0, A1 the active bits of its two ends and a0, a1 their velocity component:
+ *   both ends active:      e = a0 + t * (a1 - a0)   (float subtract, multiply, add);
+ *   only one end active:   e = that end's component;
+ *   neither end active:    the edge contributes nothing.
+ * Per component s starts at 0.0f and receives the e in edge order; kv counts the contributing edges.  The component is
+ * s / (float)kv, or +0.0f when kv == 0.  Vertex order is the mesh's.
+ * An edge with no active end cannot come from a device snapshot: an inactive -bg voxel (distance <= R - w) and an inactive +bg
+ * voxel (distance >= R + w) are 2w >= 2 apart, grid neighbours differ by at most 1, and the filter leaves inactive voxels alone.
+ * Only a hand-made leaf list reaches that rule: fluid_sdf_mesh_attr implements it, the kernel carries the same rule and cannot be
+ * driven into it.  One-ended edges do occur after a filter (the filter moves the sign change into the band's rim).
+ *
+ * Decomposed handles get FLUID_ERR_STATE from the four handle entry points below: the host merge sees values, and equal values
+ * do not imply equal m; an exact merge needs m (or an id rule on d) in the rank records. */
+#define FLUID_SDF_NO_ID 0xffffffffu
+typedef struct fluid_sdf_attr {
+    int32_t n_leaves;
+    const uint32_t* id;          /* 512 per leaf, the order of fluid_sdf_grid_t.values                               */
+    const float* velocity;       /* [leaf][axis][512]                                                                */
+} fluid_sdf_attr_t;
+#define FLUID_SDF_ATTR_LEAF_BYTES (2048 + 6144)   /* what the attributes add to a listed leaf on the way to the host   */
+typedef struct fluid_mesh_attr {
+    int64_t n_vertices;
+    const float* velocity;       /* 3 per vertex, the handle's velocity units                                        */
+} fluid_mesh_attr_t;
+/* fluid_sdf_snapshot (f == NULL) or fluid_sdf_snapshot_filtered (f != NULL) in every respect — same two slots, same copy stream,
+ * same count of outstanding snapshots (a third is FLUID_ERR_STATE), same fluid_sdf_stats —, and the values, masks and origins are
+ * byte for byte those of the plain snapshot; the record that travels behind the same event is longer by the ids and velocities:
+ * bytes_to_host = leaves_listed * (FLUID_SDF_LEAF_BYTES + FLUID_SDF_ATTR_LEAF_BYTES) + 4.  The extra scratch (4 B per particle,
+ * 8 KB per leaf of the range) is allocated by the handle's first attribute snapshot, surface or mesh, never inside a step; a
+ * caller that never asks for attributes allocates nothing more.  Nothing a later step reads is written. */
+int fluid_sdf_snapshot_attr(fluid_sim_t* s, const fluid_sdf_params_t* p, const fluid_sdf_filter_t* f);
+/* fluid_sdf_wait, and the attributes of the same snapshot (attr may be NULL).  A snapshot taken without attributes, or with no
+ * listed leaf, gives NULL attribute pointers (n_leaves is the grid's).  fluid_sdf_wait on an attribute snapshot returns the
+ * geometry alone.  Lifetime of the pointers: that of the grid's. */
+int fluid_sdf_wait_attr(fluid_sim_t* s, fluid_sdf_grid_t* grid, fluid_sdf_attr_t* attr);
+/* fluid_mesh_snapshot (f == NULL: the box dilated by 4) or fluid_mesh_snapshot_filtered (f != NULL: by 5) with a velocity per
+ * vertex: same slots, stream, count and fluid_mesh_stats, vertices and quads byte for byte the plain ones;
+ * bytes_to_host = 24 * vertices + 16 * quads + 8. */
+int fluid_mesh_snapshot_attr(fluid_sim_t* s, const fluid_sdf_params_t* p, const fluid_sdf_filter_t* f);
+/* fluid_mesh_wait, and the vertex velocities (attr may be NULL); NULL velocity for a snapshot taken without attributes or with no
+ * vertex.  fluid_mesh_wait on an attribute snapshot returns the geometry alone. */
+int fluid_mesh_wait_attr(fluid_sim_t* s, fluid_mesh_t* mesh, fluid_mesh_attr_t* attr);
+/* Host only: the vertex velocities of fluid_sdf_mesh(grid), in its vertex order, into velocity[3 * cap_vertices]; grid->values
+ * may be filtered values.  Returns the vertex count (velocity == NULL: the count only, the cap is ignored), or -FLUID_ERR_ARG
+ * with nothing written: a list fluid_sdf_to_dense refuses, attr NULL or attr->n_leaves != grid->n_leaves, leaves without the
+ * attribute arrays, a cap too small.  Works leaf by leaf with bisection for the neighbours, as fluid_sdf_mesh; no dense grid. */
+int64_t fluid_sdf_mesh_attr(const fluid_sdf_grid_t* grid, const fluid_sdf_attr_t* attr, int64_t cap_vertices, float* velocity);
+/* Host only: id[n^3] = FLUID_SDF_NO_ID and velocity[3 * n^3] ([axis][n^3], z fastest) = +0.0f everywhere, then the in-grid voxels
+ * of every listed leaf (either array may be NULL).  FLUID_ERR_ARG as fluid_sdf_to_dense, and for a leaf-count mismatch. */
+int fluid_sdf_attr_to_dense(const fluid_sdf_grid_t* grid, const fluid_sdf_attr_t* attr, uint32_t* id, float* velocity);
+/* Host only: fluid_write_ply_mesh with `property float vx / vy / vz` after `property float z`: a vertex record is six floats, the
+ * position times voxel_size and the velocity components times velocity_scale, both in float.  FLUID_ERR_ARG as there, and for
+ * attr NULL, attr->n_vertices != m->n_vertices, vertices without velocities, or a velocity_scale that is not finite. */
+int fluid_write_ply_mesh_attr(const char* path, const fluid_mesh_t* m, const fluid_mesh_attr_t* attr, float voxel_size, float velocity_scale);
+
 #ifdef __cplusplus
 }
 #endif
