@@ -315,10 +315,7 @@ void launch_pack_ids(hipStream_t st, long n, Particles p, long off, double* pos,
 void launch_unpack_particles(hipStream_t st, long n, const double* pos_aos, const double* vel_aos, Particles p);
 
 // grid
-void launch_out_mark(hipStream_t st, const float* f, int N, int off, int nl, int* flags);   // kernels_output.hip
-void launch_out_pack(hipStream_t st, const float* f, int N, int lo, int off, int nl, const int* flags, const int* slot, float* values,
-                     int* origin);
-// the owned block of a window as the leaf kernels see it (kernels_output.hip, k_out_mark_win / k_out_pack_win)
+// the owned block of a window as the leaf kernels see it (kernels_output.hip, k_out_mark / k_out_pack); one GPU: the whole grid
 struct OutWin {
     int ny, nz;            // window dims behind the row and plane strides
     int ox, oy, oz;        // global array index of window cell 0
@@ -327,8 +324,8 @@ struct OutWin {
     int l0[3], nl[3];      // first global leaf that meets the owned block, and how many do, per axis
     __host__ __device__ inline long leaves() const { return (long)nl[0] * nl[1] * nl[2]; }
 };
-void launch_out_mark_win(hipStream_t st, const float* f, const OutWin& w, int* flags);
-void launch_out_pack_win(hipStream_t st, const float* f, const OutWin& w, const int* flags, const int* slot, float* values, int* origin);
+void launch_out_mark(hipStream_t st, const float* f, const OutWin& w, int* flags);
+void launch_out_pack(hipStream_t st, const float* f, const OutWin& w, const int* flags, const int* slot, float* values, int* origin);
 // narrow-band level set of the particles (kernels_sdf.hip); coordinates are index-space coordinates, not array indices
 struct SdfGeom {
     int lo, hi;                          // the grid

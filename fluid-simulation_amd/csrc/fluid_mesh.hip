@@ -4,11 +4,9 @@
 // fluid_mesh_snapshot, all on the handle's stream: the front half of a level-set snapshot (fluid_sdf.hip: bbox, 24 bytes read back,
 // count, scan, scatter, search — the search scratch is the surface's own, shared in stream order) -> mark (mask, vertex and quad
 // count per leaf of the range) and the two totals (read back: 8 bytes, they size the slot) -> two exclusive scans of the counts ->
-// emit into the slot's device staging; the records then travel to pinned host memory on a second stream behind an event.  No leaf
-// is packed.  Two slots ([nq x 16 B of quads | nv x 12 B of vertices], one copy each): a slot is written by snapshot q, q + 2, ...,
-// so what fluid_mesh_wait handed out stays valid until the second following mesh snapshot.  Slots and the count of outstanding
-// snapshots are the mesh's own: density, surface and mesh can all be taken in one step.  The particle arrays are only read and
-// `binned` keeps holding, as for the surface.
+// emit into the slot's device staging ([nq x 16 B of quads | nv x 12 B of vertices]); the records then leave through the mesh's own
+// ring of two slots (snap_ring.h).  No leaf is packed.  The particle arrays are only read and `binned` keeps holding, as for the
+// surface.
 //
 // fluid_mesh_snapshot_filtered ("liquid surface, smoothed"): the front half runs over the box dilated by 5 cells and ends with the
 // filter's box passes (fluid_sdf.hip); the mesh kernels read the buffer the last pass wrote.  After the filter an inside voxel is
@@ -22,14 +20,10 @@
 using namespace fl;
 #define fail fluid_fail
 
-struct MeshSlot {
-    char* dev = nullptr;       // device staging
-    char* host = nullptr;      // pinned
-    size_t cap = 0;            // bytes either buffer holds
+struct MeshMeta {              // per slot of the ring
     long nv = 0, nq = 0;
     bool attr = false;         // the snapshot in the slot carries vertex velocities
     float bg = 0, R = 0, w = 0;
-    hipEvent_t done = nullptr;   // recorded on the copy stream behind the slot's copy
 };
 struct MeshState {
     long leaf_cap = 0;            // leaves of the range the per-leaf scratch holds
@@ -37,17 +31,14 @@ struct MeshState {
     int *cpre = nullptr, *vcnt = nullptr, *qcnt = nullptr, *vbase = nullptr, *qbase = nullptr, *sums = nullptr;
     int* d_scan_tot = nullptr;    // where launch_exclusive_scan puts its 32-bit totals (it always writes one; d_tot is what is read)
     unsigned *d_tot = nullptr, *h_tot = nullptr;   // vertices, quads: saturating at 2^31
-    hipStream_t copy = nullptr;
-    hipEvent_t emitted = nullptr;
-    MeshSlot s[2];
-    long n_snap = 0, n_wait = 0;   // snapshots taken / waited for: snapshot q lives in slot q & 1
+    SnapRing ring;
+    MeshMeta m[2];
     long last_v = 0, last_q = 0;
     bool last_attr = false;
 };
 
-#define MESH_GUARD(s)                                                    \
-    if (!(s)) return fail(FLUID_ERR_ARG, "null handle");                 \
-    if ((s)->dist) return fail(FLUID_ERR_STATE, "mesh snapshots are single-GPU only: a decomposed run merges its blocks' level-set lists (fluid_sdf_grids_merge) and meshes the result on the host (fluid_sdf_mesh)")
+static const char* const MESH_SINGLE = "mesh snapshots are single-GPU only: a decomposed run merges its blocks' level-set lists (fluid_sdf_grids_merge) and meshes the result on the host (fluid_sdf_mesh)";
+static const char* const MESH_FILT_SINGLE = "filtered mesh snapshots are single-GPU only: a decomposed run merges its blocks' level-set lists (fluid_sdf_grids_merge), filters the result (fluid_sdf_filter) and meshes it on the host (fluid_sdf_mesh)";
 
 static int mesh_init(fluid_sim* s)
 {
@@ -57,42 +48,24 @@ static int mesh_init(fluid_sim* s)
     HIPCHK(hipMalloc((void**)&o->d_tot, 2 * sizeof(unsigned)));
     HIPCHK(hipMalloc((void**)&o->d_scan_tot, 2 * sizeof(int)));
     HIPCHK(hipHostMalloc((void**)&o->h_tot, 2 * sizeof(unsigned)));
-    HIPCHK(hipStreamCreateWithFlags(&o->copy, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&o->emitted, hipEventDisableTiming));
-    for (auto& q : o->s) HIPCHK(hipEventCreateWithFlags(&q.done, hipEventDisableTiming));
-    return FLUID_OK;
+    return snap_init(o->ring);
 }
 
 void fl::mesh_free(fluid_sim* s)
 {
     MeshState* o = s->mesh;
     if (!o) return;
-    if (o->copy) hipStreamSynchronize(o->copy);
-    for (auto& q : o->s) {
-        if (q.dev) hipFree(q.dev);
-        if (q.host) hipHostFree(q.host);
-        if (q.done) hipEventDestroy(q.done);
-    }
+    snap_free(o->ring);
     for (void* p : {(void*)o->cmask, (void*)o->cpre, (void*)o->vcnt, (void*)o->qcnt, (void*)o->vbase, (void*)o->qbase, (void*)o->sums,
                     (void*)o->d_scan_tot, (void*)o->d_tot})
         if (p) hipFree(p);
     if (o->h_tot) hipHostFree(o->h_tot);
-    if (o->emitted) hipEventDestroy(o->emitted);
-    if (o->copy) hipStreamDestroy(o->copy);
     delete o;
     s->mesh = nullptr;
 }
 
 // (the front half's kernels are still queued on the handle's stream here; none of them touches these buffers, the mesh kernels
 // of the snapshot before have ended — the front half waited for the box behind them — and hipFree waits for the device anyway)
-template <typename T>
-static hipError_t regrow(T*& p, size_t n)
-{
-    if (p) hipFree(p);
-    p = nullptr;
-    return hipMalloc((void**)&p, n * sizeof(T));
-}
-
 static int mesh_scratch(MeshState* o, long leaves)
 {
     if (leaves <= o->leaf_cap) return FLUID_OK;
@@ -109,21 +82,6 @@ static int mesh_scratch(MeshState* o, long leaves)
     return FLUID_OK;
 }
 
-// room for `bytes` in the slot (its earlier contents were handed out two snapshots ago: no longer promised)
-static int mesh_grow(MeshSlot& q, size_t bytes)
-{
-    if (bytes <= q.cap) return FLUID_OK;
-    if (q.dev) hipFree(q.dev);
-    if (q.host) hipHostFree(q.host);
-    q.dev = q.host = nullptr;
-    q.cap = 0;
-    const size_t cap = bytes + bytes / 2 + 4096;
-    HIPCHK(hipMalloc((void**)&q.dev, cap));
-    HIPCHK(hipHostMalloc((void**)&q.host, cap));
-    q.cap = cap;
-    return FLUID_OK;
-}
-
 static int mesh_capture(fluid_sim* s, const fluid_sdf_params_t* p, const fluid_sdf_filter_t* filt, bool attr = false)
 {
     SdfFront f;
@@ -133,8 +91,9 @@ static int mesh_capture(fluid_sim* s, const fluid_sdf_params_t* p, const fluid_s
     f.attr = attr;
     if ((rc = mesh_init(s))) return rc;
     MeshState* o = s->mesh;
-    if (o->n_snap - o->n_wait >= 2) return fail(FLUID_ERR_STATE, "two mesh snapshots are waiting for fluid_mesh_wait");
-    MeshSlot& q = o->s[o->n_snap & 1];
+    if (snap_full(o->ring)) return fail(FLUID_ERR_STATE, "two mesh snapshots are waiting for fluid_mesh_wait");
+    SnapSlot& q = o->ring.s[snap_slot(o->ring)];
+    MeshMeta& m = o->m[snap_slot(o->ring)];
     if ((rc = sdf_front(s, &f))) return rc;
     const SdfGeom& g = f.g;
     long nv = 0, nq = 0;
@@ -153,10 +112,10 @@ static int mesh_capture(fluid_sim* s, const fluid_sdf_params_t* p, const fluid_s
         nv = (long)o->h_tot[0], nq = (long)o->h_tot[1];
     }
     const size_t bytes = (size_t)nq * 16 + (size_t)nv * (attr ? 24 : 12);
-    if ((rc = mesh_grow(q, bytes))) return rc;
-    q.nv = nv, q.nq = nq;
-    q.attr = attr;
-    q.bg = g.bg, q.R = g.R, q.w = g.w;
+    if ((rc = snap_reserve(q, bytes, 4096))) return rc;
+    m.nv = nv, m.nq = nq;
+    m.attr = attr;
+    m.bg = g.bg, m.R = g.R, m.w = g.w;
     if (nv > 0) {
         if (attr)
             launch_mesh_emit_attr(s->st, g, f.tv, f.flags, f.tm, f.tvel, o->cmask, o->cpre, o->vcnt, o->qcnt, o->vbase, o->qbase,
@@ -165,12 +124,8 @@ static int mesh_capture(fluid_sim* s, const fluid_sdf_params_t* p, const fluid_s
             launch_mesh_emit(s->st, g, f.tv, f.flags, o->cmask, o->cpre, o->vcnt, o->qcnt, o->vbase, o->qbase, (float*)(q.dev + (size_t)nq * 16),
                              (uint32_t*)q.dev);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(o->emitted, s->st));
-        HIPCHK(hipStreamWaitEvent(o->copy, o->emitted, 0));
-        HIPCHK(hipMemcpyAsync(q.host, q.dev, bytes, hipMemcpyDeviceToHost, o->copy));
     }
-    HIPCHK(hipEventRecord(q.done, o->copy));
-    o->n_snap++;
+    if ((rc = snap_commit(o->ring, s->st, nv > 0 ? bytes : 0))) return rc;
     o->last_v = nv, o->last_q = nq;
     o->last_attr = attr;
     return FLUID_OK;
@@ -180,22 +135,23 @@ static int mesh_wait(fluid_sim* s, fluid_mesh_t* out, fluid_mesh_attr_t* at)
 {
     if (!out) return fail(FLUID_ERR_ARG, "null argument");
     MeshState* o = s->mesh;
-    if (!o || o->n_wait >= o->n_snap) return fail(FLUID_ERR_STATE, "no mesh snapshot is outstanding");
-    MeshSlot& q = o->s[o->n_wait & 1];
-    HIPCHK(hipEventSynchronize(q.done));
+    int k = -1, rc = o ? snap_next_wait(o->ring, &k) : FLUID_OK;
+    if (rc) return rc;
+    if (k < 0) return fail(FLUID_ERR_STATE, "no mesh snapshot is outstanding");
+    const char* host = o->ring.s[k].host;
+    const MeshMeta& m = o->m[k];
     out->n = s->g.N;
-    out->n_vertices = q.nv;
-    out->n_quads = q.nq;
-    out->radius = q.R;
-    out->half_width = q.w;
-    out->background = q.bg;
-    out->quads = q.nq ? (const uint32_t*)q.host : nullptr;
-    out->vertices = q.nv ? (const float*)(q.host + (size_t)q.nq * 16) : nullptr;
+    out->n_vertices = m.nv;
+    out->n_quads = m.nq;
+    out->radius = m.R;
+    out->half_width = m.w;
+    out->background = m.bg;
+    out->quads = m.nq ? (const uint32_t*)host : nullptr;
+    out->vertices = m.nv ? (const float*)(host + (size_t)m.nq * 16) : nullptr;
     if (at) {
-        at->n_vertices = q.nv;
-        at->velocity = q.nv && q.attr ? (const float*)(q.host + (size_t)q.nq * 16 + (size_t)q.nv * 12) : nullptr;
+        at->n_vertices = m.nv;
+        at->velocity = m.nv && m.attr ? (const float*)(host + (size_t)m.nq * 16 + (size_t)m.nv * 12) : nullptr;
     }
-    o->n_wait++;
     return FLUID_OK;
 }
 
@@ -203,43 +159,38 @@ extern "C" {
 
 int fluid_mesh_snapshot(fluid_sim_t* s, const fluid_sdf_params_t* p)
 {
-    MESH_GUARD(s);
-    return mesh_capture(s, p, nullptr);
+    int rc = snap_guard(s, MESH_SINGLE);
+    return rc ? rc : mesh_capture(s, p, nullptr);
 }
 
 int fluid_mesh_snapshot_filtered(fluid_sim_t* s, const fluid_sdf_params_t* p, const fluid_sdf_filter_t* f)
 {
-    if (!s) return fail(FLUID_ERR_ARG, "null handle");
-    if (s->dist) return fail(FLUID_ERR_STATE, "filtered mesh snapshots are single-GPU only: a decomposed run merges its blocks' level-set lists (fluid_sdf_grids_merge), filters the result (fluid_sdf_filter) and meshes it on the host (fluid_sdf_mesh)");
+    if (int rc = snap_guard(s, MESH_FILT_SINGLE)) return rc;
     if (!f) return fail(FLUID_ERR_ARG, "null argument");
     return mesh_capture(s, p, f);
 }
 
 int fluid_mesh_wait(fluid_sim_t* s, fluid_mesh_t* out)
 {
-    MESH_GUARD(s);
-    return mesh_wait(s, out, nullptr);
+    int rc = snap_guard(s, MESH_SINGLE);
+    return rc ? rc : mesh_wait(s, out, nullptr);
 }
-
-#define MESH_ATTR_GUARD(s)                               \
-    if (!(s)) return fail(FLUID_ERR_ARG, "null handle"); \
-    if ((s)->dist) return fail(FLUID_ERR_STATE, "surface attributes are single-GPU only: the merge of the blocks' lists sees values, and equal values do not imply equal squared distances")
 
 int fluid_mesh_snapshot_attr(fluid_sim_t* s, const fluid_sdf_params_t* p, const fluid_sdf_filter_t* f)
 {
-    MESH_ATTR_GUARD(s);
-    return mesh_capture(s, p, f, true);
+    int rc = snap_guard(s, ATTR_SINGLE);
+    return rc ? rc : mesh_capture(s, p, f, true);
 }
 
 int fluid_mesh_wait_attr(fluid_sim_t* s, fluid_mesh_t* out, fluid_mesh_attr_t* attr)
 {
-    MESH_ATTR_GUARD(s);
-    return mesh_wait(s, out, attr);
+    int rc = snap_guard(s, ATTR_SINGLE);
+    return rc ? rc : mesh_wait(s, out, attr);
 }
 
 int fluid_mesh_stats(fluid_sim_t* s, int64_t* vertices, int64_t* quads, int64_t* bytes_to_host)
 {
-    MESH_GUARD(s);
+    if (int rc = snap_guard(s, MESH_SINGLE)) return rc;
     const int64_t nv = s->mesh ? s->mesh->last_v : 0, nq = s->mesh ? s->mesh->last_q : 0;
     if (vertices) *vertices = nv;
     if (quads) *quads = nq;

@@ -5,9 +5,8 @@
 // fluid_sdf_snapshot, all on the handle's stream: bounding box of the counted particles' base cells (24 bytes read back: it sizes
 // everything that follows) -> count per cell of the box, exclusive scan, scatter of the positions into cell order -> search over
 // the leaves of the box dilated by 4 cells (values, masks and a listed flag per leaf of that range) -> exclusive scan of the
-// flags (count read back: 4 bytes) -> pack into the slot's device staging; the records then travel to pinned host memory on a
-// second stream behind an event.  Two slots ([n x 2048 B of values | n x 64 B of masks | n x 12 B of origins], one copy each): a
-// slot is written by snapshot q, q + 2, ..., so what fluid_sdf_wait handed out stays valid until the second following snapshot.
+// flags (count read back: 4 bytes) -> pack into the slot's device staging ([n x 2048 B of values | n x 64 B of masks | n x 12 B
+// of origins]); the records then leave through the level set's own ring of two slots (snap_ring.h).
 // The particle arrays are only read; key, slot, cell_count, cell_start, the second particle buffer and every field stay as they
 // are, and `binned` keeps holding: the next step's sort starts from what FLIPadvect left, as if no snapshot had been taken.
 //
@@ -27,24 +26,20 @@
 // fluid_sdf_snapshot_attr / fluid_mesh_snapshot_attr ("liquid surface, attributes"): the scatter also writes each sorted position's
 // index in the live arrays (ssrc), the search keeps the closest particle beside the minimum and writes its id and velocity per voxel
 // (tid, tvel), and the pack lists them.  ssrc, tid and tvel exist from the handle's first attribute snapshot on.  An attribute
-// snapshot is one more kind of snapshot in the same two slots: its record is [n x 2048 B of values | n x 2048 B of ids |
-// n x 6144 B of velocities | n x 64 B of masks | n x 12 B of origins] (the 16-byte copies of the pack stay aligned for every n),
-// one copy behind the same event.
+// snapshot is one more kind of snapshot in the same ring: its record is [n x 2048 B of values | n x 2048 B of ids |
+// n x 6144 B of velocities | n x 64 B of masks | n x 12 B of origins] (the 16-byte copies of the pack stay aligned for every n).
+// Once a slot has held an attribute snapshot it keeps room for attributes (wide); a plain snapshot uses the front of it.
 #include "sim.h"
 
 using namespace fl;
 #define fail fluid_fail
 
 constexpr size_t SDF_REC = FLUID_SDF_LEAF_BYTES;
-struct SdfSlot {
-    char* dev = nullptr;       // device staging
-    char* host = nullptr;      // pinned
-    size_t cap = 0;            // leaves either buffer holds
-    bool wide = false;         // ... each with room for the attributes (the slot has held an attribute snapshot)
+struct SdfMeta {               // per slot of the ring
+    bool wide = false;         // the slot is sized for leaves with attributes (it has held an attribute snapshot)
     bool attr = false;         // the snapshot in the slot carries attributes
     int n_leaves = 0;
     float bg = 0, R = 0, w = 0;
-    hipEvent_t done = nullptr;   // recorded on the copy stream behind the slot's copy
 };
 struct SdfState {
     // scratch: cells of the particles' box, particles, leaves of the dilated box
@@ -66,16 +61,13 @@ struct SdfState {
     unsigned* visits = nullptr;   // FLUID_SDF_VISITS=1 only
     bool count_visits = false;
     int *d_small = nullptr, *h_small = nullptr;   // box[6], cell total, listed count
-    hipStream_t copy = nullptr;
-    hipEvent_t packed = nullptr;
-    SdfSlot s[2];
-    long n_snap = 0, n_wait = 0;   // snapshots taken / waited for: snapshot q lives in slot q & 1
+    SnapRing ring;
+    SdfMeta m[2];
     long last_leaves = 0, last_bytes = 0;
 };
 
-#define SDF_GUARD(s)                                                     \
-    if (!(s)) return fail(FLUID_ERR_ARG, "null handle");                 \
-    if ((s)->dist) return fail(FLUID_ERR_STATE, "level-set snapshots are single-GPU only: a decomposed handle holds a block of the particles (fluid_dist_sdf_*)")
+static const char* const SDF_SINGLE = "level-set snapshots are single-GPU only: a decomposed handle holds a block of the particles (fluid_dist_sdf_*)";
+static const char* const SDF_FILT_SINGLE = "filtered level-set snapshots are single-GPU only: a mean of per-block minima is not the mean of the minimum; filter the merged list on the host (fluid_sdf_filter)";
 
 static int sdf_init(fluid_sim* s)
 {
@@ -85,41 +77,23 @@ static int sdf_init(fluid_sim* s)
     if (const char* e = getenv("FLUID_SDF_VISITS")) o->count_visits = atoi(e) != 0;   // developer knob (tools/sdf_cost.py)
     HIPCHK(hipMalloc((void**)&o->d_small, 8 * sizeof(int)));
     HIPCHK(hipHostMalloc((void**)&o->h_small, 8 * sizeof(int)));
-    HIPCHK(hipStreamCreateWithFlags(&o->copy, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&o->packed, hipEventDisableTiming));
-    for (auto& q : o->s) HIPCHK(hipEventCreateWithFlags(&q.done, hipEventDisableTiming));
-    return FLUID_OK;
+    return snap_init(o->ring);
 }
 
 void fl::sdf_free(fluid_sim* s)
 {
     SdfState* o = s->sdf;
     if (!o) return;
-    if (o->copy) hipStreamSynchronize(o->copy);
-    for (auto& q : o->s) {
-        if (q.dev) hipFree(q.dev);
-        if (q.host) hipHostFree(q.host);
-        if (q.done) hipEventDestroy(q.done);
-    }
+    snap_free(o->ring);
     for (void* p : {(void*)o->cnt, (void*)o->start, (void*)o->cell_sums, (void*)o->place, (void*)o->spos, (void*)o->tv, (void*)o->tv2, (void*)o->ssrc, (void*)o->tid, (void*)o->tvel, (void*)o->tm, (void*)o->flags,
                     (void*)o->slot, (void*)o->leaf_sums, (void*)o->visits, (void*)o->d_small})
         if (p) hipFree(p);
     if (o->h_small) hipHostFree(o->h_small);
-    if (o->packed) hipEventDestroy(o->packed);
-    if (o->copy) hipStreamDestroy(o->copy);
     delete o;
     s->sdf = nullptr;
 }
 
 // (the handle's stream is idle here: every caller has just waited for a read-back on it)
-template <typename T>
-static hipError_t regrow(T*& p, size_t n)
-{
-    if (p) hipFree(p);
-    p = nullptr;
-    return hipMalloc((void**)&p, n * sizeof(T));
-}
-
 static int sdf_scratch(SdfState* o, long cells, long parts, long leaves, bool filtered, bool attr)
 {
     if (attr && !o->attr) {   // the first attribute snapshot of the handle: ssrc, tid and tvel beside whatever there is
@@ -166,23 +140,6 @@ static int sdf_scratch(SdfState* o, long cells, long parts, long leaves, bool fi
         if (o->count_visits) HIPCHK(regrow(o->visits, (size_t)cap));
         o->leaf_cap = cap;
     }
-    return FLUID_OK;
-}
-
-// room for n leaves in the slot (its earlier contents were handed out two snapshots ago: no longer promised)
-static int sdf_grow(SdfSlot& q, size_t n, bool attr)
-{
-    if (n <= q.cap && (!attr || q.wide)) return FLUID_OK;
-    if (attr) q.wide = true;   // (and stays so: a plain snapshot in a wide slot uses the front of it)
-    const size_t rec = q.wide ? SDF_REC + FLUID_SDF_ATTR_LEAF_BYTES : SDF_REC;
-    if (q.dev) hipFree(q.dev);
-    if (q.host) hipHostFree(q.host);
-    q.dev = q.host = nullptr;
-    q.cap = 0;
-    const size_t cap = n + n / 2 + 64;
-    HIPCHK(hipMalloc((void**)&q.dev, cap * rec));
-    HIPCHK(hipHostMalloc((void**)&q.host, cap * rec));
-    q.cap = cap;
     return FLUID_OK;
 }
 
@@ -282,8 +239,9 @@ static int sdf_capture(fluid_sim* s, const fluid_sdf_params_t* p, const fluid_sd
     if (rc) return rc;
     f.attr = attr;
     SdfState* o = s->sdf;
-    if (o->n_snap - o->n_wait >= 2) return fail(FLUID_ERR_STATE, "two level-set snapshots are waiting for fluid_sdf_wait");
-    SdfSlot& q = o->s[o->n_snap & 1];
+    if (snap_full(o->ring)) return fail(FLUID_ERR_STATE, "two level-set snapshots are waiting for fluid_sdf_wait");
+    SnapSlot& q = o->ring.s[snap_slot(o->ring)];
+    SdfMeta& m = o->m[snap_slot(o->ring)];
     if ((rc = sdf_front(s, &f))) return rc;
     const SdfGeom& g = f.g;
     const float R = g.R, w = g.w;
@@ -305,11 +263,13 @@ static int sdf_capture(fluid_sim* s, const fluid_sdf_params_t* p, const fluid_sd
             fprintf(stderr, "sdf visits: cells %.0f leaves_searched %ld leaves_in_range %ld\n", cv, searched, leaves);
         }
     }
-    if ((rc = sdf_grow(q, (size_t)n, attr))) return rc;
-    q.n_leaves = n;
-    q.attr = attr;
-    const size_t rec = attr ? SDF_REC + FLUID_SDF_ATTR_LEAF_BYTES : SDF_REC;
-    q.bg = g.bg, q.R = R, q.w = w;
+    constexpr size_t WIDE_REC = SDF_REC + FLUID_SDF_ATTR_LEAF_BYTES;
+    if (attr) m.wide = true;   // (and stays so)
+    if ((rc = snap_reserve(q, (size_t)n * (m.wide ? WIDE_REC : SDF_REC), 64 * (m.wide ? WIDE_REC : SDF_REC)))) return rc;
+    m.n_leaves = n;
+    m.attr = attr;
+    const size_t rec = attr ? WIDE_REC : SDF_REC;
+    m.bg = g.bg, m.R = R, m.w = w;
     if (n > 0) {
         const size_t a = attr ? (size_t)n * FLUID_SDF_ATTR_LEAF_BYTES : 0;   // the attributes lie between the values and the masks
         float* values = (float*)q.dev;
@@ -320,12 +280,8 @@ static int sdf_capture(fluid_sim* s, const fluid_sdf_params_t* p, const fluid_sd
                                  (float*)(q.dev + (size_t)n * 4096));
         else launch_sdf_pack(s->st, g, o->flags, o->slot, f.tv, o->tm, values, active, origin);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(o->packed, s->st));
-        HIPCHK(hipStreamWaitEvent(o->copy, o->packed, 0));
-        HIPCHK(hipMemcpyAsync(q.host, q.dev, (size_t)n * rec, hipMemcpyDeviceToHost, o->copy));
     }
-    HIPCHK(hipEventRecord(q.done, o->copy));
-    o->n_snap++;
+    if ((rc = snap_commit(o->ring, s->st, (size_t)n * rec))) return rc;
     o->last_leaves = n;
     o->last_bytes = (long)((size_t)n * rec) + 4;
     return FLUID_OK;
@@ -335,32 +291,32 @@ static int sdf_wait(fluid_sim* s, fluid_sdf_grid_t* out, fluid_sdf_attr_t* at = 
 {
     if (!out) return fail(FLUID_ERR_ARG, "null argument");
     SdfState* o = s->sdf;
-    if (!o || o->n_wait >= o->n_snap) return fail(FLUID_ERR_STATE, "no level-set snapshot is outstanding");
-    SdfSlot& q = o->s[o->n_wait & 1];
-    HIPCHK(hipEventSynchronize(q.done));
-    const size_t n = (size_t)q.n_leaves;
+    int k = -1, rc = o ? snap_next_wait(o->ring, &k) : FLUID_OK;
+    if (rc) return rc;
+    if (k < 0) return fail(FLUID_ERR_STATE, "no level-set snapshot is outstanding");
+    const char* host = o->ring.s[k].host;
+    const SdfMeta& m = o->m[k];
+    const size_t n = (size_t)m.n_leaves;
     out->n = s->g.N;
-    out->n_leaves = q.n_leaves;
-    out->background = q.bg;
-    out->radius = q.R;
-    out->half_width = q.w;
-    out->values = n ? (const float*)q.host : nullptr;
-    const size_t a = q.attr ? n * FLUID_SDF_ATTR_LEAF_BYTES : 0;
-    out->active = n ? (const uint64_t*)(q.host + n * 2048 + a) : nullptr;
-    out->origin = n ? (const int32_t*)(q.host + n * (2048 + 64) + a) : nullptr;
+    out->n_leaves = m.n_leaves;
+    out->background = m.bg;
+    out->radius = m.R;
+    out->half_width = m.w;
+    out->values = n ? (const float*)host : nullptr;
+    const size_t a = m.attr ? n * FLUID_SDF_ATTR_LEAF_BYTES : 0;
+    out->active = n ? (const uint64_t*)(host + n * 2048 + a) : nullptr;
+    out->origin = n ? (const int32_t*)(host + n * (2048 + 64) + a) : nullptr;
     if (at) {
-        at->n_leaves = q.n_leaves;
-        at->id = n && q.attr ? (const uint32_t*)(q.host + n * 2048) : nullptr;
-        at->velocity = n && q.attr ? (const float*)(q.host + n * 4096) : nullptr;
+        at->n_leaves = m.n_leaves;
+        at->id = n && m.attr ? (const uint32_t*)(host + n * 2048) : nullptr;
+        at->velocity = n && m.attr ? (const float*)(host + n * 4096) : nullptr;
     }
-    o->n_wait++;
     return FLUID_OK;
 }
 
 static int sdf_stats(fluid_sim* s, int64_t* leaves_in_grid, int64_t* leaves_listed, int64_t* bytes_to_host)
 {
-    const int lo = s->g.lo, hi = s->g.hi;
-    const int64_t nl = ((hi & ~7) - (lo & ~7)) / 8 + 1;
+    const int64_t nl = grid_leaves(s->g);
     if (leaves_in_grid) *leaves_in_grid = nl * nl * nl;
     if (leaves_listed) *leaves_listed = s->sdf ? s->sdf->last_leaves : 0;
     if (bytes_to_host) *bytes_to_host = s->sdf ? s->sdf->last_bytes : 0;
@@ -378,44 +334,39 @@ extern "C" {
 
 int fluid_sdf_snapshot(fluid_sim_t* s, const fluid_sdf_params_t* p)
 {
-    SDF_GUARD(s);
-    return sdf_capture(s, p);
+    int rc = snap_guard(s, SDF_SINGLE);
+    return rc ? rc : sdf_capture(s, p);
 }
 
 int fluid_sdf_snapshot_filtered(fluid_sim_t* s, const fluid_sdf_params_t* p, const fluid_sdf_filter_t* f)
 {
-    if (!s) return fail(FLUID_ERR_ARG, "null handle");
-    if (s->dist) return fail(FLUID_ERR_STATE, "filtered level-set snapshots are single-GPU only: a mean of per-block minima is not the mean of the minimum; filter the merged list on the host (fluid_sdf_filter)");
+    if (int rc = snap_guard(s, SDF_FILT_SINGLE)) return rc;
     if (!f) return fail(FLUID_ERR_ARG, "null argument");
     return sdf_capture(s, p, f);
 }
 
 int fluid_sdf_wait(fluid_sim_t* s, fluid_sdf_grid_t* out)
 {
-    SDF_GUARD(s);
-    return sdf_wait(s, out);
+    int rc = snap_guard(s, SDF_SINGLE);
+    return rc ? rc : sdf_wait(s, out);
 }
-
-#define SDF_ATTR_GUARD(s)                                \
-    if (!(s)) return fail(FLUID_ERR_ARG, "null handle"); \
-    if ((s)->dist) return fail(FLUID_ERR_STATE, "surface attributes are single-GPU only: the merge of the blocks' lists sees values, and equal values do not imply equal squared distances")
 
 int fluid_sdf_snapshot_attr(fluid_sim_t* s, const fluid_sdf_params_t* p, const fluid_sdf_filter_t* f)
 {
-    SDF_ATTR_GUARD(s);
-    return sdf_capture(s, p, f, true);
+    int rc = snap_guard(s, ATTR_SINGLE);
+    return rc ? rc : sdf_capture(s, p, f, true);
 }
 
 int fluid_sdf_wait_attr(fluid_sim_t* s, fluid_sdf_grid_t* out, fluid_sdf_attr_t* attr)
 {
-    SDF_ATTR_GUARD(s);
-    return sdf_wait(s, out, attr);
+    int rc = snap_guard(s, ATTR_SINGLE);
+    return rc ? rc : sdf_wait(s, out, attr);
 }
 
 int fluid_sdf_stats(fluid_sim_t* s, int64_t* leaves_in_grid, int64_t* leaves_listed, int64_t* bytes_to_host)
 {
-    SDF_GUARD(s);
-    return sdf_stats(s, leaves_in_grid, leaves_listed, bytes_to_host);
+    int rc = snap_guard(s, SDF_SINGLE);
+    return rc ? rc : sdf_stats(s, leaves_in_grid, leaves_listed, bytes_to_host);
 }
 
 int fluid_dist_sdf_snapshot(fluid_sim_t* s, const fluid_sdf_params_t* p)

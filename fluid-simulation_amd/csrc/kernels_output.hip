@@ -3,84 +3,26 @@
 //
 // Leaves have their origins at multiples of 8 in index space.  Array index a of an axis holds coordinate lo + a, the first
 // leaf starts at L0 = lo & ~7, so leaf l of an axis covers the array indices off + 8 l .. off + 8 l + 7 with off = L0 - lo
-// in (-8, 0] (N = 121: off = -4, the first leaf holds 4 in-grid cells per axis; N = 256: off = 0).  Leaf number =
-// (lx * nl + ly) * nl + lz: ascending number = ascending (x, y, z) origin.
+// in (-8, 0] (N = 121: off = -4, the first leaf holds 4 in-grid cells per axis; N = 256: off = 0).
 // A leaf is listed iff an in-grid voxel of it has a non-zero BIT PATTERN (-0.0f and NaN count).  No atomics, no
 // floating-point arithmetic: the list and the records are a function of the field alone.
 #include "common.h"
 
 namespace fl {
 
-// One block per (leaf-x, leaf-y) column: its 64 (x, y) rows are streamed along z, lanes on consecutive z.  A wave ORs the
-// bit patterns of its 16 rows in registers, one ballot per 64-cell stretch of z gives 8 leaves' flags (one byte each), the
-// four waves meet in LDS.  Reads every float of the container once; rows of an odd N are not 16-byte aligned: dword loads,
-// 16 of them in flight per lane.
-__global__ __launch_bounds__(256) void k_out_mark(const float* __restrict__ f, int N, int off, int nl, int* __restrict__ flags)
-{
-    __shared__ int hit[4][136];   // nl <= 129 (N <= 1024)
-    const int lx = blockIdx.x / nl, ly = blockIdx.x % nl;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const uint32_t* __restrict__ u = (const uint32_t*)f;
-    for (int k = 0; k * 8 < nl; ++k) {
-        const int az = off + 64 * k + lane;
-        const bool zin = az >= 0 && az < N;
-        // the wave's 16 rows: every load is issued before the first is needed (an out-of-grid voxel reads cell 0 and is masked)
-        uint32_t v[16], inm = 0;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int r = w + 4 * i;
-            const int ax = off + 8 * lx + (r >> 3), ay = off + 8 * ly + (r & 7);
-            const bool in = zin && ax >= 0 && ax < N && ay >= 0 && ay < N;
-            v[i] = u[in ? ((size_t)ax * N + ay) * N + az : 0];
-            inm |= (in ? 1u : 0u) << i;
-        }
-        uint32_t acc = 0;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc |= ((inm >> i) & 1u) ? v[i] : 0u;
-        const unsigned long long b = __ballot(acc != 0);
-        if (lane < 8 && 8 * k + lane < nl) hit[w][8 * k + lane] = ((b >> (8 * lane)) & 0xffull) != 0;
-    }
-    __syncthreads();
-    for (int lz = threadIdx.x; lz < nl; lz += 256)
-        flags[((size_t)lx * nl + ly) * nl + lz] = hit[0][lz] | hit[1][lz] | hit[2][lz] | hit[3][lz];
-}
+// The array is a window (nx, ny, nz) of the grid whose cell 0 is global array index (ox, oy, oz); the handle owns the global
+// indices [olo, ohi) per axis, inside the window (OutWin).  On one GPU window = grid = owned block: origin 0, dims N, [0, N).
+// On a rank of a decomposed run everything else the array holds (halo cells; in replicated mode the rest of the full-size array)
+// is other ranks' sums or partial sums: it neither lists a leaf nor reaches a record.  The leaves looked at are the GLOBAL leaves
+// that meet the owned block, l0 .. l0 + nl - 1 per axis; local number = ((lx - l0x) nly + (ly - l0y)) nlz + (lz - l0z), ascending
+// with the (x, y, z) origin.
 
-// One wave per leaf; the waves of unlisted leaves leave at once.  Lane = (x, y) row of the leaf: its 8 z values are the
-// lane's 32 contiguous bytes of the record, values[((x&7)*8 + (y&7))*8 + (z&7)]; voxels outside the grid hold +0.
-// slot[leaf] is the exclusive scan of the flags: the record's place in the list.
-__global__ __launch_bounds__(256) void k_out_pack(const float* __restrict__ f, int N, int lo, int off, int nl, long nleaf,
-                                                  const int* __restrict__ flags, const int* __restrict__ slot,
-                                                  float* __restrict__ values, int* __restrict__ origin)
-{
-    const long leaf = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (leaf >= nleaf || !flags[leaf]) return;
-    const int lane = threadIdx.x & 63;
-    const int lz = (int)(leaf % nl), ly = (int)((leaf / nl) % nl), lx = (int)(leaf / ((long)nl * nl));
-    const long s = slot[leaf];
-    const int ax = off + 8 * lx + (lane >> 3), ay = off + 8 * ly + (lane & 7), az0 = off + 8 * lz;
-    const bool rin = ax >= 0 && ax < N && ay >= 0 && ay < N;
-    float v[8];
-#pragma unroll
-    for (int z = 0; z < 8; ++z) {
-        const int az = az0 + z;
-        v[z] = (rin && az >= 0 && az < N) ? f[((size_t)ax * N + ay) * N + az] : 0.0f;
-    }
-    float4* dst = (float4*)(values + s * 512 + lane * 8);   // 32-byte aligned: the record base is hipMalloc's
-    dst[0] = make_float4(v[0], v[1], v[2], v[3]);
-    dst[1] = make_float4(v[4], v[5], v[6], v[7]);
-    if (lane < 3) origin[s * 3 + lane] = lo + off + 8 * (lane == 0 ? lx : lane == 1 ? ly : lz);
-}
-
-// ---- the owned block of a window (a rank of a decomposed run; fluid_dist_output_snapshot) --------------------------------------
-// The array is a window (nx, ny, nz) of the grid whose cell 0 is global array index (ox, oy, oz); this rank owns the global
-// indices [olo, ohi) per axis, inside the window.  Everything else the array holds (halo cells; in replicated mode the rest of
-// the full-size array) is other ranks' sums or partial sums: it neither lists a leaf nor reaches a record.  The leaves looked at
-// are the GLOBAL leaves that meet the owned block, l0 .. l0 + nl - 1 per axis; local number = ((lx - l0x) nly + (ly - l0y)) nlz
-// + (lz - l0z), ascending with the (x, y, z) origin.  On one GPU (window = grid = owned block) this is k_out_mark / k_out_pack.
-// Rows of a window start anywhere: dword loads throughout.
-
-// One block per (leaf-x, leaf-y) column of the leaf range; as k_out_mark, with the owned range as the in-mask.
-__global__ __launch_bounds__(256) void k_out_mark_win(const float* __restrict__ f, OutWin w, int* __restrict__ flags)
+// One block per (leaf-x, leaf-y) column of the leaf range: its 64 (x, y) rows are streamed along z, lanes on consecutive z.  A
+// wave ORs the bit patterns of its 16 rows in registers, one ballot per 64-cell stretch of z gives 8 leaves' flags (one byte
+// each), the four waves meet in LDS.  Reads every owned float of the container once; rows of an odd N or of a window are not
+// 16-byte aligned: dword loads, 16 of them in flight per lane (every load is issued before the first is needed; a voxel outside
+// the owned block reads cell 0 and is masked).
+__global__ __launch_bounds__(256) void k_out_mark(const float* __restrict__ f, OutWin w, int* __restrict__ flags)
 {
     __shared__ int hit[4][136];   // nl[2] <= 129 (N <= 1024; checked by the host)
     const int jx = blockIdx.x / w.nl[1], jy = blockIdx.x % w.nl[1];
@@ -110,9 +52,11 @@ __global__ __launch_bounds__(256) void k_out_mark_win(const float* __restrict__ 
         flags[((size_t)jx * w.nl[1] + jy) * w.nl[2] + jz] = hit[0][jz] | hit[1][jz] | hit[2][jz] | hit[3][jz];
 }
 
-// One wave per leaf of the range, as k_out_pack; a voxel this rank does not own (halo, another rank's, outside the grid) holds +0.
-__global__ __launch_bounds__(256) void k_out_pack_win(const float* __restrict__ f, OutWin w, long nleaf, const int* __restrict__ flags,
-                                                      const int* __restrict__ slot, float* __restrict__ values, int* __restrict__ origin)
+// One wave per leaf of the range; the waves of unlisted leaves leave at once.  Lane = (x, y) row of the leaf: its 8 z values are
+// the lane's 32 contiguous bytes of the record, values[((x&7)*8 + (y&7))*8 + (z&7)]; a voxel the handle does not own (halo, another
+// rank's, outside the grid) holds +0.  slot[leaf] is the exclusive scan of the flags: the record's place in the list.
+__global__ __launch_bounds__(256) void k_out_pack(const float* __restrict__ f, OutWin w, long nleaf, const int* __restrict__ flags,
+                                                  const int* __restrict__ slot, float* __restrict__ values, int* __restrict__ origin)
 {
     const long leaf = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (leaf >= nleaf || !flags[leaf]) return;
@@ -133,27 +77,15 @@ __global__ __launch_bounds__(256) void k_out_pack_win(const float* __restrict__ 
     if (lane < 3) origin[s * 3 + lane] = w.lo + w.off + 8 * (lane == 0 ? lx : lane == 1 ? ly : lz);
 }
 
-void launch_out_mark(hipStream_t st, const float* f, int N, int off, int nl, int* flags)
+void launch_out_mark(hipStream_t st, const float* f, const OutWin& w, int* flags)
 {
-    hipLaunchKernelGGL(k_out_mark, dim3((unsigned)(nl * nl)), dim3(256), 0, st, f, N, off, nl, flags);
+    hipLaunchKernelGGL(k_out_mark, dim3((unsigned)(w.nl[0] * w.nl[1])), dim3(256), 0, st, f, w, flags);
 }
 
-void launch_out_pack(hipStream_t st, const float* f, int N, int lo, int off, int nl, const int* flags, const int* slot, float* values,
-                     int* origin)
-{
-    const long nleaf = (long)nl * nl * nl;
-    hipLaunchKernelGGL(k_out_pack, dim3((unsigned)((nleaf + 3) / 4)), dim3(256), 0, st, f, N, lo, off, nl, nleaf, flags, slot, values, origin);
-}
-
-void launch_out_mark_win(hipStream_t st, const float* f, const OutWin& w, int* flags)
-{
-    hipLaunchKernelGGL(k_out_mark_win, dim3((unsigned)(w.nl[0] * w.nl[1])), dim3(256), 0, st, f, w, flags);
-}
-
-void launch_out_pack_win(hipStream_t st, const float* f, const OutWin& w, const int* flags, const int* slot, float* values, int* origin)
+void launch_out_pack(hipStream_t st, const float* f, const OutWin& w, const int* flags, const int* slot, float* values, int* origin)
 {
     const long nleaf = w.leaves();
-    hipLaunchKernelGGL(k_out_pack_win, dim3((unsigned)((nleaf + 3) / 4)), dim3(256), 0, st, f, w, nleaf, flags, slot, values, origin);
+    hipLaunchKernelGGL(k_out_pack, dim3((unsigned)((nleaf + 3) / 4)), dim3(256), 0, st, f, w, nleaf, flags, slot, values, origin);
 }
 
 }  // namespace fl

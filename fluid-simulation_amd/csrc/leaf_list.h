@@ -1,0 +1,90 @@
+// What the host-side surface code (vdb_sdf_writer.cpp, sdf_filter_host.cpp, mesh_host.cpp, mesh_attr_host.cpp) shares about a
+// level-set leaf list (fluid_sdf_grid_t): its rules, the search in it, and the walk of the surface nets over it.  Header only:
+// every file that includes it compiles on its own.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <vector>
+
+#include "fluid_hip.h"
+
+namespace {
+
+constexpr int LEAF = 8;
+inline int floor_to(int v, int m) { return v & ~(m - 1); }
+
+struct Org {
+    int32_t x, y, z;
+    bool operator<(const Org& b) const { return x != b.x ? x < b.x : y != b.y ? y < b.y : z < b.z; }
+    bool operator==(const Org& b) const { return x == b.x && y == b.y && z == b.z; }
+};
+inline Org org_of(const fluid_sdf_grid_t* g, long l)
+{
+    const int32_t* p = g->origin + 3 * (size_t)l;
+    return Org{p[0], p[1], p[2]};
+}
+
+// the list rules of fluid_sdf_to_dense.  FLUID_OK, or FLUID_ERR_ARG: no arrays behind a non-empty list, an origin off the 8-grid,
+// outside the leaves of [lo,hi]^3, or not strictly ascending in (x, y, z)
+inline int check_list(const fluid_sdf_grid_t* g)
+{
+    if (!g || g->n < 1 || g->n > 4096 || g->n_leaves < 0) return FLUID_ERR_ARG;
+    if (g->n_leaves > 0 && (!g->origin || !g->values || !g->active)) return FLUID_ERR_ARG;
+    const int lo = -(g->n / 2), hi = lo + g->n - 1, L0 = floor_to(lo, LEAF), L1 = floor_to(hi, LEAF);
+    for (int i = 0; i < g->n_leaves; ++i) {
+        const int32_t* o = g->origin + 3 * (size_t)i;
+        for (int a = 0; a < 3; ++a)
+            if ((o[a] & (LEAF - 1)) != 0 || o[a] < L0 || o[a] > L1) return FLUID_ERR_ARG;
+        if (i > 0 && !(org_of(g, i - 1) < org_of(g, i))) return FLUID_ERR_ARG;
+    }
+    return FLUID_OK;
+}
+
+// index of the leaf at o in the (checked) list, or -1: bisection
+inline long find_leaf(const fluid_sdf_grid_t* g, const Org& o)
+{
+    long a = 0, b = g->n_leaves;
+    while (a < b) {
+        const long m = (a + b) / 2;
+        if (org_of(g, m) < o) a = m + 1;
+        else b = m;
+    }
+    return a < g->n_leaves && org_of(g, a) == o ? a : -1;
+}
+
+// The leaves the surface nets work on, ascending.  A mixed cell has an inside corner, which lies in a listed leaf; its min corner
+// lies in that leaf or in one of the seven leaves at -1: the listed leaves and those neighbours, where the grid has them.
+inline std::vector<Org> mesh_work_list(const fluid_sdf_grid_t* g)
+{
+    const int L0 = floor_to(-(g->n / 2), LEAF);
+    std::vector<Org> work;
+    work.reserve((size_t)g->n_leaves * 2);
+    for (long l = 0; l < g->n_leaves; ++l) {
+        const Org o = org_of(g, l);
+        for (int d = 0; d < 8; ++d) {
+            const Org c{o.x - 8 * (d >> 2), o.y - 8 * ((d >> 1) & 1), o.z - 8 * (d & 1)};
+            if (c.x >= L0 && c.y >= L0 && c.z >= L0) work.push_back(c);
+        }
+    }
+    std::sort(work.begin(), work.end());
+    work.erase(std::unique(work.begin(), work.end()), work.end());
+    return work;
+}
+
+// The 9^3 tile of a worked-on leaf: the voxels o + (lx, ly, lz), 0 <= lx, ly, lz <= 8, the +1 faces from up to seven neighbours.
+// put(l, off, i) for every voxel of the tile that a listed leaf holds: l = the leaf's index in the list, off = the voxel's offset
+// in that leaf, i = (lx * 9 + ly) * 9 + lz = its place in the tile.  What no listed leaf holds is not visited.
+template <typename Put>
+inline void load_tile(const fluid_sdf_grid_t* g, const Org& o, Put put)
+{
+    for (int d = 0; d < 8; ++d) {
+        const int dx = d >> 2, dy = (d >> 1) & 1, dz = d & 1;
+        const long l = find_leaf(g, Org{o.x + 8 * dx, o.y + 8 * dy, o.z + 8 * dz});
+        if (l < 0) continue;
+        for (int x = 0; x < (dx ? 1 : 8); ++x)
+            for (int y = 0; y < (dy ? 1 : 8); ++y)
+                for (int z = 0; z < (dz ? 1 : 8); ++z) put(l, (x * 8 + y) * 8 + z, ((x + 8 * dx) * 9 + (y + 8 * dy)) * 9 + z + 8 * dz);
+    }
+}
+
+}  // namespace

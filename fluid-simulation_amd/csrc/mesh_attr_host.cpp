@@ -1,5 +1,5 @@
-// The liquid surface's attributes on the host (include/fluid_hip.h, "liquid surface, attributes") — no GPU, no HIP, no OpenVDB;
-// stands alone like mesh_host.cpp, whose walk it repeats.
+// The liquid surface's attributes on the host (include/fluid_hip.h, "liquid surface, attributes") — no GPU, no HIP, no OpenVDB.
+// It walks as mesh_host.cpp does: the leaves worked on and the tile loader are leaf_list.h's, the PLY body is ply_mesh.h's.
 //   fluid_sdf_mesh_attr        the vertex velocities of fluid_sdf_mesh(grid) in its vertex order: the same leaves are worked on
 //                              (the listed ones and their neighbours at -1), in the same ascending order, each with its 9^3 values,
 //                              active bits and velocities (the +1 faces from up to seven neighbours, found by bisection).  One
@@ -16,34 +16,12 @@
 #include <cstring>
 #include <vector>
 
-#include "fluid_hip.h"
+#include "leaf_list.h"
+#include "ply_mesh.h"
 
 namespace {
 
-constexpr int LEAF = 8;
 constexpr int TILE = 9 * 9 * 9;
-inline int floor_to(int v, int m) { return v & ~(m - 1); }
-
-struct Org {
-    int32_t x, y, z;
-    bool operator<(const Org& b) const { return x != b.x ? x < b.x : y != b.y ? y < b.y : z < b.z; }
-    bool operator==(const Org& b) const { return x == b.x && y == b.y && z == b.z; }
-};
-
-// the list rules of fluid_sdf_to_dense
-int check_list(const fluid_sdf_grid_t* g)
-{
-    if (!g || g->n < 1 || g->n > 4096 || g->n_leaves < 0) return FLUID_ERR_ARG;
-    if (g->n_leaves > 0 && (!g->origin || !g->values || !g->active)) return FLUID_ERR_ARG;
-    const int lo = -(g->n / 2), hi = lo + g->n - 1, L0 = floor_to(lo, LEAF), L1 = floor_to(hi, LEAF);
-    for (int i = 0; i < g->n_leaves; ++i) {
-        const int32_t* o = g->origin + 3 * (size_t)i;
-        for (int a = 0; a < 3; ++a)
-            if ((o[a] & (LEAF - 1)) != 0 || o[a] < L0 || o[a] > L1) return FLUID_ERR_ARG;
-        if (i > 0 && !(Org{o[-3], o[-2], o[-1]} < Org{o[0], o[1], o[2]})) return FLUID_ERR_ARG;
-    }
-    return FLUID_OK;
-}
 
 int check_attr(const fluid_sdf_grid_t* g, const fluid_sdf_attr_t* a)
 {
@@ -60,39 +38,15 @@ struct Tile {
     float A[3][TILE];     // velocities
     uint8_t B[TILE];      // active bits
 
-    long listed(const Org& o) const   // index in the list, or -1
-    {
-        long a = 0, b = g->n_leaves;
-        while (a < b) {
-            const long m = (a + b) / 2;
-            const int32_t* p = g->origin + 3 * (size_t)m;
-            if (Org{p[0], p[1], p[2]} < o) a = m + 1;
-            else b = m;
-        }
-        if (a == g->n_leaves) return -1;
-        const int32_t* p = g->origin + 3 * (size_t)a;
-        return Org{p[0], p[1], p[2]} == o ? a : -1;
-    }
     // [(lx * 9 + ly) * 9 + lz] = the voxel o + (lx, ly, lz), 0 <= lx, ly, lz <= 8
     void load(const Org& o)
     {
         for (int i = 0; i < TILE; ++i) V[i] = g->background, A[0][i] = A[1][i] = A[2][i] = 0.0f, B[i] = 0;
-        for (int d = 0; d < 8; ++d) {
-            const int dx = d >> 2, dy = (d >> 1) & 1, dz = d & 1;
-            const long l = listed(Org{o.x + 8 * dx, o.y + 8 * dy, o.z + 8 * dz});
-            if (l < 0) continue;
-            const float* v = g->values + 512 * (size_t)l;
-            const uint64_t* m = g->active + 8 * (size_t)l;
-            const float* vel = at->velocity + 1536 * (size_t)l;
-            for (int x = 0; x < (dx ? 1 : 8); ++x)
-                for (int y = 0; y < (dy ? 1 : 8); ++y)
-                    for (int z = 0; z < (dz ? 1 : 8); ++z) {
-                        const int off = (x * 8 + y) * 8 + z, i = ((x + 8 * dx) * 9 + (y + 8 * dy)) * 9 + z + 8 * dz;
-                        V[i] = v[off];
-                        B[i] = (uint8_t)((m[off >> 6] >> (off & 63)) & 1u);
-                        for (int a = 0; a < 3; ++a) A[a][i] = vel[512 * a + off];
-                    }
-        }
+        load_tile(g, o, [&](long l, int off, int i) {
+            V[i] = g->values[512 * (size_t)l + off];
+            B[i] = (uint8_t)((g->active[8 * (size_t)l + (off >> 6)] >> (off & 63)) & 1u);
+            for (int a = 0; a < 3; ++a) A[a][i] = at->velocity[1536 * (size_t)l + 512 * a + off];
+        });
     }
     bool mixed(int i, int px, int py, int pz) const
     {
@@ -146,18 +100,7 @@ int64_t fluid_sdf_mesh_attr(const fluid_sdf_grid_t* g, const fluid_sdf_attr_t* a
     Tile& me = holder[0];
     me.g = g, me.at = at;
     me.lo = -(g->n / 2), me.hi = me.lo + g->n - 1;
-    const int L0 = floor_to(me.lo, LEAF);
-    std::vector<Org> work;
-    work.reserve((size_t)g->n_leaves * 2);
-    for (int l = 0; l < g->n_leaves; ++l) {
-        const int32_t* o = g->origin + 3 * (size_t)l;
-        for (int d = 0; d < 8; ++d) {
-            const Org c{o[0] - 8 * (d >> 2), o[1] - 8 * ((d >> 1) & 1), o[2] - 8 * (d & 1)};
-            if (c.x >= L0 && c.y >= L0 && c.z >= L0) work.push_back(c);
-        }
-    }
-    std::sort(work.begin(), work.end());
-    work.erase(std::unique(work.begin(), work.end()), work.end());
+    const std::vector<Org> work = mesh_work_list(g);
     // pass 0 counts (nothing is written before the cap is known to hold), pass 1 writes
     int64_t nv = 0;
     for (int pass = 0; pass < (velocity ? 2 : 1); ++pass) {
@@ -205,39 +148,7 @@ int fluid_write_ply_mesh_attr(const char* path, const fluid_mesh_t* m, const flu
     if (!path || !m || !at || m->n_vertices < 0 || m->n_quads < 0 || !(voxel_size > 0.0f) || !std::isfinite(velocity_scale)) return FLUID_ERR_ARG;
     if (at->n_vertices != m->n_vertices) return FLUID_ERR_ARG;
     if ((m->n_vertices > 0 && (!m->vertices || !at->velocity)) || (m->n_quads > 0 && !m->quads)) return FLUID_ERR_ARG;
-    for (int64_t i = 0; i < 4 * m->n_quads; ++i)
-        if ((int64_t)m->quads[i] >= m->n_vertices) return FLUID_ERR_ARG;
-    FILE* f = fopen(path, "wb");
-    if (!f) return FLUID_ERR_ARG;
-    bool ok = fprintf(f,
-                      "ply\nformat binary_little_endian 1.0\nelement vertex %lld\nproperty float x\nproperty float y\nproperty float z\n"
-                      "property float vx\nproperty float vy\nproperty float vz\n"
-                      "element face %lld\nproperty list uchar uint vertex_indices\nend_header\n",
-                      (long long)m->n_vertices, (long long)m->n_quads) > 0;
-    std::vector<char> buf;
-    buf.reserve((size_t)1 << 20);
-    auto flush = [&] {
-        if (!buf.empty() && fwrite(buf.data(), 1, buf.size(), f) != buf.size()) ok = false;
-        buf.clear();
-    };
-    for (int64_t i = 0; ok && i < m->n_vertices; ++i) {
-        float rec[6];
-        for (int a = 0; a < 3; ++a) rec[a] = m->vertices[3 * i + a] * voxel_size, rec[3 + a] = at->velocity[3 * i + a] * velocity_scale;
-        const char* c = (const char*)rec;
-        buf.insert(buf.end(), c, c + 24);
-        if (buf.size() >= ((size_t)1 << 20) - 32) flush();
-    }
-    for (int64_t i = 0; ok && i < m->n_quads; ++i) {
-        buf.push_back((char)4);
-        const char* c = (const char*)(m->quads + 4 * i);
-        buf.insert(buf.end(), c, c + 16);
-        if (buf.size() >= ((size_t)1 << 20) - 32) flush();
-    }
-    flush();
-    const int frc = fclose(f);
-    if (ok && frc == 0) return FLUID_OK;
-    remove(path);   // a short write leaves no partial file behind
-    return FLUID_ERR_ARG;
+    return write_ply(path, m, voxel_size, true, at->velocity, velocity_scale);
 }
 
 }  // extern "C"

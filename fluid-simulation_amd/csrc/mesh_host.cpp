@@ -1,5 +1,5 @@
-// The liquid surface as a mesh on the host (include/fluid_hip.h, "liquid surface as a mesh") — no GPU, no HIP, no OpenVDB; stands
-// alone (it shares no code with the writers).
+// The liquid surface as a mesh on the host (include/fluid_hip.h, "liquid surface as a mesh") — no GPU, no HIP, no OpenVDB.  The
+// list's rules, the leaves worked on and the tile loader are leaf_list.h's, the PLY body is ply_mesh.h's.
 //   fluid_sdf_mesh        surface nets of a leaf list, every unlisted leaf being +bg: how a decomposed run gets its mesh (after
 //                         fluid_sdf_grids_merge), and the second implementation the kernels (kernels_mesh.hip) are compared with.
 //                         A mixed cell has an inside corner, which lies in a listed leaf; its min corner lies in that leaf or in
@@ -15,34 +15,10 @@
 #include <cstring>
 #include <vector>
 
-#include "fluid_hip.h"
+#include "leaf_list.h"
+#include "ply_mesh.h"
 
 namespace {
-
-constexpr int LEAF = 8;
-inline int floor_to(int v, int m) { return v & ~(m - 1); }
-
-struct Org {
-    int32_t x, y, z;
-    bool operator<(const Org& b) const { return x != b.x ? x < b.x : y != b.y ? y < b.y : z < b.z; }
-    bool operator==(const Org& b) const { return x == b.x && y == b.y && z == b.z; }
-};
-
-// the list rules of fluid_sdf_to_dense: arrays behind a non-empty list, origins on the 8-grid, inside the leaves of [lo,hi]^3,
-// strictly ascending in (x, y, z)
-int check_list(const fluid_sdf_grid_t* g)
-{
-    if (!g || g->n < 1 || g->n > 4096 || g->n_leaves < 0) return FLUID_ERR_ARG;
-    if (g->n_leaves > 0 && (!g->origin || !g->values || !g->active)) return FLUID_ERR_ARG;
-    const int lo = -(g->n / 2), hi = lo + g->n - 1, L0 = floor_to(lo, LEAF), L1 = floor_to(hi, LEAF);
-    for (int i = 0; i < g->n_leaves; ++i) {
-        const int32_t* o = g->origin + 3 * (size_t)i;
-        for (int a = 0; a < 3; ++a)
-            if ((o[a] & (LEAF - 1)) != 0 || o[a] < L0 || o[a] > L1) return FLUID_ERR_ARG;
-        if (i > 0 && !(Org{o[-3], o[-2], o[-1]} < Org{o[0], o[1], o[2]})) return FLUID_ERR_ARG;
-    }
-    return FLUID_OK;
-}
 
 struct Work {
     Org o;
@@ -56,32 +32,11 @@ struct Mesher {
     std::vector<Work> work;
     float V[9 * 9 * 9];
 
-    long listed(const Org& o) const   // index in the list, or -1
-    {
-        long a = 0, b = g->n_leaves;
-        while (a < b) {
-            const long m = (a + b) / 2;
-            const int32_t* p = g->origin + 3 * (size_t)m;
-            if (Org{p[0], p[1], p[2]} < o) a = m + 1;
-            else b = m;
-        }
-        if (a == g->n_leaves) return -1;
-        const int32_t* p = g->origin + 3 * (size_t)a;
-        return Org{p[0], p[1], p[2]} == o ? a : -1;
-    }
     // V[(lx * 9 + ly) * 9 + lz] = val(o + (lx, ly, lz)), 0 <= lx, ly, lz <= 8
     void load(const Org& o)
     {
         for (float& v : V) v = g->background;
-        for (int d = 0; d < 8; ++d) {
-            const int dx = d >> 2, dy = (d >> 1) & 1, dz = d & 1;
-            const long l = listed(Org{o.x + 8 * dx, o.y + 8 * dy, o.z + 8 * dz});
-            if (l < 0) continue;
-            const float* v = g->values + 512 * (size_t)l;
-            for (int x = 0; x < (dx ? 1 : 8); ++x)
-                for (int y = 0; y < (dy ? 1 : 8); ++y)
-                    for (int z = 0; z < (dz ? 1 : 8); ++z) V[((x + 8 * dx) * 9 + (y + 8 * dy)) * 9 + z + 8 * dz] = v[(x * 8 + y) * 8 + z];
-        }
+        load_tile(g, o, [&](long l, int off, int i) { V[i] = g->values[512 * (size_t)l + off]; });
     }
     // the cell with min corner p and the edges p owns: the corners' inside mask (bit dx*4 + dy*2 + dz)
     unsigned cell(const float* c, int px, int py, int pz, bool& mixed, unsigned& edges) const
@@ -189,17 +144,7 @@ int64_t fluid_sdf_mesh(const fluid_sdf_grid_t* g, int64_t cap_vertices, int64_t 
     Mesher me;
     me.g = g;
     me.lo = -(g->n / 2), me.hi = me.lo + g->n - 1;
-    const int L0 = floor_to(me.lo, LEAF);
-    me.work.reserve((size_t)g->n_leaves * 2);
-    for (int l = 0; l < g->n_leaves; ++l) {
-        const int32_t* o = g->origin + 3 * (size_t)l;
-        for (int d = 0; d < 8; ++d) {
-            const Org c{o[0] - 8 * (d >> 2), o[1] - 8 * ((d >> 1) & 1), o[2] - 8 * (d & 1)};
-            if (c.x >= L0 && c.y >= L0 && c.z >= L0) me.work.push_back(Work{c, {}, 0});
-        }
-    }
-    std::sort(me.work.begin(), me.work.end(), [](const Work& a, const Work& b) { return a.o < b.o; });
-    me.work.erase(std::unique(me.work.begin(), me.work.end(), [](const Work& a, const Work& b) { return a.o == b.o; }), me.work.end());
+    for (const Org& o : mesh_work_list(g)) me.work.push_back(Work{o, {}, 0});
     int64_t nv = 0, nq = 0;
     me.pass(nullptr, nullptr, nv, nq);
     if (nv > 0x7fffffffLL || nq > 0x7fffffffLL) return -FLUID_ERR_ARG;
@@ -216,37 +161,7 @@ int fluid_write_ply_mesh(const char* path, const fluid_mesh_t* m, float voxel_si
 {
     if (!path || !m || m->n_vertices < 0 || m->n_quads < 0 || !(voxel_size > 0.0f)) return FLUID_ERR_ARG;
     if ((m->n_vertices > 0 && !m->vertices) || (m->n_quads > 0 && !m->quads)) return FLUID_ERR_ARG;
-    for (int64_t i = 0; i < 4 * m->n_quads; ++i)
-        if ((int64_t)m->quads[i] >= m->n_vertices) return FLUID_ERR_ARG;
-    FILE* f = fopen(path, "wb");
-    if (!f) return FLUID_ERR_ARG;
-    bool ok = fprintf(f,
-                      "ply\nformat binary_little_endian 1.0\nelement vertex %lld\nproperty float x\nproperty float y\nproperty float z\n"
-                      "element face %lld\nproperty list uchar uint vertex_indices\nend_header\n",
-                      (long long)m->n_vertices, (long long)m->n_quads) > 0;
-    std::vector<char> buf;
-    buf.reserve((size_t)1 << 20);
-    auto flush = [&] {
-        if (!buf.empty() && fwrite(buf.data(), 1, buf.size(), f) != buf.size()) ok = false;
-        buf.clear();
-    };
-    for (int64_t i = 0; ok && i < 3 * m->n_vertices; ++i) {
-        const float v = m->vertices[i] * voxel_size;
-        const char* c = (const char*)&v;
-        buf.insert(buf.end(), c, c + 4);
-        if (buf.size() >= ((size_t)1 << 20) - 32) flush();
-    }
-    for (int64_t i = 0; ok && i < m->n_quads; ++i) {
-        buf.push_back((char)4);
-        const char* c = (const char*)(m->quads + 4 * i);
-        buf.insert(buf.end(), c, c + 16);
-        if (buf.size() >= ((size_t)1 << 20) - 32) flush();
-    }
-    flush();
-    const int frc = fclose(f);
-    if (ok && frc == 0) return FLUID_OK;
-    remove(path);   // a short write leaves no partial file behind
-    return FLUID_ERR_ARG;   // (the ABI has no code of its own for I/O: an unwritable path is a bad argument, as in the .vdb writers)
+    return write_ply(path, m, voxel_size, false, nullptr, 0.0f);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // The box filter and offset of the level set on the host (include/fluid_hip.h, "liquid surface, smoothed") — no GPU, no HIP, no
-// OpenVDB; stands alone.  fluid_sdf_filter applies the definition to a leaf list, every unlisted leaf and everything outside the grid
+// OpenVDB (the list's rules and the search in it: leaf_list.h).  fluid_sdf_filter applies the definition to a leaf list, every unlisted leaf and everything outside the grid
 // being +bg: how a decomposed run smooths its merged surface (after fluid_sdf_grids_merge, before fluid_write_vdb_sdf /
 // fluid_sdf_mesh), and the second implementation the kernels (kernels_sdf_filter.hip) are compared with.  Pass by pass, leaf by
 // leaf: the leaf's 8 x 8 x (8 + 2W) values along the pass's axis, the two neighbour leaves found by bisection in the sorted list;
@@ -10,48 +10,9 @@
 #include <cstring>
 #include <vector>
 
-#include "fluid_hip.h"
+#include "leaf_list.h"
 
 namespace {
-
-constexpr int LEAF = 8;
-inline int floor_to(int v, int m) { return v & ~(m - 1); }
-
-struct Org {
-    int32_t x, y, z;
-    bool operator<(const Org& b) const { return x != b.x ? x < b.x : y != b.y ? y < b.y : z < b.z; }
-    bool operator==(const Org& b) const { return x == b.x && y == b.y && z == b.z; }
-};
-
-// the list rules of fluid_sdf_to_dense: arrays behind a non-empty list, origins on the 8-grid, inside the leaves of [lo,hi]^3,
-// strictly ascending in (x, y, z)
-int check_list(const fluid_sdf_grid_t* g)
-{
-    if (!g || g->n < 1 || g->n > 4096 || g->n_leaves < 0) return FLUID_ERR_ARG;
-    if (g->n_leaves > 0 && (!g->origin || !g->values || !g->active)) return FLUID_ERR_ARG;
-    const int lo = -(g->n / 2), hi = lo + g->n - 1, L0 = floor_to(lo, LEAF), L1 = floor_to(hi, LEAF);
-    for (int i = 0; i < g->n_leaves; ++i) {
-        const int32_t* o = g->origin + 3 * (size_t)i;
-        for (int a = 0; a < 3; ++a)
-            if ((o[a] & (LEAF - 1)) != 0 || o[a] < L0 || o[a] > L1) return FLUID_ERR_ARG;
-        if (i > 0 && !(Org{o[-3], o[-2], o[-1]} < Org{o[0], o[1], o[2]})) return FLUID_ERR_ARG;
-    }
-    return FLUID_OK;
-}
-
-long listed(const fluid_sdf_grid_t* g, const Org& o)   // index in the list, or -1
-{
-    long a = 0, b = g->n_leaves;
-    while (a < b) {
-        const long m = (a + b) / 2;
-        const int32_t* p = g->origin + 3 * (size_t)m;
-        if (Org{p[0], p[1], p[2]} < o) a = m + 1;
-        else b = m;
-    }
-    if (a == g->n_leaves) return -1;
-    const int32_t* p = g->origin + 3 * (size_t)a;
-    return Org{p[0], p[1], p[2]} == o ? a : -1;
-}
 
 // one pass of width W along `axis`: src -> dst (512 per leaf, the list's order); `off` is added to the active voxels' results
 void box_pass(const fluid_sdf_grid_t* g, int axis, int W, float off, const float* src, float* dst)
@@ -66,7 +27,7 @@ void box_pass(const fluid_sdf_grid_t* g, int axis, int W, float off, const float
         Org om{o[0], o[1], o[2]}, op = om;
         (axis == 0 ? om.x : axis == 1 ? om.y : om.z) -= LEAF;
         (axis == 0 ? op.x : axis == 1 ? op.y : op.z) += LEAF;
-        const long lm = listed(g, om), lp = listed(g, op);
+        const long lm = find_leaf(g, om), lp = find_leaf(g, op);
         const float* v = src + 512 * (size_t)l;
         const float* vm = lm >= 0 ? src + 512 * (size_t)lm : nullptr;
         const float* vp = lp >= 0 ? src + 512 * (size_t)lp : nullptr;

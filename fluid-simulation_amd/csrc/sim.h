@@ -18,6 +18,7 @@ int fluid_fail(int code, const std::string& msg);   // sets fluid_last_error() o
         if (e_ != hipSuccess)                                                                                     \
             return fluid_fail(FLUID_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_) + " @" + std::to_string(__LINE__)); \
     } while (0)
+#include "snap_ring.h"   // the two-slot hand-off of the snapshots (uses HIPCHK)
 
 using namespace fl;
 
@@ -219,6 +220,22 @@ inline hipError_t dalloc(T** p, size_t n)
     if (e == hipSuccess) e = hipMemset(*p, 0, n * sizeof(T));
     return e;
 }
+// scratch that is sized again: the old array goes first (hipFree waits for the device, so whoever still reads it has ended)
+template <typename T>
+inline hipError_t regrow(T*& p, size_t n)
+{
+    if (p) hipFree(p);
+    p = nullptr;
+    return hipMalloc((void**)&p, n * sizeof(T));
+}
+inline int grid_leaves(const Grid& g) { return ((g.hi & ~7) - (g.lo & ~7)) / 8 + 1; }   // OpenVDB's 8^3 leaves that meet [lo, hi], per axis
+// entry of a snapshot call that works on one GPU only: `why` says what a decomposed handle lacks and what to call instead
+inline int snap_guard(const fluid_sim* s, const char* why)
+{
+    if (!s) return fluid_fail(FLUID_ERR_ARG, "null handle");
+    return s->dist ? fluid_fail(FLUID_ERR_STATE, why) : FLUID_OK;
+}
+constexpr const char* ATTR_SINGLE = "surface attributes are single-GPU only: the merge of the blocks' lists sees values, and equal values do not imply equal squared distances";
 inline size_t solver_elem(const fluid_sim* s) { return s->prm.precision == FLUID_PRECISION_FP32 ? 4 : 8; }
 inline bool use_mg(const fluid_sim* s) { return s->prm.preconditioner == FLUID_PRECOND_MG && s->prm.precision == FLUID_PRECISION_FP64; }
 

@@ -1,6 +1,6 @@
 // .vdb writer for the liquid surface (include/fluid_hip.h, "liquid surface") and the dense form of its leaf list — host only, no
-// GPU, no OpenVDB.  Stands alone: it shares no code with vdb_writer.cpp, whose constants describe a tree with every leaf of
-// [lo,hi]^3 present and background 0.
+// GPU, no OpenVDB.  It shares no code with vdb_writer.cpp, whose constants describe a tree with every leaf of [lo,hi]^3 present and
+// background 0; the rules of a leaf list (check_list) are leaf_list.h's.
 //
 // One FloatGrid named "surface", class "level set", in OpenVDB's file format 224 (the serialisation vdb_writer.cpp restates:
 // io/Archive.cc:939-971,1243-1328, tree/RootNode.h:2257-2288, tree/InternalNode.h:2175-2195, tree/LeafNode.h:1321-1324,1444-1453,
@@ -30,7 +30,7 @@
 #include <string>
 #include <vector>
 
-#include "fluid_hip.h"
+#include "leaf_list.h"
 
 namespace {
 
@@ -79,8 +79,7 @@ struct Out {
     }
 };
 
-constexpr int LEAF = 8, INT1 = 128, INT2 = 4096;
-inline int floor_to(int v, int m) { return v & ~(m - 1); }
+constexpr int INT1 = 128, INT2 = 4096;
 
 template <typename T> void meta(Out& o, const char* name, const char* type, const T* v, uint32_t bytes)
 {
@@ -89,26 +88,6 @@ template <typename T> void meta(Out& o, const char* name, const char* type, cons
 
 inline bool bit(const uint64_t* m, int off) { return (m[off >> 6] >> (off & 63)) & 1; }
 inline bool same_bits(float a, float b) { return memcmp(&a, &b, 4) == 0; }
-
-// FLUID_OK, or FLUID_ERR_ARG: no arrays behind a non-empty list, an origin off the 8-grid, outside the leaves of [lo,hi]^3, or
-// not strictly ascending in (x, y, z)
-int check_list(const fluid_sdf_grid_t* g)
-{
-    if (!g || g->n < 1 || g->n > 4096 || g->n_leaves < 0) return FLUID_ERR_ARG;
-    if (g->n_leaves > 0 && (!g->origin || !g->values || !g->active)) return FLUID_ERR_ARG;
-    const int lo = -(g->n / 2), hi = lo + g->n - 1, L0 = floor_to(lo, LEAF), L1 = floor_to(hi, LEAF);
-    for (int i = 0; i < g->n_leaves; ++i) {
-        const int32_t* o = g->origin + 3 * (size_t)i;
-        for (int a = 0; a < 3; ++a)
-            if ((o[a] & (LEAF - 1)) != 0 || o[a] < L0 || o[a] > L1) return FLUID_ERR_ARG;
-        if (i > 0) {
-            const int32_t* p = o - 3;
-            const bool after = o[0] != p[0] ? o[0] > p[0] : o[1] != p[1] ? o[1] > p[1] : o[2] > p[2];
-            if (!after) return FLUID_ERR_ARG;
-        }
-    }
-    return FLUID_OK;
-}
 
 // the per-node metadata byte of a leaf, or -1: an inactive value that is neither +bg nor -bg
 int leaf_code(const float* v, const uint64_t* m, float bg)
