@@ -390,12 +390,34 @@ void launch_extrap_init(hipStream_t st, Grid g, const uint8_t* solid, const floa
 void launch_extrap_layer(hipStream_t st, Grid g, int pass, int* layer, double* u, double* v, double* w, int* n_new);
 void launch_resample(hipStream_t st, Grid g, long n, Particles p, const int* cell_start, int per_cell, int xlim, double far_, int* n_parked);
 
-// particle sources and sinks (kernels_sources.hip)
+// particle sources and sinks (kernels_sources.hip): the same kernels on one GPU and on a rank of a decomposed run
 struct SinkSet { int n; Box box[8]; };
-void launch_src_count(hipStream_t st, Grid g, long n, Particles p, Box box, int* hist);
-void launch_src_plan(hipStream_t st, Grid g, Box box, uint64_t h0, int per_cell, bool fill, const uint8_t* solid, const int* hist, int* cnt);
-void launch_src_emit(hipStream_t st, Grid g, Box box, uint64_t h0, int per_cell, bool fill, const uint8_t* solid, const int* hist, const int* off,
-                     Particles p, uint32_t pid0, const double vel[3]);
+// SplitMix64 (include/fluid_hip.h, "Where a source puts its points")
+__host__ __device__ inline uint64_t sm64(uint64_t x)
+{
+    uint64_t z = x + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+// owned block in GLOBAL cell indices [lo, hi) and whether a neighbour block exists on each side ([0, N), none: one GPU)
+struct OwnBox {
+    int lo[3], hi[3];
+    int has_lo[3], has_hi[3];
+};
+// the solid bytes over a source box: a dense z-fastest array that covers it, the byte of GLOBAL index cell (ix, iy, iz) at
+// p[(ix - o[0]) * sx + (iy - o[1]) * sy + (iz - o[2])]
+struct SolidView {
+    const uint8_t* p;
+    int o[3];
+    long sx, sy;
+};
+void launch_src_count(hipStream_t st, Grid g, long n, Particles p, Box box, int* hist, bool skip_dead);
+// cnt_own == nullptr and off_own == off: the handle owns every cell of the box
+void launch_src_plan(hipStream_t st, Grid g, Box box, uint64_t h0, int per_cell, bool fill, OwnBox ob, SolidView sv, const int* hist, int* cnt,
+                     int* cnt_own);
+void launch_src_emit(hipStream_t st, Grid g, Box box, uint64_t h0, int per_cell, bool fill, OwnBox ob, SolidView sv, const int* hist, const int* off,
+                     const int* off_own, Particles p, uint32_t id0, const double vel[3]);
 void launch_src_append(hipStream_t st, long n, const double* pos, const double* vel, Particles p, uint32_t pid0);
 void launch_interp_from_grid(hipStream_t st, Grid g, long n, Particles p, const double* u, const double* v, const double* w);
 void launch_sink_mark(hipStream_t st, Grid g, long n, Particles p, const SinkSet& sk, int* keep_dev, int* keep_pid, int* removed);

@@ -21,12 +21,6 @@ struct HaloArgs {
 };
 void launch_halo_copy(hipStream_t st, const HaloArgs& a, int elem, void* stage, bool pack);
 
-// owned block in GLOBAL cell indices [lo, hi) and whether a neighbour block exists on each side
-struct OwnBox {
-    int lo[3], hi[3];
-    int has_lo[3], has_hi[3];
-};
-
 void launch_flags_box(hipStream_t st, Grid g, Box box, const uint8_t* solid, const float* container, uint8_t* flags);
 void launch_row_counts(hipStream_t st, Grid g, Box own, int rx0, int ry0, int RY, int nseg, int seg, const uint8_t* flags, int* rows);
 void launch_row_number(hipStream_t st, Grid g, Box own, int rx0, int ry0, int RY, int nseg, int seg, const uint8_t* flags, const int* starts,
@@ -41,12 +35,7 @@ void launch_mask_outside(hipStream_t st, MLevel m, Box own, T* a);
 void launch_mg_type_local(hipStream_t st, Grid g, MLevel m, int w0, int w1, int w2, const uint8_t* flags, const uint8_t* cnt, uint8_t* typ);
 void launch_copy_vel_before(hipStream_t st, Grid g, Box box, const double* u, const double* v, const double* w, double* ub, double* vb, double* wb);
 void launch_split_flags(hipStream_t st, const uint8_t* act, const uint8_t* cls, int n, uint8_t* fi, uint8_t* fb);
-// particle sources and sinks of a decomposed run (kernels_sources.hip, beside the one-GPU forms)
-void launch_src_count_live(hipStream_t st, Grid g, long n, Particles p, Box box, int* hist);
-void launch_src_plan_win(hipStream_t st, Grid g, Box box, uint64_t h0, int per_cell, bool fill, OwnBox ob, const uint8_t* mask, const int* hist, int* cnt,
-                         int* cnt_own);
-void launch_src_emit_win(hipStream_t st, Grid g, Box box, uint64_t h0, int per_cell, bool fill, OwnBox ob, const uint8_t* mask, const int* hist,
-                         const int* off, const int* off_own, Particles p, uint32_t id0, const double vel[3]);
+// what a decomposed run adds to the particle sources and sinks (kernels_sources.hip)
 void launch_sink_kill(hipStream_t st, Grid g, long n, Particles p, const SinkSet& sk, unsigned long long* removed);
 void launch_centre_avg(hipStream_t st, Grid g, Box box, const double* u, const double* v, const double* w, double* cu, double* cv, double* cw);
 void launch_interp_from_centres(hipStream_t st, Grid g, long n, Particles p, const double* cu, const double* cv, const double* cw);

@@ -139,17 +139,7 @@ struct DistState {
     std::vector<int> h_tl;            // host copy behind the (stream-ordered) upload
     uint8_t* tl_cls = nullptr;        // per level-0 leg tile: 1 = reads a received cell (the class the two lists above are cut by)
     std::vector<uint8_t> h_cls;
-    // particle sources and sinks (fluid_dist_set_source / fluid_dist_set_sink; dist_sources_apply).  Boxes are global index boxes,
-    // a slot's buffer is box-sized and holds nothing that depends on the window: re-balancing hands it on as it is.
-    struct SrcSlot {
-        bool on = false, mask_ok = false;
-        fluid_source_t src{};
-        Box box{};
-        int* buf = nullptr;   // box cells x 5 ints: FILL histogram | kept per cell | its scan | kept per owned cell | its scan; then the global solid mask of the box (bytes)
-    };
-    SrcSlot src[FLUID_MAX_SOURCES];
-    Box sink[FLUID_MAX_SINKS] = {};
-    bool sink_on[FLUID_MAX_SINKS] = {};
+    // particle sources and sinks (dist_sources_apply): the slots and the sink boxes are the handle's (sim.h), the ids are a block run's
     long long max_id = -1;            // largest id this handle was ever handed (fluid_upload_particles_ids, fluid_dist_add_particles)
     long long next_id = 0;            // id of the next emitted point as last agreed (MAX over the ranks in every step where a source is due)
     long long *src_d = nullptr, *src_h = nullptr;   // device / pinned: [0] removed by the sinks (SUM), [1] next_id (MAX)
@@ -1385,17 +1375,9 @@ int dist_step_decomposed(fluid_sim* s, fluid_step_stats_t* stats)
 }
 
 // ---- particle sources and sinks (include/fluid_hip.h, "particle sources and sinks of a decomposed run") ---------------------------
-uint64_t sm64_host(uint64_t x)
-{
-    uint64_t z = x + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-// The global solid array over a slot's box, behind the slot's five int arrays: a window holds only a part of the box, and every
+// The global solid array over a slot's box, behind the slot's int arrays: a window holds only a part of the box, and every
 // rank counts the kept points of ALL its cells (the ids follow from that count alone, with no exchange).
-int src_mask_upload(fluid_sim* s, DistState::SrcSlot& q)
+int src_mask_upload(fluid_sim* s, fluid_sim::SrcSlot& q)
 {
     DistState* d = s->ds;
     const Box b = q.box;
@@ -1409,7 +1391,7 @@ int src_mask_upload(fluid_sim* s, DistState::SrcSlot& q)
                 m[l] = d->solid_global.empty() ? outsideW : d->solid_global[((size_t)x * N + y) * N + z] != 0;
             }
     HIPCHK(hipStreamSynchronize(s->st));
-    HIPCHK(hipMemcpy(q.buf + 5 * (size_t)b.cells(), m.data(), m.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(source_buf(s, q).mask, m.data(), m.size(), hipMemcpyHostToDevice));
     q.mask_ok = true;
     return FLUID_OK;
 }
@@ -1443,11 +1425,9 @@ int dist_sources_apply(fluid_sim* s, bool* changed)
     const long t = s->n_steps;
     *changed = false;
     s->src_emit_last = s->src_rm_last = 0;
-    SinkSet sk{};
-    for (int i = 0; i < FLUID_MAX_SINKS; ++i)
-        if (d->sink_on[i]) sk.box[sk.n++] = d->sink[i];
+    const SinkSet sk = sinks_on(s);
     bool due = false;
-    for (const auto& q : d->src) due = due || (q.on && t % q.src.every == 0);
+    for (const auto& q : s->src) due = due || (q.on && t % q.src.every == 0);
     if (sk.n == 0 && !due) return FLUID_OK;
     int rc;
     // the sinks' global count (SUM) and the agreed id of the next new point (MAX): one read-back for both
@@ -1465,51 +1445,33 @@ int dist_sources_apply(fluid_sim* s, bool* changed)
     const long removed = (long)d->src_h[0];
     if (due) d->next_id = d->src_h[1];
     long emitted = 0;
-    for (auto& q : d->src) {
+    for (auto& q : s->src) {
         if (!q.on || t % q.src.every != 0) continue;
-        const fluid_source_t& c = q.src;
         const Box b = q.box;
-        const long B = b.cells();
-        int *hist = q.buf, *cnt = q.buf + B, *off = q.buf + 2 * B, *cnt_own = q.buf + 3 * B, *off_own = q.buf + 4 * B;
-        const uint8_t* mask = (const uint8_t*)(q.buf + 5 * B);
-        const bool fill = c.mode == FLUID_SOURCE_FILL;
-        const uint64_t h0 = sm64_host(sm64_host(c.seed) ^ (uint64_t)t);
         if (!q.mask_ok && (rc = dist_agree(s, src_mask_upload(s, q)))) return rc;   // (fluid_set_solid after the slot was set: every rank alike)
-        if (fill) {   // live particles per cell after the sinks, over all their holders
-            HIPCHK(hipMemsetAsync(hist, 0, B * sizeof(int), s->st));
-            launch_src_count_live(s->st, g, s->np, s->pa.shifted(s->p_off), b, hist);
-            HIPCHK(hipGetLastError());
-            if ((rc = comm_allreduce(s, hist, B, FLUID_DT_I32, FLUID_OP_SUM))) return rc;
-        }
-        launch_src_plan_win(s->st, g, b, h0, c.per_cell, fill, d->ob, mask, hist, cnt, cnt_own);
-        launch_exclusive_scan(s->st, cnt, off, B, s->src_sums, s->d_small + 1);
-        launch_exclusive_scan(s->st, cnt_own, off_own, B, s->src_sums, s->d_small + 2);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(s->h_small + 1, s->d_small + 1, 2 * sizeof(int), hipMemcpyDeviceToHost, s->st));
-        HIPCHK(hipStreamSynchronize(s->st));
-        const long m = s->h_small[1], mo = s->h_small[2];   // all ranks' new points (the same number everywhere) / this rank's
+        const SrcDue u = source_due(s, q, t, d->ob);   // (a rank that owns the whole box runs one scan: a rank-local launch shape)
+        if ((rc = source_count(s, u))) return rc;
+        // live particles per cell after the sinks, over all their holders
+        if (u.fill && (rc = comm_allreduce(s, u.a.hist, b.cells(), FLUID_DT_I32, FLUID_OP_SUM))) return rc;
+        long m = 0, mo = 0;   // all ranks' new points (the same number everywhere) / this rank's
+        if ((rc = source_plan(s, u, &m, &mo))) return rc;
         if (m == 0) continue;
         if (d->next_id + m >= (long long)PID_DEAD) return fail(FLUID_ERR_STATE, "a source would take the particle ids up to 0xFFFFFFFF, the mark of a dead particle");
         // room for this rank's share: the one allocation here that can fail on ONE rank, agreed before the next transport call
         auto grow = [&]() -> int {
-            if (s->np + mo > (long)INT32_MAX) return fail(FLUID_ERR_STATE, "a source would take the particle count past INT32_MAX");
-            const long need = s->p_off + s->np + mo;
-            if (need > s->cap && d->fail_grow_rank == d->comm.rank)   // (tests: a rank that cannot grow)
+            if (s->p_off + s->np + mo > s->cap && d->fail_grow_rank == d->comm.rank)   // (tests: a rank that cannot grow)
                 return fail(FLUID_ERR_HIP, "particle arrays for emitted points: allocation refused (FLUID_DIST_FAIL_GROW)");
-            return grow_particles(s, need);
+            return source_room(s, mo);
         };
         if ((rc = dist_agree(s, grow()))) return rc;
         const Particles p = s->pa.shifted(s->p_off + s->np);
-        const double zero[3] = {0, 0, 0};
-        if (mo > 0)
-            launch_src_emit_win(s->st, g, b, h0, c.per_cell, fill, d->ob, mask, hist, off, off_own, p, (uint32_t)d->next_id,
-                                c.vel_mode == FLUID_SOURCE_VEL_FIXED ? c.vel : zero);
+        if (mo > 0) source_emit(s, u, p, (uint32_t)d->next_id);
         HIPCHK(hipGetLastError());
-        const IBox bi{{b.x0, b.y0, b.z0}, {b.x1 + 1, b.y1 + 1, b.z1 + 1}};
-        if (c.vel_mode == FLUID_SOURCE_VEL_GRID) {
+        if (q.src.vel_mode == FLUID_SOURCE_VEL_GRID) {
             if (d->repl) {
                 launch_interp_from_grid(s->st, g, mo, p, s->u, s->v, s->w);   // full-size arrays: the one-GPU kernel as it is
             } else {
+                const IBox bi{{b.x0, b.y0, b.z0}, {b.x1 + 1, b.y1 + 1, b.z1 + 1}};
                 if ((rc = centre_halo(s, ib_grow(bi, 1)))) return rc;
                 launch_interp_from_centres(s->st, g, mo, p, s->dcx, s->dcy, s->dcz);
             }
@@ -1518,19 +1480,9 @@ int dist_sources_apply(fluid_sim* s, bool* changed)
         s->np += mo;
         d->next_id += m;
         emitted += m;
-        {   // the next sort's x-plane guess (Pb +- 3) covers the new points of this rank and those that arrive as ghosts
-            const int org[3] = {g.ox, g.oy, g.oz};
-            const IBox win{{g.ox, g.oy, g.oz}, {g.ox + g.nx, g.oy + g.ny, g.oz + g.nz}};
-            const Box w = to_box(ib_isect(bi, win), org);
-            Box& P = s->Pb;
-            if (!box_empty(w))
-                P = box_empty(P) ? w
-                                 : Box{std::min(P.x0, w.x0), std::min(P.y0, w.y0), std::min(P.z0, w.z0), std::max(P.x1, w.x1), std::max(P.y1, w.y1),
-                                       std::max(P.z1, w.z1)};
-        }
+        source_widen_Pb(s, b);   // the new points of this rank and those that arrive as ghosts
     }
-    s->src_emit_last = emitted, s->src_rm_last = removed;
-    s->src_emit_total += emitted, s->src_rm_total += removed;
+    sources_tally(s, emitted, removed);
     *changed = emitted || removed;
     return FLUID_OK;
 }
@@ -1726,17 +1678,11 @@ int dist_rebalance(fluid_sim* s)
     DistState* nd = t->ds;
     nd->rb_every = d->rb_every; nd->rb_ratio = d->rb_ratio; nd->n_rebalanced = d->n_rebalanced + 1; nd->n_routed = d->n_routed;
     nd->solid_global.swap(d->solid_global);
-    // sources and sinks: the slots (their buffers are box-sized, global: nothing in them belongs to the old window), the ids and
-    // the four counters; n_steps, the t of the sources, goes with output_move
-    for (int i = 0; i < FLUID_MAX_SOURCES; ++i) std::swap(nd->src[i], d->src[i]);
-    for (int i = 0; i < FLUID_MAX_SINKS; ++i) { nd->sink[i] = d->sink[i]; nd->sink_on[i] = d->sink_on[i]; }
+    sources_move(s, t);     // sources and sinks; here the ids of a block run and the two agreed numbers
     nd->max_id = std::max(nd->max_id, d->max_id);
     nd->next_id = d->next_id;
     std::swap(nd->src_d, d->src_d);
     std::swap(nd->src_h, d->src_h);
-    std::swap(t->src_sums, s->src_sums);
-    t->src_emit_last = s->src_emit_last, t->src_rm_last = s->src_rm_last;
-    t->src_emit_total = s->src_emit_total, t->src_rm_total = s->src_rm_total;
     t->dt = s->dt;
     t->step_counter = s->step_counter;
     t->stats = s->stats;
@@ -1786,7 +1732,7 @@ void fl::dist_keep_solid(fluid_sim* s, const uint8_t* solid_global)
 {
     if (!s->ds) return;
     s->ds->solid_global.assign(solid_global, solid_global + (size_t)s->g.N * s->g.N * s->g.N);
-    for (auto& q : s->ds->src) q.mask_ok = false;   // the sources' copies of the mask are made anew when next due
+    for (auto& q : s->src) q.mask_ok = false;   // the sources' copies of the mask are made anew when next due
 }
 
 void fl::dist_destroy(fluid_sim* s)
@@ -1795,7 +1741,6 @@ void fl::dist_destroy(fluid_sim* s)
     if (!d) return;
     void* ptrs[] = {d->hs, d->hr, d->mig_s, d->mig_r, d->d_cnt, d->repl_buf, d->rows, d->row_starts, d->cnt_pcg, d->gstage[0], d->gstage[1], d->gpq, d->gcg, d->tl_int, d->tl_bnd, d->tl_cls, d->rb_buf};
     for (void* p : ptrs) if (p) hipFree(p);
-    for (auto& q : d->src) if (q.buf) hipFree(q.buf);
     if (d->src_d) hipFree(d->src_d);
     if (d->src_h) hipHostFree(d->src_h);
     if (d->st2) { hipStreamSynchronize(d->st2); hipStreamDestroy(d->st2); }
@@ -2079,25 +2024,13 @@ int fluid_dist_get_cuts(fluid_sim_t* s, int32_t* cuts_x, int32_t* cuts_y, int32_
     return FLUID_OK;
 }
 
-// ---- particle sources and sinks of a decomposed run ----
-#define DSRC_GUARD(s)                                                    \
-    if (!(s)) return fail(FLUID_ERR_ARG, "null handle");                 \
-    if (!(s)->ds)                                                        \
-    return fail(FLUID_ERR_STATE, "not a decomposed handle: a fluid_create handle uses the one-GPU entry points (fluid_set_source, fluid_set_sink, fluid_get_source_stats, fluid_add_particles)")
-
-static bool dsrc_box(const fluid_sim* s, const int32_t lo[3], const int32_t hi[3], Box& b)
+// ---- particle sources and sinks of a decomposed run: the bodies of the one-GPU entry points (fluid_sources.hip) behind the other
+// guard, plus what the collective step needs: the two agreed numbers and the box's solid bytes ----
+static int dsrc_enter(fluid_sim* s)
 {
-    const int N = s->g.N;
-    for (int a = 0; a < 3; ++a)
-        if (lo[a] < 0 || hi[a] > N - 1 || lo[a] > hi[a]) return false;
-    b = Box{lo[0], lo[1], lo[2], hi[0], hi[1], hi[2]};
-    return true;
-}
-// what the first slot needs: the scans' block sums (any count up to INT32_MAX) and the two agreed numbers
-static int dsrc_scratch(fluid_sim* s)
-{
+    if (int rc = snap_guard(s, SRC_DIST, true)) return rc;
     DistState* d = s->ds;
-    if (!s->src_sums) HIPCHK(hipMalloc((void**)&s->src_sums, ((size_t)INT32_MAX / 2048 + 16) * sizeof(int)));
+    HIPCHK(hipSetDevice(s->prm.device));
     if (!d->src_d) HIPCHK(hipMalloc((void**)&d->src_d, 8 * sizeof(long long)));
     if (!d->src_h) HIPCHK(hipHostMalloc((void**)&d->src_h, 8 * sizeof(long long)));
     return FLUID_OK;
@@ -2105,72 +2038,27 @@ static int dsrc_scratch(fluid_sim* s)
 
 int fluid_dist_set_source(fluid_sim_t* s, int32_t slot, const fluid_source_t* src)
 {
-    DSRC_GUARD(s);
-    if (slot < 0 || slot >= FLUID_MAX_SOURCES) return fail(FLUID_ERR_ARG, "source slot out of range");
-    auto& q = s->ds->src[slot];
-    HIPCHK(hipSetDevice(s->prm.device));
-    if (!src) {
-        HIPCHK(hipStreamSynchronize(s->st));
-        if (q.buf) hipFree(q.buf);
-        q = DistState::SrcSlot{};
-        return FLUID_OK;
-    }
-    Box b;
-    if (!dsrc_box(s, src->lo, src->hi, b)) return fail(FLUID_ERR_ARG, "source box empty or off the grid");
-    if (src->per_cell < 1 || src->per_cell > 64) return fail(FLUID_ERR_ARG, "per_cell must be in 1..64");
-    if (src->mode != FLUID_SOURCE_ADD && src->mode != FLUID_SOURCE_FILL) return fail(FLUID_ERR_ARG, "bad source mode");
-    if (src->vel_mode != FLUID_SOURCE_VEL_FIXED && src->vel_mode != FLUID_SOURCE_VEL_GRID) return fail(FLUID_ERR_ARG, "bad source vel_mode");
-    if (src->every < 1) return fail(FLUID_ERR_ARG, "every must be >= 1");
-    if ((double)b.cells() * src->per_cell > (double)INT32_MAX) return fail(FLUID_ERR_ARG, "source box x per_cell exceeds INT32_MAX points");
-    int rc = dsrc_scratch(s);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(s->st));
-    if (q.buf) hipFree(q.buf);
-    q = DistState::SrcSlot{};
-    const size_t B = (size_t)b.cells();
-    HIPCHK(hipMalloc((void**)&q.buf, 5 * B * sizeof(int) + B + 16));
-    q.src = *src;
-    q.box = b;
-    if ((rc = src_mask_upload(s, q))) {
-        hipFree(q.buf);
-        q = DistState::SrcSlot{};
-        return rc;
-    }
-    q.on = true;
-    return FLUID_OK;
+    int rc = dsrc_enter(s);
+    if (rc || (rc = source_set(s, slot, src)) || !src) return rc;
+    if ((rc = src_mask_upload(s, s->src[slot]))) source_set(s, slot, nullptr);
+    return rc;
 }
 
 int fluid_dist_set_sink(fluid_sim_t* s, int32_t slot, const int32_t lo[3], const int32_t hi[3])
 {
-    DSRC_GUARD(s);
-    if (slot < 0 || slot >= FLUID_MAX_SINKS) return fail(FLUID_ERR_ARG, "sink slot out of range");
-    if (!lo) {
-        s->ds->sink_on[slot] = false;
-        return FLUID_OK;
-    }
-    Box b;
-    if (!hi || !dsrc_box(s, lo, hi, b)) return fail(FLUID_ERR_ARG, "sink box empty or off the grid");
-    HIPCHK(hipSetDevice(s->prm.device));
-    int rc = dsrc_scratch(s);
-    if (rc) return rc;
-    s->ds->sink[slot] = b;
-    s->ds->sink_on[slot] = true;
-    return FLUID_OK;
+    if (int rc = dsrc_enter(s)) return rc;
+    return sink_set(s, slot, lo, hi);
 }
 
 int fluid_dist_get_source_stats(fluid_sim_t* s, int64_t* emitted_last, int64_t* removed_last, int64_t* emitted_total, int64_t* removed_total)
 {
-    DSRC_GUARD(s);
-    if (emitted_last) *emitted_last = s->src_emit_last;
-    if (removed_last) *removed_last = s->src_rm_last;
-    if (emitted_total) *emitted_total = s->src_emit_total;
-    if (removed_total) *removed_total = s->src_rm_total;
-    return FLUID_OK;
+    if (int rc = snap_guard(s, SRC_DIST, true)) return rc;
+    return source_stats(s, emitted_last, removed_last, emitted_total, removed_total);
 }
 
 int fluid_dist_add_particles(fluid_sim_t* s, int64_t n, const double* pos, const double* vel, const uint32_t* ids)
 {
-    DSRC_GUARD(s);
+    if (int rc = snap_guard(s, SRC_DIST, true)) return rc;
     DistState* d = s->ds;
     if (n < 0 || (n > 0 && (!pos || !ids))) return fail(FLUID_ERR_ARG, "bad particle arguments");
     if (!vel && !s->vel_ok) return fail(FLUID_ERR_STATE, "add_particles with vel == NULL needs the grid velocities of a completed step on this window");

@@ -187,12 +187,14 @@ struct fluid_sim {
     long p_off = 0;              // my live particles are pa[p_off .. p_off+np)
     int* d_small = nullptr;      // device scratch ints
     int* h_small = nullptr;      // pinned mirror
-    // particle sources and sinks (fluid_sources.hip), applied at the end of fluid_step when any slot is set
+    // particle sources and sinks (fluid_sources.hip), applied at the end of fluid_step when any slot is set.  Boxes are global
+    // index boxes, a slot's buffer is box-sized and holds nothing that depends on the window: re-balancing hands it on as it is.
     struct SrcSlot {
         bool on = false;
+        bool mask_ok = false;   // decomposed: the buffer's solid bytes are those of the scene (fluid_set_solid clears it)
         fluid_source_t src{};
         Box box{};
-        int* buf = nullptr;   // box cells x 3 ints: FILL histogram | kept points per cell | their exclusive scan
+        int* buf = nullptr;     // carved by source_buf
     };
     SrcSlot src[FLUID_MAX_SOURCES];
     Box sink[FLUID_MAX_SINKS] = {};
@@ -229,11 +231,12 @@ inline hipError_t regrow(T*& p, size_t n)
     return hipMalloc((void**)&p, n * sizeof(T));
 }
 inline int grid_leaves(const Grid& g) { return ((g.hi & ~7) - (g.lo & ~7)) / 8 + 1; }   // OpenVDB's 8^3 leaves that meet [lo, hi], per axis
-// entry of a snapshot call that works on one GPU only: `why` says what a decomposed handle lacks and what to call instead
-inline int snap_guard(const fluid_sim* s, const char* why)
+// entry of a call that works on one kind of handle only (one GPU, or with want_dist a decomposed one): `why` says what the
+// other kind lacks and what to call instead
+inline int snap_guard(const fluid_sim* s, const char* why, bool want_dist = false)
 {
     if (!s) return fluid_fail(FLUID_ERR_ARG, "null handle");
-    return s->dist ? fluid_fail(FLUID_ERR_STATE, why) : FLUID_OK;
+    return s->dist != want_dist ? fluid_fail(FLUID_ERR_STATE, why) : FLUID_OK;
 }
 constexpr const char* ATTR_SINGLE = "surface attributes are single-GPU only: the merge of the blocks' lists sees values, and equal values do not imply equal squared distances";
 inline size_t solver_elem(const fluid_sim* s) { return s->prm.precision == FLUID_PRECISION_FP32 ? 4 : 8; }
@@ -256,9 +259,38 @@ int phase_pressure_pass(fluid_sim* s, double* error);
 int pic_fields(fluid_sim* s);
 int fluid_create_window(const fluid_params_t* p, const Grid& g, fluid_sim_t** out);   // fluid_create on a window of the grid
 
-// fluid_sources.hip
+// fluid_sources.hip: one GPU's step, and what it shares with dist_sources_apply and the fluid_dist_set_* entry points
 int sources_apply(fluid_sim* s);     // end of fluid_step: the sinks, then the sources in slot order (no launch when none is set)
 void sources_free(fluid_sim* s);
+void sources_move(fluid_sim* from, fluid_sim* to);   // re-balance: slots, sinks, scan scratch and counters go to the new window's handle
+extern const char* const SRC_SINGLE;   // snap_guard texts of the one-GPU / the decomposed entry points
+extern const char* const SRC_DIST;
+int source_set(fluid_sim* s, int32_t slot, const fluid_source_t* src);   // bodies of the entry points, behind the guards
+int sink_set(fluid_sim* s, int32_t slot, const int32_t lo[3], const int32_t hi[3]);
+int source_stats(const fluid_sim* s, int64_t* emitted_last, int64_t* removed_last, int64_t* emitted_total, int64_t* removed_total);
+// a slot's buffer: FILL histogram | kept per cell | its scan | kept per owned cell | its scan | the box's solid bytes.  One GPU
+// holds the first three only (cnt_own == nullptr, off_own == off, mask == nullptr)
+struct SrcBuf {
+    int *hist, *cnt, *off, *cnt_own, *off_own;
+    uint8_t* mask;
+};
+SrcBuf source_buf(const fluid_sim* s, const fluid_sim::SrcSlot& q);
+struct SrcDue {   // a due slot at step t: what its launches take
+    const fluid_sim::SrcSlot* q;
+    SrcBuf a;       // cnt_own == nullptr, off_own == off also where a rank owns the whole box
+    uint64_t h0;    // sm(sm(seed) ^ t)
+    bool fill;
+    OwnBox ob;
+    SolidView sv;
+};
+SinkSet sinks_on(const fluid_sim* s);
+SrcDue source_due(const fluid_sim* s, const fluid_sim::SrcSlot& q, long t, const OwnBox& ob);
+int source_count(fluid_sim* s, const SrcDue& u);                     // FILL: the histogram of this handle's live particles (enqueued)
+int source_plan(fluid_sim* s, const SrcDue& u, long* m, long* mo);   // plan, scan(s), read-back: the box's new points / this handle's
+int source_room(fluid_sim* s, long mo);
+void source_emit(fluid_sim* s, const SrcDue& u, Particles p, uint32_t id0);
+void source_widen_Pb(fluid_sim* s, const Box& b);
+void sources_tally(fluid_sim* s, long emitted, long removed);
 
 // fluid_output.hip
 void output_free(fluid_sim* s);      // waits for the copies in flight, frees the staging and pinned buffers

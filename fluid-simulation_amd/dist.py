@@ -15,8 +15,8 @@ import threading
 
 import numpy as np
 
-from ._lib import lib, check, Params, StepStats, LeafGridC, Source, SdfParams, SdfGridC
-from .sim import FluidSim, grid_bounds, merge_leaf_grids, _leaf_grid_copy, merge_sdf_grids, _sdf_grid_copy  # noqa: F401
+from ._lib import lib, check, Params, StepStats, LeafGridC, SdfParams, SdfGridC
+from .sim import FluidSim, source_methods, grid_bounds, merge_leaf_grids, _leaf_grid_copy, merge_sdf_grids, _sdf_grid_copy  # noqa: F401
 
 EXCHANGE_T = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                          C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p)
@@ -426,37 +426,8 @@ class DistFluidSim(FluidSim):
         check(lib.fluid_dist_sdf_stats(self._h, *[C.byref(x) for x in v]))
         return dict(zip(("leaves_in_grid", "leaves_listed", "bytes_to_host"), (x.value for x in v)))
 
-    # ---- particle sources and sinks (include/fluid_hip.h, "of a decomposed run"): FluidSim's signatures, global boxes; the set
-    # calls are collective (the same slots on every rank before the same step), ids are never renumbered ----
-    def set_source(self, slot, lo, hi, per_cell, mode="add", every=1, vel=None, seed=0):
-        src = Source()
-        src.lo[:] = [int(x) for x in lo]
-        src.hi[:] = [int(x) for x in hi]
-        src.per_cell = int(per_cell)
-        src.mode = {"add": 0, "fill": 1}[mode]
-        src.every = int(every)
-        src.vel_mode = 1 if vel is None else 0
-        if vel is not None:
-            src.vel[:] = [float(x) for x in vel]
-        src.seed = int(seed)
-        check(lib.fluid_dist_set_source(self._h, int(slot), C.byref(src)))
-
-    def clear_source(self, slot):
-        check(lib.fluid_dist_set_source(self._h, int(slot), None))
-
-    def set_sink(self, slot, lo, hi):
-        l3 = (C.c_int32 * 3)(*[int(x) for x in lo])
-        h3 = (C.c_int32 * 3)(*[int(x) for x in hi])
-        check(lib.fluid_dist_set_sink(self._h, int(slot), l3, h3))
-
-    def clear_sink(self, slot):
-        check(lib.fluid_dist_set_sink(self._h, int(slot), None, None))
-
-    def source_stats(self):
-        """Global numbers, the same on every rank."""
-        v = [C.c_int64() for _ in range(4)]
-        check(lib.fluid_dist_get_source_stats(self._h, *[C.byref(x) for x in v]))
-        return dict(zip(("emitted_last", "removed_last", "emitted_total", "removed_total"), (x.value for x in v)))
+    # ---- particle sources and sinks (include/fluid_hip.h, "of a decomposed run"): FluidSim's methods over the fluid_dist_ entry points ----
+    set_source, clear_source, set_sink, clear_sink, source_stats = source_methods("fluid_dist_")
 
     def add_particles(self, pos, vel=None, ids=None):
         """Append this rank's points (base cells in its block) with the caller's global ids.  vel=None: interpFromGrid's velocity

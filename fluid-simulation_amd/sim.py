@@ -330,6 +330,49 @@ def reference_scatter(lo=-20, hi=20, points_per_volume=10.0, seed=0, boundary=60
     return pos
 
 
+def source_methods(prefix):
+    """set_source, clear_source, set_sink, clear_sink and source_stats of a handle ``self._h`` over the entry points of its kind
+    (include/fluid_hip.h): "fluid_" on one GPU, "fluid_dist_" on a decomposed handle, where the boxes are global, the set calls
+    collective (the same slots on every rank before the same step) and ids are never renumbered.  Each class binds its own."""
+    c_set_source, c_set_sink, c_stats = (getattr(lib, prefix + f) for f in ("set_source", "set_sink", "get_source_stats"))
+
+    def set_source(self, slot, lo, hi, per_cell, mode="add", every=1, vel=None, seed=0):
+        """A persistent source over the inclusive index box [lo, hi]: mode "add" puts per_cell new points in every eligible
+        cell, "fill" tops every eligible cell up to per_cell; at the end of step t iff t % every == 0.  vel=None: the
+        velocity is interpolated from the grid; else the fixed (x, y, z)."""
+        src = Source()
+        src.lo[:] = [int(x) for x in lo]
+        src.hi[:] = [int(x) for x in hi]
+        src.per_cell = int(per_cell)
+        src.mode = {"add": 0, "fill": 1}[mode]
+        src.every = int(every)
+        src.vel_mode = 1 if vel is None else 0
+        if vel is not None:
+            src.vel[:] = [float(x) for x in vel]
+        src.seed = int(seed)
+        check(c_set_source(self._h, int(slot), C.byref(src)))
+
+    def clear_source(self, slot):
+        check(c_set_source(self._h, int(slot), None))
+
+    def set_sink(self, slot, lo, hi):
+        """Remove, at the end of every step, the particles whose base cell round(p) lies in the inclusive index box [lo, hi]."""
+        l3 = (C.c_int32 * 3)(*[int(x) for x in lo])
+        h3 = (C.c_int32 * 3)(*[int(x) for x in hi])
+        check(c_set_sink(self._h, int(slot), l3, h3))
+
+    def clear_sink(self, slot):
+        check(c_set_sink(self._h, int(slot), None, None))
+
+    def source_stats(self):
+        """(On a decomposed handle: global numbers, the same on every rank.)"""
+        v = [C.c_int64() for _ in range(4)]
+        check(c_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("emitted_last", "removed_last", "emitted_total", "removed_total"), (x.value for x in v)))
+
+    return set_source, clear_source, set_sink, clear_sink, source_stats
+
+
 class FluidSim:
     """One simulation on one MI355X.  Mirrors what main() owns in the reference:
     grids + PointList + dt, and one ``step()`` = one iteration of fluid.cc:1378-1490."""
@@ -431,38 +474,7 @@ class FluidSim:
             v = vel.ctypes.data_as(C.c_void_p)
         check(lib.fluid_add_particles(self._h, pos.shape[0], pos.ctypes.data_as(C.c_void_p), v))
 
-    def set_source(self, slot, lo, hi, per_cell, mode="add", every=1, vel=None, seed=0):
-        """A persistent source over the inclusive index box [lo, hi]: mode "add" puts per_cell new points in every eligible
-        cell, "fill" tops every eligible cell up to per_cell; at the end of step t iff t % every == 0.  vel=None: the
-        velocity is interpolated from the grid; else the fixed (x, y, z)."""
-        src = Source()
-        src.lo[:] = [int(x) for x in lo]
-        src.hi[:] = [int(x) for x in hi]
-        src.per_cell = int(per_cell)
-        src.mode = {"add": 0, "fill": 1}[mode]
-        src.every = int(every)
-        src.vel_mode = 1 if vel is None else 0
-        if vel is not None:
-            src.vel[:] = [float(x) for x in vel]
-        src.seed = int(seed)
-        check(lib.fluid_set_source(self._h, int(slot), C.byref(src)))
-
-    def clear_source(self, slot):
-        check(lib.fluid_set_source(self._h, int(slot), None))
-
-    def set_sink(self, slot, lo, hi):
-        """Remove, at the end of every step, the particles whose base cell round(p) lies in the inclusive index box [lo, hi]."""
-        l3 = (C.c_int32 * 3)(*[int(x) for x in lo])
-        h3 = (C.c_int32 * 3)(*[int(x) for x in hi])
-        check(lib.fluid_set_sink(self._h, int(slot), l3, h3))
-
-    def clear_sink(self, slot):
-        check(lib.fluid_set_sink(self._h, int(slot), None, None))
-
-    def source_stats(self):
-        v = [C.c_int64() for _ in range(4)]
-        check(lib.fluid_get_source_stats(self._h, *[C.byref(x) for x in v]))
-        return dict(zip(("emitted_last", "removed_last", "emitted_total", "removed_total"), (x.value for x in v)))
+    set_source, clear_source, set_sink, clear_sink, source_stats = source_methods("fluid_")
 
     # ---- step + phases -----------------------------------------------------------------
     def step(self):

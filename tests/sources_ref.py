@@ -47,6 +47,20 @@ def c_round(x):
     return np.where(np.abs(x - t) >= 0.5, t + np.copysign(1.0, x), t)
 
 
+def default_solid(n):
+    """The solid array of a handle that fluid_set_solid was never called on: the two outer layers."""
+    s = np.zeros((n, n, n), dtype=np.uint8)
+    s[:2] = s[-2:] = 1
+    s[:, :2] = s[:, -2:] = 1
+    s[:, :, :2] = s[:, :, -2:] = 1
+    return s
+
+
+def base_cells(n, pos):
+    """Index of the base cell round(p) of every row of pos."""
+    return c_round(pos).astype(np.int64) + n // 2
+
+
 def eligible_cells(n, lo, hi, solid):
     """The eligible cells of the inclusive index box [lo, hi] in ascending linear order: (linear, index (m, 3))."""
     ix, iy, iz = np.meshgrid(*[np.arange(lo[a], hi[a] + 1) for a in range(3)], indexing="ij")

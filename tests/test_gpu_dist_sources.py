@@ -11,23 +11,12 @@ import pytest
 
 import sources_ref as sr
 from conftest import rel_l2
+from sources_ref import base_cells, default_solid
 
 pytestmark = pytest.mark.gpu
 
 P_SOURCES = 512
 MODES = ["decomposed", "replicated"]
-
-
-def default_solid(n):
-    s = np.zeros((n, n, n), dtype=np.uint8)
-    s[:2] = s[-2:] = 1
-    s[:, :2] = s[:, -2:] = 1
-    s[:, :, :2] = s[:, :, -2:] = 1
-    return s
-
-
-def base_cells(n, pos):
-    return sr.c_round(pos).astype(np.int64) + n // 2
 
 
 def in_box(bc, lo, hi, grow=0):
@@ -129,6 +118,38 @@ def test_add_across_the_cuts(fs, mode, n, dims, cuts, lo, hi, solid_fn):
         assert r["stats"]["emitted_last"] == m and r["stats"]["emitted_total"] == m and r["stats"]["removed_last"] == 0
         assert r["paths"] & P_SOURCES
     assert emitting == len(res)                                                 # the box lies across the cuts: every rank emits
+    ids, p, v = merged(res)
+    assert np.array_equal(ids[:np0], np.arange(np0))
+    assert np.array_equal(ids[np0:], np0 + np.arange(m))
+    assert np.array_equal(p[np0:], want)                                        # bit for bit
+    assert np.array_equal(v[np0:], np.tile(np.asarray(vel), (m, 1)))
+
+
+# ---- 1b. a box wholly inside one rank's block ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("lo,hi", [((4, 8, 10), (9, 12, 14)), ((6, 9, 11), (6, 9, 11))])
+def test_add_inside_one_block(fs, mode, lo, hi):
+    """The owner of the whole box places and numbers its points with one scan; the other rank plans the same box, owns none of
+    its cells and emits nothing.  Both report the global count."""
+    n, dims = 32, (2, 1, 1)
+    cuts = cuts_at(n, dims, 20)                                                 # the box lies in x < 20: rank 0's
+    pos = fs.water_cube_drop(n, 3, seed=0)
+    np0, seed, vel = len(pos), 11, (0.25, -1.5, 0.125)
+
+    def body(sim, r):
+        sim.set_source(0, lo, hi, 5, mode="add", every=1, vel=vel, seed=seed)
+        st = sim.step()
+        return dict(local(sim), stats=sim.source_stats(), paths=st["paths"])
+
+    res, _ = run_blocks(fs, dims, n, cuts, mode, pos, None, body)
+    want = sr.source_points(n, seed, 0, lo, hi, 5, default_solid(n))
+    m = len(want)
+    assert m > 0
+    for r in res:
+        assert r["stats"]["emitted_last"] == m and r["stats"]["emitted_total"] == m and r["stats"]["removed_last"] == 0
+        assert r["paths"] & P_SOURCES
+        assert r["owns"][r["ids"] >= np0].all()
+    assert (res[0]["ids"] >= np0).sum() == m and not (res[1]["ids"] >= np0).any()   # exactly one rank emits
     ids, p, v = merged(res)
     assert np.array_equal(ids[:np0], np.arange(np0))
     assert np.array_equal(ids[np0:], np0 + np.arange(m))

@@ -12,23 +12,12 @@ import pytest
 import pressure_system as ps
 import sources_ref as sr
 from conftest import rel_l2
+from sources_ref import base_cells, default_solid
 
 pytestmark = pytest.mark.gpu
 
 TOL_F = 1e-4      # the parity tolerance of tests/test_gpu_parity.py
 P_SOURCES = 512
-
-
-def default_solid(n):
-    s = np.zeros((n, n, n), dtype=np.uint8)
-    s[:2] = s[-2:] = 1
-    s[:, :2] = s[:, -2:] = 1
-    s[:, :, :2] = s[:, :, -2:] = 1
-    return s
-
-
-def base_cells(n, pos):
-    return sr.c_round(pos).astype(np.int64) + n // 2
 
 
 def test_append_matches_the_oracle_on_the_union(fs, oracle):
@@ -210,6 +199,71 @@ def test_add_source_grid_velocity_over_many_scan_chunks(fs):
     want_v = sr.clamped_catmull_rom(n, vel, want)
     assert np.abs(want_v).max() > 0
     assert np.array_equal(v[n0:], want_v), np.abs(v[n0:] - want_v).max()
+
+
+def test_fill_source_every_branch_of_the_plan(fs):
+    """One FILL source with grid velocities whose box reaches outside W on two sides (x = 0, 1 and y = 1), holds two user solid
+    cells and meets the water, with extents 11 x 10 x 11 (no stride of the grid or of a block divides them), at t = 2: the solid
+    bytes come through the strided view, the histogram, the W test and the gather all take part."""
+    n, pc, seed = 24, 3, 7
+    lo, hi = (0, 1, 3), (10, 10, 13)                  # the cube covers the indices 8..15
+    solid = default_solid(n)
+    solid[4, 5, 6] = solid[3, 2, 12] = 1
+    pos = fs.water_cube_drop(n, 4, seed=0)
+    sim = fs.FluidSim(n=n)
+    sim.set_solid(solid)
+    sim.upload_particles(pos)
+    sim.step(); sim.step()
+    sim.set_source(0, lo, hi, pc, mode="fill", seed=seed)    # vel from the grid
+    sim.step()                                        # t = 2
+    vel = sim.field(fs.FIELD.VEL)
+    ss = sim.source_stats()
+    p, v = sim.download_particles()
+    n0 = len(pos)
+    hist = sr.base_cell_counts(n, lo, hi, p[:n0])
+    assert hist.max() >= pc and hist.min() == 0
+    want = sr.source_points(n, seed, 2, lo, hi, pc, solid, hist)
+    assert 0 < len(want) < len(sr.source_points(n, seed, 2, lo, hi, pc, default_solid(n)))   # the solid cells and the water took their share
+    assert ss["emitted_last"] == len(want) == len(p) - n0
+    assert np.array_equal(p[n0:], want)
+    c = base_cells(n, p[n0:])
+    assert (c >= 2).all() and not solid[c[:, 0], c[:, 1], c[:, 2]].any()
+    want_v = sr.clamped_catmull_rom(n, vel, want)
+    assert np.abs(want_v).max() > 0
+    assert np.array_equal(v[n0:], want_v), np.abs(v[n0:] - want_v).max()
+
+
+def test_one_gpu_and_one_block_bit_for_bit(fs):
+    """The same three steps with an ADD source (grid velocities) and a FILL source (fixed velocity), no sink (sinks renumber on
+    one GPU only), on a one-GPU handle and on a (1, 1, 1) decomposed handle: sorted by id, the same bytes.
+    (tests/test_gpu_dist_sources.py::test_whole_run_against_one_gpu[(32, (1, 1, 1))] has a sink and compares to a tolerance.)"""
+    fd = fs.load_dist()
+    n, steps = 32, 3
+    pos = fs.water_cube_drop(n, 4, seed=0)            # the cube covers the indices 11..21
+    slots = [(0, dict(lo=(14, 23, 14), hi=(18, 24, 18), per_cell=2, mode="add", every=2, vel=None, seed=21)),          # above the cube
+             (3, dict(lo=(14, 20, 14), hi=(18, 21, 18), per_cell=6, mode="fill", every=1, vel=(0.0, -2.0, 0.5), seed=22))]  # its top
+    one = fs.FluidSim(n=n)
+    one.upload_particles(pos)
+    grp = fd.LocalGroup(1)
+    blk = fd.DistFluidSim(n, (1, 1, 1), fd.uniform_cuts(n, (1, 1, 1)), grp.comms[0])
+    blk.upload_global(pos)
+    try:
+        for sim in (one, blk):
+            for slot, kw in slots:
+                sim.set_source(slot, **kw)
+        for t in range(steps):
+            one.step(); blk.step()
+            assert one.source_stats() == blk.source_stats(), t
+        ss = one.source_stats()
+        assert ss["emitted_total"] > ss["emitted_last"] > 0
+        p1, v1 = one.download_particles()             # pids are 0..np-1 in this order: no sink, nothing renumbered
+        p2, v2, ids = blk.download_local()
+        o = np.argsort(ids, kind="stable")
+        assert np.array_equal(ids[o], np.arange(len(p1)))
+        assert p2[o].tobytes() == p1.tobytes(), np.abs(p2[o] - p1).max()
+        assert v2[o].tobytes() == v1.tobytes(), np.abs(v2[o] - v1).max()
+    finally:
+        one.close(); blk.close(); grp.close()
 
 
 def test_sink(fs):
