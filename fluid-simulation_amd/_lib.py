@@ -79,6 +79,11 @@ class SdfAttrC(C.Structure):
     _fields_ = [("n_leaves", C.c_int32), ("id", C.c_void_p), ("velocity", C.c_void_p)]
 
 
+class SdfAttrPartC(C.Structure):
+    """fluid_sdf_attr_part_t: a rank's record of ids, velocities and squared distances ("liquid surface, attributes (decomposed runs)")."""
+    _fields_ = [("n_leaves", C.c_int32), ("id", C.c_void_p), ("velocity", C.c_void_p), ("dist2", C.c_void_p)]
+
+
 class MeshAttrC(C.Structure):
     """fluid_mesh_attr_t: a velocity per mesh vertex."""
     _fields_ = [("n_vertices", C.c_int64), ("velocity", C.c_void_p)]
@@ -203,6 +208,9 @@ SYMBOLS = [
     ("fluid_sdf_mesh_attr", C.c_int64, [C.POINTER(SdfGridC), C.POINTER(SdfAttrC), C.c_int64, _P]),
     ("fluid_sdf_attr_to_dense", C.c_int, [C.POINTER(SdfGridC), C.POINTER(SdfAttrC), _P, _P]),
     ("fluid_write_ply_mesh_attr", C.c_int, [C.c_char_p, C.POINTER(MeshC), C.POINTER(MeshAttrC), C.c_float, C.c_float]),
+    ("fluid_dist_sdf_snapshot_attr", C.c_int, [_P, C.POINTER(SdfParams)]),
+    ("fluid_dist_sdf_wait_attr", C.c_int, [_P, C.POINTER(SdfGridC), C.POINTER(SdfAttrPartC)]),
+    ("fluid_sdf_attr_grids_merge", C.c_int64, [C.POINTER(SdfGridC), C.POINTER(SdfAttrPartC), C.c_int32, C.c_int64, _P, _P, _P, _P, _P]),
     # the snow-MPM step (include/mpm_hip.h)
     ("mpm_default_params", C.c_int, [C.POINTER(MpmParams)]),
     ("mpm_create", C.c_int, [C.POINTER(MpmParams), C.POINTER(_P)]),

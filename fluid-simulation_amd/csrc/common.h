@@ -349,9 +349,11 @@ void launch_sdf_pack(hipStream_t st, const SdfGeom& g, const int* flags, const i
 // per leaf of the range) and narrowed velocity (tvel: [leaf][axis][512]) for the active voxels; the pack that also lists them; the emit
 // that also writes a velocity per vertex.  p: the live arrays ssrc indexes (pid, vx, vy, vz are read)
 void launch_sdf_search_attr(hipStream_t st, const SdfGeom& g, const int* start, const double* sx, const double* sy, const double* sz, float* tv,
-                            uint64_t* tm, int* flags, const int* ssrc, Particles p, uint32_t* tid, float* tvel);
+                            uint64_t* tm, int* flags, const int* ssrc, Particles p, uint32_t* tid, float* tvel,
+                            float* tmin = nullptr);   // tmin: nullptr, or 512 per leaf of the range: m of the active voxels, +inf elsewhere
 void launch_sdf_pack_attr(hipStream_t st, const SdfGeom& g, const int* flags, const int* slot, const float* tv, const uint64_t* tm, float* values,
-                          uint64_t* active, int* origin, const uint32_t* tid, const float* tvel, uint32_t* ids, float* vel);
+                          uint64_t* active, int* origin, const uint32_t* tid, const float* tvel, uint32_t* ids, float* vel,
+                          const float* tmin = nullptr, float* dist2 = nullptr);   // tmin / dist2: nullptr, or the squared distances as well
 void launch_mesh_emit_attr(hipStream_t st, const SdfGeom& g, const float* tv, const int* flags, const uint64_t* tm, const float* tvel,
                            const uint64_t* cmask, const int* cpre, const int* vcnt, const int* qcnt, const int* vbase, const int* qbase,
                            float* vertices, uint32_t* quads, float* vvel);

@@ -46,11 +46,20 @@
 // waits for it, the main thread merges the blocks' lists (fluid_sdf_grids_merge, two merge buffers in turn) and hands the grid to
 // the writer thread beside the density job.  Refused without FLUID_BLOCKS, malformed, with an empty FLUID_OUT and with
 // FLUID_STEPS=0, before any handle is created.  Stdout and every other file are what they are without it.
-//   FLUID_OUT_SMOOTH=W,K[,OFFSET] (unset: off) — what FLUID_OUT_SURFACE, FLUID_OUT_MESH and FLUID_BLOCKS_SURFACE write is the level set
+//   FLUID_BLOCKS_MESH=R,W (unset: off; with FLUID_BLOCKS only) — additionally simulation/mesh<i>.ply per step, the file FLUID_OUT_MESH
+// writes on one GPU: the blocks' level-set lists are merged as for FLUID_BLOCKS_SURFACE (with both set R,W must be the same numbers
+// and one snapshot per step serves both), and the writer thread meshes the merged list (fluid_sdf_mesh) and writes it
+// (fluid_write_ply_mesh, voxel size dx) beside the density job.  Refused without FLUID_BLOCKS, malformed, with other numbers than
+// FLUID_BLOCKS_SURFACE, with an empty FLUID_OUT and with FLUID_STEPS=0, before any handle is created.
+//   FLUID_BLOCKS_MESH_VEL=SCALE (unset: off; with FLUID_BLOCKS_MESH only) — mesh<i>.ply carries vx / vy / vz per vertex times SCALE: every
+// block takes fluid_dist_sdf_snapshot_attr, the main thread merges the rank records (fluid_sdf_attr_grids_merge: include/fluid_hip.h,
+// "liquid surface, attributes (decomposed runs)"), the writer thread adds fluid_sdf_mesh_attr and writes fluid_write_ply_mesh_attr.
+// Refused without FLUID_BLOCKS_MESH or malformed.  Stdout and every other file are what they are without the two.
+//   FLUID_OUT_SMOOTH=W,K[,OFFSET] (unset: off) — what FLUID_OUT_SURFACE, FLUID_OUT_MESH, FLUID_BLOCKS_SURFACE and FLUID_BLOCKS_MESH write is the level set
 // after K box filters of width W voxels and the offset (include/fluid_hip.h, "liquid surface, smoothed"): on one GPU the snapshots
 // are fluid_sdf_snapshot_filtered / fluid_mesh_snapshot_filtered; a block run filters the merged list on the main thread
 // (fluid_sdf_filter, two buffers in turn) before it goes to the writer thread.  Refused malformed, outside the filter's limits, or
-// with none of the three set, before any handle is created.  Without it stdout and every file are what they were.
+// with none of the four set, before any handle is created.  Without it stdout and every file are what they were.
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -97,6 +106,10 @@ struct LeafWriter {
     bool has_majob = false;
     float vel_scale = 1.0f;
     float voxel = 1.0f;
+    fluid_sdf_grid_t bjob{};     // FLUID_BLOCKS_MESH: the merged level set this thread meshes
+    bool has_bjob = false;
+    fluid_sdf_attr_t bajob{};    // FLUID_BLOCKS_MESH_VEL: its merged attributes
+    bool has_bajob = false;
     int job_step = -1;        // step whose grid is waiting (-1: none)
     int done = 0;             // grids written
     bool quit = false;
@@ -104,9 +117,26 @@ struct LeafWriter {
     std::thread th;
     void start() { th = std::thread([this] { run(); }); }
     ~LeafWriter() { stop(); }   // (an early return of main: the grid in hand is still written)
+    // FLUID_BLOCKS_MESH: the surface nets of the merged list, with vertex velocities when `at` is given, into `fm`
+    bool mesh_blocks(const std::string& fm, const fluid_sdf_grid_t& g, const fluid_sdf_attr_t* at, std::vector<float>& v, std::vector<uint32_t>& q,
+                     std::vector<float>& w)
+    {
+        int64_t nq = 0;
+        const int64_t nv = fluid_sdf_mesh(&g, 0, 0, nullptr, nullptr, &nq);
+        if (nv < 0) return false;
+        v.resize(3 * (size_t)nv + 3), q.resize(4 * (size_t)nq + 4);
+        if (nv && fluid_sdf_mesh(&g, nv, nq, v.data(), q.data(), &nq) != nv) return false;
+        const fluid_mesh_t mg{g.n, nv, nq, g.radius, g.half_width, g.background, nv ? v.data() : nullptr, nq ? q.data() : nullptr};
+        if (!at) return fluid_write_ply_mesh(fm.c_str(), &mg, voxel) == FLUID_OK;
+        w.resize(3 * (size_t)nv + 3);
+        if (nv && fluid_sdf_mesh_attr(&g, at, nv, w.data()) != nv) return false;
+        const fluid_mesh_attr_t ma{nv, nv ? w.data() : nullptr};
+        return fluid_write_ply_mesh_attr(fm.c_str(), &mg, &ma, voxel, vel_scale) == FLUID_OK;
+    }
     void run()
     {
-        std::vector<float> dense;
+        std::vector<float> dense, bv, bw;
+        std::vector<uint32_t> bq;
         for (;;) {
             std::unique_lock<std::mutex> lk(m);
             cv.wait(lk, [&] { return job_step >= 0 || quit; });
@@ -118,6 +148,10 @@ struct LeafWriter {
             const bool has_mg = has_mjob;
             const fluid_mesh_attr_t ma = majob;
             const bool has_ma = has_majob;
+            const fluid_sdf_grid_t bg = bjob;
+            const bool has_bg = has_bjob;
+            const fluid_sdf_attr_t ba = bajob;
+            const bool has_ba = has_bajob;
             const int i = job_step;
             lk.unlock();
             std::string bad;
@@ -136,6 +170,10 @@ struct LeafWriter {
             if (has_mg && bad.empty()) {
                 const std::string fm = outdir + "/mesh" + std::to_string(i) + ".ply";
                 if ((has_ma ? fluid_write_ply_mesh_attr(fm.c_str(), &mg, &ma, voxel, vel_scale) : fluid_write_ply_mesh(fm.c_str(), &mg, voxel)) != FLUID_OK) bad = fm;
+            }
+            if (has_bg && bad.empty()) {
+                const std::string fm = outdir + "/mesh" + std::to_string(i) + ".ply";
+                if (!mesh_blocks(fm, bg, has_ba ? &ba : nullptr, bv, bq, bw)) bad = fm;
             }
             if (raw_f32 && bad.empty()) {
                 const size_t ncell = (size_t)g.n * g.n * g.n;
@@ -158,7 +196,7 @@ struct LeafWriter {
         return error.empty();
     }
     void submit(int step, const fluid_leaf_grid_t& g, const fluid_sdf_grid_t* surface = nullptr, const fluid_mesh_t* mesh = nullptr,
-                const fluid_mesh_attr_t* mesh_attr = nullptr)
+                const fluid_mesh_attr_t* mesh_attr = nullptr, const fluid_sdf_grid_t* to_mesh = nullptr, const fluid_sdf_attr_t* to_mesh_attr = nullptr)
     {
         std::unique_lock<std::mutex> lk(m);
         cv.wait(lk, [&] { return job_step < 0; });
@@ -169,6 +207,10 @@ struct LeafWriter {
         if (mesh) mjob = *mesh;
         has_majob = mesh && mesh_attr;
         if (has_majob) majob = *mesh_attr;
+        has_bjob = to_mesh != nullptr;
+        if (to_mesh) bjob = *to_mesh;
+        has_bajob = to_mesh && to_mesh_attr;
+        if (has_bajob) bajob = *to_mesh_attr;
         job_step = step;
         cv.notify_all();
     }
@@ -195,6 +237,9 @@ struct BlockCfg {
     fluid_sdf_params_t sp{};
     bool smooth = false;      // FLUID_OUT_SMOOTH
     fluid_sdf_filter_t sf{};
+    bool mesh = false;        // FLUID_BLOCKS_MESH (its R,W are in sp: the same numbers as FLUID_BLOCKS_SURFACE's when both are set)
+    bool mesh_vel = false;    // FLUID_BLOCKS_MESH_VEL
+    double mesh_vel_scale = 1.0;
 };
 
 // What the main thread and the block threads share: `go` = steps released so far, done[i & 1] = blocks that finished step i.
@@ -252,8 +297,10 @@ static int run_blocks(const BlockCfg& cfg, const std::vector<double>& pos, int64
     }
     const bool output = !cfg.outdir.empty() && steps > 0;
     std::vector<fluid_leaf_grid_t> part[2] = {std::vector<fluid_leaf_grid_t>(R), std::vector<fluid_leaf_grid_t>(R)};
-    const bool surface = output && cfg.surface;
+    const bool surface = output && cfg.surface, mesh = output && cfg.mesh, attr = mesh && cfg.mesh_vel;
+    const bool level = surface || mesh;   // one level-set snapshot per block and step serves both
     std::vector<fluid_sdf_grid_t> spart[2] = {std::vector<fluid_sdf_grid_t>(R), std::vector<fluid_sdf_grid_t>(R)};
+    std::vector<fluid_sdf_attr_part_t> apart[2] = {std::vector<fluid_sdf_attr_part_t>(R), std::vector<fluid_sdf_attr_part_t>(R)};
     std::vector<fluid_step_stats_t> st0(2);   // rank 0's stats of step i in st0[i & 1]
     auto block = [&](int r) {
         fluid_sim_t* sim = nullptr;
@@ -285,8 +332,8 @@ static int run_blocks(const BlockCfg& cfg, const std::vector<double>& pos, int64
             // (the copy of this step's list is the only thing waited for here: the next step starts when the main thread says so)
             if (output && fluid_dist_output_wait(sim, &part[i & 1][r]) != FLUID_OK) { err("fluid_dist_output_wait"); break; }
             // the surface of this block's live particles as the step left them (exact whether or not the step moved the planes)
-            if (surface && fluid_dist_sdf_snapshot(sim, &cfg.sp) != FLUID_OK) { err("fluid_dist_sdf_snapshot"); break; }
-            if (surface && fluid_dist_sdf_wait(sim, &spart[i & 1][r]) != FLUID_OK) { err("fluid_dist_sdf_wait"); break; }
+            if (level && (attr ? fluid_dist_sdf_snapshot_attr(sim, &cfg.sp) : fluid_dist_sdf_snapshot(sim, &cfg.sp)) != FLUID_OK) { err("fluid_dist_sdf_snapshot"); break; }
+            if (level && (attr ? fluid_dist_sdf_wait_attr(sim, &spart[i & 1][r], &apart[i & 1][r]) : fluid_dist_sdf_wait(sim, &spart[i & 1][r])) != FLUID_OK) { err("fluid_dist_sdf_wait"); break; }
             {
                 std::lock_guard<std::mutex> lk(sy.m);
                 if (r == 0) st0[i & 1] = st;
@@ -332,6 +379,8 @@ static int run_blocks(const BlockCfg& cfg, const std::vector<double>& pos, int64
             return finish(1);
         }
         lw.outdir = cfg.outdir, lw.fin = fin, lw.all = all, lw.raw_f32 = cfg.raw_f32;
+        lw.voxel = (float)cfg.prm.dx;
+        lw.vel_scale = (float)cfg.mesh_vel_scale;
         lw.start();
     }
     // the merged grid of step i lives in buffer i & 1 until the writer thread has put grid i on disk
@@ -341,6 +390,8 @@ static int run_blocks(const BlockCfg& cfg, const std::vector<double>& pos, int64
     std::vector<float> s_val[2];
     std::vector<uint64_t> s_act[2];
     std::vector<float> s_smooth[2];   // FLUID_OUT_SMOOTH: the filtered values of the merged list
+    std::vector<uint32_t> s_id[2];    // FLUID_BLOCKS_MESH_VEL: the merged attributes
+    std::vector<float> s_vel[2];
     double dt = cfg.prm.max_dt, simulationTime = 0;
     auto release = [&](int upto) {
         {
@@ -379,15 +430,23 @@ static int run_blocks(const BlockCfg& cfg, const std::vector<double>& pos, int64
         if (org.size() < 3 * (size_t)k) { org.resize(3 * (size_t)k + 3 * 64); val.resize(512 * ((size_t)k + 64)); }
         if (fluid_leaf_grids_merge(part[i & 1].data(), R, k, org.data(), val.data()) != k) { sy.fail("fluid_leaf_grids_merge: the blocks' leaf lists do not merge"); break; }
         fluid_sdf_grid_t sg{};
-        if (surface) {
+        fluid_sdf_attr_t sat{};
+        if (level) {
             const auto& sp = spart[i & 1];
-            const int64_t ks = fluid_sdf_grids_merge(sp.data(), R, 0, nullptr, nullptr, nullptr);
+            const auto& ap = apart[i & 1];
+            const int64_t ks = attr ? fluid_sdf_attr_grids_merge(sp.data(), ap.data(), R, 0, nullptr, nullptr, nullptr, nullptr, nullptr)
+                                    : fluid_sdf_grids_merge(sp.data(), R, 0, nullptr, nullptr, nullptr);
             if (ks < 0) { sy.fail("fluid_sdf_grids_merge: the blocks' surface lists do not merge"); break; }
             auto& so = s_org[i & 1];
             auto& sv = s_val[i & 1];
             auto& sa = s_act[i & 1];
+            auto& si = s_id[i & 1];
+            auto& sw = s_vel[i & 1];
             if (so.size() < 3 * (size_t)ks) { so.resize(3 * ((size_t)ks + 64)); sv.resize(512 * ((size_t)ks + 64)); sa.resize(8 * ((size_t)ks + 64)); }
-            if (ks && fluid_sdf_grids_merge(sp.data(), R, ks, so.data(), sv.data(), sa.data()) != ks) { sy.fail("fluid_sdf_grids_merge: the blocks' surface lists do not merge"); break; }
+            if (attr && si.size() < 512 * (size_t)ks) { si.resize(512 * ((size_t)ks + 64)); sw.resize(1536 * ((size_t)ks + 64)); }
+            if (ks && (attr ? fluid_sdf_attr_grids_merge(sp.data(), ap.data(), R, ks, so.data(), sv.data(), sa.data(), si.data(), sw.data())
+                            : fluid_sdf_grids_merge(sp.data(), R, ks, so.data(), sv.data(), sa.data())) != ks) { sy.fail("fluid_sdf_grids_merge: the blocks' surface lists do not merge"); break; }
+            sat = fluid_sdf_attr_t{(int32_t)ks, attr && ks ? si.data() : nullptr, attr && ks ? sw.data() : nullptr};
             sg = fluid_sdf_grid_t{n, (int32_t)ks, sp[0].background, sp[0].radius, sp[0].half_width, ks ? so.data() : nullptr, ks ? sv.data() : nullptr,
                                   ks ? sa.data() : nullptr};
             if (cfg.smooth && ks) {
@@ -397,7 +456,8 @@ static int run_blocks(const BlockCfg& cfg, const std::vector<double>& pos, int64
                 sg.values = sm.data();
             }
         }
-        lw.submit(i, fluid_leaf_grid_t{n, (int32_t)k, k ? org.data() : nullptr, k ? val.data() : nullptr}, surface ? &sg : nullptr);
+        lw.submit(i, fluid_leaf_grid_t{n, (int32_t)k, k ? org.data() : nullptr, k ? val.data() : nullptr}, surface ? &sg : nullptr, nullptr, nullptr,
+                  mesh ? &sg : nullptr, attr ? &sat : nullptr);
     }
     bool ok = !sy.failed;
     if (output) {
@@ -496,6 +556,40 @@ int main(int, char**)
         }
         bc.surface = true;
     }
+    if (const char* bm = getenv("FLUID_BLOCKS_MESH"); bm && *bm) {
+        char tail = 0;
+        fluid_sdf_params_t bmp{};
+        if (sscanf(bm, "%lf,%lf%c", &bmp.radius, &bmp.half_width, &tail) != 2) {
+            std::cerr << "FLUID_BLOCKS_MESH must be R,W (sphere radius and band half width in voxels), e.g. 1.5,2.5" << std::endl;
+            return 1;
+        }
+        if (!(blocks && *blocks)) {
+            std::cerr << "FLUID_BLOCKS_MESH needs FLUID_BLOCKS=AxBxC (one GPU takes FLUID_OUT_MESH=R,W)" << std::endl;
+            return 1;
+        }
+        if (outdir.empty() || steps <= 0) {
+            std::cerr << "FLUID_BLOCKS_MESH needs an output directory and at least one step (FLUID_OUT is empty or FLUID_STEPS is 0)" << std::endl;
+            return 1;
+        }
+        if (bc.surface && (bmp.radius != bc.sp.radius || bmp.half_width != bc.sp.half_width)) {
+            std::cerr << "FLUID_BLOCKS_MESH and FLUID_BLOCKS_SURFACE must be the same R,W: one level-set snapshot per step serves both" << std::endl;
+            return 1;
+        }
+        bc.sp = bmp;
+        bc.mesh = true;
+    }
+    if (const char* bv = getenv("FLUID_BLOCKS_MESH_VEL"); bv && *bv) {
+        char tail = 0;
+        if (sscanf(bv, "%lf%c", &bc.mesh_vel_scale, &tail) != 1 || !std::isfinite(bc.mesh_vel_scale) || !std::isfinite((float)bc.mesh_vel_scale)) {
+            std::cerr << "FLUID_BLOCKS_MESH_VEL must be SCALE, a finite number the vertex velocities are multiplied by, e.g. 1" << std::endl;
+            return 1;
+        }
+        if (!bc.mesh) {
+            std::cerr << "FLUID_BLOCKS_MESH_VEL adds velocities to what FLUID_BLOCKS_MESH=R,W writes: it is not set" << std::endl;
+            return 1;
+        }
+        bc.mesh_vel = true;
+    }
     const char* smenv = getenv("FLUID_OUT_SMOOTH");
     const bool smooth = smenv && *smenv;
     fluid_sdf_filter_t sf{};
@@ -512,8 +606,8 @@ int main(int, char**)
             std::cerr << "FLUID_OUT_SMOOTH must be W,K[,OFFSET] (box width 1..4 voxels, iterations 0..16, a finite offset), e.g. 1,4,-0.5" << std::endl;
             return 1;
         }
-        if (!surface && !mesh && !bc.surface) {
-            std::cerr << "FLUID_OUT_SMOOTH smooths what FLUID_OUT_SURFACE, FLUID_OUT_MESH or FLUID_BLOCKS_SURFACE write: none of them is set" << std::endl;
+        if (!surface && !mesh && !bc.surface && !bc.mesh) {
+            std::cerr << "FLUID_OUT_SMOOTH smooths what FLUID_OUT_SURFACE, FLUID_OUT_MESH, FLUID_BLOCKS_SURFACE or FLUID_BLOCKS_MESH write: none of them is set" << std::endl;
             return 1;
         }
         bc.smooth = true, bc.sf = sf;

@@ -29,6 +29,12 @@
 // snapshot is one more kind of snapshot in the same ring: its record is [n x 2048 B of values | n x 2048 B of ids |
 // n x 6144 B of velocities | n x 64 B of masks | n x 12 B of origins] (the 16-byte copies of the pack stay aligned for every n).
 // Once a slot has held an attribute snapshot it keeps room for attributes (wide); a plain snapshot uses the front of it.
+//
+// fluid_dist_sdf_snapshot_attr ("liquid surface, attributes (decomposed runs)"): the attribute snapshot of the rank's live particles
+// whose search also writes the squared distance m per voxel (tmin) and whose record lists it: [values | ids | velocities |
+// n x 2048 B of dist2 | masks | origins].  The ids come through ssrc from the pid of the handle's current arrays (global ids on a
+// decomposed handle; a dead entry is never scattered, so never a winner).  tmin exists from the handle's first such snapshot on; a
+// slot keeps room for the longest record per leaf it has held (wide = 0, 1, 2).
 #include "sim.h"
 
 using namespace fl;
@@ -36,8 +42,8 @@ using namespace fl;
 
 constexpr size_t SDF_REC = FLUID_SDF_LEAF_BYTES;
 struct SdfMeta {               // per slot of the ring
-    bool wide = false;         // the slot is sized for leaves with attributes (it has held an attribute snapshot)
-    bool attr = false;         // the snapshot in the slot carries attributes
+    int wide = 0;              // the slot is sized for leaves of this kind (the longest it has held)
+    int attr = 0;              // the snapshot in the slot: 0 plain, 1 with attributes, 2 with attributes and dist2
     int n_leaves = 0;
     float bg = 0, R = 0, w = 0;
 };
@@ -56,6 +62,8 @@ struct SdfState {
     uint32_t* tid = nullptr;
     float* tvel = nullptr;
     bool attr = false;
+    float* tmin = nullptr;     // m per voxel (leaf_cap x 512): allocated once a snapshot with dist2 was asked for
+    bool dist2 = false;
     uint64_t* tm = nullptr;
     int *flags = nullptr, *slot = nullptr, *leaf_sums = nullptr;
     unsigned* visits = nullptr;   // FLUID_SDF_VISITS=1 only
@@ -85,7 +93,7 @@ void fl::sdf_free(fluid_sim* s)
     SdfState* o = s->sdf;
     if (!o) return;
     snap_free(o->ring);
-    for (void* p : {(void*)o->cnt, (void*)o->start, (void*)o->cell_sums, (void*)o->place, (void*)o->spos, (void*)o->tv, (void*)o->tv2, (void*)o->ssrc, (void*)o->tid, (void*)o->tvel, (void*)o->tm, (void*)o->flags,
+    for (void* p : {(void*)o->cnt, (void*)o->start, (void*)o->cell_sums, (void*)o->place, (void*)o->spos, (void*)o->tv, (void*)o->tv2, (void*)o->ssrc, (void*)o->tid, (void*)o->tvel, (void*)o->tmin, (void*)o->tm, (void*)o->flags,
                     (void*)o->slot, (void*)o->leaf_sums, (void*)o->visits, (void*)o->d_small})
         if (p) hipFree(p);
     if (o->h_small) hipHostFree(o->h_small);
@@ -94,8 +102,12 @@ void fl::sdf_free(fluid_sim* s)
 }
 
 // (the handle's stream is idle here: every caller has just waited for a read-back on it)
-static int sdf_scratch(SdfState* o, long cells, long parts, long leaves, bool filtered, bool attr)
+static int sdf_scratch(SdfState* o, long cells, long parts, long leaves, bool filtered, bool attr, bool dist2)
 {
+    if (dist2 && !o->dist2) {   // the first snapshot with dist2 of the handle: tmin beside whatever there is
+        o->dist2 = true;
+        if (o->leaf_cap > 0) HIPCHK(regrow(o->tmin, (size_t)o->leaf_cap * 512));
+    }
     if (attr && !o->attr) {   // the first attribute snapshot of the handle: ssrc, tid and tvel beside whatever there is
         o->attr = true;
         if (o->part_cap > 0) HIPCHK(regrow(o->ssrc, (size_t)o->part_cap));
@@ -133,6 +145,7 @@ static int sdf_scratch(SdfState* o, long cells, long parts, long leaves, bool fi
             HIPCHK(regrow(o->tid, (size_t)cap * 512));
             HIPCHK(regrow(o->tvel, (size_t)cap * 1536));
         }
+        if (o->dist2) HIPCHK(regrow(o->tmin, (size_t)cap * 512));
         HIPCHK(regrow(o->tm, (size_t)cap * 8));
         HIPCHK(regrow(o->flags, (size_t)cap));
         HIPCHK(regrow(o->slot, (size_t)cap));
@@ -172,8 +185,8 @@ int fl::sdf_begin(fluid_sim* s, const fluid_sdf_params_t* p, SdfFront* f, const 
     f->any = false;
     f->tv = nullptr, f->flags = nullptr;
     f->filt = filt, f->dilate = 4;
-    f->attr = false;
-    f->tm = nullptr, f->tid = nullptr, f->tvel = nullptr;
+    f->attr = false, f->dist2 = false;
+    f->tm = nullptr, f->tid = nullptr, f->tvel = nullptr, f->tmin = nullptr;
     return FLUID_OK;
 }
 
@@ -202,18 +215,19 @@ int fl::sdf_front(fluid_sim* s, SdfFront* f)
         }
         const long cells = g.cells(), leaves = g.leaves();
         if (cells + 1 > 0x7fffffffL || leaves > 0x7fffffffL) return fail(FLUID_ERR_ARG, "level set: the particles' box is too large");
-        if ((rc = sdf_scratch(o, cells + 1, s->np, leaves, f->filt != nullptr, f->attr))) return rc;
+        if ((rc = sdf_scratch(o, cells + 1, s->np, leaves, f->filt != nullptr, f->attr, f->dist2))) return rc;
         double *sx = o->spos, *sy = o->spos + o->part_cap, *sz = o->spos + 2 * o->part_cap;
         HIPCHK(hipMemsetAsync(o->cnt, 0, (size_t)(cells + 1) * sizeof(int), s->st));
         launch_sdf_count(s->st, s->np, live, g, o->cnt, o->place, s->dist);
         launch_exclusive_scan(s->st, o->cnt, o->start, cells + 1, o->cell_sums, o->d_small + 6);   // start[cells] = the counted particles
         launch_sdf_scatter(s->st, s->np, live, g, o->start, o->place, sx, sy, sz, f->attr ? o->ssrc : nullptr);
-        if (f->attr) launch_sdf_search_attr(s->st, g, o->start, sx, sy, sz, o->tv, o->tm, o->flags, o->ssrc, live, o->tid, o->tvel);
+        if (f->attr) launch_sdf_search_attr(s->st, g, o->start, sx, sy, sz, o->tv, o->tm, o->flags, o->ssrc, live, o->tid, o->tvel, f->dist2 ? o->tmin : nullptr);
         else launch_sdf_search(s->st, g, o->start, sx, sy, sz, o->tv, o->tm, o->flags, o->count_visits ? o->visits : nullptr);
         f->any = true;
         f->tv = o->tv, f->flags = o->flags;
         f->tm = o->tm;
         if (f->attr) f->tid = o->tid, f->tvel = o->tvel;
+        if (f->dist2) f->tmin = o->tmin;
         if (f->filt) {
             // iteration = x, z, y (the library's order); the offset rides on the last pass, or is a pass of its own without one
             static const int axes[3] = {0, 2, 1};
@@ -232,12 +246,18 @@ int fl::sdf_front(fluid_sim* s, SdfFront* f)
 }
 
 // front half -> scan of the flags -> pack -> copy
-static int sdf_capture(fluid_sim* s, const fluid_sdf_params_t* p, const fluid_sdf_filter_t* filt = nullptr, bool attr = false)
+static constexpr size_t sdf_rec(int kind)   // bytes per listed leaf of a record: plain, with attributes, with attributes and dist2
+{
+    return SDF_REC + (kind >= 1 ? (size_t)FLUID_SDF_ATTR_LEAF_BYTES : 0) + (kind >= 2 ? (size_t)2048 : 0);
+}
+static constexpr size_t sdf_between(int kind) { return sdf_rec(kind) - SDF_REC; }   // per leaf, between the values and the masks
+
+static int sdf_capture(fluid_sim* s, const fluid_sdf_params_t* p, const fluid_sdf_filter_t* filt = nullptr, int attr = 0)
 {
     SdfFront f;
     int rc = sdf_begin(s, p, &f, filt);
     if (rc) return rc;
-    f.attr = attr;
+    f.attr = attr >= 1, f.dist2 = attr >= 2;
     SdfState* o = s->sdf;
     if (snap_full(o->ring)) return fail(FLUID_ERR_STATE, "two level-set snapshots are waiting for fluid_sdf_wait");
     SnapSlot& q = o->ring.s[snap_slot(o->ring)];
@@ -263,21 +283,20 @@ static int sdf_capture(fluid_sim* s, const fluid_sdf_params_t* p, const fluid_sd
             fprintf(stderr, "sdf visits: cells %.0f leaves_searched %ld leaves_in_range %ld\n", cv, searched, leaves);
         }
     }
-    constexpr size_t WIDE_REC = SDF_REC + FLUID_SDF_ATTR_LEAF_BYTES;
-    if (attr) m.wide = true;   // (and stays so)
-    if ((rc = snap_reserve(q, (size_t)n * (m.wide ? WIDE_REC : SDF_REC), 64 * (m.wide ? WIDE_REC : SDF_REC)))) return rc;
+    if (attr > m.wide) m.wide = attr;   // (and stays so)
+    if ((rc = snap_reserve(q, (size_t)n * sdf_rec(m.wide), 64 * sdf_rec(m.wide)))) return rc;
     m.n_leaves = n;
     m.attr = attr;
-    const size_t rec = attr ? WIDE_REC : SDF_REC;
+    const size_t rec = sdf_rec(attr);
     m.bg = g.bg, m.R = R, m.w = w;
     if (n > 0) {
-        const size_t a = attr ? (size_t)n * FLUID_SDF_ATTR_LEAF_BYTES : 0;   // the attributes lie between the values and the masks
+        const size_t a = (size_t)n * sdf_between(attr);   // the attributes lie between the values and the masks
         float* values = (float*)q.dev;
         uint64_t* active = (uint64_t*)(q.dev + (size_t)n * 2048 + a);
         int* origin = (int*)(q.dev + (size_t)n * (2048 + 64) + a);
         if (attr)
             launch_sdf_pack_attr(s->st, g, o->flags, o->slot, f.tv, o->tm, values, active, origin, f.tid, f.tvel, (uint32_t*)(q.dev + (size_t)n * 2048),
-                                 (float*)(q.dev + (size_t)n * 4096));
+                                 (float*)(q.dev + (size_t)n * 4096), f.tmin, attr >= 2 ? (float*)(q.dev + (size_t)n * 10240) : nullptr);
         else launch_sdf_pack(s->st, g, o->flags, o->slot, f.tv, o->tm, values, active, origin);
         HIPCHK(hipGetLastError());
     }
@@ -287,7 +306,7 @@ static int sdf_capture(fluid_sim* s, const fluid_sdf_params_t* p, const fluid_sd
     return FLUID_OK;
 }
 
-static int sdf_wait(fluid_sim* s, fluid_sdf_grid_t* out, fluid_sdf_attr_t* at = nullptr)
+static int sdf_wait(fluid_sim* s, fluid_sdf_grid_t* out, fluid_sdf_attr_t* at = nullptr, fluid_sdf_attr_part_t* part = nullptr)
 {
     if (!out) return fail(FLUID_ERR_ARG, "null argument");
     SdfState* o = s->sdf;
@@ -303,13 +322,20 @@ static int sdf_wait(fluid_sim* s, fluid_sdf_grid_t* out, fluid_sdf_attr_t* at = 
     out->radius = m.R;
     out->half_width = m.w;
     out->values = n ? (const float*)host : nullptr;
-    const size_t a = m.attr ? n * FLUID_SDF_ATTR_LEAF_BYTES : 0;
+    const size_t a = n * sdf_between(m.attr);
     out->active = n ? (const uint64_t*)(host + n * 2048 + a) : nullptr;
     out->origin = n ? (const int32_t*)(host + n * (2048 + 64) + a) : nullptr;
     if (at) {
         at->n_leaves = m.n_leaves;
         at->id = n && m.attr ? (const uint32_t*)(host + n * 2048) : nullptr;
         at->velocity = n && m.attr ? (const float*)(host + n * 4096) : nullptr;
+    }
+    if (part) {   // a record of a rank: only a snapshot that carries dist2 has one
+        const bool has = n && m.attr >= 2;
+        part->n_leaves = m.n_leaves;
+        part->id = has ? (const uint32_t*)(host + n * 2048) : nullptr;
+        part->velocity = has ? (const float*)(host + n * 4096) : nullptr;
+        part->dist2 = has ? (const float*)(host + n * 10240) : nullptr;
     }
     return FLUID_OK;
 }
@@ -354,7 +380,7 @@ int fluid_sdf_wait(fluid_sim_t* s, fluid_sdf_grid_t* out)
 int fluid_sdf_snapshot_attr(fluid_sim_t* s, const fluid_sdf_params_t* p, const fluid_sdf_filter_t* f)
 {
     int rc = snap_guard(s, ATTR_SINGLE);
-    return rc ? rc : sdf_capture(s, p, f, true);
+    return rc ? rc : sdf_capture(s, p, f, 1);
 }
 
 int fluid_sdf_wait_attr(fluid_sim_t* s, fluid_sdf_grid_t* out, fluid_sdf_attr_t* attr)
@@ -379,6 +405,18 @@ int fluid_dist_sdf_wait(fluid_sim_t* s, fluid_sdf_grid_t* out)
 {
     if (!s) return fail(FLUID_ERR_ARG, "null handle");
     return sdf_wait(s, out);
+}
+
+int fluid_dist_sdf_snapshot_attr(fluid_sim_t* s, const fluid_sdf_params_t* p)
+{
+    if (!s) return fail(FLUID_ERR_ARG, "null handle");
+    return sdf_capture(s, p, nullptr, 2);
+}
+
+int fluid_dist_sdf_wait_attr(fluid_sim_t* s, fluid_sdf_grid_t* out, fluid_sdf_attr_part_t* part)
+{
+    if (!s) return fail(FLUID_ERR_ARG, "null handle");
+    return sdf_wait(s, out, nullptr, part);
 }
 
 int fluid_dist_sdf_stats(fluid_sim_t* s, int64_t* leaves_in_grid, int64_t* leaves_listed, int64_t* bytes_to_host)

@@ -136,6 +136,9 @@ __device__ __forceinline__ float sdf_dist2(int vx, int vy, int vz, double x, dou
 // the same fminf: values and masks are those of the plain kernel.  Every thread of a flagged leaf writes tid (512 per leaf) and
 // tvel ([leaf][axis][512]): the winner's id and narrowed velocity where the voxel is active, NO_ID / +0 elsewhere.  A block that
 // leaves early writes the flag alone: its tid / tvel are stale and never read.
+// DIST2 ("liquid surface, attributes (decomposed runs)"; with ARGMIN only): every thread of a flagged leaf also writes tmin (512 per
+// leaf), m itself where the voxel is active and +inf elsewhere: what a host merge of rank records decides on.  m is in a register at
+// that point: one more coalesced 4-byte store per thread, nothing else differs from the ARGMIN form.
 __device__ __forceinline__ void sdf_visit(float& m, float x2) { m = fminf(m, x2); }
 __device__ __forceinline__ void sdf_visit_arg(float& m, int& best, float x2, int p, const int* __restrict__ ssrc, const uint32_t* __restrict__ pid)
 {
@@ -144,13 +147,14 @@ __device__ __forceinline__ void sdf_visit_arg(float& m, int& best, float x2, int
     m = fminf(m, x2);
 }
 
-template <bool VISITS, bool ARGMIN>
+template <bool VISITS, bool ARGMIN, bool DIST2 = false>
 __global__ __launch_bounds__(512) void k_sdf_search(SdfGeom g, const int* __restrict__ start, const double* __restrict__ sx,
                                                     const double* __restrict__ sy, const double* __restrict__ sz, float* __restrict__ tv,
                                                     unsigned long long* __restrict__ tm, int* __restrict__ flags, unsigned* __restrict__ visits,
                                                     const int* __restrict__ ssrc, const uint32_t* __restrict__ pid,
                                                     const double* __restrict__ pvx, const double* __restrict__ pvy,
-                                                    const double* __restrict__ pvz, uint32_t* __restrict__ tid, float* __restrict__ tvel)
+                                                    const double* __restrict__ pvz, uint32_t* __restrict__ tid, float* __restrict__ tvel,
+                                                    float* __restrict__ tmin)
 {
     __shared__ int S[16 * 16 * 17];
     __shared__ unsigned vis[8];
@@ -235,6 +239,7 @@ __global__ __launch_bounds__(512) void k_sdf_search(SdfGeom g, const int* __rest
         tid[j * 512 + t] = id;
         float* tw = tvel + j * 1536 + t;
         tw[0] = a0, tw[512] = a1, tw[1024] = a2;
+        if (DIST2) tmin[j * 512 + t] = act ? m : INFINITY;
     }
     const unsigned long long b = __ballot(act);
     if ((t & 63) == 0) tm[j * 8 + x] = b;
@@ -250,12 +255,13 @@ __global__ __launch_bounds__(512) void k_sdf_search(SdfGeom g, const int* __rest
 
 // One wave per leaf of the range; the waves of unlisted leaves leave at once.  slot[j] = the record's place in the list.
 // ATTR: the leaf's 512 ids and 3 x 512 velocities as well, in 16-byte copies (every base is a multiple of 2048 bytes from hipMalloc's).
-template <bool ATTR>
+// DIST2 (with ATTR only): and its 512 squared distances, two more 16-byte copies per lane.
+template <bool ATTR, bool DIST2 = false>
 __global__ __launch_bounds__(256) void k_sdf_pack(SdfGeom g, long nrange, const int* __restrict__ flags, const int* __restrict__ slot,
                                                   const float* __restrict__ tv, const unsigned long long* __restrict__ tm,
                                                   float* __restrict__ values, unsigned long long* __restrict__ active, int* __restrict__ origin,
                                                   const uint32_t* __restrict__ tid, const float* __restrict__ tvel, uint32_t* __restrict__ ids,
-                                                  float* __restrict__ vel)
+                                                  float* __restrict__ vel, const float* __restrict__ tmin, float* __restrict__ dist2)
 {
     const long j = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (j >= nrange || !flags[j]) return;
@@ -277,6 +283,12 @@ __global__ __launch_bounds__(256) void k_sdf_pack(SdfGeom g, long nrange, const 
         float4* vd = (float4*)(vel + s * 1536);
 #pragma unroll
         for (int k = 0; k < 6; ++k) vd[lane + 64 * k] = vs[lane + 64 * k];
+        if (DIST2) {
+            const float4* ms = (const float4*)(tmin + j * 512);
+            float4* md = (float4*)(dist2 + s * 512);
+            md[lane] = ms[lane];
+            md[lane + 64] = ms[lane + 64];
+        }
     }
 }
 
@@ -314,17 +326,23 @@ void launch_sdf_search(hipStream_t st, const SdfGeom& g, const int* start, const
     const double* nd = nullptr;
     if (visits)
         hipLaunchKernelGGL((k_sdf_search<true, false>), dim3(nb), dim3(512), 0, st, g, start, sx, sy, sz, tv, (unsigned long long*)tm, flags, visits, ns,
-                           nu, nd, nd, nd, (uint32_t*)nullptr, (float*)nullptr);
+                           nu, nd, nd, nd, (uint32_t*)nullptr, (float*)nullptr, (float*)nullptr);
     else
         hipLaunchKernelGGL((k_sdf_search<false, false>), dim3(nb), dim3(512), 0, st, g, start, sx, sy, sz, tv, (unsigned long long*)tm, flags, visits, ns,
-                           nu, nd, nd, nd, (uint32_t*)nullptr, (float*)nullptr);
+                           nu, nd, nd, nd, (uint32_t*)nullptr, (float*)nullptr, (float*)nullptr);
 }
 
 void launch_sdf_search_attr(hipStream_t st, const SdfGeom& g, const int* start, const double* sx, const double* sy, const double* sz, float* tv,
-                            uint64_t* tm, int* flags, const int* ssrc, Particles p, uint32_t* tid, float* tvel)
+                            uint64_t* tm, int* flags, const int* ssrc, Particles p, uint32_t* tid, float* tvel, float* tmin)
 {
-    hipLaunchKernelGGL((k_sdf_search<false, true>), dim3((unsigned)g.leaves()), dim3(512), 0, st, g, start, sx, sy, sz, tv, (unsigned long long*)tm,
-                       flags, (unsigned*)nullptr, ssrc, (const uint32_t*)p.pid, (const double*)p.vx, (const double*)p.vy, (const double*)p.vz, tid, tvel);
+    if (tmin)
+        hipLaunchKernelGGL((k_sdf_search<false, true, true>), dim3((unsigned)g.leaves()), dim3(512), 0, st, g, start, sx, sy, sz, tv,
+                           (unsigned long long*)tm, flags, (unsigned*)nullptr, ssrc, (const uint32_t*)p.pid, (const double*)p.vx, (const double*)p.vy,
+                           (const double*)p.vz, tid, tvel, tmin);
+    else
+        hipLaunchKernelGGL((k_sdf_search<false, true>), dim3((unsigned)g.leaves()), dim3(512), 0, st, g, start, sx, sy, sz, tv, (unsigned long long*)tm,
+                           flags, (unsigned*)nullptr, ssrc, (const uint32_t*)p.pid, (const double*)p.vx, (const double*)p.vy, (const double*)p.vz, tid, tvel,
+                           (float*)nullptr);
 }
 
 void launch_sdf_pack(hipStream_t st, const SdfGeom& g, const int* flags, const int* slot, const float* tv, const uint64_t* tm, float* values,
@@ -332,15 +350,21 @@ void launch_sdf_pack(hipStream_t st, const SdfGeom& g, const int* flags, const i
 {
     const long nrange = g.leaves();
     hipLaunchKernelGGL(k_sdf_pack<false>, dim3((unsigned)((nrange + 3) / 4)), dim3(256), 0, st, g, nrange, flags, slot, tv, (const unsigned long long*)tm,
-                       values, (unsigned long long*)active, origin, (const uint32_t*)nullptr, (const float*)nullptr, (uint32_t*)nullptr, (float*)nullptr);
+                       values, (unsigned long long*)active, origin, (const uint32_t*)nullptr, (const float*)nullptr, (uint32_t*)nullptr, (float*)nullptr,
+                       (const float*)nullptr, (float*)nullptr);
 }
 
 void launch_sdf_pack_attr(hipStream_t st, const SdfGeom& g, const int* flags, const int* slot, const float* tv, const uint64_t* tm, float* values,
-                          uint64_t* active, int* origin, const uint32_t* tid, const float* tvel, uint32_t* ids, float* vel)
+                          uint64_t* active, int* origin, const uint32_t* tid, const float* tvel, uint32_t* ids, float* vel, const float* tmin, float* dist2)
 {
     const long nrange = g.leaves();
-    hipLaunchKernelGGL(k_sdf_pack<true>, dim3((unsigned)((nrange + 3) / 4)), dim3(256), 0, st, g, nrange, flags, slot, tv, (const unsigned long long*)tm,
-                       values, (unsigned long long*)active, origin, tid, tvel, ids, vel);
+    if (tmin)
+        hipLaunchKernelGGL((k_sdf_pack<true, true>), dim3((unsigned)((nrange + 3) / 4)), dim3(256), 0, st, g, nrange, flags, slot, tv,
+                           (const unsigned long long*)tm, values, (unsigned long long*)active, origin, tid, tvel, ids, vel, tmin, dist2);
+    else
+        hipLaunchKernelGGL((k_sdf_pack<true>), dim3((unsigned)((nrange + 3) / 4)), dim3(256), 0, st, g, nrange, flags, slot, tv,
+                           (const unsigned long long*)tm, values, (unsigned long long*)active, origin, tid, tvel, ids, vel, (const float*)nullptr,
+                           (float*)nullptr);
 }
 
 }  // namespace fl

@@ -238,7 +238,7 @@ inline int snap_guard(const fluid_sim* s, const char* why, bool want_dist = fals
     if (!s) return fluid_fail(FLUID_ERR_ARG, "null handle");
     return s->dist != want_dist ? fluid_fail(FLUID_ERR_STATE, why) : FLUID_OK;
 }
-constexpr const char* ATTR_SINGLE = "surface attributes are single-GPU only: the merge of the blocks' lists sees values, and equal values do not imply equal squared distances";
+constexpr const char* ATTR_SINGLE = "these surface attribute calls are single-GPU only: a decomposed handle gives a rank record with squared distances (fluid_dist_sdf_snapshot_attr) and the records merge on the host (fluid_sdf_attr_grids_merge)";
 inline size_t solver_elem(const fluid_sim* s) { return s->prm.precision == FLUID_PRECISION_FP32 ? 4 : 8; }
 inline bool use_mg(const fluid_sim* s) { return s->prm.preconditioner == FLUID_PRECOND_MG && s->prm.precision == FLUID_PRECISION_FP64; }
 
@@ -313,6 +313,8 @@ struct SdfFront {
     const uint64_t* tm;   // 8 mask words per leaf of the range (stale where flags[j] == 0)
     const uint32_t* tid;  // attr: 512 ids per leaf of the range, and
     const float* tvel;    // [leaf][axis][512] velocities (both stale where flags[j] == 0; nullptr without attr)
+    bool dist2;           // with attr: the search also writes m per voxel (set by the caller after sdf_begin)
+    const float* tmin;    // dist2: 512 per leaf of the range, m where active and +inf elsewhere (stale where flags[j] == 0)
 };
 // limits of the parameters (and of the filter, when one is given), the state, the constants of g
 int sdf_begin(fluid_sim* s, const fluid_sdf_params_t* p, SdfFront* f, const fluid_sdf_filter_t* filt = nullptr);

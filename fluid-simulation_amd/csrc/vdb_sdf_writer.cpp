@@ -21,6 +21,7 @@
 
 #include <algorithm>
 #include <climits>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -102,6 +103,40 @@ int leaf_code(const float* v, const uint64_t* m, float bg)
     return !neg ? 0 : (!pos ? 1 : 3);   // NO_MASK_OR_INACTIVE_VALS, NO_MASK_AND_MINUS_BG, MASK_AND_NO_INACTIVE_VALS (io/Compression.h:94-100)
 }
 
+// one more part's record of a leaf folded into acc / am (the first part's record is copied instead)
+void fold_leaf(float* acc, uint64_t* am, const float* v, const uint64_t* m, float bg)
+{
+    for (int i = 0; i < 512; ++i) {
+        const bool a_in = bit(m, i), a_acc = bit(am, i);
+        if (!a_acc && !same_bits(acc[i], bg)) continue;    // inactive -bg so far: it stays
+        if (!a_in) {
+            if (same_bits(v[i], bg)) continue;             // this part has nothing to say
+            acc[i] = v[i];                                 // inactive -bg beats whatever was there
+            am[i >> 6] &= ~(1ull << (i & 63));
+        } else if (!a_acc || v[i] < acc[i]) {              // active: the smallest value, the first part's bits on a tie
+            acc[i] = v[i];
+            am[i >> 6] |= 1ull << (i & 63);
+        }
+    }
+}
+
+// what fluid_sdf_grids_merge refuses in its parts
+bool parts_merge(const fluid_sdf_grid_t* parts, int32_t n_parts)
+{
+    const float bg = parts[0].background;
+    for (int p = 0; p < n_parts; ++p) {
+        const fluid_sdf_grid_t& g = parts[p];
+        if (check_list(&g) != FLUID_OK || g.n != parts[0].n || !same_bits(g.background, bg) || !same_bits(g.radius, parts[0].radius) ||
+            !same_bits(g.half_width, parts[0].half_width))
+            return false;
+        for (int l = 0; l < g.n_leaves; ++l)
+            if (leaf_code(g.values + 512 * (size_t)l, g.active + 8 * (size_t)l, bg) < 0) return false;
+    }
+    return true;
+}
+
+inline bool org_before(const int32_t* a, const int32_t* b) { return a[0] != b[0] ? a[0] < b[0] : a[1] != b[1] ? a[1] < b[1] : a[2] < b[2]; }
+
 using Mid = std::map<int, std::vector<std::pair<int, int>>>;   // slot of a 128^3 node in its root child -> (slot of the leaf, index in the list)
 struct Key {
     int x, y, z;
@@ -147,16 +182,8 @@ int64_t fluid_sdf_grids_merge(const fluid_sdf_grid_t* parts, int32_t n_parts, in
 {
     const bool count_only = !origin && !values && !active;
     if (!parts || n_parts < 1 || (!count_only && (!origin || !values || !active))) return -FLUID_ERR_ARG;
+    if (!parts_merge(parts, n_parts)) return -FLUID_ERR_ARG;
     const float bg = parts[0].background;
-    for (int p = 0; p < n_parts; ++p) {
-        const fluid_sdf_grid_t& g = parts[p];
-        if (check_list(&g) != FLUID_OK || g.n != parts[0].n || !same_bits(g.background, bg) || !same_bits(g.radius, parts[0].radius) ||
-            !same_bits(g.half_width, parts[0].half_width))
-            return -FLUID_ERR_ARG;
-        for (int l = 0; l < g.n_leaves; ++l)
-            if (leaf_code(g.values + 512 * (size_t)l, g.active + 8 * (size_t)l, bg) < 0) return -FLUID_ERR_ARG;
-    }
-    auto before = [](const int32_t* a, const int32_t* b) { return a[0] != b[0] ? a[0] < b[0] : a[1] != b[1] ? a[1] < b[1] : a[2] < b[2]; };
     std::vector<int32_t> cur((size_t)n_parts);
     int64_t count = 0;
     for (int pass = 0; pass < (count_only ? 1 : 2); ++pass) {
@@ -168,7 +195,7 @@ int64_t fluid_sdf_grids_merge(const fluid_sdf_grid_t* parts, int32_t n_parts, in
             for (int p = 0; p < n_parts; ++p) {
                 if (cur[p] >= parts[p].n_leaves) continue;
                 const int32_t* c = parts[p].origin + 3 * (size_t)cur[p];
-                if (!o || before(c, o)) o = c;
+                if (!o || org_before(c, o)) o = c;
             }
             if (!o) break;
             const int32_t o3[3] = {o[0], o[1], o[2]};
@@ -188,20 +215,105 @@ int64_t fluid_sdf_grids_merge(const fluid_sdf_grid_t* parts, int32_t n_parts, in
                     memcpy(am, m, 8 * sizeof(uint64_t));
                     continue;
                 }
-                for (int i = 0; i < 512; ++i) {
-                    const bool a_in = bit(m, i), a_acc = bit(am, i);
-                    if (!a_acc && !same_bits(acc[i], bg)) continue;    // inactive -bg so far: it stays
-                    if (!a_in) {
-                        if (same_bits(v[i], bg)) continue;             // this part has nothing to say
-                        acc[i] = v[i];                                 // inactive -bg beats whatever was there
-                        am[i >> 6] &= ~(1ull << (i & 63));
-                    } else if (!a_acc || v[i] < acc[i]) {              // active: the smallest value, the first part's bits on a tie
-                        acc[i] = v[i];
-                        am[i >> 6] |= 1ull << (i & 63);
-                    }
-                }
+                fold_leaf(acc, am, v, m, bg);
             }
             if (pass == 1) memcpy(origin + 3 * (size_t)count, o3, sizeof o3);
+            count++;
+        }
+    }
+    return count;
+}
+
+// Host only ("liquid surface, attributes (decomposed runs)").  The same k-way merge; the geometry of a leaf is folded by the same
+// fold_leaf, and beside it every voxel keeps the part that holds it active with the smallest (dist2, id), the first such part.
+// Both passes compute a leaf into buffers of one leaf: the first counts and, in the leaves that several parts list, looks for a
+// voxel whose closest part does not hold the smallest active value (a refusal must write nothing); the second computes every leaf
+// and copies it into the caller's arrays.
+int64_t fluid_sdf_attr_grids_merge(const fluid_sdf_grid_t* parts, const fluid_sdf_attr_part_t* attrs, int32_t n_parts, int64_t cap_leaves,
+                                   int32_t* origin, float* values, uint64_t* active, uint32_t* id, float* velocity)
+{
+    const bool count_only = !origin && !values && !active && !id && !velocity;
+    if (!parts || !attrs || n_parts < 1 || (!count_only && (!origin || !values || !active || !id || !velocity))) return -FLUID_ERR_ARG;
+    if (!parts_merge(parts, n_parts)) return -FLUID_ERR_ARG;
+    const float bg = parts[0].background;
+    for (int p = 0; p < n_parts; ++p) {
+        const fluid_sdf_grid_t& g = parts[p];
+        const fluid_sdf_attr_part_t& a = attrs[p];
+        if (a.n_leaves != g.n_leaves || (g.n_leaves > 0 && (!a.id || !a.velocity || !a.dist2))) return -FLUID_ERR_ARG;
+        for (size_t i = 0; i < 512 * (size_t)g.n_leaves; ++i)
+            if (bit(g.active + 8 * (i >> 9), (int)(i & 511)) && (!std::isfinite(a.dist2[i]) || a.id[i] == FLUID_SDF_NO_ID)) return -FLUID_ERR_ARG;
+    }
+    std::vector<int32_t> cur((size_t)n_parts);
+    std::vector<float> acc(512), low(512), bd2(512), bval(512), bvel(1536);
+    std::vector<uint32_t> bid(512);
+    std::vector<uint8_t> has(512);
+    uint64_t am[8];
+    int64_t count = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        if (pass == 1 && (count_only || count == 0)) break;
+        if (pass == 1 && count > cap_leaves) return -FLUID_ERR_ARG;
+        std::fill(cur.begin(), cur.end(), 0);
+        count = 0;
+        for (;;) {
+            const int32_t* o = nullptr;   // the smallest origin at the parts' cursors
+            for (int p = 0; p < n_parts; ++p) {
+                if (cur[p] >= parts[p].n_leaves) continue;
+                const int32_t* c = parts[p].origin + 3 * (size_t)cur[p];
+                if (!o || org_before(c, o)) o = c;
+            }
+            if (!o) break;
+            const int32_t o3[3] = {o[0], o[1], o[2]};
+            if (pass == 0) {   // a leaf that one part alone lists cannot contradict itself: counted, not folded
+                int lists = 0, who = -1;
+                for (int p = 0; p < n_parts; ++p) {
+                    if (cur[p] >= parts[p].n_leaves) continue;
+                    const int32_t* c = parts[p].origin + 3 * (size_t)cur[p];
+                    if (c[0] == o3[0] && c[1] == o3[1] && c[2] == o3[2]) ++lists, who = p;
+                }
+                if (lists == 1) {
+                    cur[who]++;
+                    count++;
+                    continue;
+                }
+            }
+            std::fill(has.begin(), has.end(), 0);
+            int n_in = 0;
+            for (int p = 0; p < n_parts; ++p) {
+                if (cur[p] >= parts[p].n_leaves) continue;
+                const int32_t* c = parts[p].origin + 3 * (size_t)cur[p];
+                if (c[0] != o3[0] || c[1] != o3[1] || c[2] != o3[2]) continue;
+                const size_t l = (size_t)cur[p]++;
+                const float* v = parts[p].values + 512 * l;
+                const uint64_t* m = parts[p].active + 8 * l;
+                const uint32_t* pi = attrs[p].id + 512 * l;
+                const float *pv = attrs[p].velocity + 1536 * l, *pd = attrs[p].dist2 + 512 * l;
+                if (n_in++ == 0) {
+                    memcpy(acc.data(), v, 512 * sizeof(float));
+                    memcpy(am, m, sizeof am);
+                } else {
+                    fold_leaf(acc.data(), am, v, m, bg);
+                }
+                for (int i = 0; i < 512; ++i) {
+                    if (!bit(m, i)) continue;
+                    if (!has[i] || v[i] < low[i]) low[i] = v[i];   // the smallest active value, the first part's bits on a tie
+                    if (!has[i] || pd[i] < bd2[i] || (pd[i] == bd2[i] && pi[i] < bid[i])) {
+                        bd2[i] = pd[i], bid[i] = pi[i], bval[i] = v[i];
+                        bvel[i] = pv[i], bvel[512 + i] = pv[512 + i], bvel[1024 + i] = pv[1024 + i];
+                    }
+                    has[i] = 1;
+                }
+            }
+            for (int i = 0; i < 512; ++i) {
+                if (has[i] && !same_bits(low[i], bval[i])) return -FLUID_ERR_ARG;   // (pass 0 meets it first: nothing is written yet)
+                if (!bit(am, i)) bid[i] = FLUID_SDF_NO_ID, bvel[i] = bvel[512 + i] = bvel[1024 + i] = 0.0f;
+            }
+            if (pass == 1) {
+                memcpy(origin + 3 * (size_t)count, o3, sizeof o3);
+                memcpy(values + 512 * (size_t)count, acc.data(), 512 * sizeof(float));
+                memcpy(active + 8 * (size_t)count, am, sizeof am);
+                memcpy(id + 512 * (size_t)count, bid.data(), 512 * sizeof(uint32_t));
+                memcpy(velocity + 1536 * (size_t)count, bvel.data(), 1536 * sizeof(float));
+            }
             count++;
         }
     }

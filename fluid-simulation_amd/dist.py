@@ -15,8 +15,8 @@ import threading
 
 import numpy as np
 
-from ._lib import lib, check, Params, StepStats, LeafGridC, SdfParams, SdfGridC
-from .sim import FluidSim, source_methods, grid_bounds, merge_leaf_grids, _leaf_grid_copy, merge_sdf_grids, _sdf_grid_copy  # noqa: F401
+from ._lib import lib, check, Params, StepStats, LeafGridC, SdfParams, SdfGridC, SdfAttrPartC
+from .sim import FluidSim, source_methods, grid_bounds, merge_leaf_grids, _leaf_grid_copy, merge_sdf_grids, _sdf_grid_copy, merge_sdf_attr_grids, _sdf_attr_part_copy  # noqa: F401
 
 EXCHANGE_T = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                          C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p)
@@ -410,16 +410,24 @@ class DistFluidSim(FluidSim):
         check(lib.fluid_dist_output_every(self._h, int(k)))
 
     # ---- liquid surface of this rank's live particles (include/fluid_hip.h, "liquid surface (decomposed runs)"); rank-local ----
-    def sdf_snapshot(self, radius, half_width):
-        """Enqueue the level set of this rank's live particles as they are now (global origins; every leaf they reach)."""
+    def sdf_snapshot(self, radius, half_width, attr=False):
+        """Enqueue the level set of this rank's live particles as they are now (global origins; every leaf they reach).
+        attr=True: with the rank record of ids, velocities and squared distances beside it (sdf_wait_attr)."""
         p = SdfParams(float(radius), float(half_width))
-        check(lib.fluid_dist_sdf_snapshot(self._h, C.byref(p)))
+        check((lib.fluid_dist_sdf_snapshot_attr if attr else lib.fluid_dist_sdf_snapshot)(self._h, C.byref(p)))
 
     def sdf_wait(self):
         """The oldest level-set snapshot not yet waited for, as an SdfGrid (merge_sdf_grids joins the ranks')."""
         g = SdfGridC()
         check(lib.fluid_dist_sdf_wait(self._h, C.byref(g)))
         return _sdf_grid_copy(g)
+
+    def sdf_wait_attr(self):
+        """The oldest level-set snapshot not yet waited for, as (SdfGrid, SdfAttrPart); the record is None for a snapshot taken
+        with attr=False that lists leaves (merge_sdf_attr_grids joins the ranks')."""
+        g, a = SdfGridC(), SdfAttrPartC()
+        check(lib.fluid_dist_sdf_wait_attr(self._h, C.byref(g), C.byref(a)))
+        return _sdf_grid_copy(g), _sdf_attr_part_copy(a)
 
     def sdf_stats(self):
         v = [C.c_int64() for _ in range(3)]

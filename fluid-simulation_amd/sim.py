@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 
-from ._lib import lib, check, FluidError, Params, StepStats, FIELD, Source, LeafGridC, SdfParams, SdfGridC, SdfFilter, MeshC, SdfAttrC, MeshAttrC
+from ._lib import lib, check, FluidError, Params, StepStats, FIELD, Source, LeafGridC, SdfParams, SdfGridC, SdfFilter, MeshC, SdfAttrC, MeshAttrC, SdfAttrPartC
 
 _FIELD_DTYPE = {
     FIELD.CONTAINER: (np.float32, 1), FIELD.WEIGHTS: (np.float32, 1), FIELD.OUTPUT: (np.float32, 1),
@@ -276,6 +276,62 @@ class SdfAttr:
     def _c(self):
         k = self.n_leaves
         return SdfAttrC(k, self.id.ctypes.data if k else None, self.velocity.ctypes.data if k else None)
+
+
+class SdfAttrPart:
+    """fluid_sdf_attr_part_t on the host ("liquid surface, attributes (decomposed runs)"): a rank's record beside its SdfGrid.
+    id (k, 512) uint32 and velocity (k, 3, 512) float32 as SdfAttr's, over the rank's live particles; dist2 (k, 512) float32, the
+    squared distance to the closest of them where the voxel is active, +inf elsewhere."""
+
+    def __init__(self, id, velocity, dist2):
+        self.id = np.ascontiguousarray(id, dtype=np.uint32).reshape(-1, 512)
+        self.velocity = np.ascontiguousarray(velocity, dtype=np.float32).reshape(-1, 3, 512)
+        self.dist2 = np.ascontiguousarray(dist2, dtype=np.float32).reshape(-1, 512)
+        assert self.id.shape[0] == self.velocity.shape[0] == self.dist2.shape[0]
+
+    @property
+    def n_leaves(self):
+        return self.id.shape[0]
+
+    def _c(self):
+        k = self.n_leaves
+        return SdfAttrPartC(k, self.id.ctypes.data if k else None, self.velocity.ctypes.data if k else None,
+                            self.dist2.ctypes.data if k else None)
+
+
+def _sdf_attr_part_copy(a):
+    """SdfAttrPart copied out of the buffers a fluid_sdf_attr_part_t points into, or None when it points nowhere with leaves
+    (the snapshot was taken without a record)."""
+    k = a.n_leaves
+    if k == 0:
+        return SdfAttrPart(np.empty((0, 512), np.uint32), np.empty((0, 3, 512), np.float32), np.empty((0, 512), np.float32))
+    if not a.id or not a.velocity or not a.dist2:
+        return None
+    return SdfAttrPart(np.ctypeslib.as_array(C.cast(a.id, C.POINTER(C.c_uint32)), shape=(k, 512)).copy(),
+                       np.ctypeslib.as_array(C.cast(a.velocity, C.POINTER(C.c_float)), shape=(k, 3, 512)).copy(),
+                       np.ctypeslib.as_array(C.cast(a.dist2, C.POINTER(C.c_float)), shape=(k, 512)).copy())
+
+
+def merge_sdf_attr_grids(parts, attrs):
+    """(SdfGrid, SdfAttr) of the whole particle set from the ranks' SdfGrids and SdfAttrParts (DistFluidSim.sdf_wait_attr of every
+    rank): the geometry of merge_sdf_grids; per active voxel the id and velocity of the part with the smallest dist2, then the
+    smallest id (fluid_sdf_attr_grids_merge: host only)."""
+    parts, attrs = list(parts), list(attrs)
+    assert len(parts) == len(attrs)
+    cs = [p._c() for p in parts]           # (struct, mask words): the words must outlive the calls
+    arr = (SdfGridC * len(parts))(*[c for c, _ in cs])
+    aarr = (SdfAttrPartC * len(attrs))(*[a._c() for a in attrs])
+    k = lib.fluid_sdf_attr_grids_merge(arr, aarr, len(parts), 0, None, None, None, None, None)
+    if k < 0:
+        raise FluidError(-k, "fluid_sdf_attr_grids_merge: the parts do not merge (what fluid_sdf_grids_merge refuses, records of "
+                             "another list, an active voxel without id or finite dist2, or dist2 that contradicts the values)")
+    org, val, words = np.empty((k, 3), np.int32), np.empty((k, 512), np.float32), np.zeros((k, 8), np.uint64)
+    ids, vel = np.empty((k, 512), np.uint32), np.empty((k, 3, 512), np.float32)
+    if k and lib.fluid_sdf_attr_grids_merge(arr, aarr, len(parts), k, *[x.ctypes.data_as(C.c_void_p) for x in (org, val, words, ids, vel)]) != k:
+        raise FluidError(1, "fluid_sdf_attr_grids_merge: the second call disagrees with the count")
+    act = np.unpackbits(words.view(np.uint8), axis=1, bitorder="little").astype(bool).reshape(k, 512)
+    p0 = parts[0]
+    return SdfGrid(p0.n, org, val, act, p0.background, p0.radius, p0.half_width), SdfAttr(ids, vel)
 
 
 def sdf_mesh_attr(grid, attr):

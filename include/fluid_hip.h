@@ -787,8 +787,8 @@ int fluid_write_ply_mesh(const char* path, const fluid_mesh_t* m, float voxel_si
  * Only a hand-made leaf list reaches that rule: fluid_sdf_mesh_attr implements it, the kernel carries the same rule and cannot be
  * driven into it.  One-ended edges do occur after a filter (the filter moves the sign change into the band's rim).
  *
- * Decomposed handles get FLUID_ERR_STATE from the four handle entry points below: the host merge sees values, and equal values
- * do not imply equal m; an exact merge needs m (or an id rule on d) in the rank records. */
+ * Decomposed handles get FLUID_ERR_STATE from the four handle entry points below: a block run takes a record per rank that also
+ * carries m and merges the records on the host ("liquid surface, attributes (decomposed runs)", below). */
 #define FLUID_SDF_NO_ID 0xffffffffu
 typedef struct fluid_sdf_attr {
     int32_t n_leaves;
@@ -830,6 +830,58 @@ int fluid_sdf_attr_to_dense(const fluid_sdf_grid_t* grid, const fluid_sdf_attr_t
  * position times voxel_size and the velocity components times velocity_scale, both in float.  FLUID_ERR_ARG as there, and for
  * attr NULL, attr->n_vertices != m->n_vertices, vertices without velocities, or a velocity_scale that is not finite. */
 int fluid_write_ply_mesh_attr(const char* path, const fluid_mesh_t* m, const fluid_mesh_attr_t* attr, float voxel_size, float velocity_scale);
+
+/* ---- liquid surface, attributes (decomposed runs) -----------------------------------------------------------------------------
+ * No new arithmetic: m(c), x2y2z2, "counted", "live" and the closest-particle rule are those of the sections above.  A merge that
+ * looks at values cannot be exact — equal values do not imply equal m (many m share one d), and with equal m the smaller id may sit
+ * on any rank — so the rank record carries m itself and the merge decides on it.
+ *
+ * Rank record.  The attribute snapshot of a rank is fluid_dist_sdf_snapshot's list for this rank's LIVE particles: origins, values
+ * and masks are byte for byte the plain snapshot's.  Per voxel it adds id, velocity and dist2:
+ *   ACTIVE voxel:       id and velocity as in "liquid surface, attributes", taken over this rank's live particles — the ids are
+ *                       the handle's global ids, as fluid_download_particles_ids returns them —, and dist2 = m(c) over those
+ *                       particles, as a float;
+ *   every other voxel:  FLUID_SDF_NO_ID, +0.0f velocity, dist2 = +infinity (bit pattern 0x7f800000).
+ *
+ * Merge.  Geometry follows the three-state rule of "liquid surface (decomposed runs)", unchanged: origins, values and masks are
+ * the bytes fluid_sdf_grids_merge gives.  Attributes of a voxel whose merged state is active: among the parts that hold it active
+ * take the smallest dist2; among equal dist2 the smallest id; among equal id the first part (a device run cannot produce this
+ * case: a particle is live on one rank only).  id and velocity are that part's.  Every other voxel gets FLUID_SDF_NO_ID and +0.0f.
+ * Exact: a minimum over a union is the minimum of the minima; d is monotone in m, so the part with the smallest dist2 also holds
+ * the smallest active value; a voxel that is -bg on any part is -bg in the union.  For the records the ranks of a run give, the
+ * result is what fluid_sdf_snapshot_attr gives on one handle that holds the union of their live particles with the same ids.
+ *
+ *   per step, every rank:    fluid_step(s, &st);  fluid_dist_sdf_snapshot_attr(s, &sp);  fluid_dist_sdf_wait_attr(s, &part[rank], &rec[rank]);
+ *   one place:               k = fluid_sdf_attr_grids_merge(part, rec, R, cap, origin, values, active, id, velocity);
+ *                            g = {n, k, ...};  a = {k, id, velocity};  fluid_sdf_filter / fluid_sdf_mesh / fluid_sdf_mesh_attr as on one GPU.
+ * The rank snapshot is unfiltered, as its sibling: a block run filters after the merge, and a filter leaves attributes alone. */
+typedef struct fluid_sdf_attr_part {
+    int32_t n_leaves;
+    const uint32_t* id;          /* 512 per leaf                                                                     */
+    const float* velocity;       /* [leaf][axis][512]                                                                */
+    const float* dist2;          /* 512 per leaf                                                                     */
+} fluid_sdf_attr_part_t;
+#define FLUID_SDF_ATTR_PART_LEAF_BYTES (2048 + 6144 + 2048)   /* what a rank record adds to a listed leaf on the way to the host */
+/* fluid_dist_sdf_snapshot in every respect — stream, the box and the 4-byte count read back, the copy stream, the surface's own two
+ * slots and its count of outstanding snapshots (a third, of whatever kind, is FLUID_ERR_STATE) — with the longer record:
+ * fluid_dist_sdf_stats reports bytes_to_host = leaves_listed * (FLUID_SDF_LEAF_BYTES + FLUID_SDF_ATTR_PART_LEAF_BYTES) + 4.  A plain
+ * fluid_create handle is accepted; its ids are rows of fluid_download_particles (or the ids of fluid_upload_particles_ids).  The
+ * extra scratch (that of fluid_sdf_snapshot_attr and 2 KB more per leaf of the range) is allocated by the handle's first snapshot
+ * of this kind, never inside a step; no other caller pays for it. */
+int fluid_dist_sdf_snapshot_attr(fluid_sim_t* s, const fluid_sdf_params_t* p);
+/* fluid_dist_sdf_wait, and the record of the same snapshot (part may be NULL).  A snapshot taken by any other call, or one with no
+ * listed leaf, gives NULL record pointers (n_leaves is the grid's).  fluid_dist_sdf_wait on such a snapshot returns the geometry
+ * alone.  Lifetime of the pointers: that of the grid's, also across a step that moves the cut planes. */
+int fluid_dist_sdf_wait_attr(fluid_sim_t* s, fluid_sdf_grid_t* grid, fluid_sdf_attr_part_t* part);
+/* Host only.  The merge defined above: origin / values / active as fluid_sdf_grids_merge, id[512 * cap_leaves] and
+ * velocity[1536 * cap_leaves] ([leaf][axis][512]) beside them.  Returns the merged leaf count (all five outputs NULL: the count only,
+ * cap_leaves is ignored; otherwise all five are required), or -FLUID_ERR_ARG with nothing written: every refusal of
+ * fluid_sdf_grids_merge; attrs NULL or attrs[i].n_leaves != parts[i].n_leaves; leaves without the three record arrays; an active
+ * voxel of a part with a dist2 that is not finite or with FLUID_SDF_NO_ID; a voxel where the part with the smallest dist2 does not
+ * hold the smallest active value as a bit pattern (only a hand-made list reaches this).  Parts with n_leaves == 0 and NULL pointers
+ * are valid.  Two passes over a k-way merge of the ascending lists; no dense grid. */
+int64_t fluid_sdf_attr_grids_merge(const fluid_sdf_grid_t* parts, const fluid_sdf_attr_part_t* attrs, int32_t n_parts, int64_t cap_leaves,
+                                   int32_t* origin, float* values, uint64_t* active, uint32_t* id, float* velocity);
 
 #ifdef __cplusplus
 }
