@@ -89,6 +89,15 @@ class MeshAttrC(C.Structure):
     _fields_ = [("n_vertices", C.c_int64), ("velocity", C.c_void_p)]
 
 
+class MeshExC(C.Structure):
+    """fluid_mesh_ex_t: the optional parts of a mesh — velocities, normals, triangles ("normals and triangles")."""
+    _fields_ = [("velocity", C.c_void_p), ("normals", C.c_void_p), ("triangles", C.c_void_p), ("n_triangles", C.c_int64)]
+
+
+class MESH:
+    VELOCITY, NORMALS, TRIANGLES = 1, 2, 4
+
+
 class MpmParams(C.Structure):
     """mpm_params_t (include/mpm_hip.h); defaults = the literals of mpm.cc."""
     _fields_ = [("B", C.c_int32), ("W", C.c_int32), ("device", C.c_int32), ("cg_max_iters", C.c_int32),
@@ -211,6 +220,11 @@ SYMBOLS = [
     ("fluid_dist_sdf_snapshot_attr", C.c_int, [_P, C.POINTER(SdfParams)]),
     ("fluid_dist_sdf_wait_attr", C.c_int, [_P, C.POINTER(SdfGridC), C.POINTER(SdfAttrPartC)]),
     ("fluid_sdf_attr_grids_merge", C.c_int64, [C.POINTER(SdfGridC), C.POINTER(SdfAttrPartC), C.c_int32, C.c_int64, _P, _P, _P, _P, _P]),
+    ("fluid_mesh_snapshot_ex", C.c_int, [_P, C.POINTER(SdfParams), C.POINTER(SdfFilter), C.c_uint32]),
+    ("fluid_mesh_wait_ex", C.c_int, [_P, C.POINTER(MeshC), C.POINTER(MeshExC)]),
+    ("fluid_sdf_mesh_normals", C.c_int64, [C.POINTER(SdfGridC), C.c_int64, _P]),
+    ("fluid_mesh_triangles", C.c_int64, [C.POINTER(MeshC), C.c_int64, _P]),
+    ("fluid_write_ply_mesh_ex", C.c_int, [C.c_char_p, C.POINTER(MeshC), C.POINTER(MeshExC), C.c_float, C.c_float]),
     # the snow-MPM step (include/mpm_hip.h)
     ("mpm_default_params", C.c_int, [C.POINTER(MpmParams)]),
     ("mpm_create", C.c_int, [C.POINTER(MpmParams), C.POINTER(_P)]),

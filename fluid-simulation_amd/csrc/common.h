@@ -354,9 +354,6 @@ void launch_sdf_search_attr(hipStream_t st, const SdfGeom& g, const int* start, 
 void launch_sdf_pack_attr(hipStream_t st, const SdfGeom& g, const int* flags, const int* slot, const float* tv, const uint64_t* tm, float* values,
                           uint64_t* active, int* origin, const uint32_t* tid, const float* tvel, uint32_t* ids, float* vel,
                           const float* tmin = nullptr, float* dist2 = nullptr);   // tmin / dist2: nullptr, or the squared distances as well
-void launch_mesh_emit_attr(hipStream_t st, const SdfGeom& g, const float* tv, const int* flags, const uint64_t* tm, const float* tvel,
-                           const uint64_t* cmask, const int* cpre, const int* vcnt, const int* qcnt, const int* vbase, const int* qbase,
-                           float* vertices, uint32_t* quads, float* vvel);
 // box filter of that level set (kernels_sdf_filter.hip): one pass of width W along `axis` from src to dst (both 512 values per leaf of
 // the range; only flagged leaves are read or written), `off` added to the active voxels' results (0.0f: none); and the offset alone
 void launch_sdf_box(hipStream_t st, const SdfGeom& g, int axis, int W, float off, const int* flags, const uint64_t* tm, const float* src,
@@ -366,8 +363,13 @@ void launch_sdf_offset(hipStream_t st, const SdfGeom& g, float off, const int* f
 // words' popcounts, the vertex and the quad count; tot[2] = the two totals, saturating at 2^31 (a one-block sum of the counts)
 void launch_mesh_mark(hipStream_t st, const SdfGeom& g, const float* tv, const int* flags, uint64_t* cmask, int* cpre, int* vcnt, int* qcnt,
                       unsigned* tot);
-void launch_mesh_emit(hipStream_t st, const SdfGeom& g, const float* tv, const int* flags, const uint64_t* cmask, const int* cpre, const int* vcnt,
-                      const int* qcnt, const int* vbase, const int* qbase, float* vertices, uint32_t* quads);
+// vertices and quads; tm / tvel / vvel non-NULL: a velocity per vertex as well ("liquid surface, attributes"); vnrm non-NULL: a unit
+// normal per vertex ("normals and triangles")
+void launch_mesh_emit(hipStream_t st, const SdfGeom& g, const float* tv, const int* flags, const uint64_t* tm, const float* tvel,
+                      const uint64_t* cmask, const int* cpre, const int* vcnt, const int* qcnt, const int* vbase, const int* qbase, float* vertices,
+                      uint32_t* quads, float* vvel, float* vnrm);
+// behind emit: quad i's two triangles to tris[6 i ..], cut along the shorter diagonal; tris is 16-byte aligned
+void launch_mesh_tris(hipStream_t st, long nq, long nv, const uint32_t* quads, const float* vertices, uint32_t* tris);
 void launch_exclusive_scan(hipStream_t st, const int* in, int* out, long n, int* block_sums, int* total);
 void launch_sort_tail(hipStream_t st, const int* cell_count, int* cell_start, long c1, long ncell);
 void launch_index_scan(hipStream_t st, Grid g, const uint8_t* flags, int* indices, int* block_sums, int* total);

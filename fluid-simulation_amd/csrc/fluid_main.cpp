@@ -24,6 +24,11 @@
 // fluid_mesh_wait_attr, fluid_write_ply_mesh_attr) times SCALE, a finite number.  Composes with FLUID_OUT_SMOOTH.  Refused without
 // FLUID_OUT_MESH or malformed, before any handle is created.  Positions and faces are those of the file without it; unset, every file
 // is byte for byte what it was.
+//   FLUID_OUT_MESH_NORMALS=1, FLUID_OUT_MESH_TRIS=1 (unset or 0: off; with FLUID_OUT_MESH only) — mesh<i>.ply carries nx / ny / nz per vertex,
+// the normalised gradient of the level set at the vertex, and / or its faces are two triangles per quad, cut along the shorter diagonal
+// (include/fluid_hip.h, "normals and triangles": fluid_mesh_snapshot_ex, fluid_mesh_wait_ex, fluid_write_ply_mesh_ex).  Compose with
+// FLUID_OUT_MESH_VEL and FLUID_OUT_SMOOTH.  Refused without FLUID_OUT_MESH or with a value other than 0 or 1, before any handle is
+// created.  Unset, every file is byte for byte what it was.
 // Initial particles: with the defaults (N = 121, 10 per voxel) exactly the reference's — fill(CoordBBox(-20, 20)) scattered by
 // UniformPointScatter with std::mt19937(FLUID_SEED) (fluid_scene_uniform_scatter: 689210 points); any other N / PPC takes the
 // scaled synthetic cube (fluid_scene_water_cube_drop).
@@ -55,6 +60,9 @@
 // block takes fluid_dist_sdf_snapshot_attr, the main thread merges the rank records (fluid_sdf_attr_grids_merge: include/fluid_hip.h,
 // "liquid surface, attributes (decomposed runs)"), the writer thread adds fluid_sdf_mesh_attr and writes fluid_write_ply_mesh_attr.
 // Refused without FLUID_BLOCKS_MESH or malformed.  Stdout and every other file are what they are without the two.
+//   FLUID_BLOCKS_MESH_NORMALS=1, FLUID_BLOCKS_MESH_TRIS=1 (unset or 0: off; with FLUID_BLOCKS_MESH only) — the same two options for the block
+// run's mesh<i>.ply, through the host functions on the writer thread (fluid_sdf_mesh_normals on the merged list, after the filter if
+// FLUID_OUT_SMOOTH is set; fluid_mesh_triangles on the mesh).  Refused without FLUID_BLOCKS_MESH or with a value other than 0 or 1.
 //   FLUID_OUT_SMOOTH=W,K[,OFFSET] (unset: off) — what FLUID_OUT_SURFACE, FLUID_OUT_MESH, FLUID_BLOCKS_SURFACE and FLUID_BLOCKS_MESH write is the level set
 // after K box filters of width W voxels and the offset (include/fluid_hip.h, "liquid surface, smoothed"): on one GPU the snapshots
 // are fluid_sdf_snapshot_filtered / fluid_mesh_snapshot_filtered; a block run filters the merged list on the main thread
@@ -81,6 +89,23 @@ static long env_long(const char* k, long d)
 }
 
 // FLUID_RAW=1: the bare float32 dump (int32 n, then n^3 floats, z fastest)
+// a 0 / 1 switch that adds to what `base` writes: 0 = off (unset, empty or "0"), 1 = on, -1 = refused (the message is printed)
+static int env_option(const char* name, const char* base, bool base_set, const char* adds)
+{
+    const char* v = getenv(name);
+    if (!v || !*v) return 0;
+    const std::string t = v;
+    if (t != "0" && t != "1") {
+        std::cerr << name << " must be 0 or 1 (it adds " << adds << " to what " << base << " writes)" << std::endl;
+        return -1;
+    }
+    if (!base_set) {
+        std::cerr << name << " adds " << adds << " to what " << base << "=R,W writes: it is not set" << std::endl;
+        return -1;
+    }
+    return t == "1";
+}
+
 static bool write_f32(const std::string& fr, int32_t n32, const float* v, size_t ncell)
 {
     FILE* f = fopen(fr.c_str(), "wb");
@@ -104,6 +129,8 @@ struct LeafWriter {
     bool has_mjob = false;
     fluid_mesh_attr_t majob{};   // FLUID_OUT_MESH_VEL: its vertex velocities
     bool has_majob = false;
+    fluid_mesh_ex_t mxjob{};     // FLUID_OUT_MESH_NORMALS / _TRIS: its normals and triangles (and velocities)
+    unsigned mesh_what = 0;      // FLUID_MESH_* bits of what mesh<i>.ply carries, one GPU or blocks
     float vel_scale = 1.0f;
     float voxel = 1.0f;
     fluid_sdf_grid_t bjob{};     // FLUID_BLOCKS_MESH: the merged level set this thread meshes
@@ -118,8 +145,18 @@ struct LeafWriter {
     void start() { th = std::thread([this] { run(); }); }
     ~LeafWriter() { stop(); }   // (an early return of main: the grid in hand is still written)
     // FLUID_BLOCKS_MESH: the surface nets of the merged list, with vertex velocities when `at` is given, into `fm`
+    // fluid_write_ply_mesh_ex of the parts mesh_what names; a part an empty mesh lacks still gets its header lines
+    bool write_ex(const std::string& fm, const fluid_mesh_t& mg, fluid_mesh_ex_t ex) const
+    {
+        static const float none_f[3] = {0.0f, 0.0f, 0.0f};
+        static const uint32_t none_u[3] = {0, 0, 0};
+        if ((mesh_what & FLUID_MESH_VELOCITY) && !ex.velocity) ex.velocity = none_f;
+        if ((mesh_what & FLUID_MESH_NORMALS) && !ex.normals) ex.normals = none_f;
+        if ((mesh_what & FLUID_MESH_TRIANGLES) && !ex.triangles) ex.triangles = none_u, ex.n_triangles = 2 * mg.n_quads;
+        return fluid_write_ply_mesh_ex(fm.c_str(), &mg, &ex, voxel, vel_scale) == FLUID_OK;
+    }
     bool mesh_blocks(const std::string& fm, const fluid_sdf_grid_t& g, const fluid_sdf_attr_t* at, std::vector<float>& v, std::vector<uint32_t>& q,
-                     std::vector<float>& w)
+                     std::vector<float>& w, std::vector<float>& nr, std::vector<uint32_t>& tr)
     {
         int64_t nq = 0;
         const int64_t nv = fluid_sdf_mesh(&g, 0, 0, nullptr, nullptr, &nq);
@@ -127,6 +164,26 @@ struct LeafWriter {
         v.resize(3 * (size_t)nv + 3), q.resize(4 * (size_t)nq + 4);
         if (nv && fluid_sdf_mesh(&g, nv, nq, v.data(), q.data(), &nq) != nv) return false;
         const fluid_mesh_t mg{g.n, nv, nq, g.radius, g.half_width, g.background, nv ? v.data() : nullptr, nq ? q.data() : nullptr};
+        if (mesh_what & (FLUID_MESH_NORMALS | FLUID_MESH_TRIANGLES)) {
+            fluid_mesh_ex_t ex{};
+            if (at) {
+                w.resize(3 * (size_t)nv + 3);
+                if (nv && fluid_sdf_mesh_attr(&g, at, nv, w.data()) != nv) return false;
+                ex.velocity = nv ? w.data() : nullptr;
+            }
+            if (mesh_what & FLUID_MESH_NORMALS) {
+                nr.resize(3 * (size_t)nv + 3);
+                if (nv && fluid_sdf_mesh_normals(&g, nv, nr.data()) != nv) return false;
+                ex.normals = nv ? nr.data() : nullptr;
+            }
+            if (mesh_what & FLUID_MESH_TRIANGLES) {
+                tr.resize(6 * (size_t)nq + 6);
+                if (nq && fluid_mesh_triangles(&mg, 2 * nq, tr.data()) != 2 * nq) return false;
+                ex.triangles = nq ? tr.data() : nullptr;
+                ex.n_triangles = nq ? 2 * nq : 0;
+            }
+            return write_ex(fm, mg, ex);
+        }
         if (!at) return fluid_write_ply_mesh(fm.c_str(), &mg, voxel) == FLUID_OK;
         w.resize(3 * (size_t)nv + 3);
         if (nv && fluid_sdf_mesh_attr(&g, at, nv, w.data()) != nv) return false;
@@ -135,8 +192,8 @@ struct LeafWriter {
     }
     void run()
     {
-        std::vector<float> dense, bv, bw;
-        std::vector<uint32_t> bq;
+        std::vector<float> dense, bv, bw, bn;
+        std::vector<uint32_t> bq, bt;
         for (;;) {
             std::unique_lock<std::mutex> lk(m);
             cv.wait(lk, [&] { return job_step >= 0 || quit; });
@@ -148,6 +205,7 @@ struct LeafWriter {
             const bool has_mg = has_mjob;
             const fluid_mesh_attr_t ma = majob;
             const bool has_ma = has_majob;
+            const fluid_mesh_ex_t mx = mxjob;
             const fluid_sdf_grid_t bg = bjob;
             const bool has_bg = has_bjob;
             const fluid_sdf_attr_t ba = bajob;
@@ -169,11 +227,13 @@ struct LeafWriter {
             }
             if (has_mg && bad.empty()) {
                 const std::string fm = outdir + "/mesh" + std::to_string(i) + ".ply";
-                if ((has_ma ? fluid_write_ply_mesh_attr(fm.c_str(), &mg, &ma, voxel, vel_scale) : fluid_write_ply_mesh(fm.c_str(), &mg, voxel)) != FLUID_OK) bad = fm;
+                if (mesh_what & (FLUID_MESH_NORMALS | FLUID_MESH_TRIANGLES)) {
+                    if (!write_ex(fm, mg, mx)) bad = fm;
+                } else if ((has_ma ? fluid_write_ply_mesh_attr(fm.c_str(), &mg, &ma, voxel, vel_scale) : fluid_write_ply_mesh(fm.c_str(), &mg, voxel)) != FLUID_OK) bad = fm;
             }
             if (has_bg && bad.empty()) {
                 const std::string fm = outdir + "/mesh" + std::to_string(i) + ".ply";
-                if (!mesh_blocks(fm, bg, has_ba ? &ba : nullptr, bv, bq, bw)) bad = fm;
+                if (!mesh_blocks(fm, bg, has_ba ? &ba : nullptr, bv, bq, bw, bn, bt)) bad = fm;
             }
             if (raw_f32 && bad.empty()) {
                 const size_t ncell = (size_t)g.n * g.n * g.n;
@@ -196,7 +256,8 @@ struct LeafWriter {
         return error.empty();
     }
     void submit(int step, const fluid_leaf_grid_t& g, const fluid_sdf_grid_t* surface = nullptr, const fluid_mesh_t* mesh = nullptr,
-                const fluid_mesh_attr_t* mesh_attr = nullptr, const fluid_sdf_grid_t* to_mesh = nullptr, const fluid_sdf_attr_t* to_mesh_attr = nullptr)
+                const fluid_mesh_attr_t* mesh_attr = nullptr, const fluid_sdf_grid_t* to_mesh = nullptr, const fluid_sdf_attr_t* to_mesh_attr = nullptr,
+                const fluid_mesh_ex_t* mesh_ex = nullptr)
     {
         std::unique_lock<std::mutex> lk(m);
         cv.wait(lk, [&] { return job_step < 0; });
@@ -207,6 +268,7 @@ struct LeafWriter {
         if (mesh) mjob = *mesh;
         has_majob = mesh && mesh_attr;
         if (has_majob) majob = *mesh_attr;
+        mxjob = mesh && mesh_ex ? *mesh_ex : fluid_mesh_ex_t{};
         has_bjob = to_mesh != nullptr;
         if (to_mesh) bjob = *to_mesh;
         has_bajob = to_mesh && to_mesh_attr;
@@ -239,6 +301,7 @@ struct BlockCfg {
     fluid_sdf_filter_t sf{};
     bool mesh = false;        // FLUID_BLOCKS_MESH (its R,W are in sp: the same numbers as FLUID_BLOCKS_SURFACE's when both are set)
     bool mesh_vel = false;    // FLUID_BLOCKS_MESH_VEL
+    unsigned mesh_more = 0;   // FLUID_BLOCKS_MESH_NORMALS / _TRIS: FLUID_MESH_NORMALS | FLUID_MESH_TRIANGLES
     double mesh_vel_scale = 1.0;
 };
 
@@ -381,6 +444,7 @@ static int run_blocks(const BlockCfg& cfg, const std::vector<double>& pos, int64
         lw.outdir = cfg.outdir, lw.fin = fin, lw.all = all, lw.raw_f32 = cfg.raw_f32;
         lw.voxel = (float)cfg.prm.dx;
         lw.vel_scale = (float)cfg.mesh_vel_scale;
+        lw.mesh_what = cfg.mesh_more | (cfg.mesh_vel ? FLUID_MESH_VELOCITY : 0u);
         lw.start();
     }
     // the merged grid of step i lives in buffer i & 1 until the writer thread has put grid i on disk
@@ -539,6 +603,13 @@ int main(int, char**)
             return 1;
         }
     }
+    unsigned mesh_more = 0;
+    for (int k = 0; k < 2; ++k) {
+        const int on = env_option(k ? "FLUID_OUT_MESH_TRIS" : "FLUID_OUT_MESH_NORMALS", "FLUID_OUT_MESH", mesh, k ? "triangles" : "vertex normals");
+        if (on < 0) return 1;
+        if (on) mesh_more |= k ? FLUID_MESH_TRIANGLES : FLUID_MESH_NORMALS;
+    }
+    const unsigned mesh_what = mesh_more | (mesh_vel ? FLUID_MESH_VELOCITY : 0u);
     BlockCfg bc;
     if (const char* bs = getenv("FLUID_BLOCKS_SURFACE"); bs && *bs) {
         char tail = 0;
@@ -589,6 +660,11 @@ int main(int, char**)
             return 1;
         }
         bc.mesh_vel = true;
+    }
+    for (int k = 0; k < 2; ++k) {
+        const int on = env_option(k ? "FLUID_BLOCKS_MESH_TRIS" : "FLUID_BLOCKS_MESH_NORMALS", "FLUID_BLOCKS_MESH", bc.mesh, k ? "triangles" : "vertex normals");
+        if (on < 0) return 1;
+        if (on) bc.mesh_more |= k ? FLUID_MESH_TRIANGLES : FLUID_MESH_NORMALS;
     }
     const char* smenv = getenv("FLUID_OUT_SMOOTH");
     const bool smooth = smenv && *smenv;
@@ -680,6 +756,7 @@ int main(int, char**)
         lw.outdir = outdir, lw.fin = fin, lw.all = all, lw.raw_f32 = raw_f32;
         lw.voxel = (float)prm.dx;
         lw.vel_scale = (float)mesh_vel_scale;
+        lw.mesh_what = mesh_what;
         lw.start();
     }
     // hands the oldest snapshot to the writer thread
@@ -696,11 +773,13 @@ int main(int, char**)
         }
         fluid_mesh_t mg;
         fluid_mesh_attr_t ma;
-        if (mesh && (mesh_vel ? fluid_mesh_wait_attr(sim, &mg, &ma) : fluid_mesh_wait(sim, &mg)) != FLUID_OK) {
+        fluid_mesh_ex_t mx{};
+        if (mesh && (mesh_more ? fluid_mesh_wait_ex(sim, &mg, &mx) : mesh_vel ? fluid_mesh_wait_attr(sim, &mg, &ma) : fluid_mesh_wait(sim, &mg)) != FLUID_OK) {
             std::cerr << "fluid_mesh_wait: " << fluid_last_error() << std::endl;
             return false;
         }
-        lw.submit(step, g, surface ? &sg : nullptr, mesh ? &mg : nullptr, mesh && mesh_vel ? &ma : nullptr);
+        lw.submit(step, g, surface ? &sg : nullptr, mesh ? &mg : nullptr, mesh && mesh_vel && !mesh_more ? &ma : nullptr, nullptr, nullptr,
+                  mesh && mesh_more ? &mx : nullptr);
         return true;
     };
 
@@ -746,7 +825,8 @@ int main(int, char**)
                 lw.stop();
                 return 1;
             }
-            if (mesh && (mesh_vel ? fluid_mesh_snapshot_attr(sim, &mp, smooth ? &sf : nullptr)
+            if (mesh && (mesh_more ? fluid_mesh_snapshot_ex(sim, &mp, smooth ? &sf : nullptr, mesh_what)
+                         : mesh_vel ? fluid_mesh_snapshot_attr(sim, &mp, smooth ? &sf : nullptr)
                          : smooth ? fluid_mesh_snapshot_filtered(sim, &mp, &sf)
                                   : fluid_mesh_snapshot(sim, &mp)) != FLUID_OK) {
                 std::cerr << "fluid_mesh_snapshot: " << fluid_last_error() << std::endl;

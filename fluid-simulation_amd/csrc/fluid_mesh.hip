@@ -15,6 +15,11 @@
 //
 // fluid_mesh_snapshot_attr ("liquid surface, attributes"): the front half's search also leaves the closest particle's velocity per
 // voxel, the emit kernel writes a velocity per vertex, and the slot's record is [quads | vertices | nv x 12 B of velocities].
+//
+// fluid_mesh_snapshot_ex ("normals and triangles"): `what` chooses velocities, normals and triangles; the record is
+// [quads | nq x 24 B of triangles | vertices | velocities | normals], each part only if asked for.  The triangles sit right behind
+// the quads so that they start at a multiple of 16 for every nv and nq (behind the vertices 12 nv would leave 4); k_mesh_tris runs
+// behind emit on the handle's stream.  what = 0 and 1 give the records above byte for byte.
 #include "sim.h"
 
 using namespace fl;
@@ -22,7 +27,12 @@ using namespace fl;
 
 struct MeshMeta {              // per slot of the ring
     long nv = 0, nq = 0;
-    bool attr = false;         // the snapshot in the slot carries vertex velocities
+    unsigned what = 0;         // FLUID_MESH_* bits: what the snapshot in the slot carries beside vertices and quads
+    size_t tris_at() const { return (size_t)nq * 16; }
+    size_t vert_at() const { return (size_t)nq * ((what & FLUID_MESH_TRIANGLES) ? 40 : 16); }
+    size_t vel_at() const { return vert_at() + (size_t)nv * 12; }
+    size_t nrm_at() const { return vel_at() + ((what & FLUID_MESH_VELOCITY) ? (size_t)nv * 12 : 0); }
+    size_t bytes() const { return nrm_at() + ((what & FLUID_MESH_NORMALS) ? (size_t)nv * 12 : 0); }
     float bg = 0, R = 0, w = 0;
 };
 struct MeshState {
@@ -34,10 +44,11 @@ struct MeshState {
     SnapRing ring;
     MeshMeta m[2];
     long last_v = 0, last_q = 0;
-    bool last_attr = false;
+    unsigned last_what = 0;
 };
 
 static const char* const MESH_SINGLE = "mesh snapshots are single-GPU only: a decomposed run merges its blocks' level-set lists (fluid_sdf_grids_merge) and meshes the result on the host (fluid_sdf_mesh)";
+static const char* const MESH_EX_SINGLE = "mesh snapshots with normals or triangles are single-GPU only: a decomposed run merges its blocks' level-set lists (fluid_sdf_grids_merge), meshes the result on the host (fluid_sdf_mesh) and adds fluid_sdf_mesh_normals and fluid_mesh_triangles";
 static const char* const MESH_FILT_SINGLE = "filtered mesh snapshots are single-GPU only: a decomposed run merges its blocks' level-set lists (fluid_sdf_grids_merge), filters the result (fluid_sdf_filter) and meshes it on the host (fluid_sdf_mesh)";
 
 static int mesh_init(fluid_sim* s)
@@ -82,8 +93,9 @@ static int mesh_scratch(MeshState* o, long leaves)
     return FLUID_OK;
 }
 
-static int mesh_capture(fluid_sim* s, const fluid_sdf_params_t* p, const fluid_sdf_filter_t* filt, bool attr = false)
+static int mesh_capture(fluid_sim* s, const fluid_sdf_params_t* p, const fluid_sdf_filter_t* filt, unsigned what = 0)
 {
+    const bool attr = (what & FLUID_MESH_VELOCITY) != 0;
     SdfFront f;
     int rc = sdf_begin(s, p, &f, filt);
     if (rc) return rc;
@@ -111,27 +123,28 @@ static int mesh_capture(fluid_sim* s, const fluid_sdf_params_t* p, const fluid_s
             return fail(FLUID_ERR_ARG, "mesh: more than 2^31 - 1 vertices or quads");
         nv = (long)o->h_tot[0], nq = (long)o->h_tot[1];
     }
-    const size_t bytes = (size_t)nq * 16 + (size_t)nv * (attr ? 24 : 12);
+    MeshMeta nm;
+    nm.nv = nv, nm.nq = nq;
+    nm.what = what;
+    nm.bg = g.bg, nm.R = g.R, nm.w = g.w;
+    const size_t bytes = nm.bytes();
     if ((rc = snap_reserve(q, bytes, 4096))) return rc;
-    m.nv = nv, m.nq = nq;
-    m.attr = attr;
-    m.bg = g.bg, m.R = g.R, m.w = g.w;
+    m = nm;
     if (nv > 0) {
-        if (attr)
-            launch_mesh_emit_attr(s->st, g, f.tv, f.flags, f.tm, f.tvel, o->cmask, o->cpre, o->vcnt, o->qcnt, o->vbase, o->qbase,
-                                  (float*)(q.dev + (size_t)nq * 16), (uint32_t*)q.dev, (float*)(q.dev + (size_t)nq * 16 + (size_t)nv * 12));
-        else
-            launch_mesh_emit(s->st, g, f.tv, f.flags, o->cmask, o->cpre, o->vcnt, o->qcnt, o->vbase, o->qbase, (float*)(q.dev + (size_t)nq * 16),
-                             (uint32_t*)q.dev);
+        float* const vert = (float*)(q.dev + m.vert_at());
+        launch_mesh_emit(s->st, g, f.tv, f.flags, attr ? f.tm : nullptr, attr ? f.tvel : nullptr, o->cmask, o->cpre, o->vcnt, o->qcnt, o->vbase, o->qbase,
+                         vert, (uint32_t*)q.dev, attr ? (float*)(q.dev + m.vel_at()) : nullptr,
+                         (what & FLUID_MESH_NORMALS) ? (float*)(q.dev + m.nrm_at()) : nullptr);
+        if (what & FLUID_MESH_TRIANGLES) launch_mesh_tris(s->st, nq, nv, (const uint32_t*)q.dev, vert, (uint32_t*)(q.dev + m.tris_at()));
         HIPCHK(hipGetLastError());
     }
     if ((rc = snap_commit(o->ring, s->st, nv > 0 ? bytes : 0))) return rc;
     o->last_v = nv, o->last_q = nq;
-    o->last_attr = attr;
+    o->last_what = what;
     return FLUID_OK;
 }
 
-static int mesh_wait(fluid_sim* s, fluid_mesh_t* out, fluid_mesh_attr_t* at)
+static int mesh_wait(fluid_sim* s, fluid_mesh_t* out, fluid_mesh_attr_t* at, fluid_mesh_ex_t* ex = nullptr)
 {
     if (!out) return fail(FLUID_ERR_ARG, "null argument");
     MeshState* o = s->mesh;
@@ -147,10 +160,18 @@ static int mesh_wait(fluid_sim* s, fluid_mesh_t* out, fluid_mesh_attr_t* at)
     out->half_width = m.w;
     out->background = m.bg;
     out->quads = m.nq ? (const uint32_t*)host : nullptr;
-    out->vertices = m.nv ? (const float*)(host + (size_t)m.nq * 16) : nullptr;
+    out->vertices = m.nv ? (const float*)(host + m.vert_at()) : nullptr;
+    const float* const vel = m.nv && (m.what & FLUID_MESH_VELOCITY) ? (const float*)(host + m.vel_at()) : nullptr;
     if (at) {
         at->n_vertices = m.nv;
-        at->velocity = m.nv && m.attr ? (const float*)(host + (size_t)m.nq * 16 + (size_t)m.nv * 12) : nullptr;
+        at->velocity = vel;
+    }
+    if (ex) {
+        const bool tris = m.nq && (m.what & FLUID_MESH_TRIANGLES);
+        ex->velocity = vel;
+        ex->normals = m.nv && (m.what & FLUID_MESH_NORMALS) ? (const float*)(host + m.nrm_at()) : nullptr;
+        ex->triangles = tris ? (const uint32_t*)(host + m.tris_at()) : nullptr;
+        ex->n_triangles = tris ? 2 * m.nq : 0;
     }
     return FLUID_OK;
 }
@@ -179,7 +200,7 @@ int fluid_mesh_wait(fluid_sim_t* s, fluid_mesh_t* out)
 int fluid_mesh_snapshot_attr(fluid_sim_t* s, const fluid_sdf_params_t* p, const fluid_sdf_filter_t* f)
 {
     int rc = snap_guard(s, ATTR_SINGLE);
-    return rc ? rc : mesh_capture(s, p, f, true);
+    return rc ? rc : mesh_capture(s, p, f, FLUID_MESH_VELOCITY);
 }
 
 int fluid_mesh_wait_attr(fluid_sim_t* s, fluid_mesh_t* out, fluid_mesh_attr_t* attr)
@@ -188,13 +209,31 @@ int fluid_mesh_wait_attr(fluid_sim_t* s, fluid_mesh_t* out, fluid_mesh_attr_t* a
     return rc ? rc : mesh_wait(s, out, attr);
 }
 
+int fluid_mesh_snapshot_ex(fluid_sim_t* s, const fluid_sdf_params_t* p, const fluid_sdf_filter_t* f, uint32_t what)
+{
+    if (int rc = snap_guard(s, MESH_EX_SINGLE)) return rc;
+    if (what & ~(FLUID_MESH_VELOCITY | FLUID_MESH_NORMALS | FLUID_MESH_TRIANGLES)) return fail(FLUID_ERR_ARG, "fluid_mesh_snapshot_ex: unknown bits in `what`");
+    return mesh_capture(s, p, f, what);
+}
+
+int fluid_mesh_wait_ex(fluid_sim_t* s, fluid_mesh_t* out, fluid_mesh_ex_t* ex)
+{
+    int rc = snap_guard(s, MESH_EX_SINGLE);
+    return rc ? rc : mesh_wait(s, out, nullptr, ex);
+}
+
 int fluid_mesh_stats(fluid_sim_t* s, int64_t* vertices, int64_t* quads, int64_t* bytes_to_host)
 {
     if (int rc = snap_guard(s, MESH_SINGLE)) return rc;
     const int64_t nv = s->mesh ? s->mesh->last_v : 0, nq = s->mesh ? s->mesh->last_q : 0;
     if (vertices) *vertices = nv;
     if (quads) *quads = nq;
-    if (bytes_to_host) *bytes_to_host = s->mesh ? (s->mesh->last_attr ? 24 : 12) * nv + 16 * nq + 8 : 0;
+    if (bytes_to_host) {
+        MeshMeta m;
+        m.nv = nv, m.nq = nq;
+        m.what = s->mesh ? s->mesh->last_what : 0;
+        *bytes_to_host = s->mesh ? (int64_t)m.bytes() + 8 : 0;
+    }
     return FLUID_OK;
 }
 

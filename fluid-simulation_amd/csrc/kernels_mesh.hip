@@ -25,6 +25,10 @@
 //          lower voxels (ballots of the three edge bits) — position alone decides the place, there is no ordering by arrival.  The
 //          number of a vertex in a neighbour leaf at -1 is vbase[leaf'] + the popcount of that leaf's stored mask below the cell.
 //   emit<true> ("liquid surface, attributes") also writes a velocity per vertex from the search's per-voxel velocities and masks.
+//   emit<., true> ("normals and triangles") also writes a unit normal per vertex: the gradient of the trilinear interpolant of the
+//          cell's eight corners at the vertex's offset in its cell, from the tile the block has staged anyway.
+//   tris   a launch of its own behind emit (a quad's vertices may be another block's of the same emit launch): one thread per
+//          quad, its 16 bytes and its four vertices in, two triangles cut along the shorter diagonal out.
 // Arithmetic of a vertex: include/fluid_hip.h; float, no FMA (-ffp-contract=off), the division correctly rounded
 // (-fhip-fp32-correctly-rounded-divide-sqrt).
 #include "common.h"
@@ -182,13 +186,15 @@ __device__ __forceinline__ void mesh_edge_vel(const float* A, const unsigned cha
 // ATTR: beside the values the block stages the velocities (3 x 9^3 floats) and the active bits (one byte each) of the same up to
 // eight leaves, not active wherever the leaf is unflagged or outside the range (the search's tm / tvel of such a leaf are stale or
 // do not exist); each mixed cell's thread writes its vertex velocity to the place its vertex goes.
-template <bool ATTR>
+// NORMALS: each mixed cell's thread also writes the unit normal of its vertex (include/fluid_hip.h, "normals and triangles") from
+// the offsets it has just formed and the eight corners in V: no further LDS, loads or atomics.
+template <bool ATTR, bool NORMALS>
 __global__ __launch_bounds__(512) void k_mesh_emit(SdfGeom g, const float* __restrict__ tv, const int* __restrict__ flags,
                                                    const unsigned long long* __restrict__ cmask, const int* __restrict__ cpre,
                                                    const int* __restrict__ vcnt, const int* __restrict__ qcnt, const int* __restrict__ vbase,
                                                    const int* __restrict__ qbase, float* __restrict__ vertices, uint4* __restrict__ quads,
                                                    const unsigned long long* __restrict__ tm, const float* __restrict__ tvel,
-                                                   float* __restrict__ vvel)
+                                                   float* __restrict__ vvel, float* __restrict__ vnrm)
 {
     __shared__ float V[MESH_V];
     __shared__ float A[ATTR ? 3 * MESH_V : 1];
@@ -264,9 +270,39 @@ __global__ __launch_bounds__(512) void k_mesh_emit(SdfGeom g, const float* __res
         const float kf = (float)k;
         const size_t vn = (size_t)(vbase[l.j] + cpre[l.j * 8 + x] + __popcll(b & lt));
         float* out = vertices + 3 * vn;
-        out[0] = (float)px + sx / kf;
-        out[1] = (float)py + sy / kf;
-        out[2] = (float)pz + sz / kf;
+        const float fx = sx / kf;   // the vertex's offset in its cell
+        out[0] = (float)px + fx;
+        const float fy = sy / kf;
+        out[1] = (float)py + fy;
+        const float fz = sz / kf;
+        out[2] = (float)pz + fz;
+        if (NORMALS) {
+            // all 12 edges, the order of the vertex: per axis the two other axes, ascending, at (0,0), (0,1), (1,0), (1,1)
+            const float ex = 1.0f - fx, ey = 1.0f - fy, ez = 1.0f - fz;
+            float gx = 0.0f, gy = 0.0f, gz = 0.0f;
+#pragma unroll
+            for (int o = 0; o < 4; ++o) {
+                const int d1 = o >> 1, d2 = o & 1;
+                const float wx = (d1 ? fy : ey) * (d2 ? fz : ez);
+                const float wy = (d1 ? fx : ex) * (d2 ? fz : ez);
+                const float wz = (d1 ? fx : ex) * (d2 ? fy : ey);
+                const float dx = c[81 + d1 * 9 + d2] - c[d1 * 9 + d2];
+                const float dy = c[d1 * 81 + 9 + d2] - c[d1 * 81 + d2];
+                const float dz = c[d1 * 81 + d2 * 9 + 1] - c[d1 * 81 + d2 * 9];
+                gx = gx + wx * dx;
+                gy = gy + wy * dy;
+                gz = gz + wz * dz;
+            }
+            float l2 = gx * gx;
+            l2 = l2 + gy * gy;
+            l2 = l2 + gz * gz;
+            const float len = sqrtf(l2);
+            const bool some = len > 0.0f;   // (false for a NaN too)
+            float* on = vnrm + 3 * vn;
+            on[0] = some ? gx / len : 0.0f;
+            on[1] = some ? gy / len : 0.0f;
+            on[2] = some ? gz / len : 0.0f;
+        }
         if (ATTR) {
             const float kvf = (float)kv;
             float* ov = vvel + 3 * vn;
@@ -294,6 +330,51 @@ __global__ __launch_bounds__(512) void k_mesh_emit(SdfGeom g, const float* __res
     }
 }
 
+// Triangles ("normals and triangles"): thread i owns quad i = (a, b, c, d) and writes triangles 2i and 2i + 1, cut along the shorter
+// diagonal of the vertex positions (d13 < d02: (a, b, d), (b, c, d); otherwise, ties and NaN included: (a, b, c), (a, c, d)).  tris
+// is 16-byte aligned (fluid_mesh.hip puts it right behind the quads), so quad i's 24-byte record starts at a multiple of 8 for every
+// i and at a multiple of 16 for even i: one 16-byte and one 8-byte store, in the order the record's alignment allows.  An entry
+// >= nv cannot come from emit (mesh_vertex_number's header); the guard keeps a wrong number from reading out of the slot.
+__global__ __launch_bounds__(256) void k_mesh_tris(long nq, long nv, const uint4* __restrict__ quads, const float* __restrict__ vertices,
+                                                   uint2* __restrict__ tris)
+{
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nq) return;
+    const uint4 q = quads[i];
+    const unsigned e[4] = {q.x, q.y, q.z, q.w};
+    float P[4][3];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const size_t at = (long)e[k] < nv ? 3 * (size_t)e[k] : 0;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) P[k][a] = vertices[at + a];
+    }
+    float d02, d13;
+    {
+        const float x = P[2][0] - P[0][0], y = P[2][1] - P[0][1], z = P[2][2] - P[0][2];
+        d02 = x * x;
+        d02 = d02 + y * y;
+        d02 = d02 + z * z;
+    }
+    {
+        const float x = P[3][0] - P[1][0], y = P[3][1] - P[1][1], z = P[3][2] - P[1][2];
+        d13 = x * x;
+        d13 = d13 + y * y;
+        d13 = d13 + z * z;
+    }
+    const bool cut13 = d13 < d02;
+    const unsigned t0 = q.x, t1 = q.y, t2 = cut13 ? q.w : q.z;
+    const unsigned t3 = cut13 ? q.y : q.x, t4 = q.z, t5 = q.w;
+    uint2* out = tris + 3 * i;
+    if (i & 1) {
+        out[0] = make_uint2(t0, t1);
+        *(uint4*)(out + 1) = make_uint4(t2, t3, t4, t5);
+    } else {
+        *(uint4*)out = make_uint4(t0, t1, t2, t3);
+        out[2] = make_uint2(t4, t5);
+    }
+}
+
 void launch_mesh_mark(hipStream_t st, const SdfGeom& g, const float* tv, const int* flags, uint64_t* cmask, int* cpre, int* vcnt, int* qcnt,
                       unsigned* tot)
 {
@@ -301,19 +382,23 @@ void launch_mesh_mark(hipStream_t st, const SdfGeom& g, const float* tv, const i
     hipLaunchKernelGGL(k_mesh_totals, dim3(1), dim3(1024), 0, st, g.leaves(), (const int*)vcnt, (const int*)qcnt, tot);
 }
 
-void launch_mesh_emit(hipStream_t st, const SdfGeom& g, const float* tv, const int* flags, const uint64_t* cmask, const int* cpre, const int* vcnt,
-                      const int* qcnt, const int* vbase, const int* qbase, float* vertices, uint32_t* quads)
+// tm / tvel / vvel: non-NULL for a velocity per vertex; vnrm: non-NULL for a normal per vertex
+void launch_mesh_emit(hipStream_t st, const SdfGeom& g, const float* tv, const int* flags, const uint64_t* tm, const float* tvel,
+                      const uint64_t* cmask, const int* cpre, const int* vcnt, const int* qcnt, const int* vbase, const int* qbase, float* vertices,
+                      uint32_t* quads, float* vvel, float* vnrm)
 {
-    hipLaunchKernelGGL(k_mesh_emit<false>, dim3((unsigned)g.leaves()), dim3(512), 0, st, g, tv, flags, (const unsigned long long*)cmask, cpre, vcnt, qcnt,
-                       vbase, qbase, vertices, (uint4*)quads, (const unsigned long long*)nullptr, (const float*)nullptr, (float*)nullptr);
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)g.leaves()), dim3(512), 0, st, g, tv, flags, (const unsigned long long*)cmask, cpre, vcnt, qcnt, vbase,
+                           qbase, vertices, (uint4*)quads, (const unsigned long long*)tm, tvel, vvel, vnrm);
+    };
+    if (vvel) vnrm ? go(k_mesh_emit<true, true>) : go(k_mesh_emit<true, false>);
+    else vnrm ? go(k_mesh_emit<false, true>) : go(k_mesh_emit<false, false>);
 }
 
-void launch_mesh_emit_attr(hipStream_t st, const SdfGeom& g, const float* tv, const int* flags, const uint64_t* tm, const float* tvel,
-                           const uint64_t* cmask, const int* cpre, const int* vcnt, const int* qcnt, const int* vbase, const int* qbase,
-                           float* vertices, uint32_t* quads, float* vvel)
+void launch_mesh_tris(hipStream_t st, long nq, long nv, const uint32_t* quads, const float* vertices, uint32_t* tris)
 {
-    hipLaunchKernelGGL(k_mesh_emit<true>, dim3((unsigned)g.leaves()), dim3(512), 0, st, g, tv, flags, (const unsigned long long*)cmask, cpre, vcnt, qcnt,
-                       vbase, qbase, vertices, (uint4*)quads, (const unsigned long long*)tm, tvel, vvel);
+    if (nq <= 0) return;
+    hipLaunchKernelGGL(k_mesh_tris, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, nq, nv, (const uint4*)quads, vertices, (uint2*)tris);
 }
 
 }  // namespace fl

@@ -8,6 +8,10 @@
 //                              a hand-made list can drive into the rule for an edge with no active end.
 //   fluid_sdf_attr_to_dense    ids and velocities of a leaf list on the dense grid.
 //   fluid_write_ply_mesh_attr  binary little-endian PLY with vx / vy / vz per vertex.
+//   fluid_sdf_mesh_normals     ("normals and triangles") the vertex normals of fluid_sdf_mesh(grid): the same walk with the values
+//                              alone in the tile.  The second implementation k_mesh_emit<., true> is compared with, and the only
+//                              one a hand-made list can drive into a NaN or a zero gradient.
+//   fluid_mesh_triangles, fluid_write_ply_mesh_ex   their bodies are ply_mesh.h's.
 // Arithmetic: float, no contraction (the build states -ffp-contract=off).
 #include <algorithm>
 #include <cmath>
@@ -89,9 +93,119 @@ struct Tile {
     }
 };
 
+// the walk of fluid_sdf_mesh_attr with the values alone: what fluid_sdf_mesh_normals needs
+struct NormalTile {
+    const fluid_sdf_grid_t* g;
+    int lo, hi;
+    float V[TILE];
+
+    void load(const Org& o)
+    {
+        for (int i = 0; i < TILE; ++i) V[i] = g->background;
+        load_tile(g, o, [&](long l, int off, int i) { V[i] = g->values[512 * (size_t)l + off]; });
+    }
+    bool mixed(int i, int px, int py, int pz) const
+    {
+        unsigned m = 0;
+        for (int d = 0; d < 8; ++d) m |= (V[i + (d >> 2) * 81 + ((d >> 1) & 1) * 9 + (d & 1)] < 0.0f ? 1u : 0u) << d;
+        const bool cx = px >= lo && px <= hi - 1, cy = py >= lo && py <= hi - 1, cz = pz >= lo && pz <= hi - 1;
+        return cx && cy && cz && m != 0 && m != 255;
+    }
+    // the normal of the vertex of the (mixed) cell whose min corner is place i of the tile
+    void normal(int i, float* out) const
+    {
+        static const int stride[3] = {81, 9, 1};
+        // the vertex's offset in its cell, as mesh_host.cpp forms it
+        float s[3] = {0.0f, 0.0f, 0.0f};
+        int k = 0;
+        for (int a = 0; a < 3; ++a) {
+            const int b1 = a == 0 ? 1 : 0, b2 = a == 2 ? 1 : 2;
+            for (int o = 0; o < 4; ++o) {
+                const int d1 = o >> 1, d2 = o & 1;
+                const int i0 = i + d1 * stride[b1] + d2 * stride[b2];
+                const float v0 = V[i0], v1 = V[i0 + stride[a]];
+                if ((v0 < 0.0f) == (v1 < 0.0f)) continue;
+                const float den = v0 - v1;
+                const float t = v0 / den;
+                s[a] += t;
+                s[b1] += (float)d1;
+                s[b2] += (float)d2;
+                ++k;
+            }
+        }
+        const float kf = (float)k;
+        const float f[3] = {s[0] / kf, s[1] / kf, s[2] / kf};
+        const float e[3] = {1.0f - f[0], 1.0f - f[1], 1.0f - f[2]};
+        float g3[3];
+        for (int a = 0; a < 3; ++a) {
+            const int b1 = a == 0 ? 1 : 0, b2 = a == 2 ? 1 : 2;
+            float ga = 0.0f;
+            for (int o = 0; o < 4; ++o) {
+                const int d1 = o >> 1, d2 = o & 1;
+                const int i0 = i + d1 * stride[b1] + d2 * stride[b2];
+                const float w1 = d1 ? f[b1] : e[b1], w2 = d2 ? f[b2] : e[b2];
+                const float w = w1 * w2;
+                const float dv = V[i0 + stride[a]] - V[i0];
+                const float wd = w * dv;
+                ga = ga + wd;
+            }
+            g3[a] = ga;
+        }
+        float l2 = g3[0] * g3[0];
+        const float yy = g3[1] * g3[1], zz = g3[2] * g3[2];
+        l2 = l2 + yy;
+        l2 = l2 + zz;
+        const float len = std::sqrt(l2);
+        const bool some = len > 0.0f;   // (false for a NaN too)
+        for (int a = 0; a < 3; ++a) out[a] = some ? g3[a] / len : 0.0f;
+    }
+};
+
 }  // namespace
 
 extern "C" {
+
+int64_t fluid_sdf_mesh_normals(const fluid_sdf_grid_t* g, int64_t cap_vertices, float* normals)
+{
+    if (check_list(g) != FLUID_OK) return -FLUID_ERR_ARG;
+    NormalTile me;
+    me.g = g;
+    me.lo = -(g->n / 2), me.hi = me.lo + g->n - 1;
+    const std::vector<Org> work = mesh_work_list(g);
+    // pass 0 counts (nothing is written before the cap is known to hold), pass 1 writes
+    int64_t nv = 0;
+    for (int pass = 0; pass < (normals ? 2 : 1); ++pass) {
+        if (pass == 1 && nv > cap_vertices) return -FLUID_ERR_ARG;
+        int64_t k = 0;
+        for (const Org& w : work) {
+            me.load(w);
+            for (int off = 0; off < 512; ++off) {
+                const int x = off >> 6, y = (off >> 3) & 7, z = off & 7;
+                const int i = (x * 9 + y) * 9 + z;
+                if (!me.mixed(i, w.x + x, w.y + y, w.z + z)) continue;
+                if (pass == 1) me.normal(i, normals + 3 * (size_t)k);
+                ++k;
+            }
+        }
+        nv = k;
+        if (nv > 0x7fffffffLL) return -FLUID_ERR_ARG;
+    }
+    return nv;
+}
+
+int64_t fluid_mesh_triangles(const fluid_mesh_t* m, int64_t cap_triangles, uint32_t* triangles) { return mesh_triangles(m, cap_triangles, triangles); }
+
+int fluid_write_ply_mesh_ex(const char* path, const fluid_mesh_t* m, const fluid_mesh_ex_t* ex, float voxel_size, float velocity_scale)
+{
+    if (!path || !m || m->n_vertices < 0 || m->n_quads < 0 || !(voxel_size > 0.0f)) return FLUID_ERR_ARG;
+    if ((m->n_vertices > 0 && !m->vertices) || (m->n_quads > 0 && !m->quads)) return FLUID_ERR_ARG;
+    const float* vel = ex ? ex->velocity : nullptr;
+    const float* nrm = ex ? ex->normals : nullptr;
+    const uint32_t* tri = ex ? ex->triangles : nullptr;
+    if (vel && !std::isfinite(velocity_scale)) return FLUID_ERR_ARG;
+    if (tri && ex->n_triangles != 2 * m->n_quads) return FLUID_ERR_ARG;
+    return write_ply(path, m, voxel_size, vel != nullptr, vel, velocity_scale, nrm, tri);
+}
 
 int64_t fluid_sdf_mesh_attr(const fluid_sdf_grid_t* g, const fluid_sdf_attr_t* at, int64_t cap_vertices, float* velocity)
 {

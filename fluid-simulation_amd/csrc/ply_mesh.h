@@ -1,5 +1,7 @@
-// The body of fluid_write_ply_mesh (mesh_host.cpp) and fluid_write_ply_mesh_attr (mesh_attr_host.cpp), which check their own
-// arguments first: binary little-endian PLY, a vertex record of 12 bytes of scaled position, or 24 with the scaled velocity.
+// The body of fluid_write_ply_mesh (mesh_host.cpp), fluid_write_ply_mesh_attr and fluid_write_ply_mesh_ex (mesh_attr_host.cpp),
+// which check their own arguments first: binary little-endian PLY, a vertex record of 12 bytes of scaled position, 12 more of the
+// normal and 12 more of the scaled velocity where given; faces are the quads, or the triangles where given.  And the body of
+// fluid_mesh_triangles (include/fluid_hip.h, "normals and triangles").
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -9,17 +11,53 @@
 
 namespace {
 
-// with_velocity: vx / vy / vz in the header and velocity[3 i ..] * velocity_scale behind vertex i's position
-inline int write_ply(const char* path, const fluid_mesh_t* m, float voxel_size, bool with_velocity, const float* velocity, float velocity_scale)
+// quad i = (a, b, c, d) of the (checked) mesh -> triangles 2i and 2i + 1 at t[0..5], cut along the shorter diagonal
+inline void quad_triangles(const float* V, const uint32_t* q, uint32_t* t)
+{
+    float d[2];
+    for (int k = 0; k < 2; ++k) {
+        const float* p0 = V + 3 * (size_t)q[k];
+        const float* p1 = V + 3 * (size_t)q[k + 2];
+        const float x = p1[0] - p0[0], y = p1[1] - p0[1], z = p1[2] - p0[2];
+        float s = x * x;
+        s = s + y * y;
+        s = s + z * z;
+        d[k] = s;
+    }
+    const bool cut13 = d[1] < d[0];   // ties and NaN: the 0-2 diagonal
+    t[0] = q[0], t[1] = q[1], t[2] = cut13 ? q[3] : q[2];
+    t[3] = cut13 ? q[1] : q[0], t[4] = q[2], t[5] = q[3];
+}
+
+// the body of fluid_mesh_triangles
+inline int64_t mesh_triangles(const fluid_mesh_t* m, int64_t cap_triangles, uint32_t* triangles)
+{
+    if (!m || m->n_vertices < 0 || m->n_quads < 0 || m->n_quads > 0x7fffffffLL) return -FLUID_ERR_ARG;
+    if ((m->n_vertices > 0 && !m->vertices) || (m->n_quads > 0 && !m->quads)) return -FLUID_ERR_ARG;
+    for (int64_t i = 0; i < 4 * m->n_quads; ++i)
+        if ((int64_t)m->quads[i] >= m->n_vertices) return -FLUID_ERR_ARG;
+    if (!triangles) return 2 * m->n_quads;
+    if (2 * m->n_quads > cap_triangles) return -FLUID_ERR_ARG;
+    for (int64_t i = 0; i < m->n_quads; ++i) quad_triangles(m->vertices, m->quads + 4 * i, triangles + 6 * i);
+    return 2 * m->n_quads;
+}
+
+// with_velocity: vx / vy / vz in the header and velocity[3 i ..] * velocity_scale in vertex i's record; normals: nx / ny / nz between
+// the position and the velocity, unscaled; triangles (3 uint32 each, 2 per quad): the faces, instead of the quads
+inline int write_ply(const char* path, const fluid_mesh_t* m, float voxel_size, bool with_velocity, const float* velocity, float velocity_scale,
+                     const float* normals = nullptr, const uint32_t* triangles = nullptr)
 {
     for (int64_t i = 0; i < 4 * m->n_quads; ++i)
         if ((int64_t)m->quads[i] >= m->n_vertices) return FLUID_ERR_ARG;
+    for (int64_t i = 0; triangles && i < 6 * m->n_quads; ++i)
+        if ((int64_t)triangles[i] >= m->n_vertices) return FLUID_ERR_ARG;
     FILE* f = fopen(path, "wb");
     if (!f) return FLUID_ERR_ARG;
     bool ok = fprintf(f,
                       "ply\nformat binary_little_endian 1.0\nelement vertex %lld\nproperty float x\nproperty float y\nproperty float z\n"
-                      "%selement face %lld\nproperty list uchar uint vertex_indices\nend_header\n",
-                      (long long)m->n_vertices, with_velocity ? "property float vx\nproperty float vy\nproperty float vz\n" : "", (long long)m->n_quads) > 0;
+                      "%s%selement face %lld\nproperty list uchar uint vertex_indices\nend_header\n",
+                      (long long)m->n_vertices, normals ? "property float nx\nproperty float ny\nproperty float nz\n" : "",
+                      with_velocity ? "property float vx\nproperty float vy\nproperty float vz\n" : "", (long long)(triangles ? 2 * m->n_quads : m->n_quads)) > 0;
     std::vector<char> buf;
     buf.reserve((size_t)1 << 20);
     auto flush = [&] {
@@ -27,15 +65,24 @@ inline int write_ply(const char* path, const fluid_mesh_t* m, float voxel_size, 
         buf.clear();
     };
     for (int64_t i = 0; ok && i < m->n_vertices; ++i) {
-        float rec[6];
+        float rec[9];
+        int k = 3;
         for (int a = 0; a < 3; ++a) rec[a] = m->vertices[3 * i + a] * voxel_size;
+        if (normals)
+            for (int a = 0; a < 3; ++a) rec[k++] = normals[3 * i + a];
         if (with_velocity)
-            for (int a = 0; a < 3; ++a) rec[3 + a] = velocity[3 * i + a] * velocity_scale;
+            for (int a = 0; a < 3; ++a) rec[k++] = velocity[3 * i + a] * velocity_scale;
         const char* c = (const char*)rec;
-        buf.insert(buf.end(), c, c + (with_velocity ? 24 : 12));
+        buf.insert(buf.end(), c, c + 4 * k);
         if (buf.size() >= ((size_t)1 << 20) - 32) flush();
     }
-    for (int64_t i = 0; ok && i < m->n_quads; ++i) {
+    for (int64_t i = 0; ok && triangles && i < 2 * m->n_quads; ++i) {
+        buf.push_back((char)3);
+        const char* c = (const char*)(triangles + 3 * i);
+        buf.insert(buf.end(), c, c + 12);
+        if (buf.size() >= ((size_t)1 << 20) - 32) flush();
+    }
+    for (int64_t i = 0; ok && !triangles && i < m->n_quads; ++i) {
         buf.push_back((char)4);
         const char* c = (const char*)(m->quads + 4 * i);
         buf.insert(buf.end(), c, c + 16);

@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 
-from ._lib import lib, check, FluidError, Params, StepStats, FIELD, Source, LeafGridC, SdfParams, SdfGridC, SdfFilter, MeshC, SdfAttrC, MeshAttrC, SdfAttrPartC
+from ._lib import lib, check, FluidError, Params, StepStats, FIELD, Source, LeafGridC, SdfParams, SdfGridC, SdfFilter, MeshC, SdfAttrC, MeshAttrC, SdfAttrPartC, MeshExC, MESH
 
 _FIELD_DTYPE = {
     FIELD.CONTAINER: (np.float32, 1), FIELD.WEIGHTS: (np.float32, 1), FIELD.OUTPUT: (np.float32, 1),
@@ -243,12 +243,31 @@ def sdf_mesh(grid):
     return Mesh(grid.n, v, q, grid.background, grid.radius, grid.half_width)
 
 
-def write_ply_mesh(path, mesh, voxel_size, velocity=None, velocity_scale=1.0):
+def write_ply_mesh(path, mesh, voxel_size, velocity=None, velocity_scale=1.0, normals=None, triangles=None):
     """Binary little-endian PLY of a Mesh (or of a (vertices, quads) pair); positions are index space times voxel_size
     (fluid_write_ply_mesh: host only).  velocity (nv, 3): vx / vy / vz per vertex as well, times velocity_scale
-    (fluid_write_ply_mesh_attr)."""
+    (fluid_write_ply_mesh_attr).  normals (nv, 3): nx / ny / nz per vertex, unscaled; triangles (2 nq, 3): the faces are these
+    instead of the quads (fluid_write_ply_mesh_ex)."""
     if not isinstance(mesh, Mesh):
         mesh = Mesh(0, mesh[0], mesh[1])
+    if normals is not None or triangles is not None:
+        nv = len(mesh.vertices)
+        keep = [np.zeros(4, np.float32)]                     # an empty part still selects its header lines: any non-NULL pointer
+        ex = MeshExC(None, None, None, 0)
+        for name, arr, dt, rows in (("velocity", velocity, np.float32, nv), ("normals", normals, np.float32, nv), ("triangles", triangles, np.uint32, None)):
+            if arr is None:
+                continue
+            a = np.ascontiguousarray(arr, dtype=dt).reshape(-1, 3)
+            if rows is not None and len(a) != rows:
+                raise FluidError(1, f"fluid_write_ply_mesh_ex: {len(a)} {name} for {rows} vertices")
+            keep.append(a)
+            setattr(ex, name, a.ctypes.data if len(a) else keep[0].ctypes.data)
+            if name == "triangles":
+                ex.n_triangles = len(a)
+        rc = lib.fluid_write_ply_mesh_ex(str(path).encode(), C.byref(mesh._c()), C.byref(ex), float(voxel_size), float(velocity_scale))
+        if rc != 0:
+            raise FluidError(rc, "fluid_write_ply_mesh_ex: a bad mesh, a triangle count that is not twice the quad count, an entry beyond the vertices, a bad scale or path")
+        return
     if velocity is None:
         check(lib.fluid_write_ply_mesh(str(path).encode(), C.byref(mesh._c()), float(voxel_size)))
         return
@@ -345,6 +364,28 @@ def sdf_mesh_attr(grid, attr):
     if nv and lib.fluid_sdf_mesh_attr(C.byref(c), C.byref(a), nv, vel.ctypes.data_as(C.c_void_p)) != nv:
         raise FluidError(1, "fluid_sdf_mesh_attr: the second call disagrees with the count")
     return vel
+
+
+def sdf_mesh_normals(grid):
+    """normals (nv, 3) float32: the unit vertex normals of sdf_mesh(grid), in its vertex order (fluid_sdf_mesh_normals: host only)."""
+    c, _keep = grid._c()
+    nv = lib.fluid_sdf_mesh_normals(C.byref(c), 0, None)
+    if nv < 0:
+        raise FluidError(-nv, "fluid_sdf_mesh_normals: a bad leaf list")
+    nrm = np.empty((nv, 3), np.float32)
+    if nv and lib.fluid_sdf_mesh_normals(C.byref(c), nv, nrm.ctypes.data_as(C.c_void_p)) != nv:
+        raise FluidError(1, "fluid_sdf_mesh_normals: the second call disagrees with the count")
+    return nrm
+
+
+def mesh_triangles(vertices, quads):
+    """triangles (2 nq, 3) uint32: every quad cut along its shorter diagonal, in quad order (fluid_mesh_triangles: host only)."""
+    m = Mesh(0, vertices, quads)
+    tri = np.empty((2 * len(m.quads), 3), np.uint32)
+    k = lib.fluid_mesh_triangles(C.byref(m._c()), len(tri), tri.ctypes.data_as(C.c_void_p) if len(tri) else None)
+    if k != len(tri):
+        raise FluidError(1 if k >= 0 else -k, "fluid_mesh_triangles: a bad mesh (a quad entry beyond the vertices?)")
+    return tri
 
 
 def sdf_attr_to_dense(grid, attr):
@@ -644,11 +685,16 @@ class FluidSim:
         return dict(zip(("leaves_in_grid", "leaves_listed", "bytes_to_host"), (x.value for x in v)))
 
     # ---- liquid surface as a mesh: surface nets of the level set (single GPU; include/fluid_hip.h) ----
-    def mesh_snapshot(self, radius, half_width, smooth=None, attr=False):
+    def mesh_snapshot(self, radius, half_width, smooth=None, attr=False, normals=False, triangles=False):
         """Enqueue the surface nets of the level set of the particles as they are now (parameters as sdf_snapshot, `smooth`
-        included); a step() called next overlaps the copy to the host.  attr=True: with a velocity per vertex (mesh_wait_attr)."""
+        included); a step() called next overlaps the copy to the host.  attr=True: with a velocity per vertex (mesh_wait_attr).
+        normals=True / triangles=True: with a unit normal per vertex / two triangles per quad (mesh_wait_ex)."""
         p = SdfParams(float(radius), float(half_width))
-        if attr:
+        if normals or triangles:
+            f = None if smooth is None else C.byref(_sdf_filter_of(smooth))
+            what = (MESH.VELOCITY if attr else 0) | (MESH.NORMALS if normals else 0) | (MESH.TRIANGLES if triangles else 0)
+            check(lib.fluid_mesh_snapshot_ex(self._h, C.byref(p), f, what))
+        elif attr:
             f = None if smooth is None else C.byref(_sdf_filter_of(smooth))
             check(lib.fluid_mesh_snapshot_attr(self._h, C.byref(p), f))
         elif smooth is None:
@@ -682,6 +728,24 @@ class FluidSim:
         if a.velocity:
             vel = np.ctypeslib.as_array(C.cast(a.velocity, C.POINTER(C.c_float)), shape=(m.n_vertices, 3)).copy()
         return v, q, vel
+
+    def mesh_wait_ex(self):
+        """(vertices, quads, {"velocity", "normals", "triangles"}) of the oldest mesh snapshot not yet waited for: (nv, 3) float32,
+        (nv, 3) float32, (2 nq, 3) uint32, each None if that snapshot was taken without it (or has no vertex / no quad)."""
+        m, e = MeshC(), MeshExC()
+        check(lib.fluid_mesh_wait_ex(self._h, C.byref(m), C.byref(e)))
+        v, q = np.empty((m.n_vertices, 3), np.float32), np.empty((m.n_quads, 4), np.uint32)
+        if m.n_vertices:
+            v[:] = np.ctypeslib.as_array(C.cast(m.vertices, C.POINTER(C.c_float)), shape=(m.n_vertices, 3))
+        if m.n_quads:
+            q[:] = np.ctypeslib.as_array(C.cast(m.quads, C.POINTER(C.c_uint32)), shape=(m.n_quads, 4))
+        parts = {"velocity": None, "normals": None, "triangles": None}
+        for name in ("velocity", "normals"):
+            if getattr(e, name):
+                parts[name] = np.ctypeslib.as_array(C.cast(getattr(e, name), C.POINTER(C.c_float)), shape=(m.n_vertices, 3)).copy()
+        if e.triangles:
+            parts["triangles"] = np.ctypeslib.as_array(C.cast(e.triangles, C.POINTER(C.c_uint32)), shape=(e.n_triangles, 3)).copy()
+        return v, q, parts
 
     def mesh_stats(self):
         v = [C.c_int64() for _ in range(3)]

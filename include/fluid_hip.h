@@ -736,7 +736,8 @@ int fluid_mesh_snapshot(fluid_sim_t* s, const fluid_sdf_params_t* p);
 /* The oldest snapshot not yet waited for (FLUID_ERR_STATE when there is none).  No counted particle or no mixed cell: counts 0 and
  * NULL pointers (quads is NULL whenever n_quads is 0).  The pointers stay valid until the SECOND following mesh snapshot. */
 int fluid_mesh_wait(fluid_sim_t* s, fluid_mesh_t* out);
-/* Of the last snapshot (any pointer may be NULL): bytes_to_host = 12 * vertices + 16 * quads + 8. */
+/* Of the last snapshot (any pointer may be NULL): bytes_to_host = 12 * vertices + 16 * quads + 8 (more for a snapshot with
+ * velocities, normals or triangles: "liquid surface, attributes" and "normals and triangles" below). */
 int fluid_mesh_stats(fluid_sim_t* s, int64_t* vertices, int64_t* quads, int64_t* bytes_to_host);
 /* Host only: the definition above applied to a leaf list, every unlisted leaf being +bg.  Returns the vertex count and *n_quads (may
  * be NULL).  vertices == quads == NULL: the counts only, the caps are ignored; otherwise both arrays are required, 3 * cap_vertices
@@ -882,6 +883,76 @@ int fluid_dist_sdf_wait_attr(fluid_sim_t* s, fluid_sdf_grid_t* grid, fluid_sdf_a
  * are valid.  Two passes over a k-way merge of the ascending lists; no dense grid. */
 int64_t fluid_sdf_attr_grids_merge(const fluid_sdf_grid_t* parts, const fluid_sdf_attr_part_t* attrs, int32_t n_parts, int64_t cap_leaves,
                                    int32_t* origin, float* values, uint64_t* active, uint32_t* id, float* velocity);
+
+/* ---- liquid surface as a mesh: normals and triangles ------------------------------------------------------------------------------
+ * Game engines and most realtime viewers take triangles and want a shading normal per vertex; face normals recomputed from a
+ * surface-nets mesh show facets.  The level set's gradient IS the normal, and the emit kernel holds the cell's eight corner values
+ * at the moment it writes the vertex.  Both are options of the mesh: with them off every byte and every stat is what it was.  Like
+ * the mesh itself they are exact and order-free: the kernels, the host functions below and the tests' numpy form (tests/
+ * mesh_normals_ref.py) are compared with ==.  Float throughout, no FMA; division and sqrtf are the correctly rounded IEEE operations;
+ * denormals are kept.
+ *
+ * Normal of a mixed cell's vertex.  f_axis = s_axis / (float)k is the vertex's offset in its cell, exactly as "liquid surface as a
+ * mesh" forms it before (float)c_axis is added (NOT vertex - c, which differs by the rounding of that add).  The normal is the
+ * gradient of the trilinear interpolant of the cell's eight corner values val(c + {0,1}^3) — inactive +-bg included, filtered values
+ * after a filter, the active mask plays no part — at f, normalised.  For axis a = x, y, z, with b1 < b2 the two other axes:
+ *   g_a = 0.0f
+ *   for (d1, d2) in (0,0), (0,1), (1,0), (1,1):                 (the mesh's edge order)
+ *       w1 = d1 ? f_b1 : (1.0f - f_b1);   w2 = d2 ? f_b2 : (1.0f - f_b2)
+ *       g_a = g_a + (w1 * w2) * (v1 - v0)                        (v0: the corner at (d1, d2) on (b1, b2) and 0 on a; v1: 1 on a)
+ *   l2 = g_x * g_x;  l2 = l2 + g_y * g_y;  l2 = l2 + g_z * g_z;  len = sqrtf(l2)
+ *   n_a = (len > 0.0f) ? g_a / len : +0.0f                       (all three components; a NaN length gives +0 too)
+ * Values are negative inside, so the normal points out of the liquid, as the quads' winding does.  All 12 edges enter, not only the
+ * counting ones.  Order: the mesh's vertex order.
+ * Stated limit: corners further than w from the surface are clamped to +-bg, so with w = 1 the direction is slightly biased in cells
+ * whose far corners sit on the plateau; w >= 2 avoids it.  On sheets thinner than a cell (under-resolved surface nets) a normal may
+ * oppose its quads' winding.  A central-difference gradient over a wider tile is not offered.
+ *
+ * Triangles.  Quad i with entries (a, b, c, d) gives triangles 2i and 2i + 1, cut along the shorter diagonal of the vertex positions
+ * in index space:  d02 = |V_c - V_a|^2, d13 = |V_d - V_b|^2, each as dx*dx, then + dy*dy, then + dz*dz over float differences;
+ *   d13 < d02:  (a, b, d), (b, c, d);      otherwise (ties and NaN):  (a, b, c), (a, c, d).
+ * The winding is the quad's, degenerate triangles are kept, the entries are uint32 vertex numbers: exactly 2 * n_quads triangles, in
+ * quad order.
+ *
+ * A decomposed run: mesh the merged list (fluid_sdf_mesh), then fluid_sdf_mesh_normals(&g, nv, normals) and
+ * fluid_mesh_triangles(&mesh, 2 * nq, triangles). */
+#define FLUID_MESH_VELOCITY  1u
+#define FLUID_MESH_NORMALS   2u
+#define FLUID_MESH_TRIANGLES 4u
+typedef struct fluid_mesh_ex {
+    const float* velocity;       /* 3 per vertex ("liquid surface, attributes"), or NULL                             */
+    const float* normals;        /* 3 per vertex, unit length or +0, or NULL                                         */
+    const uint32_t* triangles;   /* 3 per triangle, or NULL                                                          */
+    int64_t n_triangles;         /* 2 * n_quads with triangles, else 0                                               */
+} fluid_mesh_ex_t;
+/* fluid_mesh_snapshot / _filtered / _attr with any of the three parts: what = 0 is fluid_mesh_snapshot (f == NULL) or
+ * fluid_mesh_snapshot_filtered (f != NULL), what = FLUID_MESH_VELOCITY is fluid_mesh_snapshot_attr.  Same slots, stream, count of
+ * outstanding snapshots and range (the box dilated by 4 without a filter, 5 with one); vertices and quads are byte for byte the plain
+ * ones.  The record that travels is [quads | 24 B of triangles per quad | vertices | velocities | normals], each part only if asked
+ * for: the triangles start at a multiple of 16 for every count, so the kernel writes each quad's pair with one 16-byte and one
+ * 8-byte store.  fluid_mesh_stats: bytes_to_host = 16 nq + 12 nv (1 + velocity + normals) + 24 nq triangles + 8.  No scratch beyond
+ * what `what` asks for (velocities alone need the attribute scratch).  FLUID_ERR_ARG: as the siblings, or unknown bits in `what`.
+ * FLUID_ERR_STATE on a decomposed handle (both entry points): see the two host functions below. */
+int fluid_mesh_snapshot_ex(fluid_sim_t* s, const fluid_sdf_params_t* p, const fluid_sdf_filter_t* f /* NULL: unfiltered */, uint32_t what);
+/* fluid_mesh_wait, and the parts of the same snapshot (ex may be NULL): NULL for every part the snapshot was taken without, for
+ * velocity and normals with no vertex, for triangles with no quad.  fluid_mesh_wait and fluid_mesh_wait_attr on such a snapshot
+ * return what they know (the geometry; the velocity).  Lifetime of the pointers: that of the mesh's. */
+int fluid_mesh_wait_ex(fluid_sim_t* s, fluid_mesh_t* mesh, fluid_mesh_ex_t* ex);
+/* Host only: the vertex normals of fluid_sdf_mesh(grid), in its vertex order, into normals[3 * cap_vertices]; grid->values may be
+ * filtered values.  Returns the vertex count (normals == NULL: the count only, the cap is ignored), or -FLUID_ERR_ARG with nothing
+ * written: a list fluid_sdf_to_dense refuses, a cap too small, more than 2^31 - 1 vertices.  Works leaf by leaf with bisection for
+ * the neighbours, as fluid_sdf_mesh; no dense grid. */
+int64_t fluid_sdf_mesh_normals(const fluid_sdf_grid_t* grid, int64_t cap_vertices, float* normals);
+/* Host only: the triangles of any mesh into triangles[3 * cap_triangles].  Returns 2 * n_quads (triangles == NULL: the count only,
+ * the cap is ignored), or -FLUID_ERR_ARG with nothing written: mesh NULL, negative counts, a count without its array, a quad entry
+ * >= n_vertices, a cap too small, more than 2^31 - 1 quads. */
+int64_t fluid_mesh_triangles(const fluid_mesh_t* mesh, int64_t cap_triangles, uint32_t* triangles);
+/* Host only: fluid_write_ply_mesh / _attr with any of the parts of ex (NULL, or all parts NULL: fluid_write_ply_mesh's bytes).  The
+ * vertex record is x y z [nx ny nz] [vx vy vz]: `property float nx / ny / nz` after z, the normals unscaled; then vx / vy / vz times
+ * velocity_scale.  With ex->triangles the faces are `element face <2 nq>`, each the byte 3 and three uint32, instead of the quads;
+ * otherwise the quads are written as there.  FLUID_ERR_ARG as the siblings, and for n_triangles != 2 * n_quads with triangles, a
+ * triangle entry >= n_vertices, a velocity_scale that is not finite with velocities. */
+int fluid_write_ply_mesh_ex(const char* path, const fluid_mesh_t* m, const fluid_mesh_ex_t* ex, float voxel_size, float velocity_scale);
 
 #ifdef __cplusplus
 }
