@@ -288,9 +288,18 @@ __global__ __launch_bounds__(256) void k_drop_solve(Grid g, LBox L, int n_comp, 
     const double bb = wsum_d(bv * bv);
     double rz = wsum_d(r * z), rr = bb;
     const double thr = tol * tol * bb;
+    // The cap.  In exact arithmetic n iterations end the loop; a droplet in open air ends it well inside n (a 4^3 cube: 16).  A pocket
+    // cast in solid with one open face (Neumann rows, Jacobi-scaled condition 200 - 1 200) loses orthogonality at this tolerance and
+    // needs more: the float64 restatement (tests/test_droplet_ref.py, largest count over 60 right-hand sides) takes 22 for a line of
+    // 11, 42 for a path of 21, 61 for three arms of 10 (31 cells), 54 for a comb of 41, 38 for the 4^3 cube — up to 2 n for the paths,
+    // about 60 whatever n for the branched ones.  The earlier cap n + 8 ended four of these five short (restatement: recursive
+    // residual 5e-16 .. 6e-16 of |b| at the cap; on the device FLUID_PATH_DROPLETS_SHORT came up for seven of eight right-hand
+    // sides of tests/test_gpu_droplets.py's sealed scene).  2 n + 16 covers the counts above with at least 16 to spare (the wave
+    // sum adds in another order than the restatement); a pocket that met the old cap runs as before.
+    const int cap = 2 * n + 16;
     if (bb > 0) {
 #pragma unroll 1
-        for (int it = 0; it < n + 8 && rr > thr; ++it) {
+        for (int it = 0; it < cap && rr > thr; ++it) {
             double q = diag * s;
             double acc = 0;
 #pragma unroll
