@@ -98,6 +98,28 @@ class MESH:
     VELOCITY, NORMALS, TRIANGLES = 1, 2, 4
 
 
+class Camera(C.Structure):
+    """fluid_camera_t: eye, the direction of pixel (-0.5, -0.5) and its change per column and row, in index space; the march
+    (include/fluid_hip.h, "liquid surface as an image")."""
+    _fields_ = [("eye", C.c_float * 3), ("dir00", C.c_float * 3), ("du", C.c_float * 3), ("dv", C.c_float * 3),
+                ("width", C.c_int32), ("height", C.c_int32), ("t_near", C.c_float), ("step", C.c_float), ("n_steps", C.c_int32)]
+
+
+class Shade(C.Structure):
+    """fluid_shade_t: the diffuse base colour of a hit and the bytes of a miss."""
+    _fields_ = [("base", C.c_float * 3), ("background", C.c_uint8 * 3), ("pad_", C.c_uint8)]
+
+
+class ImageC(C.Structure):
+    """fluid_image_t: the parts of a render snapshot."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("n_hit", C.c_int64), ("rgb", C.c_void_p), ("depth", C.c_void_p),
+                ("normals", C.c_void_p)]
+
+
+class RENDER:
+    RGB, DEPTH, NORMALS = 1, 2, 4
+
+
 class MpmParams(C.Structure):
     """mpm_params_t (include/mpm_hip.h); defaults = the literals of mpm.cc."""
     _fields_ = [("B", C.c_int32), ("W", C.c_int32), ("device", C.c_int32), ("cg_max_iters", C.c_int32),
@@ -225,6 +247,13 @@ SYMBOLS = [
     ("fluid_sdf_mesh_normals", C.c_int64, [C.POINTER(SdfGridC), C.c_int64, _P]),
     ("fluid_mesh_triangles", C.c_int64, [C.POINTER(MeshC), C.c_int64, _P]),
     ("fluid_write_ply_mesh_ex", C.c_int, [C.c_char_p, C.POINTER(MeshC), C.POINTER(MeshExC), C.c_float, C.c_float]),
+    ("fluid_render_snapshot", C.c_int, [_P, C.POINTER(SdfParams), C.POINTER(SdfFilter), C.POINTER(Camera), C.POINTER(Shade), C.c_uint32]),
+    ("fluid_render_wait", C.c_int, [_P, C.POINTER(ImageC)]),
+    ("fluid_render_stats", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("fluid_sdf_render", C.c_int, [C.POINTER(SdfGridC), C.POINTER(Camera), C.POINTER(Shade), C.c_uint32, _P, _P, _P, C.POINTER(C.c_int64)]),
+    ("fluid_camera_look_at", C.c_int, [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_int32,
+                                        C.c_int32, C.c_double, C.POINTER(Camera)]),
+    ("fluid_write_png", C.c_int, [C.c_char_p, C.c_int32, C.c_int32, _P]),
     # the snow-MPM step (include/mpm_hip.h)
     ("mpm_default_params", C.c_int, [C.POINTER(MpmParams)]),
     ("mpm_create", C.c_int, [C.POINTER(MpmParams), C.POINTER(_P)]),

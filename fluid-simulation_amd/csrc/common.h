@@ -370,6 +370,23 @@ void launch_mesh_emit(hipStream_t st, const SdfGeom& g, const float* tv, const i
                       uint32_t* quads, float* vvel, float* vnrm);
 // behind emit: quad i's two triangles to tris[6 i ..], cut along the shorter diagonal; tris is 16-byte aligned
 void launch_mesh_tris(hipStream_t st, long nq, long nv, const uint32_t* quads, const float* vertices, uint32_t* tris);
+// ray caster of that level set (kernels_render.hip; include/fluid_hip.h, "liquid surface as an image").  The range extended by one
+// leaf towards -x, -y, -z holds the min corner of every cell that can have a corner < 0; E = its cells clipped to [lo - 1, hi + 1)
+struct RenderGeom {
+    SdfGeom g;
+    int any;               // some particle counts (0: every pixel is a miss, g and the rest are not looked at)
+    int ne[3];             // leaves of the extended range per axis: nl + 1
+    int e0[3], e1[3];      // E: e0 <= p_a < e1
+    __host__ __device__ inline long ext_leaves() const { return (long)ne[0] * ne[1] * ne[2]; }
+};
+}  // namespace fl
+struct fluid_camera;
+struct fluid_shade;
+namespace fl {
+// neg: a byte per leaf of the range; occ: a bit per leaf of the extended range, in 32-bit words; hits: one word, zeroed on st before;
+// rgb (3 bytes per pixel) / depth / normals: nullptr for a part that is not asked for
+void launch_render(hipStream_t st, const RenderGeom& r, const fluid_camera& cam, const fluid_shade& sh, const float* tv, const int* flags,
+                   unsigned char* neg, unsigned* occ, unsigned* hits, unsigned char* rgb, float* depth, float* normals);
 void launch_exclusive_scan(hipStream_t st, const int* in, int* out, long n, int* block_sums, int* total);
 void launch_sort_tail(hipStream_t st, const int* cell_count, int* cell_start, long c1, long ncell);
 void launch_index_scan(hipStream_t st, Grid g, const uint8_t* flags, int* indices, int* block_sums, int* total);

@@ -173,6 +173,7 @@ int fluid_destroy(fluid_sim_t* s)
     free_particles(s);
     sources_free(s);
     output_free(s);
+    render_free(s);
     mesh_free(s);
     sdf_free(s);
     void* ptrs[] = {s->solid, s->flags, s->container, s->rhs, s->diver, s->diver2, s->u, s->v, s->w, s->ub, s->vb, s->wb, s->dcx, s->dcy,

@@ -63,6 +63,14 @@
 //   FLUID_BLOCKS_MESH_NORMALS=1, FLUID_BLOCKS_MESH_TRIS=1 (unset or 0: off; with FLUID_BLOCKS_MESH only) — the same two options for the block
 // run's mesh<i>.ply, through the host functions on the writer thread (fluid_sdf_mesh_normals on the merged list, after the filter if
 // FLUID_OUT_SMOOTH is set; fluid_mesh_triangles on the mesh).  Refused without FLUID_BLOCKS_MESH or with a value other than 0 or 1.
+//   FLUID_OUT_RENDER=R,W[,WIDTHxHEIGHT] (unset: off; default 640x360) — additionally simulation/frame<i>.png per step: the level set of
+// the same R,W ray-cast on the device (include/fluid_hip.h, "liquid surface as an image": fluid_render_snapshot beside the other
+// snapshots, fluid_write_png on the writer thread), white on black, seen by fluid_camera_look_at from FLUID_OUT_RENDER_EYE=x,y,z
+// (index space; default a three-quarter view from outside the grid, N * (-0.9, 0.5, -1.2)) towards the origin, up = +y, 40 degrees,
+// step 0.5.  Composes with FLUID_OUT_SMOOTH.  One GPU and the leaf output only, refused where FLUID_OUT_SURFACE is.
+//   FLUID_BLOCKS_RENDER=R,W[,WIDTHxHEIGHT] (unset: off; with FLUID_BLOCKS only) — the same file from a block run: the writer thread
+// renders the merged list (fluid_sdf_render, after the filter if FLUID_OUT_SMOOTH is set).  The same R,W as FLUID_BLOCKS_SURFACE /
+// FLUID_BLOCKS_MESH when set together.  Without these variables stdout and every file are what they are.
 //   FLUID_OUT_SMOOTH=W,K[,OFFSET] (unset: off) — what FLUID_OUT_SURFACE, FLUID_OUT_MESH, FLUID_BLOCKS_SURFACE and FLUID_BLOCKS_MESH write is the level set
 // after K box filters of width W voxels and the offset (include/fluid_hip.h, "liquid surface, smoothed"): on one GPU the snapshots
 // are fluid_sdf_snapshot_filtered / fluid_mesh_snapshot_filtered; a block run filters the merged list on the main thread
@@ -106,6 +114,31 @@ static int env_option(const char* name, const char* base, bool base_set, const c
     return t == "1";
 }
 
+// "R,W[,WIDTHxHEIGHT]" of FLUID_OUT_RENDER / FLUID_BLOCKS_RENDER
+static bool parse_render(const char* v, fluid_sdf_params_t* p, int* w, int* h)
+{
+    char tail = 0;
+    *w = 640, *h = 360;
+    const int got = sscanf(v, "%lf,%lf,%dx%d%c", &p->radius, &p->half_width, w, h, &tail);
+    if (got == 2) {   // "R,W" alone: nothing may follow W
+        int used = 0;
+        return sscanf(v, "%lf,%lf%n", &p->radius, &p->half_width, &used) == 2 && v[used] == 0;
+    }
+    return got == 4 && *w >= 1 && *w <= 8192 && *h >= 1 && *h <= 8192 && (long)*w * *h <= (1L << 24);
+}
+
+// the camera of FLUID_OUT_RENDER / FLUID_BLOCKS_RENDER; false: FLUID_OUT_RENDER_EYE is malformed or the view is degenerate
+static bool render_camera(int n, int w, int h, fluid_camera_t* cam)
+{
+    double eye[3] = {-0.9 * n, 0.5 * n, -1.2 * n};
+    if (const char* e = getenv("FLUID_OUT_RENDER_EYE"); e && *e) {
+        char tail = 0;
+        if (sscanf(e, "%lf,%lf,%lf%c", &eye[0], &eye[1], &eye[2], &tail) != 3) return false;
+    }
+    const double target[3] = {0.0, 0.0, 0.0}, up[3] = {0.0, 1.0, 0.0};
+    return fluid_camera_look_at(n, eye, target, up, 40.0, w, h, 0.5, cam) == FLUID_OK;
+}
+
 static bool write_f32(const std::string& fr, int32_t n32, const float* v, size_t ncell)
 {
     FILE* f = fopen(fr.c_str(), "wb");
@@ -137,6 +170,10 @@ struct LeafWriter {
     bool has_bjob = false;
     fluid_sdf_attr_t bajob{};    // FLUID_BLOCKS_MESH_VEL: its merged attributes
     bool has_bajob = false;
+    bool b_mesh = false, b_render = false;   // what this thread makes of bjob: mesh<i>.ply (FLUID_BLOCKS_MESH), frame<i>.png (FLUID_BLOCKS_RENDER)
+    fluid_camera_t cam{};        // FLUID_BLOCKS_RENDER: the camera
+    fluid_image_t ijob{};        // FLUID_OUT_RENDER: the same step's image
+    bool has_ijob = false;
     int job_step = -1;        // step whose grid is waiting (-1: none)
     int done = 0;             // grids written
     bool quit = false;
@@ -194,6 +231,7 @@ struct LeafWriter {
     {
         std::vector<float> dense, bv, bw, bn;
         std::vector<uint32_t> bq, bt;
+        std::vector<uint8_t> pix;
         for (;;) {
             std::unique_lock<std::mutex> lk(m);
             cv.wait(lk, [&] { return job_step >= 0 || quit; });
@@ -210,6 +248,8 @@ struct LeafWriter {
             const bool has_bg = has_bjob;
             const fluid_sdf_attr_t ba = bajob;
             const bool has_ba = has_bajob;
+            const fluid_image_t im = ijob;
+            const bool has_im = has_ijob;
             const int i = job_step;
             lk.unlock();
             std::string bad;
@@ -231,9 +271,19 @@ struct LeafWriter {
                     if (!write_ex(fm, mg, mx)) bad = fm;
                 } else if ((has_ma ? fluid_write_ply_mesh_attr(fm.c_str(), &mg, &ma, voxel, vel_scale) : fluid_write_ply_mesh(fm.c_str(), &mg, voxel)) != FLUID_OK) bad = fm;
             }
-            if (has_bg && bad.empty()) {
+            if (has_bg && b_mesh && bad.empty()) {
                 const std::string fm = outdir + "/mesh" + std::to_string(i) + ".ply";
                 if (!mesh_blocks(fm, bg, has_ba ? &ba : nullptr, bv, bq, bw, bn, bt)) bad = fm;
+            }
+            if (has_im && bad.empty()) {
+                const std::string fp = outdir + "/frame" + std::to_string(i) + ".png";
+                if (!im.rgb || fluid_write_png(fp.c_str(), im.width, im.height, im.rgb) != FLUID_OK) bad = fp;
+            }
+            if (has_bg && b_render && bad.empty()) {
+                const std::string fp = outdir + "/frame" + std::to_string(i) + ".png";
+                pix.resize(3 * (size_t)cam.width * cam.height);
+                if (fluid_sdf_render(&bg, &cam, nullptr, FLUID_RENDER_RGB, pix.data(), nullptr, nullptr, nullptr) != FLUID_OK ||
+                    fluid_write_png(fp.c_str(), cam.width, cam.height, pix.data()) != FLUID_OK) bad = fp;
             }
             if (raw_f32 && bad.empty()) {
                 const size_t ncell = (size_t)g.n * g.n * g.n;
@@ -257,7 +307,7 @@ struct LeafWriter {
     }
     void submit(int step, const fluid_leaf_grid_t& g, const fluid_sdf_grid_t* surface = nullptr, const fluid_mesh_t* mesh = nullptr,
                 const fluid_mesh_attr_t* mesh_attr = nullptr, const fluid_sdf_grid_t* to_mesh = nullptr, const fluid_sdf_attr_t* to_mesh_attr = nullptr,
-                const fluid_mesh_ex_t* mesh_ex = nullptr)
+                const fluid_mesh_ex_t* mesh_ex = nullptr, const fluid_image_t* image = nullptr)
     {
         std::unique_lock<std::mutex> lk(m);
         cv.wait(lk, [&] { return job_step < 0; });
@@ -273,6 +323,8 @@ struct LeafWriter {
         if (to_mesh) bjob = *to_mesh;
         has_bajob = to_mesh && to_mesh_attr;
         if (has_bajob) bajob = *to_mesh_attr;
+        has_ijob = image != nullptr;
+        if (image) ijob = *image;
         job_step = step;
         cv.notify_all();
     }
@@ -303,6 +355,8 @@ struct BlockCfg {
     bool mesh_vel = false;    // FLUID_BLOCKS_MESH_VEL
     unsigned mesh_more = 0;   // FLUID_BLOCKS_MESH_NORMALS / _TRIS: FLUID_MESH_NORMALS | FLUID_MESH_TRIANGLES
     double mesh_vel_scale = 1.0;
+    bool render = false;      // FLUID_BLOCKS_RENDER (its R,W are in sp as well)
+    fluid_camera_t cam{};
 };
 
 // What the main thread and the block threads share: `go` = steps released so far, done[i & 1] = blocks that finished step i.
@@ -361,7 +415,8 @@ static int run_blocks(const BlockCfg& cfg, const std::vector<double>& pos, int64
     const bool output = !cfg.outdir.empty() && steps > 0;
     std::vector<fluid_leaf_grid_t> part[2] = {std::vector<fluid_leaf_grid_t>(R), std::vector<fluid_leaf_grid_t>(R)};
     const bool surface = output && cfg.surface, mesh = output && cfg.mesh, attr = mesh && cfg.mesh_vel;
-    const bool level = surface || mesh;   // one level-set snapshot per block and step serves both
+    const bool render = output && cfg.render;
+    const bool level = surface || mesh || render;   // one level-set snapshot per block and step serves all of them
     std::vector<fluid_sdf_grid_t> spart[2] = {std::vector<fluid_sdf_grid_t>(R), std::vector<fluid_sdf_grid_t>(R)};
     std::vector<fluid_sdf_attr_part_t> apart[2] = {std::vector<fluid_sdf_attr_part_t>(R), std::vector<fluid_sdf_attr_part_t>(R)};
     std::vector<fluid_step_stats_t> st0(2);   // rank 0's stats of step i in st0[i & 1]
@@ -445,6 +500,7 @@ static int run_blocks(const BlockCfg& cfg, const std::vector<double>& pos, int64
         lw.voxel = (float)cfg.prm.dx;
         lw.vel_scale = (float)cfg.mesh_vel_scale;
         lw.mesh_what = cfg.mesh_more | (cfg.mesh_vel ? FLUID_MESH_VELOCITY : 0u);
+        lw.b_mesh = mesh, lw.b_render = render, lw.cam = cfg.cam;
         lw.start();
     }
     // the merged grid of step i lives in buffer i & 1 until the writer thread has put grid i on disk
@@ -521,7 +577,7 @@ static int run_blocks(const BlockCfg& cfg, const std::vector<double>& pos, int64
             }
         }
         lw.submit(i, fluid_leaf_grid_t{n, (int32_t)k, k ? org.data() : nullptr, k ? val.data() : nullptr}, surface ? &sg : nullptr, nullptr, nullptr,
-                  mesh ? &sg : nullptr, attr ? &sat : nullptr);
+                  mesh || render ? &sg : nullptr, attr ? &sat : nullptr);
     }
     bool ok = !sy.failed;
     if (output) {
@@ -666,6 +722,55 @@ int main(int, char**)
         if (on < 0) return 1;
         if (on) bc.mesh_more |= k ? FLUID_MESH_TRIANGLES : FLUID_MESH_NORMALS;
     }
+    const char* renv = getenv("FLUID_OUT_RENDER");
+    const bool render = renv && *renv;
+    fluid_sdf_params_t rp{};
+    fluid_camera_t rcam{};
+    if (render) {
+        int rw = 0, rh = 0;
+        if (!parse_render(renv, &rp, &rw, &rh)) {
+            std::cerr << "FLUID_OUT_RENDER must be R,W[,WIDTHxHEIGHT] (sphere radius and band half width in voxels; at most 8192 a side and 2^24 pixels), e.g. 1.5,2.5,640x360" << std::endl;
+            return 1;
+        }
+        if ((blocks && *blocks) || out_dense) {
+            std::cerr << "FLUID_OUT_RENDER cannot be combined with " << (out_dense ? "FLUID_OUT_DENSE=1" : "FLUID_BLOCKS (a block run takes FLUID_BLOCKS_RENDER=R,W)") << std::endl;
+            return 1;
+        }
+        if (outdir.empty() || steps <= 0) {
+            std::cerr << "FLUID_OUT_RENDER needs an output directory and at least one step (FLUID_OUT is empty or FLUID_STEPS is 0)" << std::endl;
+            return 1;
+        }
+        if (!render_camera(prm.n, rw, rh, &rcam)) {
+            std::cerr << "FLUID_OUT_RENDER_EYE must be x,y,z (index space), away from the origin and not straight above or below it" << std::endl;
+            return 1;
+        }
+    }
+    if (const char* br = getenv("FLUID_BLOCKS_RENDER"); br && *br) {
+        fluid_sdf_params_t brp{};
+        int rw = 0, rh = 0;
+        if (!parse_render(br, &brp, &rw, &rh)) {
+            std::cerr << "FLUID_BLOCKS_RENDER must be R,W[,WIDTHxHEIGHT] (sphere radius and band half width in voxels; at most 8192 a side and 2^24 pixels), e.g. 1.5,2.5,640x360" << std::endl;
+            return 1;
+        }
+        if (!(blocks && *blocks)) {
+            std::cerr << "FLUID_BLOCKS_RENDER needs FLUID_BLOCKS=AxBxC (one GPU takes FLUID_OUT_RENDER=R,W)" << std::endl;
+            return 1;
+        }
+        if (outdir.empty() || steps <= 0) {
+            std::cerr << "FLUID_BLOCKS_RENDER needs an output directory and at least one step (FLUID_OUT is empty or FLUID_STEPS is 0)" << std::endl;
+            return 1;
+        }
+        if ((bc.surface || bc.mesh) && (brp.radius != bc.sp.radius || brp.half_width != bc.sp.half_width)) {
+            std::cerr << "FLUID_BLOCKS_RENDER must be the same R,W as FLUID_BLOCKS_SURFACE / FLUID_BLOCKS_MESH: one level-set snapshot per step serves all" << std::endl;
+            return 1;
+        }
+        if (!render_camera(prm.n, rw, rh, &bc.cam)) {
+            std::cerr << "FLUID_OUT_RENDER_EYE must be x,y,z (index space), away from the origin and not straight above or below it" << std::endl;
+            return 1;
+        }
+        bc.sp = brp;
+        bc.render = true;
+    }
     const char* smenv = getenv("FLUID_OUT_SMOOTH");
     const bool smooth = smenv && *smenv;
     fluid_sdf_filter_t sf{};
@@ -682,8 +787,8 @@ int main(int, char**)
             std::cerr << "FLUID_OUT_SMOOTH must be W,K[,OFFSET] (box width 1..4 voxels, iterations 0..16, a finite offset), e.g. 1,4,-0.5" << std::endl;
             return 1;
         }
-        if (!surface && !mesh && !bc.surface && !bc.mesh) {
-            std::cerr << "FLUID_OUT_SMOOTH smooths what FLUID_OUT_SURFACE, FLUID_OUT_MESH, FLUID_BLOCKS_SURFACE or FLUID_BLOCKS_MESH write: none of them is set" << std::endl;
+        if (!surface && !mesh && !bc.surface && !bc.mesh && !render && !bc.render) {
+            std::cerr << "FLUID_OUT_SMOOTH smooths what FLUID_OUT_SURFACE, FLUID_OUT_MESH, FLUID_OUT_RENDER, FLUID_BLOCKS_SURFACE, FLUID_BLOCKS_MESH or FLUID_BLOCKS_RENDER write: none of them is set" << std::endl;
             return 1;
         }
         bc.smooth = true, bc.sf = sf;
@@ -778,8 +883,13 @@ int main(int, char**)
             std::cerr << "fluid_mesh_wait: " << fluid_last_error() << std::endl;
             return false;
         }
+        fluid_image_t im;
+        if (render && fluid_render_wait(sim, &im) != FLUID_OK) {
+            std::cerr << "fluid_render_wait: " << fluid_last_error() << std::endl;
+            return false;
+        }
         lw.submit(step, g, surface ? &sg : nullptr, mesh ? &mg : nullptr, mesh && mesh_vel && !mesh_more ? &ma : nullptr, nullptr, nullptr,
-                  mesh && mesh_more ? &mx : nullptr);
+                  mesh && mesh_more ? &mx : nullptr, render ? &im : nullptr);
         return true;
     };
 
@@ -830,6 +940,11 @@ int main(int, char**)
                          : smooth ? fluid_mesh_snapshot_filtered(sim, &mp, &sf)
                                   : fluid_mesh_snapshot(sim, &mp)) != FLUID_OK) {
                 std::cerr << "fluid_mesh_snapshot: " << fluid_last_error() << std::endl;
+                lw.stop();
+                return 1;
+            }
+            if (render && fluid_render_snapshot(sim, &rp, smooth ? &sf : nullptr, &rcam, nullptr, FLUID_RENDER_RGB) != FLUID_OK) {
+                std::cerr << "fluid_render_snapshot: " << fluid_last_error() << std::endl;
                 lw.stop();
                 return 1;
             }

@@ -207,6 +207,7 @@ struct fluid_sim {
     int out_every = 0;                // fluid_dist_output_every: fluid_step snapshots the owned block at the end of step t iff t % every == 0
     struct SdfState* sdf = nullptr;   // level-set snapshots of the particles (fluid_sdf.hip): slots, streams and scratch of their own
     struct MeshState* mesh = nullptr; // surface-net snapshots of that level set (fluid_mesh.hip): slots, stream and per-leaf scratch of their own
+    struct RenderState* render = nullptr;   // ray-cast images of that level set (fluid_render.hip): slots, stream and per-leaf scratch of their own
     // profiling
     int prof_every = 0;
     ProfClass prof[FLUID_PROF_COUNT];
@@ -322,6 +323,9 @@ int sdf_front(fluid_sim* s, SdfFront* f);   // bbox (waits for the stream) -> co
 
 // fluid_mesh.hip
 void mesh_free(fluid_sim* s);        // waits for the copies in flight, frees the scratch, the staging and the pinned buffers
+
+// fluid_render.hip
+void render_free(fluid_sim* s);      // waits for the copies in flight, frees the scratch, the staging and the pinned buffers
 
 // fluid_dist.hip
 int dist_step(fluid_sim* s, fluid_step_stats_t* stats);

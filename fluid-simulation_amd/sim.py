@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 
-from ._lib import lib, check, FluidError, Params, StepStats, FIELD, Source, LeafGridC, SdfParams, SdfGridC, SdfFilter, MeshC, SdfAttrC, MeshAttrC, SdfAttrPartC, MeshExC, MESH
+from ._lib import lib, check, FluidError, Params, StepStats, FIELD, Source, LeafGridC, SdfParams, SdfGridC, SdfFilter, MeshC, SdfAttrC, MeshAttrC, SdfAttrPartC, MeshExC, MESH, Camera, Shade, ImageC, RENDER
 
 _FIELD_DTYPE = {
     FIELD.CONTAINER: (np.float32, 1), FIELD.WEIGHTS: (np.float32, 1), FIELD.OUTPUT: (np.float32, 1),
@@ -388,6 +388,67 @@ def mesh_triangles(vertices, quads):
     return tri
 
 
+def camera(eye, dir00, du, dv, width, height, t_near, step, n_steps):
+    """A Camera (fluid_camera_t) from plain sequences; every float is narrowed once."""
+    c = Camera()
+    for name, v in (("eye", eye), ("dir00", dir00), ("du", du), ("dv", dv)):
+        setattr(c, name, (C.c_float * 3)(*[float(x) for x in v]))
+    c.width, c.height, c.t_near, c.step, c.n_steps = int(width), int(height), float(t_near), float(step), int(n_steps)
+    return c
+
+
+def _shade_of(shade):
+    """fluid_shade_t of None, a Shade, or a (base (3 floats), background (3 bytes)) pair."""
+    if shade is None or isinstance(shade, Shade):
+        return shade
+    base, background = shade
+    return Shade((C.c_float * 3)(*[float(x) for x in base]), (C.c_uint8 * 3)(*[int(x) for x in background]), 0)
+
+
+def _render_what(rgb, depth, normals):
+    return (RENDER.RGB if rgb else 0) | (RENDER.DEPTH if depth else 0) | (RENDER.NORMALS if normals else 0)
+
+
+def camera_look_at(n, eye, target=(0.0, 0.0, 0.0), up=(0.0, 1.0, 0.0), fov_y_degrees=40.0, width=640, height=360, step=0.5):
+    """The pinhole Camera of a grid of n^3 cells that looks from `eye` at `target` (fluid_camera_look_at: host only)."""
+    c = Camera()
+    d3 = lambda v: (C.c_double * 3)(*[float(x) for x in v])   # noqa: E731
+    rc = lib.fluid_camera_look_at(int(n), d3(eye), d3(target), d3(up), float(fov_y_degrees), int(width), int(height), float(step), C.byref(c))
+    if rc != 0:
+        raise FluidError(rc, "fluid_camera_look_at: a degenerate view or a size, field of view or step outside the limits")
+    return c
+
+
+def sdf_render(grid, camera, shade=None, rgb=True, depth=False, normals=False):
+    """The image of an SdfGrid, every unlisted leaf being +background (fluid_sdf_render: host only): {"rgb" (H, W, 3) uint8,
+    "depth" (H, W) float32, "normals" (H, W, 3) float32, "n_hit"}, None for a part that is not asked for.  A decomposed run renders
+    sdf_render(merge_sdf_grids(parts), ...)."""
+    c, _keep = grid._c()
+    sh = _shade_of(shade)
+    H, W = camera.height, camera.width
+    ok = 1 <= W <= 8192 and 1 <= H <= 8192
+    out = {"rgb": np.empty((H, W, 3), np.uint8) if rgb and ok else None, "depth": np.empty((H, W), np.float32) if depth and ok else None,
+           "normals": np.empty((H, W, 3), np.float32) if normals and ok else None}
+    n_hit = C.c_int64(0)
+    ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)   # noqa: E731
+    rc = lib.fluid_sdf_render(C.byref(c), C.byref(camera), None if sh is None else C.byref(sh), _render_what(rgb, depth, normals),
+                              ptr(out["rgb"]), ptr(out["depth"]), ptr(out["normals"]), C.byref(n_hit))
+    if rc != 0:
+        raise FluidError(rc, "fluid_sdf_render: a bad leaf list, camera, shade or choice of parts")
+    out["n_hit"] = n_hit.value
+    return out
+
+
+def write_png(path, rgb):
+    """An 8-bit RGB PNG of rgb (H, W, 3) uint8 (fluid_write_png: host only)."""
+    rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+    if rgb.ndim != 3 or rgb.shape[2] != 3:
+        raise ValueError("rgb must be (height, width, 3)")
+    rc = lib.fluid_write_png(str(path).encode(), rgb.shape[1], rgb.shape[0], rgb.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise FluidError(rc, "fluid_write_png: a size outside 1..8192 or a path that cannot be written")
+
+
 def sdf_attr_to_dense(grid, attr):
     """(id uint32 (n, n, n), velocity float32 (3, n, n, n)) of an SdfGrid's attributes: 0xffffffff / +0 outside the listed leaves
     (fluid_sdf_attr_to_dense: host only)."""
@@ -751,6 +812,37 @@ class FluidSim:
         v = [C.c_int64() for _ in range(3)]
         check(lib.fluid_mesh_stats(self._h, *[C.byref(x) for x in v]))
         return dict(zip(("vertices", "quads", "bytes_to_host"), (x.value for x in v)))
+
+    # ---- liquid surface as an image: the level set ray-cast on the device (single GPU; include/fluid_hip.h) ----
+    def render_snapshot(self, radius, half_width, camera, smooth=None, shade=None, rgb=True, depth=False, normals=False):
+        """Enqueue an image of the level set of the particles as they are now (parameters as sdf_snapshot, `smooth` included),
+        seen through `camera` (a Camera: camera() or camera_look_at()); a step() called next overlaps the copy to the host.
+        shade: None (white on black), a Shade, or (base, background)."""
+        p = SdfParams(float(radius), float(half_width))
+        f = None if smooth is None else C.byref(_sdf_filter_of(smooth))
+        sh = _shade_of(shade)
+        check(lib.fluid_render_snapshot(self._h, C.byref(p), f, C.byref(camera), None if sh is None else C.byref(sh),
+                                        _render_what(rgb, depth, normals)))
+
+    def render_wait(self):
+        """The oldest render snapshot not yet waited for: {"rgb" (H, W, 3) uint8, "depth" (H, W) float32, "normals" (H, W, 3)
+        float32, "n_hit"}, copied out of the handle's pinned buffer; None for a part the snapshot was taken without."""
+        m = ImageC()
+        check(lib.fluid_render_wait(self._h, C.byref(m)))
+        H, W = m.height, m.width
+        out = {"rgb": None, "depth": None, "normals": None, "n_hit": m.n_hit}
+        if m.rgb:
+            out["rgb"] = np.ctypeslib.as_array(C.cast(m.rgb, C.POINTER(C.c_uint8)), shape=(H, W, 3)).copy()
+        if m.depth:
+            out["depth"] = np.ctypeslib.as_array(C.cast(m.depth, C.POINTER(C.c_float)), shape=(H, W)).copy()
+        if m.normals:
+            out["normals"] = np.ctypeslib.as_array(C.cast(m.normals, C.POINTER(C.c_float)), shape=(H, W, 3)).copy()
+        return out
+
+    def render_stats(self):
+        v = [C.c_int64() for _ in range(3)]
+        check(lib.fluid_render_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("pixels", "hits", "bytes_to_host"), (x.value for x in v)))
 
     def extrapolate(self):
         """fluid.cc:705-802 after p2g(): velocities for every cell inside W (dead code in the reference; optional here).  Returns the passes run."""

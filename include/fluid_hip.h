@@ -954,6 +954,110 @@ int64_t fluid_mesh_triangles(const fluid_mesh_t* mesh, int64_t cap_triangles, ui
  * triangle entry >= n_vertices, a velocity_scale that is not finite with velocities. */
 int fluid_write_ply_mesh_ex(const char* path, const fluid_mesh_t* m, const fluid_mesh_ex_t* ex, float voxel_size, float velocity_scale);
 
+/* ---- liquid surface as an image: a ray caster for the level set -----------------------------------------------------------------
+ * What the reference delivers is pictures: OpenVDB's vdb_render over the files its run wrote.  The level set sits on the device after
+ * the front half of a surface snapshot, one launch away from an image.  Like the surface, the filter, the mesh and the normals the
+ * image gets an exact, order-free definition of its own, restated from the library's LinearSearchImpl (tools/RayIntersector.h:539-692:
+ * uniform steps, the first sign change, one linear interpolation of the hit time) and DiffuseShader; the kernels
+ * (kernels_render.hip), fluid_sdf_render below and the tests' numpy form (tests/render_ref.py) give the same bytes.  Float throughout,
+ * no FMA; / and sqrtf are the correctly rounded IEEE operations; denormals are kept.
+ *
+ * Input.  The level set of "liquid surface" for a fluid_sdf_params_t, optionally after a fluid_sdf_filter_t: val(c), c in [lo,hi]^3,
+ * inactive voxels included (+-bg).  Every voxel of an unlisted leaf and every voxel outside the grid is +bg.  The active mask plays
+ * no part.
+ *
+ * Camera (fluid_camera_t, index space).  Pixel (i, j) = column i, row j, row 0 first (as in a PNG); its record index is j * width + i.
+ *   pi = (float)i + 0.5f;  pj = (float)j + 0.5f
+ *   D_a = (dir00_a + pi * du_a) + pj * dv_a                                    (grouped as written)
+ *   l2 = D_x * D_x;  l2 = l2 + D_y * D_y;  l2 = l2 + D_z * D_z;  len = sqrtf(l2)
+ *   !(len > 0.0f) or len not finite: the pixel is a MISS.  Otherwise d_a = D_a / len.
+ * A pinhole, an orthographic camera (du, dv chosen by the caller) and anything between are the caller's numbers; no trigonometry
+ * crosses the ABI (fluid_camera_look_at below is a convenience on top).
+ *
+ * Value at a point p.  If any p_a is NaN, or p_a < (float)(lo - 1), or p_a >= (float)(hi + 1): value(p) = +bg, the constant, no
+ * arithmetic.  Otherwise c_a = (int)floorf(p_a), which lies in [lo - 1, hi], f_a = p_a - (float)c_a in [0, 1], the corners
+ * v[dx][dy][dz] = val(c + (dx, dy, dz)) (+bg outside the grid), lerp(a, b, t) = a + t * (b - a) (a subtraction, a multiplication, an
+ * addition), and the value is four lerps along z with f_z (in the order (dx, dy) = (0,0), (0,1), (1,0), (1,1)), then two along y
+ * with f_y, then one along x with f_x.
+ *
+ * March.  t_k = t_near + (float)k * step,  p_k,a = eye_a + t_k * d_a,  k = 0 .. n_steps - 1.  The pixel HITS at the smallest k with
+ * value(p_k) < 0.0f; with none it is a miss.  k = 0 (the eye is in the liquid): t = t_0.  Otherwise v0 = value(p_{k-1}),
+ * v1 = value(p_k) and  t = t_{k-1} + ((t_k - t_{k-1}) * v0) / (v0 - v1)  (the library's interpTime; no iteration of the hit).  v0 >= 0 >
+ * v1, so the divisor is positive.
+ *
+ * Normal at the hit.  p_h,a = eye_a + t * d_a.  If p_h is out of bounds by the rule of value(): (+0, +0, +0).  Otherwise the cell c and
+ * f as in value(), and the g_a / l2 / len / n_a formula of "normals and triangles", unchanged, on that cell's eight corners at f.
+ *
+ * Outputs per pixel.  depth: t, or +infinity (0x7f800000) on a miss.  normal: n, or +0 on a miss.  rgb from fluid_shade_t: a miss takes
+ * `background`; a hit  s = n_x * d_x;  s = s + n_y * d_y;  s = s + n_z * d_z;  s = fabsf(s)  (DiffuseShader), per channel
+ * x = base_c * s clamped to [0, 1] (x > 0 ? (x < 1 ? x : 1) : 0, so NaN gives 0), byte = (uint8_t)(x * 255.0f + 0.5f).  n_hit counts
+ * the hit pixels.
+ *
+ * Skipping empty space changes nothing.  For a, b >= 0 and t in [0, 1], lerp(a, b, t) >= 0 in float: t * |b - a| <= max(a, b) survives
+ * the rounding of the product and of the sum (tests/test_render_ref.py tries 2 M triples, denormals and t = 1 - ulp included).  So a
+ * cell whose eight corners are all >= 0 never gives the first negative sample, and an implementation may leave out every sample that
+ * is out of bounds or whose cell lies in a leaf L with no negative voxel in L + {0,1}^3.  Only v0 at a hit must then be evaluated by
+ * the formula: one more value() per hit pixel.  Per axis p_k,a is monotone in k (every operation that forms it is), so the samples
+ * between two samples of one axis-aligned box lie in that box.
+ *
+ * What this is not.  No voxel DDA (math/DDA.h): the march is uniform in t, a feature thinner than `step` can be stepped over, and
+ * step <= 0.5 is the advice.  No iteration of the hit, no shadows, no refraction, no solids, no colour by velocity, no anti-aliasing
+ * (render larger and average).
+ * Limits (anything else is FLUID_ERR_ARG): width, height in 1..8192 and width * height <= 2^24; n_steps in 1..65536; step > 0 and
+ * t_near >= 0; every camera float and every `base` finite; pad_ == 0; `what` non-zero and within the three bits. */
+typedef struct fluid_camera {
+    float eye[3], dir00[3], du[3], dv[3];
+    int32_t width, height;
+    float t_near, step;
+    int32_t n_steps;
+} fluid_camera_t;
+typedef struct fluid_shade { float base[3]; uint8_t background[3]; uint8_t pad_; } fluid_shade_t;
+#define FLUID_RENDER_RGB     1u
+#define FLUID_RENDER_DEPTH   2u
+#define FLUID_RENDER_NORMALS 4u
+typedef struct fluid_image {
+    int32_t width, height;
+    int64_t n_hit;
+    const uint8_t* rgb;          /* 3 per pixel, or NULL                                                             */
+    const float* depth;          /* 1 per pixel, or NULL                                                             */
+    const float* normals;        /* 3 per pixel, or NULL                                                             */
+} fluid_image_t;
+/* The front half of fluid_sdf_snapshot (box, 24 bytes read back; bins; search; with f the box passes, over the box dilated by 5 as for
+ * a filtered mesh: a negative voxel is active or -bg, so a cell with a negative corner has its min corner in [-5, +4] of a base cell),
+ * then the render kernels on the handle's stream; no leaf is packed.  shade == NULL: base (1, 1, 1) on a black background.  The record
+ * [16 bytes: uint32 hits and three zero words | rgb, padded to a multiple of 16 | depth | normals], each part only if asked for,
+ * travels to pinned host memory on a second stream and is not waited for; the hit count is an integer sum in the record's header, so
+ * there is no host wait beyond the front half's box.  The slots and the count of outstanding snapshots are the image's own: density,
+ * surface, mesh and image can all be taken in one step; two may be outstanding, a third returns FLUID_ERR_STATE.  Buffers grow here,
+ * never inside a step, and are freed by the destroy call after the copies in flight have ended.  With no counted particle every pixel
+ * is a miss and the record is produced all the same.  Nothing a later step reads is written.  FLUID_ERR_ARG: bad parameters or filter
+ * (as the siblings), a limit above.  FLUID_ERR_STATE on a decomposed handle (all three entry points): see fluid_sdf_render. */
+int fluid_render_snapshot(fluid_sim_t* s, const fluid_sdf_params_t* p, const fluid_sdf_filter_t* f /* NULL: unfiltered */,
+                          const fluid_camera_t* cam, const fluid_shade_t* shade, uint32_t what);
+/* The oldest snapshot not yet waited for (FLUID_ERR_STATE when there is none); parts not asked for are NULL.  The pointers stay valid
+ * until the SECOND following render snapshot on the handle. */
+int fluid_render_wait(fluid_sim_t* s, fluid_image_t* out);
+/* pixels = width * height and bytes_to_host = 16 + pad16(3 W H) [rgb] + 4 W H [depth] + 12 W H [normals] of the last snapshot TAKEN;
+ * hits of the last snapshot WAITED FOR (the count travels with the record; 0 before the first wait).  Any pointer may be NULL. */
+int fluid_render_stats(fluid_sim_t* s, int64_t* pixels, int64_t* hits, int64_t* bytes_to_host);
+/* Host only: the definition above applied to a leaf list (grid->values may be filtered values), every sample evaluated, the leaves
+ * found by bisection; no dense grid.  How a block run renders: after fluid_sdf_grids_merge (and fluid_sdf_filter).  rgb[3 W H],
+ * depth[W H], normals[3 W H]: required for the parts `what` names, ignored otherwise; n_hit may be NULL; shade == NULL as above.
+ * FLUID_ERR_ARG with nothing written: a list fluid_sdf_to_dense refuses, a limit above, a part asked for without its array. */
+int fluid_sdf_render(const fluid_sdf_grid_t* grid, const fluid_camera_t* cam, const fluid_shade_t* shade, uint32_t what, uint8_t* rgb,
+                     float* depth, float* normals, int64_t* n_hit);
+/* Host only, a convenience: the pinhole camera of a grid of n^3 cells that looks from `eye` at `target` (index space) with `up`
+ * roughly upwards and a vertical field of view of fov_y_degrees; square pixels, row 0 at the top.  Computed in double and narrowed
+ * once; t_near = 0, n_steps just enough to pass the grid's farthest corner (at most 65536).  Not pinned bit for bit (libm's tan).
+ * FLUID_ERR_ARG: n < 1, a non-finite input, eye == target, up parallel to the view, fov outside (0, 180), width or height outside
+ * 1..8192 or more than 2^24 pixels, step not > 0. */
+int fluid_camera_look_at(int32_t n, const double eye[3], const double target[3], const double up[3], double fov_y_degrees, int32_t width,
+                         int32_t height, double step, fluid_camera_t* out);
+/* Host only: an 8-bit RGB PNG, filter type 0 on every row, one IDAT chunk through zlib.  The file's bytes depend on zlib's version;
+ * its pixels do not.  FLUID_ERR_ARG: width or height outside 1..8192, rgb NULL, a path that cannot be opened or written in full (the
+ * partial file is removed). */
+int fluid_write_png(const char* path, int32_t width, int32_t height, const uint8_t* rgb);
+
 #ifdef __cplusplus
 }
 #endif
