@@ -29,13 +29,16 @@
 //          cell's eight corners at the vertex's offset in its cell, from the tile the block has staged anyway.
 //   tris   a launch of its own behind emit (a quad's vertices may be another block's of the same emit launch): one thread per
 //          quad, its 16 bytes and its four vertices in, two triangles cut along the shorter diagonal out.
-// Arithmetic of a vertex: include/fluid_hip.h; float, no FMA (-ffp-contract=off), the division correctly rounded
+// What happens in a cell — mask and owned edges, each of the 12 edges, vertex, velocity, normal, quad, triangles — is mesh_def.h's, the
+// text mesh_host.cpp compiles too; these kernels are how the device fetches a tile (LDS), numbers a vertex (ballots, cmask / cpre /
+// vbase) and writes.  Arithmetic of a vertex: include/fluid_hip.h; float, no FMA (-ffp-contract=off), the division correctly rounded
 // (-fhip-fp32-correctly-rounded-divide-sqrt).
 #include "common.h"
+#include "mesh_def.h"
 
 namespace fl {
 
-constexpr int MESH_V = 9 * 9 * 9;
+constexpr int MESH_V = mdef::TILE;
 
 struct MeshLeaf {
     long j;
@@ -72,24 +75,6 @@ __device__ __forceinline__ void mesh_load(const SdfGeom& g, const MeshLeaf& l, c
     }
 }
 
-// The thread's cell and edges.  Returns the inside mask of the 8 corners (bit dx*4 + dy*2 + dz); mixed = the cell exists and its
-// corners disagree; edges bit a = the owned edge along axis a gives a quad (its ends disagree and the four cells round it exist).
-__device__ __forceinline__ unsigned mesh_cell(const SdfGeom& g, const float* c, int px, int py, int pz, bool& mixed, unsigned& edges)
-{
-    unsigned m = 0;
-#pragma unroll
-    for (int d = 0; d < 8; ++d) m |= (c[(d >> 2) * 81 + ((d >> 1) & 1) * 9 + (d & 1)] < 0.0f ? 1u : 0u) << d;
-    const bool cx = px >= g.lo && px <= g.hi - 1, cy = py >= g.lo && py <= g.hi - 1, cz = pz >= g.lo && pz <= g.hi - 1;        // the cell's axis range
-    const bool qx = px >= g.lo + 1 && cx, qy = py >= g.lo + 1 && cy, qz = pz >= g.lo + 1 && cz;                                // ... and the cell at -1 too
-    mixed = cx && cy && cz && m != 0 && m != 255;
-    const unsigned in0 = m & 1;
-    edges = 0;
-    if (cx && qy && qz && ((m >> 4) & 1) != in0) edges |= 1;
-    if (cy && qz && qx && ((m >> 2) & 1) != in0) edges |= 2;
-    if (cz && qx && qy && ((m >> 1) & 1) != in0) edges |= 4;
-    return m;
-}
-
 __global__ __launch_bounds__(512) void k_mesh_mark(SdfGeom g, const float* __restrict__ tv, const int* __restrict__ flags,
                                                    unsigned long long* __restrict__ cmask, int* __restrict__ cpre, int* __restrict__ vcnt,
                                                    int* __restrict__ qcnt)
@@ -113,7 +98,7 @@ __global__ __launch_bounds__(512) void k_mesh_mark(SdfGeom g, const float* __res
     const int x = t >> 6, y = (t >> 3) & 7, z = t & 7;
     bool mixed;
     unsigned edges;
-    mesh_cell(g, V + (x * 9 + y) * 9 + z, l.ox + x, l.oy + y, l.oz + z, mixed, edges);
+    mdef::cell(g, V + (x * 9 + y) * 9 + z, l.ox + x, l.oy + y, l.oz + z, mixed, edges);
     const unsigned long long b = __ballot(mixed);
     const int nq = __popcll(__ballot(edges & 1)) + __popcll(__ballot(edges & 2)) + __popcll(__ballot(edges & 4));
     if ((t & 63) == 0) {
@@ -164,25 +149,6 @@ __device__ __forceinline__ unsigned mesh_vertex_number(const SdfGeom& g, int cx,
     return (unsigned)(vbase[q] + cpre[q * 8 + (off >> 6)] + __popcll(below));
 }
 
-// One counting edge's share of the vertex velocity ("liquid surface, attributes"): i0, i1 = the ends' places in the 9^3 tile
-__device__ __forceinline__ void mesh_edge_vel(const float* A, const unsigned char* B, int i0, int i1, float t, float* s, int& kv)
-{
-    const bool b0 = B[i0] != 0, b1 = B[i1] != 0;
-    if (!b0 && !b1) return;   // (cannot be on a device snapshot: include/fluid_hip.h)
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float a0 = A[a * MESH_V + i0], a1 = A[a * MESH_V + i1];
-        float e;
-        if (b0 && b1) {
-            const float d = a1 - a0;
-            const float td = t * d;
-            e = a0 + td;
-        } else e = b0 ? a0 : a1;
-        s[a] += e;
-    }
-    ++kv;
-}
-
 // ATTR: beside the values the block stages the velocities (3 x 9^3 floats) and the active bits (one byte each) of the same up to
 // eight leaves, not active wherever the leaf is unflagged or outside the range (the search's tm / tvel of such a leaf are stale or
 // do not exist); each mixed cell's thread writes its vertex velocity to the place its vertex goes.
@@ -226,106 +192,46 @@ __global__ __launch_bounds__(512) void k_mesh_emit(SdfGeom g, const float* __res
     const float* c = V + (x * 9 + y) * 9 + z;
     bool mixed;
     unsigned edges;
-    const unsigned m = mesh_cell(g, c, px, py, pz, mixed, edges);
+    const unsigned m = mdef::cell(g, c, px, py, pz, mixed, edges);
     const unsigned long long lt = (1ull << (t & 63)) - 1ull;
     const unsigned long long b = __ballot(mixed), bx = __ballot(edges & 1), by = __ballot(edges & 2), bz = __ballot(edges & 4);
     if ((t & 63) == 0) wq[x] = __popcll(bx) + __popcll(by) + __popcll(bz);
     __syncthreads();
     if (mixed) {
-        // the 12 edges: axis x, y, z; the two other axes, in ascending order, at (0,0), (0,1), (1,0), (1,1)
-        float sx = 0.0f, sy = 0.0f, sz = 0.0f;
-        float sv[3] = {0.0f, 0.0f, 0.0f};
-        int k = 0, kv = 0;
+        int kv = 0, k = 0;
+        float sx = 0.0f, sy = 0.0f, sz = 0.0f, sv[3] = {0.0f, 0.0f, 0.0f};
         const int c0 = (x * 9 + y) * 9 + z;   // the cell's min corner in the tile
 #pragma unroll
-        for (int o = 0; o < 4; ++o) {
-            const int d1 = o >> 1, d2 = o & 1;
-            const float v0 = c[d1 * 9 + d2], v1 = c[81 + d1 * 9 + d2];
-            if ((v0 < 0.0f) != (v1 < 0.0f)) {
-                const float tt = v0 / (v0 - v1);
-                sx += tt, sy += (float)d1, sz += (float)d2, ++k;
-                if (ATTR) mesh_edge_vel(A, B, c0 + d1 * 9 + d2, c0 + 81 + d1 * 9 + d2, tt, sv, kv);
-            }
-        }
-#pragma unroll
-        for (int o = 0; o < 4; ++o) {
-            const int d1 = o >> 1, d2 = o & 1;
-            const float v0 = c[d1 * 81 + d2], v1 = c[d1 * 81 + 9 + d2];
-            if ((v0 < 0.0f) != (v1 < 0.0f)) {
-                const float tt = v0 / (v0 - v1);
-                sx += (float)d1, sy += tt, sz += (float)d2, ++k;
-                if (ATTR) mesh_edge_vel(A, B, c0 + d1 * 81 + d2, c0 + d1 * 81 + 9 + d2, tt, sv, kv);
-            }
-        }
-#pragma unroll
-        for (int o = 0; o < 4; ++o) {
-            const int d1 = o >> 1, d2 = o & 1;
-            const float v0 = c[d1 * 81 + d2 * 9], v1 = c[d1 * 81 + d2 * 9 + 1];
-            if ((v0 < 0.0f) != (v1 < 0.0f)) {
-                const float tt = v0 / (v0 - v1);
-                sx += (float)d1, sy += (float)d2, sz += tt, ++k;
-                if (ATTR) mesh_edge_vel(A, B, c0 + d1 * 81 + d2 * 9, c0 + d1 * 81 + d2 * 9 + 1, tt, sv, kv);
-            }
-        }
+        for (int e = 0; e < 12; ++e) mdef::edge<ATTR>(c, e, A, B, c0, sx, sy, sz, sv, k, kv);
         const float kf = (float)k;
         const size_t vn = (size_t)(vbase[l.j] + cpre[l.j * 8 + x] + __popcll(b & lt));
-        float* out = vertices + 3 * vn;
-        const float fx = sx / kf;   // the vertex's offset in its cell
-        out[0] = (float)px + fx;
-        const float fy = sy / kf;
-        out[1] = (float)py + fy;
-        const float fz = sz / kf;
-        out[2] = (float)pz + fz;
+        float f[3];   // the vertex's offset in its cell
+        mdef::vertex(sx, sy, sz, kf, px, py, pz, f, vertices + 3 * vn);
         if (NORMALS) {
-            // all 12 edges, the order of the vertex: per axis the two other axes, ascending, at (0,0), (0,1), (1,0), (1,1)
-            const float ex = 1.0f - fx, ey = 1.0f - fy, ez = 1.0f - fz;
-            float gx = 0.0f, gy = 0.0f, gz = 0.0f;
+            mdef::Vec3 g = {0.0f, 0.0f, 0.0f};
 #pragma unroll
-            for (int o = 0; o < 4; ++o) {
-                const int d1 = o >> 1, d2 = o & 1;
-                const float wx = (d1 ? fy : ey) * (d2 ? fz : ez);
-                const float wy = (d1 ? fx : ex) * (d2 ? fz : ez);
-                const float wz = (d1 ? fx : ex) * (d2 ? fy : ey);
-                const float dx = c[81 + d1 * 9 + d2] - c[d1 * 9 + d2];
-                const float dy = c[d1 * 81 + 9 + d2] - c[d1 * 81 + d2];
-                const float dz = c[d1 * 81 + d2 * 9 + 1] - c[d1 * 81 + d2 * 9];
-                gx = gx + wx * dx;
-                gy = gy + wy * dy;
-                gz = gz + wz * dz;
-            }
-            float l2 = gx * gx;
-            l2 = l2 + gy * gy;
-            l2 = l2 + gz * gz;
-            const float len = sqrtf(l2);
-            const bool some = len > 0.0f;   // (false for a NaN too)
+            for (int o = 0; o < 4; ++o) g = mdef::gradient_term(c, f, o, g);
+            const mdef::Vec3 n = mdef::unit(g);
             float* on = vnrm + 3 * vn;
-            on[0] = some ? gx / len : 0.0f;
-            on[1] = some ? gy / len : 0.0f;
-            on[2] = some ? gz / len : 0.0f;
+            on[0] = n.x, on[1] = n.y, on[2] = n.z;
         }
-        if (ATTR) {
-            const float kvf = (float)kv;
-            float* ov = vvel + 3 * vn;
-            ov[0] = kv ? sv[0] / kvf : 0.0f;
-            ov[1] = kv ? sv[1] / kvf : 0.0f;
-            ov[2] = kv ? sv[2] / kvf : 0.0f;
-        }
+        if (ATTR) mdef::velocity(sv, kv, vvel + 3 * vn);
     }
     if (edges) {
         size_t at = (size_t)qbase[l.j] + __popcll(bx & lt) + __popcll(by & lt) + __popcll(bz & lt);
         for (int k = 0; k < x; ++k) at += wq[k];
-        const bool inside = m & 1;
         const unsigned q2 = mesh_vertex_number(g, px, py, pz, cmask, cpre, vbase);
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             if (!((edges >> a) & 1)) continue;
-            // (b, c) = the two other axes in cyclic order; Q0 = p - e_b - e_c, Q1 = p - e_c, Q3 = p - e_b
-            const int bxs = a == 2, bys = a == 0, bzs = a == 1;
-            const int cxs = a == 1, cys = a == 2, czs = a == 0;
-            const unsigned q0 = mesh_vertex_number(g, px - bxs - cxs, py - bys - cys, pz - bzs - czs, cmask, cpre, vbase);
-            const unsigned q1 = mesh_vertex_number(g, px - cxs, py - cys, pz - czs, cmask, cpre, vbase);
-            const unsigned q3 = mesh_vertex_number(g, px - bxs, py - bys, pz - bzs, cmask, cpre, vbase);
-            quads[at++] = inside ? make_uint4(q0, q1, q2, q3) : make_uint4(q0, q3, q2, q1);
+            int Q[4][3];
+            mdef::quad_cells(a, px, py, pz, Q);
+            const unsigned q0 = mesh_vertex_number(g, Q[0][0], Q[0][1], Q[0][2], cmask, cpre, vbase);
+            const unsigned q1 = mesh_vertex_number(g, Q[1][0], Q[1][1], Q[1][2], cmask, cpre, vbase);
+            const unsigned q3 = mesh_vertex_number(g, Q[3][0], Q[3][1], Q[3][2], cmask, cpre, vbase);
+            unsigned q[4];
+            mdef::quad_order(m, q0, q1, q2, q3, q);
+            quads[at++] = make_uint4(q[0], q[1], q[2], q[3]);
         }
     }
 }
@@ -349,29 +255,15 @@ __global__ __launch_bounds__(256) void k_mesh_tris(long nq, long nv, const uint4
 #pragma unroll
         for (int a = 0; a < 3; ++a) P[k][a] = vertices[at + a];
     }
-    float d02, d13;
-    {
-        const float x = P[2][0] - P[0][0], y = P[2][1] - P[0][1], z = P[2][2] - P[0][2];
-        d02 = x * x;
-        d02 = d02 + y * y;
-        d02 = d02 + z * z;
-    }
-    {
-        const float x = P[3][0] - P[1][0], y = P[3][1] - P[1][1], z = P[3][2] - P[1][2];
-        d13 = x * x;
-        d13 = d13 + y * y;
-        d13 = d13 + z * z;
-    }
-    const bool cut13 = d13 < d02;
-    const unsigned t0 = q.x, t1 = q.y, t2 = cut13 ? q.w : q.z;
-    const unsigned t3 = cut13 ? q.y : q.x, t4 = q.z, t5 = q.w;
+    unsigned t[6];
+    mdef::quad_triangles(e, P[0], P[1], P[2], P[3], t);
     uint2* out = tris + 3 * i;
     if (i & 1) {
-        out[0] = make_uint2(t0, t1);
-        *(uint4*)(out + 1) = make_uint4(t2, t3, t4, t5);
+        out[0] = make_uint2(t[0], t[1]);
+        *(uint4*)(out + 1) = make_uint4(t[2], t[3], t[4], t[5]);
     } else {
-        *(uint4*)out = make_uint4(t0, t1, t2, t3);
-        out[2] = make_uint2(t4, t5);
+        *(uint4*)out = make_uint4(t[0], t[1], t[2], t[3]);
+        out[2] = make_uint2(t[4], t[5]);
     }
 }
 

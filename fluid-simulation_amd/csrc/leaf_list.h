@@ -1,6 +1,6 @@
-// What the host-side surface code (vdb_sdf_writer.cpp, sdf_filter_host.cpp, mesh_host.cpp, mesh_attr_host.cpp) shares about a
-// level-set leaf list (fluid_sdf_grid_t): its rules, the search in it, and the walk of the surface nets over it.  Header only:
-// every file that includes it compiles on its own.
+// What the host-side surface code (vdb_sdf_writer.cpp, sdf_filter_host.cpp, mesh_host.cpp, render_host.cpp) shares about a
+// level-set leaf list (fluid_sdf_grid_t): its rules, the search in it, and the leaves and the 9^3 tiles the surface nets work on
+// (what happens in a tile's cell is mesh_def.h's).  Header only: every file that includes it compiles on its own.
 #pragma once
 #include <algorithm>
 #include <cstdint>

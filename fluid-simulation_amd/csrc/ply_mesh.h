@@ -1,33 +1,16 @@
-// The body of fluid_write_ply_mesh (mesh_host.cpp), fluid_write_ply_mesh_attr and fluid_write_ply_mesh_ex (mesh_attr_host.cpp),
-// which check their own arguments first: binary little-endian PLY, a vertex record of 12 bytes of scaled position, 12 more of the
-// normal and 12 more of the scaled velocity where given; faces are the quads, or the triangles where given.  And the body of
-// fluid_mesh_triangles (include/fluid_hip.h, "normals and triangles").
+// The body of fluid_write_ply_mesh, fluid_write_ply_mesh_attr and fluid_write_ply_mesh_ex (mesh_host.cpp), which check their own
+// arguments first: binary little-endian PLY, a vertex record of 12 bytes of scaled position, 12 more of the normal and 12 more of
+// the scaled velocity where given; faces are the quads, or the triangles where given.  And the body of fluid_mesh_triangles
+// (include/fluid_hip.h, "normals and triangles"), whose cut of a quad is mesh_def.h's.
 #pragma once
 #include <cstdint>
 #include <cstdio>
 #include <vector>
 
 #include "fluid_hip.h"
+#include "mesh_def.h"
 
 namespace {
-
-// quad i = (a, b, c, d) of the (checked) mesh -> triangles 2i and 2i + 1 at t[0..5], cut along the shorter diagonal
-inline void quad_triangles(const float* V, const uint32_t* q, uint32_t* t)
-{
-    float d[2];
-    for (int k = 0; k < 2; ++k) {
-        const float* p0 = V + 3 * (size_t)q[k];
-        const float* p1 = V + 3 * (size_t)q[k + 2];
-        const float x = p1[0] - p0[0], y = p1[1] - p0[1], z = p1[2] - p0[2];
-        float s = x * x;
-        s = s + y * y;
-        s = s + z * z;
-        d[k] = s;
-    }
-    const bool cut13 = d[1] < d[0];   // ties and NaN: the 0-2 diagonal
-    t[0] = q[0], t[1] = q[1], t[2] = cut13 ? q[3] : q[2];
-    t[3] = cut13 ? q[1] : q[0], t[4] = q[2], t[5] = q[3];
-}
 
 // the body of fluid_mesh_triangles
 inline int64_t mesh_triangles(const fluid_mesh_t* m, int64_t cap_triangles, uint32_t* triangles)
@@ -38,7 +21,12 @@ inline int64_t mesh_triangles(const fluid_mesh_t* m, int64_t cap_triangles, uint
         if ((int64_t)m->quads[i] >= m->n_vertices) return -FLUID_ERR_ARG;
     if (!triangles) return 2 * m->n_quads;
     if (2 * m->n_quads > cap_triangles) return -FLUID_ERR_ARG;
-    for (int64_t i = 0; i < m->n_quads; ++i) quad_triangles(m->vertices, m->quads + 4 * i, triangles + 6 * i);
+    // quad i = (a, b, c, d) -> triangles 2i and 2i + 1
+    for (int64_t i = 0; i < m->n_quads; ++i) {
+        const uint32_t* q = m->quads + 4 * i;
+        const float* V = m->vertices;
+        mdef::quad_triangles(q, V + 3 * (size_t)q[0], V + 3 * (size_t)q[1], V + 3 * (size_t)q[2], V + 3 * (size_t)q[3], triangles + 6 * i);
+    }
     return 2 * m->n_quads;
 }
 

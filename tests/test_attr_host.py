@@ -190,8 +190,8 @@ def test_ply_with_velocities_refusals(fs, tmp_path):
 def test_attribute_host_code_under_asan_ubsan(tmp_path):
     exe = tmp_path / "attr_san"
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off",
-           "-fno-omit-frame-pointer", "-I", os.path.join(ROOT, "include"), os.path.join(CSRC, "mesh_attr_host.cpp"),
-           os.path.join(CSRC, "mesh_host.cpp"), os.path.join(ROOT, "tests", "attr_san_main.cpp"), "-o", str(exe)]
+           "-fno-omit-frame-pointer", "-I", os.path.join(ROOT, "include"), os.path.join(CSRC, "mesh_host.cpp"),
+           os.path.join(ROOT, "tests", "attr_san_main.cpp"), "-o", str(exe)]
     b = subprocess.run(cmd, capture_output=True, text=True)
     if b.returncode != 0 and "asan" in (b.stderr or "").lower() and "cannot find" in b.stderr.lower():
         pytest.skip("sanitizer runtime not installed")
