@@ -210,21 +210,14 @@ int64_t fluid_mesh_triangles(const fluid_mesh_t* m, int64_t cap_triangles, uint3
 int fluid_sdf_attr_to_dense(const fluid_sdf_grid_t* g, const fluid_sdf_attr_t* at, uint32_t* id, float* velocity)
 {
     if (check_attr(g, at) != FLUID_OK) return FLUID_ERR_ARG;
-    const int n = g->n, lo = -(n / 2), hi = lo + n - 1;
-    const size_t n3 = (size_t)n * n * n;
+    const size_t n3 = (size_t)g->n * g->n * g->n;
     if (id) std::fill(id, id + n3, (uint32_t)FLUID_SDF_NO_ID);
     if (velocity) std::fill(velocity, velocity + 3 * n3, 0.0f);
-    for (int l = 0; l < g->n_leaves; ++l) {
-        const int32_t* o = g->origin + 3 * (size_t)l;
-        for (int off = 0; off < 512; ++off) {
-            const int x = o[0] + (off >> 6), y = o[1] + ((off >> 3) & 7), z = o[2] + (off & 7);
-            if (x < lo || x > hi || y < lo || y > hi || z < lo || z > hi) continue;
-            const size_t c = ((size_t)(x - lo) * n + (size_t)(y - lo)) * n + (size_t)(z - lo);
-            if (id) id[c] = at->id[512 * (size_t)l + off];
-            if (velocity)
-                for (int a = 0; a < 3; ++a) velocity[a * n3 + c] = at->velocity[1536 * (size_t)l + 512 * a + off];
-        }
-    }
+    scatter_leaves(g, [&](size_t l, int off, size_t c) {
+        if (id) id[c] = at->id[512 * l + off];
+        if (velocity)
+            for (int a = 0; a < 3; ++a) velocity[a * n3 + c] = at->velocity[1536 * l + 512 * a + off];
+    });
     return FLUID_OK;
 }
 
