@@ -68,6 +68,11 @@ class SdfFilter(C.Structure):
     _fields_ = [("width", C.c_int32), ("iterations", C.c_int32), ("offset", C.c_double)]
 
 
+class SdfTrack(C.Structure):
+    """fluid_sdf_track_t: normalisation passes per track, trim, scheme (include/fluid_hip.h, "liquid surface, renormalised")."""
+    _fields_ = [("normalize", C.c_int32), ("trim", C.c_int32), ("scheme", C.c_int32)]
+
+
 class MeshC(C.Structure):
     """fluid_mesh_t: the surface nets of the level set (include/fluid_hip.h, "liquid surface as a mesh")."""
     _fields_ = [("n", C.c_int32), ("n_vertices", C.c_int64), ("n_quads", C.c_int64), ("radius", C.c_float),
@@ -227,6 +232,8 @@ SYMBOLS = [
     ("fluid_sdf_snapshot_filtered", C.c_int, [_P, C.POINTER(SdfParams), C.POINTER(SdfFilter)]),
     ("fluid_mesh_snapshot_filtered", C.c_int, [_P, C.POINTER(SdfParams), C.POINTER(SdfFilter)]),
     ("fluid_sdf_filter", C.c_int, [C.POINTER(SdfGridC), C.POINTER(SdfFilter), _P]),
+    ("fluid_sdf_set_track", C.c_int, [_P, C.POINTER(SdfTrack)]),
+    ("fluid_sdf_filter_tracked", C.c_int64, [C.POINTER(SdfGridC), C.POINTER(SdfFilter), C.POINTER(SdfTrack), C.c_int64, _P, _P, _P, _P]),
     ("fluid_mesh_snapshot", C.c_int, [_P, C.POINTER(SdfParams)]),
     ("fluid_mesh_wait", C.c_int, [_P, C.POINTER(MeshC)]),
     ("fluid_mesh_stats", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -359,6 +359,13 @@ void launch_sdf_pack_attr(hipStream_t st, const SdfGeom& g, const int* flags, co
 void launch_sdf_box(hipStream_t st, const SdfGeom& g, int axis, int W, float off, const int* flags, const uint64_t* tm, const float* src,
                     float* dst);
 void launch_sdf_offset(hipStream_t st, const SdfGeom& g, float off, const int* flags, const uint64_t* tm, float* tv);
+// renormalisation of that level set (kernels_sdf_track.hip): norm = one normalisation pass from src to dst (only flagged leaves are
+// read or written; flags are never cleared); trim = the trim on the pass's results, which rewrites tm and, with tid / tvel non-NULL,
+// resets the deactivated voxels' id and velocity; norm == false: the trim alone, in place (src == dst).  relist: list[j] = the leaf
+// is flagged and holds anything but inactive +bg
+void launch_sdf_track(hipStream_t st, const SdfGeom& g, bool norm, bool trim, const int* flags, uint64_t* tm, const float* src, float* dst,
+                      uint32_t* tid, float* tvel);
+void launch_sdf_relist(hipStream_t st, const SdfGeom& g, const int* flags, const uint64_t* tm, const float* tv, int* list);
 // surface nets of that level set (kernels_mesh.hip): per leaf of the range the mixed-cell mask (8 words), the exclusive prefix of the
 // words' popcounts, the vertex and the quad count; tot[2] = the two totals, saturating at 2^31 (a one-block sum of the counts)
 void launch_mesh_mark(hipStream_t st, const SdfGeom& g, const float* tv, const int* flags, uint64_t* cmask, int* cpre, int* vcnt, int* qcnt,

@@ -76,6 +76,12 @@
 // are fluid_sdf_snapshot_filtered / fluid_mesh_snapshot_filtered; a block run filters the merged list on the main thread
 // (fluid_sdf_filter, two buffers in turn) before it goes to the writer thread.  Refused malformed, outside the filter's limits, or
 // with none of the four set, before any handle is created.  Without it stdout and every file are what they were.
+//   FLUID_OUT_TRACK=N[,TRIM] (unset: off; with FLUID_OUT_SMOOTH only; TRIM defaults to 1) — the filter runs tracked: N normalisation
+// passes (0..8) and, with TRIM = 1, the trim after every box iteration and every offset step (include/fluid_hip.h, "liquid
+// surface, renormalised"), for everything FLUID_OUT_SMOOTH applies to: one GPU through fluid_sdf_set_track, a block run through
+// fluid_sdf_filter_tracked on the main thread after the merge (the trim can shorten the list).  Refused without FLUID_OUT_SMOOTH,
+// malformed or outside the limits, or with FLUID_BLOCKS_MESH_VEL (the block driver does not gather attributes through `kept`),
+// before any handle is created.  Without it stdout and every file are what they were.
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -351,6 +357,8 @@ struct BlockCfg {
     fluid_sdf_params_t sp{};
     bool smooth = false;      // FLUID_OUT_SMOOTH
     fluid_sdf_filter_t sf{};
+    bool track = false;       // FLUID_OUT_TRACK
+    fluid_sdf_track_t tk{};
     bool mesh = false;        // FLUID_BLOCKS_MESH (its R,W are in sp: the same numbers as FLUID_BLOCKS_SURFACE's when both are set)
     bool mesh_vel = false;    // FLUID_BLOCKS_MESH_VEL
     unsigned mesh_more = 0;   // FLUID_BLOCKS_MESH_NORMALS / _TRIS: FLUID_MESH_NORMALS | FLUID_MESH_TRIANGLES
@@ -510,6 +518,8 @@ static int run_blocks(const BlockCfg& cfg, const std::vector<double>& pos, int64
     std::vector<float> s_val[2];
     std::vector<uint64_t> s_act[2];
     std::vector<float> s_smooth[2];   // FLUID_OUT_SMOOTH: the filtered values of the merged list
+    std::vector<int32_t> t_org[2];    // FLUID_OUT_TRACK: the tracked list (the trim can shorten it)
+    std::vector<uint64_t> t_act[2];
     std::vector<uint32_t> s_id[2];    // FLUID_BLOCKS_MESH_VEL: the merged attributes
     std::vector<float> s_vel[2];
     double dt = cfg.prm.max_dt, simulationTime = 0;
@@ -569,7 +579,18 @@ static int run_blocks(const BlockCfg& cfg, const std::vector<double>& pos, int64
             sat = fluid_sdf_attr_t{(int32_t)ks, attr && ks ? si.data() : nullptr, attr && ks ? sw.data() : nullptr};
             sg = fluid_sdf_grid_t{n, (int32_t)ks, sp[0].background, sp[0].radius, sp[0].half_width, ks ? so.data() : nullptr, ks ? sv.data() : nullptr,
                                   ks ? sa.data() : nullptr};
-            if (cfg.smooth && ks) {
+            if (cfg.smooth && cfg.track && ks) {
+                auto& sm = s_smooth[i & 1];
+                auto& to = t_org[i & 1];
+                auto& ta = t_act[i & 1];
+                if (sm.size() < sv.size()) sm.resize(sv.size());
+                if (to.size() < so.size()) to.resize(so.size());
+                if (ta.size() < sa.size()) ta.resize(sa.size());
+                const int64_t kt = fluid_sdf_filter_tracked(&sg, &cfg.sf, &cfg.tk, ks, to.data(), sm.data(), ta.data(), nullptr);
+                if (kt < 0) { sy.fail("fluid_sdf_filter_tracked: the merged surface list, or an offset beyond the background, was refused"); break; }
+                sg = fluid_sdf_grid_t{n, (int32_t)kt, sg.background, sg.radius, sg.half_width, kt ? to.data() : nullptr, kt ? sm.data() : nullptr,
+                                      kt ? ta.data() : nullptr};
+            } else if (cfg.smooth && ks) {
                 auto& sm = s_smooth[i & 1];
                 if (sm.size() < sv.size()) sm.resize(sv.size());
                 if (fluid_sdf_filter(&sg, &cfg.sf, sm.data()) != FLUID_OK) { sy.fail("fluid_sdf_filter: the merged surface list was refused"); break; }
@@ -793,6 +814,26 @@ int main(int, char**)
         }
         bc.smooth = true, bc.sf = sf;
     }
+    const char* tkenv = getenv("FLUID_OUT_TRACK");
+    const bool track = tkenv && *tkenv;
+    fluid_sdf_track_t tk{0, 1, FLUID_SDF_TRACK_FIRST_BIAS};
+    if (track) {
+        int used = 0;
+        const int got = sscanf(tkenv, "%d%n,%d%n", &tk.normalize, &used, &tk.trim, &used);
+        if (got < 1 || tkenv[used] != 0 || tk.normalize < 0 || tk.normalize > 8 || (tk.trim != 0 && tk.trim != 1)) {
+            std::cerr << "FLUID_OUT_TRACK must be N[,TRIM] (normalisation passes 0..8, trim 0 or 1), e.g. 3 or 3,1" << std::endl;
+            return 1;
+        }
+        if (!smooth) {
+            std::cerr << "FLUID_OUT_TRACK renormalises what FLUID_OUT_SMOOTH filters: FLUID_OUT_SMOOTH is not set" << std::endl;
+            return 1;
+        }
+        if (bc.mesh_vel) {
+            std::cerr << "FLUID_OUT_TRACK cannot be combined with FLUID_BLOCKS_MESH_VEL: the trim can shorten the merged list and the block driver does not gather the attributes" << std::endl;
+            return 1;
+        }
+        bc.track = true, bc.tk = tk;
+    }
     if (blocks && *blocks) {
         char tail = 0;
         if (sscanf(blocks, "%dx%dx%d%c", &bc.dims[0], &bc.dims[1], &bc.dims[2], &tail) != 3 || bc.dims[0] < 1 || bc.dims[1] < 1 || bc.dims[2] < 1 ||
@@ -820,6 +861,10 @@ int main(int, char**)
     fluid_sim_t* sim = nullptr;
     if (!(blocks && *blocks) && fluid_create(&prm, &sim) != FLUID_OK) {
         std::cerr << "fluid_create: " << fluid_last_error() << std::endl;
+        return 1;
+    }
+    if (sim && track && fluid_sdf_set_track(sim, &tk) != FLUID_OK) {
+        std::cerr << "fluid_sdf_set_track: " << fluid_last_error() << std::endl;
         return 1;
     }
     const bool ref_scene = prm.n == 121 && ppc == 10;   // fluid.cc:1176,1347-1350

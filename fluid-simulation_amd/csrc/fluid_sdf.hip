@@ -23,6 +23,13 @@
 // ends with the filter's box passes, one launch each, 3 per iteration (x, z, y), from tv to tv2 and back; what follows reads
 // whichever buffer the last pass wrote.  tv2 exists from the handle's first filtered snapshot on.
 //
+// fluid_sdf_set_track ("liquid surface, renormalised"; kernels_sdf_track.hip): with the setting on, every filter of the front half
+// runs its tracked form: a track (N normalisation passes, one launch each, ping-pong like the box passes; the trim rides on the
+// last) after every iteration's three box passes and after every step of the offset, which is then taken in steps of at most
+// dx / 2 by the offset kernel.  `flags` keeps meaning "this leaf's values are valid" throughout (neighbour blocks read it); after
+// the last trim one more launch derives the LIST flags (lflags) from what the trim left, and the scan and the pack run off those.
+// lflags exists from the handle's first tracked snapshot on.
+//
 // fluid_sdf_snapshot_attr / fluid_mesh_snapshot_attr ("liquid surface, attributes"): the scatter also writes each sorted position's
 // index in the live arrays (ssrc), the search keeps the closest particle beside the minimum and writes its id and velocity per voxel
 // (tid, tvel), and the pack lists them.  ssrc, tid and tvel exist from the handle's first attribute snapshot on.  An attribute
@@ -36,6 +43,7 @@
 // decomposed handle; a dead entry is never scattered, so never a winner).  tmin exists from the handle's first such snapshot on; a
 // slot keeps room for the longest record per leaf it has held (wide = 0, 1, 2).
 #include "sim.h"
+#include "sdf_track_def.h"
 
 using namespace fl;
 #define fail fluid_fail
@@ -56,6 +64,10 @@ struct SdfState {
     float* tv = nullptr;
     float* tv2 = nullptr;      // the box passes' second buffer, leaf_cap x 512 like tv: allocated once a filtered snapshot was asked for
     bool filtered = false;
+    int* lflags = nullptr;     // the list flags after a trim, leaf_cap like flags: allocated once a tracked snapshot was asked for
+    bool tracked = false;
+    int track_n = 0;           // fluid_sdf_set_track: passes per track and the trim (0 / false: off)
+    bool track_trim = false;
     // attributes: index in the live arrays per sorted position (part_cap), winner's id (leaf_cap x 512) and velocity (leaf_cap x 3 x 512)
     // per voxel: allocated once an attribute snapshot was asked for
     int* ssrc = nullptr;
@@ -77,6 +89,8 @@ struct SdfState {
 static const char* const SDF_SINGLE = "level-set snapshots are single-GPU only: a decomposed handle holds a block of the particles (fluid_dist_sdf_*)";
 static const char* const SDF_FILT_SINGLE = "filtered level-set snapshots are single-GPU only: a mean of per-block minima is not the mean of the minimum; filter the merged list on the host (fluid_sdf_filter)";
 
+static const char* const SDF_TRACK_SINGLE = "tracked level-set snapshots are single-GPU only: a decomposed handle's filter runs on the merged list on the host (fluid_sdf_filter_tracked)";
+
 static int sdf_init(fluid_sim* s)
 {
     if (s->sdf) return FLUID_OK;
@@ -93,7 +107,7 @@ void fl::sdf_free(fluid_sim* s)
     SdfState* o = s->sdf;
     if (!o) return;
     snap_free(o->ring);
-    for (void* p : {(void*)o->cnt, (void*)o->start, (void*)o->cell_sums, (void*)o->place, (void*)o->spos, (void*)o->tv, (void*)o->tv2, (void*)o->ssrc, (void*)o->tid, (void*)o->tvel, (void*)o->tmin, (void*)o->tm, (void*)o->flags,
+    for (void* p : {(void*)o->cnt, (void*)o->start, (void*)o->cell_sums, (void*)o->place, (void*)o->spos, (void*)o->tv, (void*)o->tv2, (void*)o->lflags, (void*)o->ssrc, (void*)o->tid, (void*)o->tvel, (void*)o->tmin, (void*)o->tm, (void*)o->flags,
                     (void*)o->slot, (void*)o->leaf_sums, (void*)o->visits, (void*)o->d_small})
         if (p) hipFree(p);
     if (o->h_small) hipHostFree(o->h_small);
@@ -102,8 +116,12 @@ void fl::sdf_free(fluid_sim* s)
 }
 
 // (the handle's stream is idle here: every caller has just waited for a read-back on it)
-static int sdf_scratch(SdfState* o, long cells, long parts, long leaves, bool filtered, bool attr, bool dist2)
+static int sdf_scratch(SdfState* o, long cells, long parts, long leaves, bool filtered, bool attr, bool dist2, bool tracked)
 {
+    if (tracked && !o->tracked) {   // the first tracked snapshot of the handle: lflags beside whatever flags there are
+        o->tracked = true;
+        if (o->leaf_cap > 0) HIPCHK(regrow(o->lflags, (size_t)o->leaf_cap));
+    }
     if (dist2 && !o->dist2) {   // the first snapshot with dist2 of the handle: tmin beside whatever there is
         o->dist2 = true;
         if (o->leaf_cap > 0) HIPCHK(regrow(o->tmin, (size_t)o->leaf_cap * 512));
@@ -148,6 +166,7 @@ static int sdf_scratch(SdfState* o, long cells, long parts, long leaves, bool fi
         if (o->dist2) HIPCHK(regrow(o->tmin, (size_t)cap * 512));
         HIPCHK(regrow(o->tm, (size_t)cap * 8));
         HIPCHK(regrow(o->flags, (size_t)cap));
+        if (o->tracked) HIPCHK(regrow(o->lflags, (size_t)cap));
         HIPCHK(regrow(o->slot, (size_t)cap));
         HIPCHK(regrow(o->leaf_sums, (size_t)cap / 2048 + 16));
         if (o->count_visits) HIPCHK(regrow(o->visits, (size_t)cap));
@@ -183,7 +202,10 @@ int fl::sdf_begin(fluid_sim* s, const fluid_sdf_params_t* p, SdfFront* f, const 
     const float mn = std::fmax(0.0f, R - w);
     g.min2 = mn * mn;
     f->any = false;
-    f->tv = nullptr, f->flags = nullptr;
+    f->tv = nullptr, f->flags = nullptr, f->list = nullptr;
+    f->track_n = filt ? s->sdf->track_n : 0, f->track_trim = filt && s->sdf->track_trim;
+    if ((f->track_n > 0 || f->track_trim) && std::fabs((float)filt->offset) > g.bg)
+        return fail(FLUID_ERR_ARG, "tracked level-set filter: an offset beyond the background in magnitude leaves no surface");
     f->filt = filt, f->dilate = 4;
     f->attr = false, f->dist2 = false;
     f->tm = nullptr, f->tid = nullptr, f->tvel = nullptr, f->tmin = nullptr;
@@ -214,8 +236,9 @@ int fl::sdf_front(fluid_sim* s, SdfFront* f)
             g.nl[a] = ((c1 - g.L0) >> 3) - g.l0[a] + 1;
         }
         const long cells = g.cells(), leaves = g.leaves();
+        const bool tracked = f->track_n > 0 || f->track_trim;
         if (cells + 1 > 0x7fffffffL || leaves > 0x7fffffffL) return fail(FLUID_ERR_ARG, "level set: the particles' box is too large");
-        if ((rc = sdf_scratch(o, cells + 1, s->np, leaves, f->filt != nullptr, f->attr, f->dist2))) return rc;
+        if ((rc = sdf_scratch(o, cells + 1, s->np, leaves, f->filt != nullptr, f->attr, f->dist2, tracked))) return rc;
         double *sx = o->spos, *sy = o->spos + o->part_cap, *sz = o->spos + 2 * o->part_cap;
         HIPCHK(hipMemsetAsync(o->cnt, 0, (size_t)(cells + 1) * sizeof(int), s->st));
         launch_sdf_count(s->st, s->np, live, g, o->cnt, o->place, s->dist);
@@ -224,7 +247,7 @@ int fl::sdf_front(fluid_sim* s, SdfFront* f)
         if (f->attr) launch_sdf_search_attr(s->st, g, o->start, sx, sy, sz, o->tv, o->tm, o->flags, o->ssrc, live, o->tid, o->tvel, f->dist2 ? o->tmin : nullptr);
         else launch_sdf_search(s->st, g, o->start, sx, sy, sz, o->tv, o->tm, o->flags, o->count_visits ? o->visits : nullptr);
         f->any = true;
-        f->tv = o->tv, f->flags = o->flags;
+        f->tv = o->tv, f->flags = o->flags, f->list = o->flags;
         f->tm = o->tm;
         if (f->attr) f->tid = o->tid, f->tvel = o->tvel;
         if (f->dist2) f->tmin = o->tmin;
@@ -234,11 +257,41 @@ int fl::sdf_front(fluid_sim* s, SdfFront* f)
             const int W = f->filt->width, passes = 3 * f->filt->iterations;
             const float off = (float)f->filt->offset;
             float *src = o->tv, *dst = o->tv2;
-            for (int k = 0; k < passes; ++k) {
-                launch_sdf_box(s->st, g, axes[k % 3], W, k == passes - 1 ? off : 0.0f, o->flags, o->tm, src, dst);
-                std::swap(src, dst);
+            if (tracked) {
+                // one track: N passes src -> dst, the trim on the last; without a pass the trim alone, in place
+                bool trimmed = false;
+                auto track = [&]() {
+                    for (int i = 0; i < f->track_n; ++i) {
+                        const bool last = i == f->track_n - 1;
+                        launch_sdf_track(s->st, g, true, last && f->track_trim, o->flags, o->tm, src, dst, f->attr ? o->tid : nullptr, o->tvel);
+                        std::swap(src, dst);
+                    }
+                    if (f->track_n == 0) launch_sdf_track(s->st, g, false, true, o->flags, o->tm, src, src, f->attr ? o->tid : nullptr, o->tvel);
+                    trimmed = f->track_trim;
+                };
+                for (int k = 0; k < passes; ++k) {
+                    launch_sdf_box(s->st, g, axes[k % 3], W, 0.0f, o->flags, o->tm, src, dst);
+                    std::swap(src, dst);
+                    if (k % 3 == 2) track();
+                }
+                const float a = std::fabs(off);
+                float d = 0.0f;
+                for (float delta; (delta = tdef::offset_step(a, d, g.dxf)) != 0.0f;) {
+                    d = d + delta;
+                    launch_sdf_offset(s->st, g, std::copysign(delta, off), o->flags, o->tm, src);
+                    track();
+                }
+                if (trimmed) {   // what is listed is what the last trim left
+                    launch_sdf_relist(s->st, g, o->flags, o->tm, src, o->lflags);
+                    f->list = o->lflags;
+                }
+            } else {
+                for (int k = 0; k < passes; ++k) {
+                    launch_sdf_box(s->st, g, axes[k % 3], W, k == passes - 1 ? off : 0.0f, o->flags, o->tm, src, dst);
+                    std::swap(src, dst);
+                }
+                if (passes == 0 && off != 0.0f) launch_sdf_offset(s->st, g, off, o->flags, o->tm, src);
             }
-            if (passes == 0 && off != 0.0f) launch_sdf_offset(s->st, g, off, o->flags, o->tm, src);
             f->tv = src;
         }
     }
@@ -268,7 +321,7 @@ static int sdf_capture(fluid_sim* s, const fluid_sdf_params_t* p, const fluid_sd
     int n = 0;
     if (f.any) {
         const long leaves = g.leaves();
-        launch_exclusive_scan(s->st, o->flags, o->slot, leaves, o->leaf_sums, o->d_small + 7);
+        launch_exclusive_scan(s->st, f.list, o->slot, leaves, o->leaf_sums, o->d_small + 7);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(o->h_small + 7, o->d_small + 7, sizeof(int), hipMemcpyDeviceToHost, s->st));
         HIPCHK(hipStreamSynchronize(s->st));
@@ -295,9 +348,9 @@ static int sdf_capture(fluid_sim* s, const fluid_sdf_params_t* p, const fluid_sd
         uint64_t* active = (uint64_t*)(q.dev + (size_t)n * 2048 + a);
         int* origin = (int*)(q.dev + (size_t)n * (2048 + 64) + a);
         if (attr)
-            launch_sdf_pack_attr(s->st, g, o->flags, o->slot, f.tv, o->tm, values, active, origin, f.tid, f.tvel, (uint32_t*)(q.dev + (size_t)n * 2048),
+            launch_sdf_pack_attr(s->st, g, f.list, o->slot, f.tv, o->tm, values, active, origin, f.tid, f.tvel, (uint32_t*)(q.dev + (size_t)n * 2048),
                                  (float*)(q.dev + (size_t)n * 4096), f.tmin, attr >= 2 ? (float*)(q.dev + (size_t)n * 10240) : nullptr);
-        else launch_sdf_pack(s->st, g, o->flags, o->slot, f.tv, o->tm, values, active, origin);
+        else launch_sdf_pack(s->st, g, f.list, o->slot, f.tv, o->tm, values, active, origin);
         HIPCHK(hipGetLastError());
     }
     if ((rc = snap_commit(o->ring, s->st, (size_t)n * rec))) return rc;
@@ -369,6 +422,18 @@ int fluid_sdf_snapshot_filtered(fluid_sim_t* s, const fluid_sdf_params_t* p, con
     if (int rc = snap_guard(s, SDF_FILT_SINGLE)) return rc;
     if (!f) return fail(FLUID_ERR_ARG, "null argument");
     return sdf_capture(s, p, f);
+}
+
+int fluid_sdf_set_track(fluid_sim_t* s, const fluid_sdf_track_t* t)
+{
+    if (int rc = snap_guard(s, SDF_TRACK_SINGLE)) return rc;
+    if (t && (t->normalize < 0 || t->normalize > tdef::MAX_PASSES || (t->trim != 0 && t->trim != 1) || t->scheme != FLUID_SDF_TRACK_FIRST_BIAS))
+        return fail(FLUID_ERR_ARG, "level-set tracking: normalize in 0..8, trim 0 or 1 and scheme FLUID_SDF_TRACK_FIRST_BIAS are required");
+    HIPCHK(hipSetDevice(s->prm.device));
+    if (int rc = sdf_init(s)) return rc;
+    s->sdf->track_n = t ? t->normalize : 0;
+    s->sdf->track_trim = t && t->trim != 0;
+    return FLUID_OK;
 }
 
 int fluid_sdf_wait(fluid_sim_t* s, fluid_sdf_grid_t* out)

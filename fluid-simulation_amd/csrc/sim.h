@@ -307,7 +307,10 @@ struct SdfFront {
     SdfGeom g;
     bool any;             // some particle counts: g holds the box and the range, tv / flags are filled for every leaf of the range
     const float* tv;      // 512 values per leaf of the range (stale where flags[j] == 0): the filter's last buffer when filt is set
-    const int* flags;     // the leaf is listed
+    const int* flags;     // the leaf's values are valid (the search's listed flag); what the mesh and the ray caster read by
+    const int* list;      // the leaf is listed: flags, or after a tracked filter's trim the flags derived from what the trim left
+    int track_n;          // "liquid surface, renormalised": the handle's setting, copied by sdf_begin when a filter is given:
+    bool track_trim;      // passes per track and the trim; 0 / false: the filter runs untracked
     const fluid_sdf_filter_t* filt;   // nullptr: unfiltered.  Set by sdf_begin from its argument (limits checked there)
     int dilate;           // cells the base-cell box is dilated by for the range: 4; 5 for a filtered mesh (set by the caller after sdf_begin)
     bool attr;            // "liquid surface, attributes": the search also keeps the closest particle (set by the caller after sdf_begin)
@@ -319,7 +322,7 @@ struct SdfFront {
 };
 // limits of the parameters (and of the filter, when one is given), the state, the constants of g
 int sdf_begin(fluid_sim* s, const fluid_sdf_params_t* p, SdfFront* f, const fluid_sdf_filter_t* filt = nullptr);
-int sdf_front(fluid_sim* s, SdfFront* f);   // bbox (waits for the stream) -> count, scan, scatter -> search -> the filter's passes
+int sdf_front(fluid_sim* s, SdfFront* f);   // bbox (waits for the stream) -> count, scan, scatter -> search -> the filter's passes and tracks
 
 // fluid_mesh.hip
 void mesh_free(fluid_sim* s);        // waits for the copies in flight, frees the scratch, the staging and the pinned buffers

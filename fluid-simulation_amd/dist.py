@@ -15,7 +15,7 @@ import threading
 
 import numpy as np
 
-from ._lib import lib, check, Params, StepStats, LeafGridC, SdfParams, SdfGridC, SdfAttrPartC
+from ._lib import lib, check, Params, StepStats, LeafGridC, SdfParams, SdfGridC, SdfAttrPartC, SdfTrack
 from .sim import FluidSim, source_methods, grid_bounds, merge_leaf_grids, _leaf_grid_copy, merge_sdf_grids, _sdf_grid_copy, merge_sdf_attr_grids, _sdf_attr_part_copy  # noqa: F401
 
 EXCHANGE_T = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
@@ -415,6 +415,11 @@ class DistFluidSim(FluidSim):
         attr=True: with the rank record of ids, velocities and squared distances beside it (sdf_wait_attr)."""
         p = SdfParams(float(radius), float(half_width))
         check((lib.fluid_dist_sdf_snapshot_attr if attr else lib.fluid_dist_sdf_snapshot)(self._h, C.byref(p)))
+
+    def sdf_set_track(self, normalize, trim=True):
+        """Refused: a decomposed handle takes no tracked snapshots; track the merged list (sdf_filter_tracked)."""
+        t = None if normalize is None else SdfTrack(int(normalize), int(bool(trim)), 0)
+        check(lib.fluid_sdf_set_track(self._h, None if t is None else C.byref(t)))   # FLUID_ERR_STATE: the library names the host function
 
     def sdf_wait(self):
         """The oldest level-set snapshot not yet waited for, as an SdfGrid (merge_sdf_grids joins the ranks')."""

@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 
-from ._lib import lib, check, FluidError, Params, StepStats, FIELD, Source, LeafGridC, SdfParams, SdfGridC, SdfFilter, MeshC, SdfAttrC, MeshAttrC, SdfAttrPartC, MeshExC, MESH, Camera, Shade, ImageC, RENDER
+from ._lib import lib, check, FluidError, Params, StepStats, FIELD, Source, LeafGridC, SdfParams, SdfGridC, SdfFilter, SdfTrack, MeshC, SdfAttrC, MeshAttrC, SdfAttrPartC, MeshExC, MESH, Camera, Shade, ImageC, RENDER
 
 _FIELD_DTYPE = {
     FIELD.CONTAINER: (np.float32, 1), FIELD.WEIGHTS: (np.float32, 1), FIELD.OUTPUT: (np.float32, 1),
@@ -206,6 +206,38 @@ def sdf_filter(grid, width, iterations, offset=0.0):
     if rc != 0:
         raise FluidError(rc, "fluid_sdf_filter: a bad leaf list or filter (width 1..4, iterations 0..16, finite offset)")
     return SdfGrid(grid.n, grid.origin, val, grid.active, grid.background, grid.radius, grid.half_width)
+
+
+def _sdf_track_of(track):
+    """fluid_sdf_track_t of None (off), a pass count, or (normalize[, trim]); the trim defaults to on."""
+    if track is None:
+        return None
+    if isinstance(track, (tuple, list)):
+        if len(track) not in (1, 2):
+            raise ValueError("track must be None, normalize or (normalize, trim)")
+        return SdfTrack(int(track[0]), int(bool(track[1])) if len(track) == 2 else 1, 0)
+    return SdfTrack(int(track), 1, 0)
+
+
+def sdf_filter_tracked(grid, filt, track):
+    """(SdfGrid, kept): the tracked filter of an SdfGrid (fluid_sdf_filter_tracked: host only).  filt = (width, iterations[,
+    offset]); track = None, normalize or (normalize, trim): after every box iteration and every offset step the level set is
+    renormalised and trimmed (include/fluid_hip.h, "liquid surface, renormalised").  The trim can unlist leaves: kept[i] is the
+    index in `grid` of leaf i of the result.  A decomposed run tracks sdf_filter_tracked(merge_sdf_grids(parts), ...)."""
+    c, _keep = grid._c()
+    f, t = _sdf_filter_of(filt), _sdf_track_of(track)
+    pt = None if t is None else C.byref(t)
+    k = lib.fluid_sdf_filter_tracked(C.byref(c), C.byref(f), pt, 0, None, None, None, None)
+    if k < 0:
+        raise FluidError(-k, "fluid_sdf_filter_tracked: a bad leaf list, filter (width 1..4, iterations 0..16, finite offset) or "
+                             "track (normalize 0..8; |offset| <= background)")
+    org, val, words = np.empty((k, 3), np.int32), np.empty((k, 512), np.float32), np.zeros((k, 8), np.uint64)
+    kept = np.empty(k, np.int32)
+    if k and lib.fluid_sdf_filter_tracked(C.byref(c), C.byref(f), pt, k, org.ctypes.data_as(C.c_void_p), val.ctypes.data_as(C.c_void_p),
+                                          words.ctypes.data_as(C.c_void_p), kept.ctypes.data_as(C.c_void_p)) != k:
+        raise FluidError(1, "fluid_sdf_filter_tracked: the second call disagrees with the count")
+    act = np.unpackbits(words.view(np.uint8), axis=1, bitorder="little").astype(bool).reshape(k, 512)
+    return SdfGrid(grid.n, org, val, act, grid.background, grid.radius, grid.half_width), kept
 
 
 class Mesh:
@@ -720,6 +752,13 @@ class FluidSim:
             check(lib.fluid_sdf_snapshot(self._h, C.byref(p)))
         else:
             check(lib.fluid_sdf_snapshot_filtered(self._h, C.byref(p), C.byref(_sdf_filter_of(smooth))))
+
+    def sdf_set_track(self, normalize, trim=True):
+        """A setting of the handle: every later snapshot given smooth= renormalises (`normalize` passes, 0..8; the library's
+        default is 3) and, with `trim`, trims the level set after every box iteration and every offset step (include/fluid_hip.h,
+        "liquid surface, renormalised").  sdf_set_track(None): off, the default."""
+        t = None if normalize is None else SdfTrack(int(normalize), int(bool(trim)), 0)
+        check(lib.fluid_sdf_set_track(self._h, None if t is None else C.byref(t)))
 
     def sdf_wait(self):
         """The oldest level-set snapshot not yet waited for, as an SdfGrid (copied out of the handle's pinned buffer)."""

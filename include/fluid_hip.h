@@ -657,8 +657,9 @@ int64_t fluid_sdf_grids_merge(const fluid_sdf_grid_t* parts, int32_t n_parts, in
  * Topology does not change: the active masks, the set of listed leaves and their order stay, inactive values stay +-bg, only
  * the values of active voxels differ.
  *
- * What this is not.  LevelSetTracker::track() is NOT run (the library's mean() / gaussian() run it after every box): there is no
- * renormalisation and no rebuild of the band; mean(W) corresponds to K = 1, gaussian(W) to K = 4.  An offset of more than about
+ * What this is not.  By itself the filter does NOT run LevelSetTracker::track() (the library's mean() / gaussian() run it after
+ * every box): no renormalisation unless it is switched on — "liquid surface, renormalised" below — and never a rebuild (dilation)
+ * of the band; mean(W) corresponds to K = 1, gaussian(W) to K = 4.  Untracked, an offset of more than about
  * bg - dx in magnitude pushes the surface into the band's edge, where the inactive +-bg plateau begins.
  * Limits: width in 1..4, iterations in 0..16, offset finite; anything else is FLUID_ERR_ARG.
  *
@@ -683,6 +684,69 @@ int fluid_mesh_snapshot_filtered(fluid_sim_t* s, const fluid_sdf_params_t* p, co
  * leaf, the two neighbours on the pass's axis found by bisection; no dense grid is made.  FLUID_ERR_ARG with nothing written: a
  * list fluid_sdf_to_dense refuses, bad filter limits, values NULL with leaves, values overlapping g->values. */
 int fluid_sdf_filter(const fluid_sdf_grid_t* g, const fluid_sdf_filter_t* f, float* values);
+
+/* ---- liquid surface, renormalised: normalise and trim after every filter step ---------------------------------------------------
+ * A box pass flattens the field: after it |grad val| is no longer 1, the values are no signed distance, `val + offset` moves the
+ * surface by `offset` only where the slope is 1, and every later iteration smooths a flatter field than the library would.
+ * LevelSetFilter therefore runs LevelSetTracker::track() after every box iteration and after every offset step.  This is that
+ * stage — normalize() with the FIRST_BIAS / TVD_RK1 scheme, then Trim — restated from the library's arithmetic
+ * (tools/LevelSetTracker.h:293-306, 455-475, 485-494, 596-609; math/Operators.h:252-284; math/FiniteDifference.h:352-374;
+ * math/Math.h:118; the offset's steps: tools/LevelSetFilter.h:352-368) as an exact, order-free definition of its own: the kernel,
+ * fluid_sdf_filter_tracked below and the tests' numpy form give the same bytes.
+ *
+ * Constants: dx = (float)params.dx, dt = dx * 0.3f, inv = 1.0f / dx, tol = 1e-8f, bg = the level set's background.  Float
+ * throughout, no FMA, IEEE division and square root, denormals kept.  max(a, b) is a < b ? b : a and min(a, b) is b < a ? b : a.
+ * Input: val, act as in "liquid surface, smoothed": unlisted leaves and everything outside the grid read as +bg, inactive voxels
+ * as their stored +-bg.
+ *
+ * One normalisation pass (Jacobi: it reads only the complete result of the pass before).  Every ACTIVE voxel c, p = val(c):
+ *   out = p > 0;  per axis a in the order x, y, z:  dm = p - val(c - e_a), dp = val(c + e_a) - p,
+ *     out:  A = max(dm, 0), B = min(dp, 0);   otherwise:  A = min(dm, 0), B = max(dp, 0);   t_a = max(A*A, B*B);
+ *   G = t_x;  G = G + t_y;  G = G + t_z;   S = p / (sqrtf(p*p + G) + tol);   val_new(c) = p - (dt * S) * (sqrtf(G) * inv - 1.0f).
+ * Inactive voxels keep their value.
+ * Trim.  An active voxel with val <= -bg becomes inactive -bg, one with val >= bg inactive +bg.
+ * track(N, trim) = N normalisation passes, then the trim if `trim`.
+ *
+ * With tracking on (N > 0 or trim), a filter (W, K, offset) is: K times the three box passes x, z, y and then one track; then the
+ * offset in the library's steps:  off = (float)offset, CFL = 0.5f * dx, a = fabsf(off), d = 0.0f;  while a - d > 0.001f * CFL:
+ * delta = (a - d < CFL) ? a - d : CFL;  d = d + delta;  every active voxel gets val + copysignf(delta, off);  then one track.
+ * fabsf(off) > bg is FLUID_ERR_ARG (no surface would be left; it also bounds the launches).  K = 0 with off == 0 runs nothing.
+ * Tracking off, or N = 0 with trim = 0, is "liquid surface, smoothed" byte for byte, its single-step offset included.
+ *
+ * What holds.  Where G * inv^2 >= 1 the correction is smaller than 0.3 |p| in magnitude and directed towards 0; where it is < 1
+ * the correction moves p away from 0; for p = 0, S = 0.  So a normalisation pass never changes a voxel's sign (up to rounding),
+ * and the trim keeps the sign class: with K = 1 and no offset the mesh of the tracked level set has the untracked mesh's vertex
+ * and quad COUNTS, only positions move, and the range argument of fluid_mesh_snapshot_filtered (the particles' box dilated by 5)
+ * holds unchanged for the tracked mesh and image.
+ * Listing.  A leaf is listed iff it holds anything but inactive +bg, evaluated AFTER the last trim: trimming can unlist leaves and
+ * can empty the list (n_leaves = 0).  Attributes: a voxel the trim deactivated has FLUID_SDF_NO_ID and +0 velocity like every
+ * other inactive voxel; ids and velocities of the voxels still active are untouched.
+ *
+ * What this is not.  The band never grows: dilateActiveValues, the first line of track(), is NOT run, so a surface that leaves
+ * the band is lost to the trim instead of followed.  HJWENO5, the library's default spatial scheme, and TVD_RK2/3 are not built;
+ * neither are the tracker's dilate / erode / resize.  Decomposed handles take no tracked snapshots: track the merged list. */
+#define FLUID_SDF_TRACK_FIRST_BIAS 0
+typedef struct fluid_sdf_track { int32_t normalize; /* passes per track: 0..8; the library's default is 3 */
+                                 int32_t trim;      /* 0 or 1 */
+                                 int32_t scheme;    /* FLUID_SDF_TRACK_FIRST_BIAS only */ } fluid_sdf_track_t;
+/* A setting of the handle, like fluid_set_dt: every later snapshot that is given a filter runs the tracked form of it —
+ * fluid_sdf_snapshot_filtered, fluid_sdf_snapshot_attr, fluid_mesh_snapshot_filtered, fluid_mesh_snapshot_attr,
+ * fluid_mesh_snapshot_ex and fluid_render_snapshot; unfiltered snapshots are untouched.  NULL: off (the default).  One launch per
+ * normalisation pass on the handle's stream, one more after the last trim; the scratch it needs is allocated by the first tracked
+ * snapshot, never inside a step.  FLUID_ERR_ARG: bad limits or an unknown scheme.  FLUID_ERR_STATE on a decomposed handle: track
+ * the merged list (fluid_sdf_filter_tracked). */
+int fluid_sdf_set_track(fluid_sim_t* s, const fluid_sdf_track_t* t);
+/* Host only: the tracked filter applied to a leaf list, how a block run gets it after fluid_sdf_grids_merge.  Returns the number
+ * of leaves still listed and writes the compacted list: origin[3 k] ascending, values[512 k], active[8 k], and, when kept is not
+ * NULL, kept[i] = the index in g of output leaf i (to gather attribute arrays by).  With origin, values and active all NULL it
+ * returns the count only.  t == NULL (and N = 0 with trim = 0): fluid_sdf_filter plus the copy of masks and origins; every leaf
+ * stays.  dx is background / half_width (a list carries no dx), or the float next to that quotient whose product with half_width
+ * gives the background back.  Voxels of listed leaves outside the grid are read as +bg, copied unchanged, and do not count for the listing.  Works
+ * leaf by leaf, the six face neighbours found by bisection; no dense grid is made.  -FLUID_ERR_ARG with nothing written: whatever
+ * fluid_sdf_filter refuses, bad track limits, fabsf(offset) > background with tracking on, cap_leaves smaller than the count,
+ * some but not all of the three outputs NULL, outputs overlapping g's arrays. */
+int64_t fluid_sdf_filter_tracked(const fluid_sdf_grid_t* g, const fluid_sdf_filter_t* f, const fluid_sdf_track_t* t,
+                                 int64_t cap_leaves, int32_t* origin, float* values, uint64_t* active, int32_t* kept /* may be NULL */);
 
 /* ---- liquid surface as a mesh: surface nets of the level set ----------------------------------------------------------------
  * Polygons for everyone who is no volume renderer.  The reference names tools/VolumeToMesh.h, whose output depends on the library's

@@ -1,0 +1,216 @@
+"""CPU (-m "not gpu"): the host half of the renormalised liquid surface — fluid_sdf_filter_tracked on tests/sdf_ref.py leaf lists
+against tests/sdf_track_ref.py (values as bit patterns, masks, origins, kept), fluid_sdf_mesh of the tracked list against
+tests/mesh_ref.py of the tracked field, the count-only mode, the refusals (none writes), hand-made lists, and the file under
+ASan + UBSan as a stand-alone program."""
+import ctypes as C
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import mesh_ref
+import sdf_filter_ref
+import sdf_ref
+import sdf_track_ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "fluid-simulation_amd", "csrc")
+ERR_ARG = 1
+SCENES = ["one", "corner", "lo", "hi", "cloud"]
+TRACKS = sdf_track_ref.TRACKS
+
+
+def u32(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def grid_of(fs, name, n, R, w, dx):
+    """The unfiltered scene as an SdfGrid."""
+    _, val, act, bg, _ = sdf_filter_ref.scene(name, n, R, w, dx, (1, 0, 0.0))
+    fR, fw = sdf_ref.constants(R, w, dx)[:2]
+    org, v, a = sdf_ref.leaf_list(val, act, bg)
+    return fs.SdfGrid(n, org, v, a, bg, fR, fw)
+
+
+def args_of(case, dx):
+    W, K, units, N, tr = case
+    return (W, K, units * dx), (N, bool(tr))
+
+
+@pytest.mark.parametrize("R,w,dx", mesh_ref.SETS)
+@pytest.mark.parametrize("n", [16, 25])
+@pytest.mark.parametrize("name", SCENES)
+def test_tracked_filter_and_mesh_are_the_reference(fs, name, n, R, w, dx):
+    g = grid_of(fs, name, n, R, w, dx)
+    assert g.n_leaves > 0
+    for case in TRACKS:
+        _, vt, at, bg, ref = sdf_track_ref.scene(name, n, R, w, dx, case)
+        org, v, a = sdf_ref.leaf_list(vt, at, bg)
+        filt, track = args_of(case, dx)
+        out, kept = fs.sdf_filter_tracked(g, filt, track)
+        assert out.n_leaves == len(org) and np.array_equal(out.origin, org), case
+        assert np.array_equal(out.active, a), case
+        assert np.array_equal(u32(out.values), u32(v)), case
+        assert np.array_equal(g.origin[kept], out.origin) and (np.diff(kept) > 0).all(), case
+        dv, da = fs.sdf_to_dense(out)
+        assert np.array_equal(u32(dv), u32(vt)) and np.array_equal(da, at), case
+        if case[3] == 0 and case[4] == 0:                                        # tracking that does nothing: fluid_sdf_filter's bytes
+            plain = fs.sdf_filter(g, *filt)
+            assert np.array_equal(u32(out.values), u32(plain.values)) and np.array_equal(out.active, g.active), case
+            assert np.array_equal(kept, np.arange(g.n_leaves))
+        m = fs.sdf_mesh(out)
+        assert m.vertices.shape == ref[0].shape and m.quads.shape == ref[1].shape, (case, m.vertices.shape, ref[0].shape)
+        assert np.array_equal(u32(m.vertices), u32(ref[0])) and np.array_equal(m.quads, ref[1]), case
+
+
+def raw_call(fs, g, filt, track, cap, org, val, act, kept):
+    c, _keep = g._c()
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)   # noqa: E731
+    f = None if filt is None else C.byref(fs.SdfFilter(*filt))
+    t = None if track is None else C.byref(fs.SdfTrack(*track))
+    return fs.lib.fluid_sdf_filter_tracked(C.byref(c), f, t, cap, p(org), p(val), p(act), p(kept))
+
+
+def test_count_only_null_track_and_refusals(fs):
+    R, w, dx = mesh_ref.SETS[0]
+    g = grid_of(fs, "hi", 25, R, w, dx)
+    k0 = g.n_leaves
+    assert k0 == 5
+    filt, tr = (1, 1, 0.0), (3, 1, 0)
+    assert raw_call(fs, g, filt, tr, 0, None, None, None, None) == 4                # the count alone: one leaf leaves the list
+    org, val, act, kept = np.full((k0, 3), 7, np.int32), np.full((k0, 512), 7, np.float32), np.full((k0, 8), 7, np.uint64), np.full(k0, 7, np.int32)
+
+    def untouched():
+        return (org == 7).all() and (val == 7).all() and (act == 7).all() and (kept == 7).all()
+
+    assert raw_call(fs, g, filt, tr, 3, org, val, act, kept) == -ERR_ARG and untouched()          # cap too small
+    for bad in ((0, 1, 0.0), (5, 1, 0.0), (1, -1, 0.0), (1, 17, 0.0), (1, 1, float("nan")), (1, 1, float("inf")), (1, 0, 1e300)):
+        assert raw_call(fs, g, bad, tr, k0, org, val, act, kept) == -ERR_ARG, bad
+        assert raw_call(fs, g, bad, None, k0, org, val, act, kept) == -ERR_ARG, bad
+    for bad in ((-1, 1, 0), (9, 1, 0), (3, 2, 0), (3, -1, 0), (3, 1, 1)):
+        assert raw_call(fs, g, filt, bad, k0, org, val, act, kept) == -ERR_ARG, bad
+        assert raw_call(fs, g, filt, bad, 0, None, None, None, None) == -ERR_ARG, bad
+    for bad in (-1, 9):
+        with pytest.raises(fs.FluidError):
+            fs.sdf_filter_tracked(g, filt, bad)
+    bg = float(g.background)
+    assert raw_call(fs, g, (1, 1, bg * 1.01), tr, k0, org, val, act, kept) == -ERR_ARG           # |off| > bg, tracked
+    assert raw_call(fs, g, (1, 1, -bg * 1.01), (0, 1, 0), k0, org, val, act, kept) == -ERR_ARG
+    assert raw_call(fs, g, None, tr, k0, org, val, act, kept) == -ERR_ARG
+    assert raw_call(fs, g, filt, tr, k0, org, None, act, kept) == -ERR_ARG          # some but not all outputs
+    assert raw_call(fs, g, filt, tr, k0, None, val, act, kept) == -ERR_ARG
+    assert untouched()
+    # outputs overlapping g's arrays
+    c, words = g._c()
+    t = fs.SdfTrack(*tr)
+    f = fs.SdfFilter(*filt)
+    call = lambda o, v, a, kp: fs.lib.fluid_sdf_filter_tracked(C.byref(c), C.byref(f), C.byref(t), k0, C.c_void_p(o), C.c_void_p(v), C.c_void_p(a), C.c_void_p(kp))   # noqa: E731
+    po, pv, pa, pk = org.ctypes.data, val.ctypes.data, act.ctypes.data, kept.ctypes.data
+    before = (g.origin.copy(), g.values.copy(), words.copy())
+    assert call(po, g.values.ctypes.data, pa, pk) == -ERR_ARG
+    assert call(po, g.values.ctypes.data + 2048 * (k0 - 1), pa, pk) == -ERR_ARG
+    assert call(g.origin.ctypes.data, pv, pa, pk) == -ERR_ARG
+    assert call(po, pv, words.ctypes.data, pk) == -ERR_ARG
+    assert call(po, pv, pa, g.values.ctypes.data) == -ERR_ARG
+    assert untouched() and np.array_equal(before[0], g.origin) and np.array_equal(u32(before[1]), u32(g.values)) and np.array_equal(before[2], words)
+    # a list out of order, an origin off the 8-grid
+    o = g.origin.copy(); o[[1, 2]] = o[[2, 1]]
+    with pytest.raises(fs.FluidError):
+        fs.sdf_filter_tracked(fs.SdfGrid(25, o, g.values, g.active, g.background, g.radius, g.half_width), filt, 3)
+    o = g.origin.copy(); o[0, 1] += 4
+    with pytest.raises(fs.FluidError):
+        fs.sdf_filter_tracked(fs.SdfGrid(25, o, g.values, g.active, g.background, g.radius, g.half_width), filt, 3)
+    # the limits themselves; untracked, an offset beyond bg stays allowed as in fluid_sdf_filter
+    assert raw_call(fs, g, (4, 16, -bg), (8, 1, 0), k0, org, val, act, kept) >= 0
+    assert raw_call(fs, g, (1, 1, bg * 1.01), None, k0, org, val, act, kept) == k0
+    assert raw_call(fs, g, (1, 1, bg * 1.01), (0, 0, 0), k0, org, val, act, kept) == k0
+    # t == NULL: fluid_sdf_filter plus the copy of masks and origins
+    for filt2 in sdf_filter_ref.FILTERS:
+        out, kp = fs.sdf_filter_tracked(g, filt2, None)
+        plain = fs.sdf_filter(g, *filt2)
+        assert np.array_equal(u32(out.values), u32(plain.values)) and np.array_equal(out.active, g.active) and np.array_equal(out.origin, g.origin)
+        assert np.array_equal(kp, np.arange(k0))
+    e = fs.SdfGrid(16, np.empty((0, 3)), np.empty((0, 512)), np.empty((0, 512)), 2.5, 1.5, 2.5)
+    out, kp = fs.sdf_filter_tracked(e, (2, 3, -0.5), 3)
+    assert out.n_leaves == 0 and len(kp) == 0
+
+
+def test_hand_made_lists(fs):
+    """The cloud's list at n = 25 (leaves cut by the grid's faces on both sides) with every second leaf taken off the list — bands
+    that end at an unlisted neighbour — equals the reference on the dense field with those leaves blanked; and a list whose
+    out-of-grid voxels hold junk: they are read as +bg, copied unchanged, and do not keep a leaf listed."""
+    n, (R, w, dx) = 25, mesh_ref.SETS[3]
+    g = grid_of(fs, "cloud", n, R, w, dx)
+    lo, hi, _, _ = sdf_ref.geometry(n)
+    bg = g.background
+    keep = np.arange(g.n_leaves) % 2 == 0
+    h = fs.SdfGrid(n, g.origin[keep], g.values[keep], g.active[keep], bg, g.radius, g.half_width)
+    val, act = fs.sdf_to_dense(h)
+    assert act.any() and h.n_leaves < g.n_leaves
+    rng = np.random.default_rng(5)
+    off = np.arange(512)
+    junk_v, junk_a = h.values.copy(), h.active.copy()
+    n_out = 0
+    for i, o in enumerate(h.origin):
+        c = np.stack([o[0] + (off >> 6), o[1] + ((off >> 3) & 7), o[2] + (off & 7)], axis=1)
+        out = ((c < lo) | (c > hi)).any(axis=1)
+        n_out += int(out.sum())
+        junk_v[i, out] = rng.uniform(-9, 9, int(out.sum())).astype(np.float32)
+        junk_a[i, out] = rng.integers(0, 2, int(out.sum())).astype(bool)
+    assert n_out > 1000
+    hj = fs.SdfGrid(n, h.origin, junk_v, junk_a, bg, g.radius, g.half_width)
+    for case in TRACKS:
+        filt, track = args_of(case, dx)
+        vt, at = sdf_track_ref.tracked(val, act, bg, dx, case[0], case[1], case[2] * dx, case[3], bool(case[4]))
+        org, v, a = sdf_ref.leaf_list(vt, at, bg)
+        out, kept = fs.sdf_filter_tracked(h, filt, track)
+        tracked_on = case[3] > 0 or case[4]
+        if case[4]:
+            assert np.array_equal(out.origin, org) and np.array_equal(u32(out.values), u32(v)) and np.array_equal(out.active, a), case
+        dv, da = fs.sdf_to_dense(out)
+        assert np.array_equal(u32(dv), u32(vt)) and np.array_equal(da, at), case
+        outj, keptj = fs.sdf_filter_tracked(hj, filt, track)
+        assert np.array_equal(keptj, kept), case
+        dj, aj = fs.sdf_to_dense(outj)
+        assert np.array_equal(u32(dj), u32(vt)) and np.array_equal(aj, at), case
+        inside = np.zeros((len(keptj), 512), bool)
+        for i, o in enumerate(outj.origin):
+            c = np.stack([o[0] + (off >> 6), o[1] + ((off >> 3) & 7), o[2] + (off & 7)], axis=1)
+            inside[i] = ((c >= lo) & (c <= hi)).all(axis=1)
+        assert np.array_equal(u32(outj.values[~inside]), u32(junk_v[keptj][~inside])), case
+        assert np.array_equal(outj.active[~inside], junk_a[keptj][~inside]), (case, tracked_on)
+
+
+@pytest.mark.parametrize("extra", [{"FLUID_OUT_SMOOTH": ""}, {"FLUID_OUT_TRACK": "9"}, {"FLUID_OUT_TRACK": "3,2"}, {"FLUID_OUT_TRACK": "x"},
+                                   {"FLUID_OUT_TRACK": "3,"}, {"FLUID_OUT_TRACK": "-1"},
+                                   {"FLUID_OUT_MESH": "", "FLUID_BLOCKS": "2x1x1", "FLUID_BLOCKS_MESH": "1.5,2.5", "FLUID_BLOCKS_MESH_VEL": "1"}])
+def test_driver_refuses_a_tracking_it_would_not_apply(fs, tmp_path, extra):
+    """FLUID_OUT_TRACK without FLUID_OUT_SMOOTH, malformed or out of limits, or with FLUID_BLOCKS_MESH_VEL: refused before any handle
+    is created — the message is the variable's own, not the missing device's."""
+    env = dict(os.environ, FLUID_N="16", FLUID_PPC="1", FLUID_STEPS="1", FLUID_OUT=str(tmp_path / "simulation"), FLUID_OUT_MESH="1.5,2.5",
+               FLUID_OUT_SMOOTH="1,1", FLUID_OUT_TRACK="3")
+    for k in ("FLUID_OUT_DENSE", "FLUID_BLOCKS", "FLUID_SOURCE_EVERY", "FLUID_RAW", "FLUID_OUT_SURFACE", "FLUID_BLOCKS_SURFACE", "FLUID_BLOCKS_MESH",
+              "FLUID_BLOCKS_MESH_VEL"):
+        env.pop(k, None)
+    env.update(extra)
+    r = subprocess.run([os.path.join(ROOT, "fluid-simulation_amd", "fluid")], capture_output=True, text=True, env=env, cwd=tmp_path, timeout=60)
+    assert r.returncode == 1 and "FLUID_OUT_TRACK" in r.stderr and "fluid_create" not in r.stderr, (r.returncode, r.stderr[-500:])
+    assert not list(tmp_path.rglob("*.ply")) and not list(tmp_path.rglob("*.vdb"))
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_tracked_filter_under_asan_ubsan(tmp_path):
+    exe = tmp_path / "host_san_track"
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off",
+           "-fno-omit-frame-pointer", "-I", os.path.join(ROOT, "include"), os.path.join(CSRC, "sdf_filter_host.cpp"),
+           os.path.join(ROOT, "tests", "host_san_track_main.cpp"), "-o", str(exe)]
+    b = subprocess.run(cmd, capture_output=True, text=True)
+    if b.returncode != 0 and "asan" in (b.stderr or "").lower() and "cannot find" in b.stderr.lower():
+        pytest.skip("sanitizer runtime not installed")
+    assert b.returncode == 0, b.stderr[-3000:]
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600,
+                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
+    assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
+    assert "host sanitizer run (track): ok" in r.stdout
