@@ -234,6 +234,9 @@ SYMBOLS = [
     ("fluid_sdf_filter", C.c_int, [C.POINTER(SdfGridC), C.POINTER(SdfFilter), _P]),
     ("fluid_sdf_set_track", C.c_int, [_P, C.POINTER(SdfTrack)]),
     ("fluid_sdf_filter_tracked", C.c_int64, [C.POINTER(SdfGridC), C.POINTER(SdfFilter), C.POINTER(SdfTrack), C.c_int64, _P, _P, _P, _P]),
+    ("fluid_sdf_set_track_grow", C.c_int, [_P, C.c_int32]),
+    ("fluid_sdf_filter_grown", C.c_int64, [C.POINTER(SdfGridC), C.POINTER(SdfAttrC), C.POINTER(SdfFilter), C.POINTER(SdfTrack), C.c_int64, _P, _P, _P,
+                                           _P, _P]),
     ("fluid_mesh_snapshot", C.c_int, [_P, C.POINTER(SdfParams)]),
     ("fluid_mesh_wait", C.c_int, [_P, C.POINTER(MeshC)]),
     ("fluid_mesh_stats", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -366,6 +366,11 @@ void launch_sdf_offset(hipStream_t st, const SdfGeom& g, float off, const int* f
 void launch_sdf_track(hipStream_t st, const SdfGeom& g, bool norm, bool trim, const int* flags, uint64_t* tm, const float* src, float* dst,
                       uint32_t* tid, float* tvel);
 void launch_sdf_relist(hipStream_t st, const SdfGeom& g, const int* flags, const uint64_t* tm, const float* tv, int* list);
+// band dilation of that level set (kernels_sdf_grow.hip): reads flags / tm, writes flags2 / tm2 for every leaf of the range (the
+// caller swaps the pairs); a leaf that becomes flagged gets +bg in val and, with tid / tvel non-NULL, NO_ID and +0; with them a
+// newly active voxel inherits its first active face neighbour's id and velocity
+void launch_sdf_grow(hipStream_t st, const SdfGeom& g, const int* flags, const uint64_t* tm, int* flags2, uint64_t* tm2, float* val, uint32_t* tid,
+                     float* tvel);
 // surface nets of that level set (kernels_mesh.hip): per leaf of the range the mixed-cell mask (8 words), the exclusive prefix of the
 // words' popcounts, the vertex and the quad count; tot[2] = the two totals, saturating at 2^31 (a one-block sum of the counts)
 void launch_mesh_mark(hipStream_t st, const SdfGeom& g, const float* tv, const int* flags, uint64_t* cmask, int* cpre, int* vcnt, int* qcnt,

@@ -82,6 +82,10 @@
 // fluid_sdf_filter_tracked on the main thread after the merge (the trim can shorten the list).  Refused without FLUID_OUT_SMOOTH,
 // malformed or outside the limits, or with FLUID_BLOCKS_MESH_VEL (the block driver does not gather attributes through `kept`),
 // before any handle is created.  Without it stdout and every file are what they were.
+//   FLUID_OUT_TRACK=N,1,GROW (GROW 0 or 1, default 0) — with GROW = 1 every track begins with a dilation of the band (include/fluid_hip.h,
+// "liquid surface, grown band"; N >= 1 and TRIM = 1 are required, and |OFFSET| of FLUID_OUT_SMOOTH may reach 4 voxels): one GPU
+// through fluid_sdf_set_track_grow, a block run through fluid_sdf_filter_grown after the merge, which returns the attributes in
+// full — so FLUID_BLOCKS_MESH_VEL is accepted with GROW = 1.
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -358,6 +362,7 @@ struct BlockCfg {
     bool smooth = false;      // FLUID_OUT_SMOOTH
     fluid_sdf_filter_t sf{};
     bool track = false;       // FLUID_OUT_TRACK
+    bool grow = false;        // ... with GROW = 1
     fluid_sdf_track_t tk{};
     bool mesh = false;        // FLUID_BLOCKS_MESH (its R,W are in sp: the same numbers as FLUID_BLOCKS_SURFACE's when both are set)
     bool mesh_vel = false;    // FLUID_BLOCKS_MESH_VEL
@@ -520,6 +525,8 @@ static int run_blocks(const BlockCfg& cfg, const std::vector<double>& pos, int64
     std::vector<float> s_smooth[2];   // FLUID_OUT_SMOOTH: the filtered values of the merged list
     std::vector<int32_t> t_org[2];    // FLUID_OUT_TRACK: the tracked list (the trim can shorten it)
     std::vector<uint64_t> t_act[2];
+    std::vector<uint32_t> t_id[2];    // ... with GROW = 1 and FLUID_BLOCKS_MESH_VEL: the grown list's attributes
+    std::vector<float> t_vel[2];
     std::vector<uint32_t> s_id[2];    // FLUID_BLOCKS_MESH_VEL: the merged attributes
     std::vector<float> s_vel[2];
     double dt = cfg.prm.max_dt, simulationTime = 0;
@@ -579,7 +586,24 @@ static int run_blocks(const BlockCfg& cfg, const std::vector<double>& pos, int64
             sat = fluid_sdf_attr_t{(int32_t)ks, attr && ks ? si.data() : nullptr, attr && ks ? sw.data() : nullptr};
             sg = fluid_sdf_grid_t{n, (int32_t)ks, sp[0].background, sp[0].radius, sp[0].half_width, ks ? so.data() : nullptr, ks ? sv.data() : nullptr,
                                   ks ? sa.data() : nullptr};
-            if (cfg.smooth && cfg.track && ks) {
+            if (cfg.smooth && cfg.track && cfg.grow && ks) {   // the grown list can be longer than the merged one: count, then fill
+                const fluid_sdf_attr_t* in = attr ? &sat : nullptr;
+                const int64_t kg = fluid_sdf_filter_grown(&sg, in, &cfg.sf, &cfg.tk, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
+                if (kg < 0) { sy.fail("fluid_sdf_filter_grown: the merged surface list, or an offset beyond 4 voxels, was refused"); break; }
+                auto& sm = s_smooth[i & 1];
+                auto& to = t_org[i & 1];
+                auto& ta = t_act[i & 1];
+                auto& ti = t_id[i & 1];
+                auto& tv = t_vel[i & 1];
+                if (to.size() < 3 * (size_t)kg) { to.resize(3 * ((size_t)kg + 64)); ta.resize(8 * ((size_t)kg + 64)); }
+                if (sm.size() < 512 * (size_t)kg) sm.resize(512 * ((size_t)kg + 64));
+                if (attr && ti.size() < 512 * (size_t)kg) { ti.resize(512 * ((size_t)kg + 64)); tv.resize(1536 * ((size_t)kg + 64)); }
+                if (kg && fluid_sdf_filter_grown(&sg, in, &cfg.sf, &cfg.tk, kg, to.data(), sm.data(), ta.data(), attr ? ti.data() : nullptr,
+                                                 attr ? tv.data() : nullptr) != kg) { sy.fail("fluid_sdf_filter_grown: the second call disagrees with the count"); break; }
+                sg = fluid_sdf_grid_t{n, (int32_t)kg, sg.background, sg.radius, sg.half_width, kg ? to.data() : nullptr, kg ? sm.data() : nullptr,
+                                      kg ? ta.data() : nullptr};
+                sat = fluid_sdf_attr_t{(int32_t)kg, attr && kg ? ti.data() : nullptr, attr && kg ? tv.data() : nullptr};
+            } else if (cfg.smooth && cfg.track && ks) {
                 auto& sm = s_smooth[i & 1];
                 auto& to = t_org[i & 1];
                 auto& ta = t_act[i & 1];
@@ -816,23 +840,29 @@ int main(int, char**)
     }
     const char* tkenv = getenv("FLUID_OUT_TRACK");
     const bool track = tkenv && *tkenv;
+    bool track_grow = false;
     fluid_sdf_track_t tk{0, 1, FLUID_SDF_TRACK_FIRST_BIAS};
     if (track) {
-        int used = 0;
-        const int got = sscanf(tkenv, "%d%n,%d%n", &tk.normalize, &used, &tk.trim, &used);
-        if (got < 1 || tkenv[used] != 0 || tk.normalize < 0 || tk.normalize > 8 || (tk.trim != 0 && tk.trim != 1)) {
-            std::cerr << "FLUID_OUT_TRACK must be N[,TRIM] (normalisation passes 0..8, trim 0 or 1), e.g. 3 or 3,1" << std::endl;
+        int used = 0, grow = 0;
+        const int got = sscanf(tkenv, "%d%n,%d%n,%d%n", &tk.normalize, &used, &tk.trim, &used, &grow, &used);
+        if (got < 1 || tkenv[used] != 0 || tk.normalize < 0 || tk.normalize > 8 || (tk.trim != 0 && tk.trim != 1) || (grow != 0 && grow != 1)) {
+            std::cerr << "FLUID_OUT_TRACK must be N[,TRIM[,GROW]] (normalisation passes 0..8, trim 0 or 1, grow 0 or 1), e.g. 3 or 3,1 or 3,1,1" << std::endl;
             return 1;
         }
+        if (grow && (tk.normalize < 1 || tk.trim != 1)) {
+            std::cerr << "FLUID_OUT_TRACK: GROW = 1 needs N >= 1 and TRIM = 1 (the library's track())" << std::endl;
+            return 1;
+        }
+        track_grow = grow != 0;
         if (!smooth) {
             std::cerr << "FLUID_OUT_TRACK renormalises what FLUID_OUT_SMOOTH filters: FLUID_OUT_SMOOTH is not set" << std::endl;
             return 1;
         }
-        if (bc.mesh_vel) {
-            std::cerr << "FLUID_OUT_TRACK cannot be combined with FLUID_BLOCKS_MESH_VEL: the trim can shorten the merged list and the block driver does not gather the attributes" << std::endl;
+        if (bc.mesh_vel && !track_grow) {
+            std::cerr << "FLUID_OUT_TRACK cannot be combined with FLUID_BLOCKS_MESH_VEL: the trim can shorten the merged list and the block driver does not gather the attributes (GROW = 1 returns them in full)" << std::endl;
             return 1;
         }
-        bc.track = true, bc.tk = tk;
+        bc.track = true, bc.tk = tk, bc.grow = track_grow;
     }
     if (blocks && *blocks) {
         char tail = 0;
@@ -865,6 +895,10 @@ int main(int, char**)
     }
     if (sim && track && fluid_sdf_set_track(sim, &tk) != FLUID_OK) {
         std::cerr << "fluid_sdf_set_track: " << fluid_last_error() << std::endl;
+        return 1;
+    }
+    if (sim && track_grow && fluid_sdf_set_track_grow(sim, 1) != FLUID_OK) {
+        std::cerr << "fluid_sdf_set_track_grow: " << fluid_last_error() << std::endl;
         return 1;
     }
     const bool ref_scene = prm.n == 121 && ppc == 10;   // fluid.cc:1176,1347-1350

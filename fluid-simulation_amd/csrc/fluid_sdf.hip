@@ -30,6 +30,14 @@
 // the last trim one more launch derives the LIST flags (lflags) from what the trim left, and the scan and the pack run off those.
 // lflags exists from the handle's first tracked snapshot on.
 //
+// fluid_sdf_set_track_grow ("liquid surface, grown band"; kernels_sdf_grow.hip): with the setting on, every track begins with one
+// dilation launch, and the range is the particles' box dilated by f->dilate + T cells, T = the number of tracks the filter runs,
+// which the host knows before anything is sized.  The launch reads flags / tm and writes flags2 / tm2 (ping-pong: neighbour blocks
+// of the launch read this leaf's flag and words); the host swaps the two pairs after it, and whoever follows — passes, relist,
+// pack, mesh, ray caster — is handed the pair that is current (f->flags, f->tm).  The search of the next snapshot writes flags / tm
+// again, every leaf of its range, so nothing of an earlier snapshot is read.  flags2 and tm2 exist from the handle's first grown
+// snapshot on.
+//
 // fluid_sdf_snapshot_attr / fluid_mesh_snapshot_attr ("liquid surface, attributes"): the scatter also writes each sorted position's
 // index in the live arrays (ssrc), the search keeps the closest particle beside the minimum and writes its id and velocity per voxel
 // (tid, tvel), and the pack lists them.  ssrc, tid and tvel exist from the handle's first attribute snapshot on.  An attribute
@@ -68,6 +76,10 @@ struct SdfState {
     bool tracked = false;
     int track_n = 0;           // fluid_sdf_set_track: passes per track and the trim (0 / false: off)
     bool track_trim = false;
+    int* flags2 = nullptr;     // the dilation's second flags and masks (leaf_cap, leaf_cap x 8): allocated once a grown snapshot was asked for
+    uint64_t* tm2 = nullptr;
+    bool grown = false;
+    bool track_grow = false;   // fluid_sdf_set_track_grow
     // attributes: index in the live arrays per sorted position (part_cap), winner's id (leaf_cap x 512) and velocity (leaf_cap x 3 x 512)
     // per voxel: allocated once an attribute snapshot was asked for
     int* ssrc = nullptr;
@@ -80,6 +92,7 @@ struct SdfState {
     int *flags = nullptr, *slot = nullptr, *leaf_sums = nullptr;
     unsigned* visits = nullptr;   // FLUID_SDF_VISITS=1 only
     bool count_visits = false;
+    bool grow_stats = false;      // FLUID_SDF_GROW_STATS=1 only
     int *d_small = nullptr, *h_small = nullptr;   // box[6], cell total, listed count
     SnapRing ring;
     SdfMeta m[2];
@@ -89,6 +102,7 @@ struct SdfState {
 static const char* const SDF_SINGLE = "level-set snapshots are single-GPU only: a decomposed handle holds a block of the particles (fluid_dist_sdf_*)";
 static const char* const SDF_FILT_SINGLE = "filtered level-set snapshots are single-GPU only: a mean of per-block minima is not the mean of the minimum; filter the merged list on the host (fluid_sdf_filter)";
 
+static const char* const SDF_GROW_SINGLE = "grown level-set snapshots are single-GPU only: a decomposed handle's filter runs on the merged list on the host (fluid_sdf_filter_grown)";
 static const char* const SDF_TRACK_SINGLE = "tracked level-set snapshots are single-GPU only: a decomposed handle's filter runs on the merged list on the host (fluid_sdf_filter_tracked)";
 
 static int sdf_init(fluid_sim* s)
@@ -97,6 +111,7 @@ static int sdf_init(fluid_sim* s)
     SdfState* o = new SdfState();
     s->sdf = o;   // from here on sdf_free releases whatever the lines below got
     if (const char* e = getenv("FLUID_SDF_VISITS")) o->count_visits = atoi(e) != 0;   // developer knob (tools/sdf_cost.py)
+    if (const char* e = getenv("FLUID_SDF_GROW_STATS")) o->grow_stats = atoi(e) != 0;   // developer knob (tools/grow_cost.py)
     HIPCHK(hipMalloc((void**)&o->d_small, 8 * sizeof(int)));
     HIPCHK(hipHostMalloc((void**)&o->h_small, 8 * sizeof(int)));
     return snap_init(o->ring);
@@ -107,7 +122,7 @@ void fl::sdf_free(fluid_sim* s)
     SdfState* o = s->sdf;
     if (!o) return;
     snap_free(o->ring);
-    for (void* p : {(void*)o->cnt, (void*)o->start, (void*)o->cell_sums, (void*)o->place, (void*)o->spos, (void*)o->tv, (void*)o->tv2, (void*)o->lflags, (void*)o->ssrc, (void*)o->tid, (void*)o->tvel, (void*)o->tmin, (void*)o->tm, (void*)o->flags,
+    for (void* p : {(void*)o->cnt, (void*)o->start, (void*)o->cell_sums, (void*)o->place, (void*)o->spos, (void*)o->tv, (void*)o->tv2, (void*)o->lflags, (void*)o->flags2, (void*)o->tm2, (void*)o->ssrc, (void*)o->tid, (void*)o->tvel, (void*)o->tmin, (void*)o->tm, (void*)o->flags,
                     (void*)o->slot, (void*)o->leaf_sums, (void*)o->visits, (void*)o->d_small})
         if (p) hipFree(p);
     if (o->h_small) hipHostFree(o->h_small);
@@ -116,8 +131,15 @@ void fl::sdf_free(fluid_sim* s)
 }
 
 // (the handle's stream is idle here: every caller has just waited for a read-back on it)
-static int sdf_scratch(SdfState* o, long cells, long parts, long leaves, bool filtered, bool attr, bool dist2, bool tracked)
+static int sdf_scratch(SdfState* o, long cells, long parts, long leaves, bool filtered, bool attr, bool dist2, bool tracked, bool grown)
 {
+    if (grown && !o->grown) {   // the first grown snapshot of the handle: flags2 and tm2 beside whatever flags and tm there are
+        o->grown = true;
+        if (o->leaf_cap > 0) {
+            HIPCHK(regrow(o->flags2, (size_t)o->leaf_cap));
+            HIPCHK(regrow(o->tm2, (size_t)o->leaf_cap * 8));
+        }
+    }
     if (tracked && !o->tracked) {   // the first tracked snapshot of the handle: lflags beside whatever flags there are
         o->tracked = true;
         if (o->leaf_cap > 0) HIPCHK(regrow(o->lflags, (size_t)o->leaf_cap));
@@ -167,12 +189,26 @@ static int sdf_scratch(SdfState* o, long cells, long parts, long leaves, bool fi
         HIPCHK(regrow(o->tm, (size_t)cap * 8));
         HIPCHK(regrow(o->flags, (size_t)cap));
         if (o->tracked) HIPCHK(regrow(o->lflags, (size_t)cap));
+        if (o->grown) {
+            HIPCHK(regrow(o->flags2, (size_t)cap));
+            HIPCHK(regrow(o->tm2, (size_t)cap * 8));
+        }
         HIPCHK(regrow(o->slot, (size_t)cap));
         HIPCHK(regrow(o->leaf_sums, (size_t)cap / 2048 + 16));
         if (o->count_visits) HIPCHK(regrow(o->visits, (size_t)cap));
         o->leaf_cap = cap;
     }
     return FLUID_OK;
+}
+
+// FLUID_SDF_GROW_STATS=1: how many leaves of the range are flagged (two host waits: a figure for tools/grow_cost.py, never a default)
+static long sdf_count_flags(fluid_sim* s, const int* flags, long leaves)
+{
+    std::vector<int> h((size_t)leaves);
+    if (hipMemcpyAsync(h.data(), flags, (size_t)leaves * sizeof(int), hipMemcpyDeviceToHost, s->st) != hipSuccess || hipStreamSynchronize(s->st) != hipSuccess) return -1;
+    long k = 0;
+    for (int v : h) k += v != 0;
+    return k;
 }
 
 // The front half of a snapshot, shared with the mesh (fluid_mesh.hip).  sdf_begin: the parameters' limits, the state, the constants
@@ -204,7 +240,12 @@ int fl::sdf_begin(fluid_sim* s, const fluid_sdf_params_t* p, SdfFront* f, const 
     f->any = false;
     f->tv = nullptr, f->flags = nullptr, f->list = nullptr;
     f->track_n = filt ? s->sdf->track_n : 0, f->track_trim = filt && s->sdf->track_trim;
-    if ((f->track_n > 0 || f->track_trim) && std::fabs((float)filt->offset) > g.bg)
+    f->grow = filt && s->sdf->track_grow;
+    if (f->grow && !(f->track_n >= 1 && f->track_trim))
+        return fail(FLUID_ERR_ARG, "grown level-set filter: growing the band requires tracking with normalize >= 1 and trim = 1 (fluid_sdf_set_track)");
+    if (f->grow && std::fabs((float)filt->offset) > 4.0f * g.dxf)
+        return fail(FLUID_ERR_ARG, "grown level-set filter: an offset beyond 4 dx in magnitude is refused");
+    if (!f->grow && (f->track_n > 0 || f->track_trim) && std::fabs((float)filt->offset) > g.bg)
         return fail(FLUID_ERR_ARG, "tracked level-set filter: an offset beyond the background in magnitude leaves no surface");
     f->filt = filt, f->dilate = 4;
     f->attr = false, f->dist2 = false;
@@ -230,15 +271,22 @@ int fl::sdf_front(fluid_sim* s, SdfFront* f)
             if (box[a] < g.lo || box[3 + a] > g.hi || box[3 + a] < box[a]) return fail(FLUID_ERR_HIP, "level set: particle box out of range");
         g.bx0 = box[0], g.by0 = box[1], g.bz0 = box[2];
         g.bnx = box[3] - box[0] + 1, g.bny = box[4] - box[1] + 1, g.bnz = box[5] - box[2] + 1;
+        int dilate = f->dilate;
+        if (f->grow) {   // T grown tracks move the active set by at most T cells (Manhattan): one per iteration and per offset step
+            dilate += f->filt->iterations;
+            const float a = std::fabs((float)f->filt->offset);
+            float d = 0.0f;
+            for (float delta; (delta = tdef::offset_step(a, d, g.dxf)) != 0.0f;) d = d + delta, ++dilate;
+        }
         for (int a = 0; a < 3; ++a) {
-            const int c0 = std::max(box[a] - f->dilate, g.lo), c1 = std::min(box[3 + a] + f->dilate, g.hi);
+            const int c0 = std::max(box[a] - dilate, g.lo), c1 = std::min(box[3 + a] + dilate, g.hi);
             g.l0[a] = (c0 - g.L0) >> 3;
             g.nl[a] = ((c1 - g.L0) >> 3) - g.l0[a] + 1;
         }
         const long cells = g.cells(), leaves = g.leaves();
         const bool tracked = f->track_n > 0 || f->track_trim;
         if (cells + 1 > 0x7fffffffL || leaves > 0x7fffffffL) return fail(FLUID_ERR_ARG, "level set: the particles' box is too large");
-        if ((rc = sdf_scratch(o, cells + 1, s->np, leaves, f->filt != nullptr, f->attr, f->dist2, tracked))) return rc;
+        if ((rc = sdf_scratch(o, cells + 1, s->np, leaves, f->filt != nullptr, f->attr, f->dist2, tracked, f->grow))) return rc;
         double *sx = o->spos, *sy = o->spos + o->part_cap, *sz = o->spos + 2 * o->part_cap;
         HIPCHK(hipMemsetAsync(o->cnt, 0, (size_t)(cells + 1) * sizeof(int), s->st));
         launch_sdf_count(s->st, s->np, live, g, o->cnt, o->place, s->dist);
@@ -257,20 +305,27 @@ int fl::sdf_front(fluid_sim* s, SdfFront* f)
             const int W = f->filt->width, passes = 3 * f->filt->iterations;
             const float off = (float)f->filt->offset;
             float *src = o->tv, *dst = o->tv2;
+            int *flags = o->flags, *flags2 = o->flags2;   // grown: the dilation's ping-pong
+            const long flagged0 = o->grow_stats && tracked ? sdf_count_flags(s, o->flags, leaves) : 0;
+            uint64_t *tm = o->tm, *tm2 = o->tm2;
             if (tracked) {
                 // one track: N passes src -> dst, the trim on the last; without a pass the trim alone, in place
                 bool trimmed = false;
                 auto track = [&]() {
+                    if (f->grow) {   // a newly flagged leaf gets its +bg in src, which the first pass below reads
+                        launch_sdf_grow(s->st, g, flags, tm, flags2, tm2, src, f->attr ? o->tid : nullptr, o->tvel);
+                        std::swap(flags, flags2), std::swap(tm, tm2);
+                    }
                     for (int i = 0; i < f->track_n; ++i) {
                         const bool last = i == f->track_n - 1;
-                        launch_sdf_track(s->st, g, true, last && f->track_trim, o->flags, o->tm, src, dst, f->attr ? o->tid : nullptr, o->tvel);
+                        launch_sdf_track(s->st, g, true, last && f->track_trim, flags, tm, src, dst, f->attr ? o->tid : nullptr, o->tvel);
                         std::swap(src, dst);
                     }
-                    if (f->track_n == 0) launch_sdf_track(s->st, g, false, true, o->flags, o->tm, src, src, f->attr ? o->tid : nullptr, o->tvel);
+                    if (f->track_n == 0) launch_sdf_track(s->st, g, false, true, flags, tm, src, src, f->attr ? o->tid : nullptr, o->tvel);
                     trimmed = f->track_trim;
                 };
                 for (int k = 0; k < passes; ++k) {
-                    launch_sdf_box(s->st, g, axes[k % 3], W, 0.0f, o->flags, o->tm, src, dst);
+                    launch_sdf_box(s->st, g, axes[k % 3], W, 0.0f, flags, tm, src, dst);
                     std::swap(src, dst);
                     if (k % 3 == 2) track();
                 }
@@ -278,12 +333,19 @@ int fl::sdf_front(fluid_sim* s, SdfFront* f)
                 float d = 0.0f;
                 for (float delta; (delta = tdef::offset_step(a, d, g.dxf)) != 0.0f;) {
                     d = d + delta;
-                    launch_sdf_offset(s->st, g, std::copysign(delta, off), o->flags, o->tm, src);
+                    launch_sdf_offset(s->st, g, std::copysign(delta, off), flags, tm, src);
                     track();
                 }
                 if (trimmed) {   // what is listed is what the last trim left
-                    launch_sdf_relist(s->st, g, o->flags, o->tm, src, o->lflags);
+                    launch_sdf_relist(s->st, g, flags, tm, src, o->lflags);
                     f->list = o->lflags;
+                } else f->list = flags;
+                f->flags = flags, f->tm = tm;
+                if (o->grow_stats) {
+                    const size_t per_leaf = 2 * 2048 + 64 + 3 * sizeof(int) + (o->tracked ? sizeof(int) : 0) + (o->grown ? 64 + sizeof(int) : 0) +
+                                            (o->attr ? 2048 + 6144 : 0) + (o->dist2 ? 2048 : 0);
+                    fprintf(stderr, "sdf grow: grow %d leaves_in_range %ld flagged_by_search %ld flagged_at_end %ld leaf_scratch_bytes %zu\n", f->grow ? 1 : 0, leaves,
+                            flagged0, sdf_count_flags(s, flags, leaves), (size_t)o->leaf_cap * per_leaf);
                 }
             } else {
                 for (int k = 0; k < passes; ++k) {
@@ -348,9 +410,9 @@ static int sdf_capture(fluid_sim* s, const fluid_sdf_params_t* p, const fluid_sd
         uint64_t* active = (uint64_t*)(q.dev + (size_t)n * 2048 + a);
         int* origin = (int*)(q.dev + (size_t)n * (2048 + 64) + a);
         if (attr)
-            launch_sdf_pack_attr(s->st, g, f.list, o->slot, f.tv, o->tm, values, active, origin, f.tid, f.tvel, (uint32_t*)(q.dev + (size_t)n * 2048),
+            launch_sdf_pack_attr(s->st, g, f.list, o->slot, f.tv, f.tm, values, active, origin, f.tid, f.tvel, (uint32_t*)(q.dev + (size_t)n * 2048),
                                  (float*)(q.dev + (size_t)n * 4096), f.tmin, attr >= 2 ? (float*)(q.dev + (size_t)n * 10240) : nullptr);
-        else launch_sdf_pack(s->st, g, f.list, o->slot, f.tv, o->tm, values, active, origin);
+        else launch_sdf_pack(s->st, g, f.list, o->slot, f.tv, f.tm, values, active, origin);
         HIPCHK(hipGetLastError());
     }
     if ((rc = snap_commit(o->ring, s->st, (size_t)n * rec))) return rc;
@@ -433,6 +495,16 @@ int fluid_sdf_set_track(fluid_sim_t* s, const fluid_sdf_track_t* t)
     if (int rc = sdf_init(s)) return rc;
     s->sdf->track_n = t ? t->normalize : 0;
     s->sdf->track_trim = t && t->trim != 0;
+    return FLUID_OK;
+}
+
+int fluid_sdf_set_track_grow(fluid_sim_t* s, int32_t grow)
+{
+    if (int rc = snap_guard(s, SDF_GROW_SINGLE)) return rc;
+    if (grow != 0 && grow != 1) return fail(FLUID_ERR_ARG, "level-set tracking: grow is 0 or 1");
+    HIPCHK(hipSetDevice(s->prm.device));
+    if (int rc = sdf_init(s)) return rc;
+    s->sdf->track_grow = grow != 0;
     return FLUID_OK;
 }
 

@@ -7,6 +7,9 @@
 // fluid_sdf_filter_tracked ("liquid surface, renormalised") is the same for the tracked filter: the box passes above, a
 // normalisation pass that finds the six face neighbours by bisection (the per-voxel arithmetic is sdf_track_def.h's, shared with
 // kernels_sdf_track.hip), the trim on masks of its own, and the list compacted to the leaves that still hold something.
+// fluid_sdf_filter_grown ("liquid surface, grown band") is the tracked filter whose every track begins with a dilation of the
+// masks (the word arithmetic is sdf_grow_def.h's, shared with kernels_sdf_grow.hip): the list is a working copy that the dilation
+// lengthens by the unlisted face neighbours it activates voxels in, and the attributes travel with it.
 // Arithmetic: float, no contraction (x86-64 has none without -mfma; the builds state -ffp-contract=off).
 #include <cmath>
 #include <cstdint>
@@ -14,6 +17,7 @@
 #include <vector>
 
 #include "leaf_list.h"
+#include "sdf_grow_def.h"
 #include "sdf_track_def.h"
 
 namespace {
@@ -138,10 +142,150 @@ void trim_pass(const fluid_sdf_grid_t* g, float* val, uint64_t* mask)
         }
 }
 
+// the list carries bg = dx * half_width, not dx: the quotient, or its float neighbour whose product gives bg back
+float list_dx(const fluid_sdf_grid_t* g)
+{
+    const float bg = g->background, dx = bg / g->half_width;
+    for (const float c : {dx, std::nextafter(dx, 0.0f), std::nextafter(dx, INFINITY)})
+        if (c * g->half_width == bg) return c;
+    return dx;
+}
+
 bool overlaps(const void* a, size_t na, const void* b, size_t nb)
 {
     const uintptr_t a0 = (uintptr_t)a, a1 = a0 + na, b0 = (uintptr_t)b, b1 = b0 + nb;
     return a && b && na && nb && a0 < b1 && b0 < a1;
+}
+
+// ---- "liquid surface, grown band": the working list of the grown filter, which a dilation can lengthen ---------------------------
+struct Band {
+    std::vector<int32_t> org;      // 3 per leaf, ascending
+    std::vector<uint64_t> mask;    // 8 per leaf
+    std::vector<float> val[2];     // 512 per leaf: the passes' ping-pong, `at` = the one that holds the values
+    int at = 0;
+    bool attr = false;
+    std::vector<uint32_t> id;      // 512 per leaf
+    std::vector<float> vel;        // 3 x 512 per leaf
+    size_t leaves() const { return org.size() / 3; }
+};
+
+// One dilation of the band's masks (the mask words: sdf_grow_def.h).  `cur` describes the band as it is (origin, active, n_leaves
+// point into b) and is pointed at the new arrays on return.  Leaf by leaf: the listed leaves, then the unlisted face neighbours of
+// listed leaves, which join the list (+bg, NO_ID, +0) when a voxel of theirs becomes active.
+void dilate(fluid_sdf_grid_t* cur, Band& b)
+{
+    const int lo = -(cur->n / 2), hi = lo + cur->n - 1, L0 = floor_to(lo, LEAF), L1 = floor_to(hi, LEAF);
+    const size_t nl = b.leaves();
+    std::vector<uint64_t> eff(8 * nl);   // the masks as the definition reads them: nothing outside the grid is active
+    for (size_t l = 0; l < nl; ++l)
+        for (int x = 0; x < 8; ++x)
+            eff[8 * l + x] = b.mask[8 * l + x] & gdef::grid_word(b.org[3 * l] + x, b.org[3 * l + 1], b.org[3 * l + 2], lo, hi);
+    // the new bits of the leaf at o (self = its index, -1: unlisted), and for each its id and velocity (into id512 / vel1536)
+    auto grow_leaf = [&](const Org& o, long self, uint64_t fresh[8], uint32_t* id512, float* vel1536) {
+        long nb[6];
+        for (int d = 0; d < 6; ++d) {
+            Org q = o;
+            (d < 2 ? q.x : d < 4 ? q.y : q.z) += (d & 1) ? LEAF : -LEAF;
+            nb[d] = find_leaf(cur, q);
+        }
+        auto word = [&](long l, int x) { return l >= 0 ? eff[8 * (size_t)l + x] : 0ull; };
+        bool any = false;
+        for (int x = 0; x < 8; ++x) {
+            uint64_t c[6];
+            gdef::neighbours(word(self, x), x > 0 ? word(self, x - 1) : word(nb[0], 7), x < 7 ? word(self, x + 1) : word(nb[1], 0), word(nb[2], x),
+                             word(nb[3], x), word(nb[4], x), word(nb[5], x), c);
+            fresh[x] = (c[0] | c[1] | c[2] | c[3] | c[4] | c[5]) & gdef::grid_word(o.x + x, o.y, o.z, lo, hi) & ~word(self, x);
+            any = any || fresh[x];
+            if (!b.attr) continue;
+            for (int bit = 0; bit < 64; ++bit) {
+                if (!((fresh[x] >> bit) & 1ull)) continue;
+                int d = 0;
+                while (!((c[d] >> bit) & 1ull)) ++d;   // the first neighbour in the order -x +x -y +y -z +z that was active
+                const int at = x * 64 + bit, from = gdef::neighbour_offset(at, d);
+                const size_t src = (size_t)(gdef::neighbour_crosses(at, d) ? nb[d] : self);
+                id512[at] = b.id[512 * src + from];
+                for (int a = 0; a < 3; ++a) vel1536[512 * a + at] = b.vel[1536 * src + 512 * a + from];
+            }
+        }
+        return any;
+    };
+    // the unlisted face neighbours of the listed leaves, inside the grid's leaves
+    std::vector<Org> cand;
+    for (size_t l = 0; l < nl; ++l)
+        for (int d = 0; d < 6; ++d) {
+            Org q{b.org[3 * l], b.org[3 * l + 1], b.org[3 * l + 2]};
+            int32_t& k = d < 2 ? q.x : d < 4 ? q.y : q.z;
+            k += (d & 1) ? LEAF : -LEAF;
+            if (k >= L0 && k <= L1 && find_leaf(cur, q) < 0) cand.push_back(q);
+        }
+    std::sort(cand.begin(), cand.end());
+    cand.erase(std::unique(cand.begin(), cand.end()), cand.end());
+    std::vector<Org> add;
+    std::vector<uint64_t> add_mask;
+    std::vector<uint32_t> add_id;
+    std::vector<float> add_vel;
+    for (const Org& o : cand) {
+        uint64_t fresh[8];
+        uint32_t id512[512];
+        float vel1536[1536];
+        for (int i = 0; i < 512; ++i) id512[i] = FLUID_SDF_NO_ID;
+        for (int i = 0; i < 1536; ++i) vel1536[i] = 0.0f;
+        if (!grow_leaf(o, -1, fresh, id512, vel1536)) continue;
+        add.push_back(o);
+        add_mask.insert(add_mask.end(), fresh, fresh + 8);
+        if (b.attr) add_id.insert(add_id.end(), id512, id512 + 512), add_vel.insert(add_vel.end(), vel1536, vel1536 + 1536);
+    }
+    // the listed leaves: a new voxel's source was active before, so it is never one this loop writes
+    std::vector<uint64_t> grown(8 * nl);
+    for (size_t l = 0; l < nl; ++l)
+        grow_leaf(Org{b.org[3 * l], b.org[3 * l + 1], b.org[3 * l + 2]}, (long)l, &grown[8 * l], b.attr ? &b.id[512 * l] : nullptr,
+                  b.attr ? &b.vel[1536 * l] : nullptr);
+    for (size_t i = 0; i < 8 * nl; ++i) b.mask[i] |= grown[i];
+    if (!add.empty()) {   // merge the two ascending lists
+        Band m;
+        m.at = b.at, m.attr = b.attr;
+        const size_t total = nl + add.size();
+        m.org.reserve(3 * total), m.mask.reserve(8 * total), m.val[0].reserve(512 * total), m.val[1].resize(512 * total);
+        if (b.attr) m.id.reserve(512 * total), m.vel.reserve(1536 * total);
+        const std::vector<float>& v = b.val[b.at];
+        for (size_t i = 0, k = 0; i < nl || k < add.size();) {
+            const bool old = k == add.size() || (i < nl && Org{b.org[3 * i], b.org[3 * i + 1], b.org[3 * i + 2]} < add[k]);
+            if (old) {
+                m.org.insert(m.org.end(), &b.org[3 * i], &b.org[3 * i] + 3);
+                m.mask.insert(m.mask.end(), &b.mask[8 * i], &b.mask[8 * i] + 8);
+                m.val[0].insert(m.val[0].end(), &v[512 * i], &v[512 * i] + 512);
+                if (b.attr) m.id.insert(m.id.end(), &b.id[512 * i], &b.id[512 * i] + 512), m.vel.insert(m.vel.end(), &b.vel[1536 * i], &b.vel[1536 * i] + 1536);
+                ++i;
+            } else {
+                const int32_t o[3] = {add[k].x, add[k].y, add[k].z};
+                m.org.insert(m.org.end(), o, o + 3);
+                m.mask.insert(m.mask.end(), &add_mask[8 * k], &add_mask[8 * k] + 8);
+                m.val[0].insert(m.val[0].end(), 512, cur->background);
+                if (b.attr) m.id.insert(m.id.end(), &add_id[512 * k], &add_id[512 * k] + 512), m.vel.insert(m.vel.end(), &add_vel[1536 * k], &add_vel[1536 * k] + 1536);
+                ++k;
+            }
+        }
+        m.at = 0;
+        b = std::move(m);
+    }
+    cur->n_leaves = (int32_t)b.leaves();
+    cur->origin = b.org.data();
+    cur->active = b.mask.data();
+    cur->values = nullptr;
+}
+
+// trim_pass, which also takes the id and velocity from the voxels it deactivates
+void trim_pass_attr(const fluid_sdf_grid_t* g, Band& b)
+{
+    if (!b.attr) return trim_pass(g, b.val[b.at].data(), b.mask.data());
+    const std::vector<uint64_t> before = b.mask;
+    trim_pass(g, b.val[b.at].data(), b.mask.data());
+    for (size_t l = 0; l < b.leaves(); ++l)
+        for (int at = 0; at < 512; ++at)
+            if (((before[8 * l + (at >> 6)] ^ b.mask[8 * l + (at >> 6)]) >> (at & 63)) & 1ull) {
+                b.id[512 * l + at] = FLUID_SDF_NO_ID;
+                for (int a = 0; a < 3; ++a) b.vel[1536 * l + 512 * a + at] = 0.0f;
+            }
 }
 
 }  // namespace
@@ -220,13 +364,7 @@ int64_t fluid_sdf_filter_tracked(const fluid_sdf_grid_t* g, const fluid_sdf_filt
         std::vector<float> other(count);
         fluid_sdf_grid_t cur = *g;   // the list with the mask as it is now
         cur.active = mask.data();
-        // the list carries bg = dx * half_width, not dx: the quotient, or its float neighbour whose product gives bg back
-        float dx = bg / g->half_width;
-        for (const float c : {dx, std::nextafter(dx, 0.0f), std::nextafter(dx, INFINITY)})
-            if (c * g->half_width == bg) {
-                dx = c;
-                break;
-            }
+        const float dx = list_dx(g);
         memcpy(val.data(), g->values, count * sizeof(float));
         float *src = val.data(), *dst = other.data();
         bool trimmed = false;
@@ -272,6 +410,89 @@ int64_t fluid_sdf_filter_tracked(const fluid_sdf_grid_t* g, const fluid_sdf_filt
         memcpy(values + 512 * i, val.data() + 512 * l, 512 * sizeof(float));
         memcpy(active + 8 * i, mask.data() + 8 * l, 8 * sizeof(uint64_t));
         if (kept) kept[i] = keep[i];
+    }
+    return (int64_t)keep.size();
+}
+
+int64_t fluid_sdf_filter_grown(const fluid_sdf_grid_t* g, const fluid_sdf_attr_t* attr, const fluid_sdf_filter_t* f, const fluid_sdf_track_t* t,
+                               int64_t cap_leaves, int32_t* origin, float* values, uint64_t* active, uint32_t* id, float* velocity)
+{
+    // everything that can be refused first; the result is made in arrays of our own and copied last
+    if (check_list(g) != FLUID_OK || !filter_ok(f)) return -FLUID_ERR_ARG;
+    if (!t || t->normalize < 1 || t->normalize > tdef::MAX_PASSES || t->trim != 1 || t->scheme != FLUID_SDF_TRACK_FIRST_BIAS) return -FLUID_ERR_ARG;
+    const float off = (float)f->offset, bg = g->background;
+    if (!(bg > 0.0f) || !(g->half_width > 0.0f)) return -FLUID_ERR_ARG;
+    const float dx = list_dx(g);
+    if (std::fabs(off) > 4.0f * dx) return -FLUID_ERR_ARG;
+    const size_t nl = (size_t)g->n_leaves;
+    if (attr && (attr->n_leaves != g->n_leaves || (nl > 0 && (!attr->id || !attr->velocity)))) return -FLUID_ERR_ARG;
+    const bool count_only = !origin && !values && !active && !id && !velocity;
+    if (!count_only) {
+        if (!origin || !values || !active || cap_leaves < 0) return -FLUID_ERR_ARG;
+        if (attr ? (!id || !velocity) : (id || velocity)) return -FLUID_ERR_ARG;
+        const size_t cap = (size_t)cap_leaves;
+        const void* in[5] = {g->origin, g->values, g->active, attr ? attr->id : nullptr, attr ? attr->velocity : nullptr};
+        const size_t nin[5] = {12 * nl, 2048 * nl, 64 * nl, 2048 * nl, 6144 * nl};
+        const void* out[5] = {origin, values, active, id, velocity};
+        const size_t nout[5] = {12 * cap, 2048 * cap, 64 * cap, 2048 * cap, 6144 * cap};
+        for (int i = 0; i < 5; ++i)
+            for (int k = 0; k < 5; ++k)
+                if (overlaps(in[i], nin[i], out[k], nout[k])) return -FLUID_ERR_ARG;
+    }
+    if (nl == 0) return 0;
+    Band b;
+    b.org.assign(g->origin, g->origin + 3 * nl);
+    b.mask.assign(g->active, g->active + 8 * nl);
+    b.val[0].assign(g->values, g->values + 512 * nl);
+    b.val[1].resize(512 * nl);
+    b.attr = attr != nullptr;
+    if (attr) b.id.assign(attr->id, attr->id + 512 * nl), b.vel.assign(attr->velocity, attr->velocity + 1536 * nl);
+    fluid_sdf_grid_t cur = *g;   // the band as it is now
+    cur.origin = b.org.data(), cur.active = b.mask.data(), cur.values = nullptr;
+    const int N = t->normalize;
+    auto track = [&]() {
+        dilate(&cur, b);
+        for (int i = 0; i < N; ++i) {
+            norm_pass(&cur, dx, b.val[b.at].data(), b.val[1 - b.at].data());
+            b.at = 1 - b.at;
+        }
+        trim_pass_attr(&cur, b);
+    };
+    static const int axes[3] = {0, 2, 1};
+    for (int k = 0; k < 3 * f->iterations; ++k) {
+        box_pass(&cur, axes[k % 3], f->width, 0.0f, b.val[b.at].data(), b.val[1 - b.at].data());
+        b.at = 1 - b.at;
+        if (k % 3 == 2) track();
+    }
+    const float a = std::fabs(off);
+    float d = 0.0f;
+    bool tracked = f->iterations > 0;
+    for (float delta; (delta = tdef::offset_step(a, d, dx)) != 0.0f;) {
+        d = d + delta;
+        const float step = std::copysign(delta, off);
+        float* v = b.val[b.at].data();
+        for (size_t l = 0; l < b.leaves(); ++l)
+            for (int at = 0; at < 512; ++at)
+                if (((b.mask[8 * l + (at >> 6)] >> (at & 63)) & 1ull) && in_grid(&cur, &b.org[3 * l], at)) v[512 * l + at] = v[512 * l + at] + step;
+        track();
+        tracked = true;
+    }
+    const float* v = b.val[b.at].data();
+    std::vector<size_t> keep;
+    for (size_t l = 0; l < b.leaves(); ++l) {   // listed: an in-grid voxel that is anything but inactive +bg (with no track run: every leaf)
+        bool any = !tracked;
+        for (int at = 0; at < 512 && !any; ++at)
+            any = in_grid(&cur, &b.org[3 * l], at) && (((b.mask[8 * l + (at >> 6)] >> (at & 63)) & 1ull) || v[512 * l + at] != bg);
+        if (any) keep.push_back(l);
+    }
+    if (count_only) return (int64_t)keep.size();
+    if (cap_leaves < (int64_t)keep.size()) return -FLUID_ERR_ARG;
+    for (size_t i = 0; i < keep.size(); ++i) {
+        const size_t l = keep[i];
+        memcpy(origin + 3 * i, &b.org[3 * l], 3 * sizeof(int32_t));
+        memcpy(values + 512 * i, v + 512 * l, 512 * sizeof(float));
+        memcpy(active + 8 * i, &b.mask[8 * l], 8 * sizeof(uint64_t));
+        if (attr) memcpy(id + 512 * i, &b.id[512 * l], 512 * sizeof(uint32_t)), memcpy(velocity + 1536 * i, &b.vel[1536 * l], 1536 * sizeof(float));
     }
     return (int64_t)keep.size();
 }

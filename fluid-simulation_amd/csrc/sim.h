@@ -307,12 +307,13 @@ struct SdfFront {
     SdfGeom g;
     bool any;             // some particle counts: g holds the box and the range, tv / flags are filled for every leaf of the range
     const float* tv;      // 512 values per leaf of the range (stale where flags[j] == 0): the filter's last buffer when filt is set
-    const int* flags;     // the leaf's values are valid (the search's listed flag); what the mesh and the ray caster read by
+    const int* flags;     // the leaf's values are valid (the search's listed flag, or what the last dilation left); what the mesh and the ray caster read by
     const int* list;      // the leaf is listed: flags, or after a tracked filter's trim the flags derived from what the trim left
     int track_n;          // "liquid surface, renormalised": the handle's setting, copied by sdf_begin when a filter is given:
     bool track_trim;      // passes per track and the trim; 0 / false: the filter runs untracked
+    bool grow;            // "liquid surface, grown band": every track begins with a dilation, and the range is dilate + T cells
     const fluid_sdf_filter_t* filt;   // nullptr: unfiltered.  Set by sdf_begin from its argument (limits checked there)
-    int dilate;           // cells the base-cell box is dilated by for the range: 4; 5 for a filtered mesh (set by the caller after sdf_begin)
+    int dilate;           // cells the base-cell box is dilated by for the range: 4; 5 for a filtered mesh (set by the caller after sdf_begin); with grow sdf_front adds T
     bool attr;            // "liquid surface, attributes": the search also keeps the closest particle (set by the caller after sdf_begin)
     const uint64_t* tm;   // 8 mask words per leaf of the range (stale where flags[j] == 0)
     const uint32_t* tid;  // attr: 512 ids per leaf of the range, and

@@ -416,8 +416,11 @@ class DistFluidSim(FluidSim):
         p = SdfParams(float(radius), float(half_width))
         check((lib.fluid_dist_sdf_snapshot_attr if attr else lib.fluid_dist_sdf_snapshot)(self._h, C.byref(p)))
 
-    def sdf_set_track(self, normalize, trim=True):
-        """Refused: a decomposed handle takes no tracked snapshots; track the merged list (sdf_filter_tracked)."""
+    def sdf_set_track(self, normalize, trim=True, grow=False):
+        """Refused: a decomposed handle takes no tracked snapshots; track the merged list (sdf_filter_tracked, or with grow
+        sdf_filter_grown: the library's FLUID_ERR_STATE names it)."""
+        if grow:
+            check(lib.fluid_sdf_set_track_grow(self._h, int(grow)))   # FLUID_ERR_STATE
         t = None if normalize is None else SdfTrack(int(normalize), int(bool(trim)), 0)
         check(lib.fluid_sdf_set_track(self._h, None if t is None else C.byref(t)))   # FLUID_ERR_STATE: the library names the host function
 

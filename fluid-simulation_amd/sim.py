@@ -240,6 +240,33 @@ def sdf_filter_tracked(grid, filt, track):
     return SdfGrid(grid.n, org, val, act, grid.background, grid.radius, grid.half_width), kept
 
 
+def sdf_filter_grown(grid, filt, track, attr=None):
+    """The grown filter of an SdfGrid (fluid_sdf_filter_grown: host only): the tracked filter whose every track begins with a
+    dilation of the band (include/fluid_hip.h, "liquid surface, grown band").  filt = (width, iterations[, offset]), |offset| <=
+    4 dx; track = normalize (1..8) or (normalize, True).  Returns the new SdfGrid, which can list leaves `grid` does not, or with
+    attr (an SdfAttr of `grid`'s leaves) the pair (SdfGrid, SdfAttr).  A decomposed run grows the merged list."""
+    c, _keep = grid._c()
+    f, t = _sdf_filter_of(filt), _sdf_track_of(track)
+    pt = None if t is None else C.byref(t)
+    pa = None
+    if attr is not None:
+        ac = attr._c()
+        pa = C.byref(ac)
+    k = lib.fluid_sdf_filter_grown(C.byref(c), pa, C.byref(f), pt, 0, None, None, None, None, None)
+    if k < 0:
+        raise FluidError(-k, "fluid_sdf_filter_grown: a bad leaf list or attributes, filter (width 1..4, iterations 0..16, |offset| <= 4 dx) "
+                             "or track (normalize 1..8 with the trim)")
+    org, val, words = np.empty((k, 3), np.int32), np.empty((k, 512), np.float32), np.zeros((k, 8), np.uint64)
+    ids = np.empty((k, 512), np.uint32) if attr is not None else None
+    vel = np.empty((k, 3, 512), np.float32) if attr is not None else None
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)   # noqa: E731
+    if k and lib.fluid_sdf_filter_grown(C.byref(c), pa, C.byref(f), pt, k, p(org), p(val), p(words), p(ids), p(vel)) != k:
+        raise FluidError(1, "fluid_sdf_filter_grown: the second call disagrees with the count")
+    act = np.unpackbits(words.view(np.uint8), axis=1, bitorder="little").astype(bool).reshape(k, 512)
+    out = SdfGrid(grid.n, org, val, act, grid.background, grid.radius, grid.half_width)
+    return out if attr is None else (out, SdfAttr(ids, vel))
+
+
 class Mesh:
     """fluid_mesh_t on the host: the surface nets of the level set (include/fluid_hip.h, "liquid surface as a mesh").  vertices
     (nv, 3) float32 in index space, quads (nq, 4) uint32 vertex numbers, counter-clockwise seen from outside the liquid."""
@@ -753,12 +780,15 @@ class FluidSim:
         else:
             check(lib.fluid_sdf_snapshot_filtered(self._h, C.byref(p), C.byref(_sdf_filter_of(smooth))))
 
-    def sdf_set_track(self, normalize, trim=True):
+    def sdf_set_track(self, normalize, trim=True, grow=False):
         """A setting of the handle: every later snapshot given smooth= renormalises (`normalize` passes, 0..8; the library's
         default is 3) and, with `trim`, trims the level set after every box iteration and every offset step (include/fluid_hip.h,
-        "liquid surface, renormalised").  sdf_set_track(None): off, the default."""
+        "liquid surface, renormalised").  sdf_set_track(None): off, the default.  grow=True: every track begins with a dilation of
+        the band ("liquid surface, grown band"; it needs normalize >= 1 and the trim, which the next filtered snapshot checks);
+        grow is passed on as it is, so an integer other than 0 / 1 is the library's FLUID_ERR_ARG."""
         t = None if normalize is None else SdfTrack(int(normalize), int(bool(trim)), 0)
         check(lib.fluid_sdf_set_track(self._h, None if t is None else C.byref(t)))
+        check(lib.fluid_sdf_set_track_grow(self._h, int(grow)))
 
     def sdf_wait(self):
         """The oldest level-set snapshot not yet waited for, as an SdfGrid (copied out of the handle's pinned buffer)."""

@@ -722,8 +722,9 @@ int fluid_sdf_filter(const fluid_sdf_grid_t* g, const fluid_sdf_filter_t* f, flo
  * can empty the list (n_leaves = 0).  Attributes: a voxel the trim deactivated has FLUID_SDF_NO_ID and +0 velocity like every
  * other inactive voxel; ids and velocities of the voxels still active are untouched.
  *
- * What this is not.  The band never grows: dilateActiveValues, the first line of track(), is NOT run, so a surface that leaves
- * the band is lost to the trim instead of followed.  HJWENO5, the library's default spatial scheme, and TVD_RK2/3 are not built;
+ * What this is not.  By itself the band never grows: dilateActiveValues, the first line of track(), is run only with growing
+ * switched on ("liquid surface, grown band" below); without it a surface that leaves the band is lost to the trim instead of
+ * followed.  HJWENO5, the library's default spatial scheme, and TVD_RK2/3 are not built;
  * neither are the tracker's dilate / erode / resize.  Decomposed handles take no tracked snapshots: track the merged list. */
 #define FLUID_SDF_TRACK_FIRST_BIAS 0
 typedef struct fluid_sdf_track { int32_t normalize; /* passes per track: 0..8; the library's default is 3 */
@@ -747,6 +748,69 @@ int fluid_sdf_set_track(fluid_sim_t* s, const fluid_sdf_track_t* t);
  * some but not all of the three outputs NULL, outputs overlapping g's arrays. */
 int64_t fluid_sdf_filter_tracked(const fluid_sdf_grid_t* g, const fluid_sdf_filter_t* f, const fluid_sdf_track_t* t,
                                  int64_t cap_leaves, int32_t* origin, float* values, uint64_t* active, int32_t* kept /* may be NULL */);
+
+/* ---- liquid surface, grown band: dilate, normalise, trim ---------------------------------------------------------------------------
+ * The section above stops one line short of the library's track(), which is dilateActiveValues(leafs, 1, NN_FACE, IGNORE_TILES),
+ * normalize(), prune() (tools/LevelSetTracker.h:299, 302, 305).  Without the dilation the band stays where the rasteriser put it:
+ * a tracked offset cannot exceed bg, and within bg the surface runs into the rim of a band that does not follow it.  With growing
+ * on every track begins with one dilation, so the band walks with the surface — outwards through +bg, inwards through the
+ * inactive -bg interior.  An exact, order-free definition: the kernel (kernels_sdf_grow.hip), fluid_sdf_filter_grown below and
+ * the tests' numpy form give the same bytes.
+ *
+ * One dilation.  Input val, act as in "liquid surface, smoothed".  For every voxel c of [lo,hi]^3:
+ *   act_new(c) = act(c) OR act of any of its six face neighbours; a neighbour outside the grid is inactive.
+ * Values do not change: a newly active voxel keeps its stored inactive value, -bg or +bg (+bg is what every voxel of an unlisted
+ * leaf holds).  Voxels of a leaf outside the grid never become active.  Jacobi: the masks are read as they were before the
+ * dilation.  The dilation is clipped by the grid and by nothing else — no range of an implementation clips it.
+ * Grown track = one dilation, then N normalisation passes, then the trim (tdef::track_value, tdef::trim_class, unchanged).
+ *
+ * Settings and limits.  Growing requires normalize >= 1 and trim = 1: that is the library's track().  A filtered snapshot taken
+ * with growing on and any other track setting, or with tracking off, is FLUID_ERR_ARG.
+ * Tracked filter with growing on = "liquid surface, renormalised" with every track replaced by the grown track: the box
+ * iterations, the stepped offset and tdef::offset_step stay; the offset limit becomes fabsf(off) > 4.0f * dx -> FLUID_ERR_ARG
+ * (instead of > bg); a leaf is listed iff it holds anything but inactive +bg after the last trim, and the list can now hold leaves
+ * the unfiltered list does not.  K = 0 with off == 0 runs nothing.
+ *
+ * Attributes (an extension of this project's own: the library does not extend its attribute grid).  A voxel that a dilation
+ * activates takes the id and velocity of the first of its face neighbours, in the order -x, +x, -y, +y, -z, +z, that was active
+ * BEFORE that dilation.  That neighbour carries an id, by induction: initially active voxels have one, the trim gives
+ * FLUID_SDF_NO_ID only to voxels it deactivates, and a voxel activated later inherits again.  So "active <=> id != FLUID_SDF_NO_ID"
+ * still holds and the vertex-velocity rule of "liquid surface, attributes" needs no change.
+ *
+ * Range.  After T grown tracks the active set lies within the Manhattan dilation by T of the initial one, which lies within 4
+ * cells (Chebyshev) of the particles' base-cell box.  T = iterations + the number of offset steps is known on the host before
+ * anything is sized, so the device works on the leaves of that box dilated by 4 + T cells — 5 + T for the mesh and the image, by
+ * the argument at fluid_mesh_snapshot_filtered: an inside voxel is active or inactive -bg, hence within 4 + T cells of the box
+ * (the trim makes -bg only of active voxels), and a mixed cell's min corner is one cell below an inside voxel at most — clipped
+ * to the grid: exact, no clipping by the range ever happens.  The scratch for the larger range is allocated by the snapshot call, never inside a step, and only a
+ * handle that has taken a grown snapshot pays for it.
+ * With growing off every byte of every entry point is what it was.
+ *
+ * What this is not.  LevelSetTracker::dilate(n) / erode / resize, which change the half width and the background; HJWENO5; tracked
+ * rank snapshots of decomposed handles; a two-offset "closing" entry point — a caller composes one on the host with two
+ * fluid_sdf_filter_grown calls. */
+/* A setting of the handle like fluid_sdf_set_track, and independent of it in order: grow = 1 makes every later filtered snapshot
+ * (the list of fluid_sdf_set_track) run grown tracks; 0 (the default): off.  The rule "normalize >= 1 and trim = 1" is checked
+ * where a filtered snapshot begins: FLUID_ERR_ARG from that snapshot; unfiltered snapshots are untouched.  One more launch per
+ * track; a second set of masks and flags, which the launch writes while it reads the first (no block reads a word another block
+ * of the launch writes), is allocated by the first grown snapshot.  FLUID_ERR_ARG: grow is neither 0 nor 1.  FLUID_ERR_STATE on a
+ * decomposed handle: grow the merged list (fluid_sdf_filter_grown). */
+int fluid_sdf_set_track_grow(fluid_sim_t* s, int32_t grow);
+/* Host only: the grown filter applied to a leaf list, how a block run gets it after fluid_sdf_grids_merge /
+ * fluid_sdf_attr_grids_merge.  Returns the number of leaves listed and writes the new list, which can be longer than g's:
+ * origin[3 k] ascending, values[512 k], active[8 k], and with attr (ids and velocities of g's leaves, attr->n_leaves ==
+ * g->n_leaves) id[512 k] and velocity[3 * 512 k] in full — there is no `kept`: grown leaves have no source leaf.  A leaf the
+ * dilation adds holds +bg, FLUID_SDF_NO_ID and +0 wherever nothing was activated, its voxels outside the grid included.  With all
+ * five outputs NULL it returns the count only.  dx, the voxels of listed leaves outside the grid (never active, never a
+ * neighbour, copied unchanged) and the listing are fluid_sdf_filter_tracked's.  Works leaf by leaf on a working copy of the list,
+ * the six face neighbours found by bisection; no dense grid is made.  -FLUID_ERR_ARG with nothing written: whatever
+ * fluid_sdf_filter refuses; t NULL, normalize outside 1..8, trim != 1 or an unknown scheme; fabsf(offset) > 4 dx; attr whose
+ * n_leaves differs or whose arrays are NULL with leaves; id or velocity NULL with attr, or given without it; cap_leaves smaller than
+ * the count; some but not all of origin, values and active NULL; outputs overlapping g's or attr's arrays. */
+struct fluid_sdf_attr;   /* fluid_sdf_attr_t: "liquid surface, attributes" below */
+int64_t fluid_sdf_filter_grown(const fluid_sdf_grid_t* g, const struct fluid_sdf_attr* attr /* may be NULL */, const fluid_sdf_filter_t* f,
+                               const fluid_sdf_track_t* t, int64_t cap_leaves, int32_t* origin, float* values, uint64_t* active,
+                               uint32_t* id /* NULL iff attr NULL */, float* velocity /* likewise */);
 
 /* ---- liquid surface as a mesh: surface nets of the level set ----------------------------------------------------------------
  * Polygons for everyone who is no volume renderer.  The reference names tools/VolumeToMesh.h, whose output depends on the library's

@@ -1,0 +1,260 @@
+"""CPU (-m "not gpu"): the host half of the grown band — fluid_sdf_filter_grown on tests/sdf_ref.py leaf lists against
+tests/sdf_grow_ref.py (origins, masks, values as bit patterns, ids, velocity bits), with and without attributes, the count-only
+form, every refusal (none writes), hand-made lists that pin the inheritance order and the voxels outside the grid, the offsets
+fluid_sdf_filter_tracked refuses, and the file under ASan + UBSan as a stand-alone program."""
+import ctypes as C
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import attr_ref
+import mesh_ref
+import sdf_grow_ref as G
+import sdf_ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "fluid-simulation_amd", "csrc")
+ERR_ARG = 1
+SETS = [(2.0, 2.0, 1.0), (1.5, 2.5, 1.0), (1.0, 2.0, 0.5)]
+SCENES = ["one", "corner", "lo", "hi", "cloud", "faces"]
+NO_ID = G.NO_ID
+
+
+def u32(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def lists_of(fs, name, n, R, w, dx):
+    """The unfiltered scene as (SdfGrid, SdfAttr)."""
+    _, _, val, act, ids, v32, bg = G.base(name, n, R, w, dx)
+    fR, fw = sdf_ref.constants(R, w, dx)[:2]
+    org, v, a = sdf_ref.leaf_list(val, act, bg)
+    li, lv = attr_ref.leaf_attr(ids, v32, org)
+    return fs.SdfGrid(n, org, v, a, bg, fR, fw), fs.SdfAttr(li, lv)
+
+
+def expected(name, n, R, w, dx, case):
+    vt, at, it, velt = G.scene(name, n, R, w, dx, case)
+    bg = G.base(name, n, R, w, dx)[6]
+    org, v, a = sdf_ref.leaf_list(vt, at, bg)
+    li, lv = attr_ref.leaf_attr(it, velt, org)
+    return org, v, a, li, lv
+
+
+def same(out, oa, exp):
+    org, v, a, li, lv = exp
+    ok = out.n_leaves == len(org) and np.array_equal(out.origin, org) and np.array_equal(out.active, a) and np.array_equal(u32(out.values), u32(v))
+    if oa is not None:
+        ok = ok and np.array_equal(oa.id, li) and np.array_equal(u32(oa.velocity), u32(lv))
+    return ok
+
+
+def filt_of(case, dx):
+    return (case[0], case[1], case[2] * dx), case[3]
+
+
+@pytest.mark.parametrize("R,w,dx", SETS)
+@pytest.mark.parametrize("n", [20, 32])
+@pytest.mark.parametrize("name", SCENES)
+def test_grown_filter_is_the_reference(fs, name, n, R, w, dx):
+    g, at = lists_of(fs, name, n, R, w, dx)
+    assert g.n_leaves > 0
+    for case in G.GROWS:
+        exp = expected(name, n, R, w, dx, case)
+        filt, track = filt_of(case, dx)
+        out, oa = fs.sdf_filter_grown(g, filt, track, attr=at)
+        assert same(out, oa, exp), case
+        plain = fs.sdf_filter_grown(g, filt, track)                          # without attributes: the same geometry
+        assert same(plain, None, exp), case
+        assert np.array_equal(oa.id != NO_ID, out.active), case               # active <=> has an id
+        assert not oa.velocity.transpose(0, 2, 1)[~out.active].any(), case
+
+
+@pytest.mark.parametrize("R,w", [(3.0, 1.0), (2.0, 1.0)])
+def test_block_walks_inwards_where_the_tracked_filter_refuses(fs, R, w):
+    n, dx = 32, 1.0
+    g, at = lists_of(fs, "block", n, R, w, dx)
+    for case in G.BLOCK_GROWS:
+        filt, track = filt_of(case, dx)
+        out, oa = fs.sdf_filter_grown(g, filt, track, attr=at)
+        assert same(out, oa, expected("block", n, R, w, dx, case)), case
+        assert 0 < out.n_leaves < g.n_leaves, case                           # whole leaves leave the list
+        if case[2] > w:                                                       # |offset| > bg
+            with pytest.raises(fs.FluidError):
+                fs.sdf_filter_tracked(g, filt, track)
+            c, _keep = g._c()
+            f, t = fs.SdfFilter(*filt), fs.SdfTrack(track, 1, 0)
+            assert fs.lib.fluid_sdf_filter_tracked(C.byref(c), C.byref(f), C.byref(t), 0, None, None, None, None) == -ERR_ARG
+            V = fs.sdf_mesh(out).vertices
+            assert len(V) and abs(float(np.abs(V).max()) - (R + 6 - case[2])) <= 0.5
+
+
+def raw_call(fs, g, attr, filt, track, cap, org, val, act, ids, vel):
+    c, _keep = g._c()
+    ac = None if attr is None else attr._c()
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)   # noqa: E731
+    f = None if filt is None else C.byref(fs.SdfFilter(*filt))
+    t = None if track is None else C.byref(fs.SdfTrack(*track))
+    return fs.lib.fluid_sdf_filter_grown(C.byref(c), None if ac is None else C.byref(ac), f, t, cap, p(org), p(val), p(act), p(ids), p(vel))
+
+
+def test_count_only_and_refusals(fs):
+    n, (R, w, dx) = 20, SETS[0]
+    g, at = lists_of(fs, "faces", n, R, w, dx)
+    filt, tr = (1, 0, -3.0 * dx), (3, 1, 0)
+    k = 19
+    assert raw_call(fs, g, None, filt, tr, 0, None, None, None, None, None) == k       # the count alone, cap ignored
+    assert raw_call(fs, g, at, filt, tr, 0, None, None, None, None, None) == k
+    org, val, act = np.full((k, 3), 7, np.int32), np.full((k, 512), 7, np.float32), np.full((k, 8), 7, np.uint64)
+    ids, vel = np.full((k, 512), 7, np.uint32), np.full((k, 3, 512), 7, np.float32)
+
+    def untouched():
+        return (org == 7).all() and (val == 7).all() and (act == 7).all() and (ids == 7).all() and (vel == 7).all()
+
+    assert raw_call(fs, g, at, filt, tr, k - 1, org, val, act, ids, vel) == -ERR_ARG and untouched()        # cap too small
+    assert raw_call(fs, g, None, filt, tr, 1, org, val, act, None, None) == -ERR_ARG                        # (the input's count is not enough)
+    for bad in ((0, 1, 0), (9, 1, 0), (-1, 1, 0), (3, 0, 0), (3, 2, 0), (3, 1, 1)):                       # N = 0, trim 0, bad limits, scheme
+        assert raw_call(fs, g, at, filt, bad, k, org, val, act, ids, vel) == -ERR_ARG, bad
+        assert raw_call(fs, g, None, filt, bad, 0, None, None, None, None, None) == -ERR_ARG, bad
+    assert raw_call(fs, g, at, filt, None, k, org, val, act, ids, vel) == -ERR_ARG                          # tracking off
+    assert raw_call(fs, g, at, None, tr, k, org, val, act, ids, vel) == -ERR_ARG
+    for bad in ((0, 1, 0.0), (5, 1, 0.0), (1, -1, 0.0), (1, 17, 0.0), (1, 1, float("nan")), (1, 1, float("inf")), (1, 0, 1e300)):
+        assert raw_call(fs, g, at, bad, tr, k, org, val, act, ids, vel) == -ERR_ARG, bad
+    four = float(np.float32(4.0) * np.float32(dx))
+    above = float(np.nextafter(np.float32(four), np.float32(np.inf)))
+    for sign in (1.0, -1.0):
+        assert raw_call(fs, g, None, (1, 0, sign * above), tr, 0, None, None, None, None, None) == -ERR_ARG    # just above 4 dx
+        assert raw_call(fs, g, None, (1, 0, sign * four), tr, 0, None, None, None, None, None) >= 0            # exactly 4 dx is taken
+    assert raw_call(fs, g, at, filt, tr, k, org, val, act, None, vel) == -ERR_ARG                           # attr without id / velocity outputs
+    assert raw_call(fs, g, at, filt, tr, k, org, val, act, ids, None) == -ERR_ARG
+    assert raw_call(fs, g, at, filt, tr, k, org, val, act, None, None) == -ERR_ARG
+    assert raw_call(fs, g, None, filt, tr, k, org, val, act, ids, vel) == -ERR_ARG                          # ... and outputs without attr
+    assert raw_call(fs, g, at, filt, tr, k, org, None, act, ids, vel) == -ERR_ARG                           # some but not all outputs
+    assert raw_call(fs, g, at, filt, tr, k, None, val, act, ids, vel) == -ERR_ARG
+    short = fs.SdfAttr(np.zeros((0, 512), np.uint32), np.zeros((0, 3, 512), np.float32))
+    assert raw_call(fs, g, short, filt, tr, k, org, val, act, ids, vel) == -ERR_ARG                         # attributes of another list
+    assert untouched()
+    # outputs overlapping the inputs
+    c, words = g._c()
+    ac = at._c()
+    t, f = fs.SdfTrack(*tr), fs.SdfFilter(*filt)
+    call = lambda o, v, a, i, ve: fs.lib.fluid_sdf_filter_grown(C.byref(c), C.byref(ac), C.byref(f), C.byref(t), k, C.c_void_p(o), C.c_void_p(v),   # noqa: E731
+                                                                 C.c_void_p(a), C.c_void_p(i), C.c_void_p(ve))
+    po, pv, pa, pi, pve = org.ctypes.data, val.ctypes.data, act.ctypes.data, ids.ctypes.data, vel.ctypes.data
+    before = (g.origin.copy(), g.values.copy(), words.copy(), at.id.copy(), at.velocity.copy())
+    assert call(po, g.values.ctypes.data, pa, pi, pve) == -ERR_ARG
+    assert call(g.origin.ctypes.data, pv, pa, pi, pve) == -ERR_ARG
+    assert call(po, pv, words.ctypes.data, pi, pve) == -ERR_ARG
+    assert call(po, pv, pa, at.id.ctypes.data, pve) == -ERR_ARG
+    assert call(po, pv, pa, pi, at.velocity.ctypes.data) == -ERR_ARG
+    assert call(po, pv, pa, pi, at.id.ctypes.data + 2044) == -ERR_ARG                                       # a tail that reaches the input
+    assert untouched() and np.array_equal(before[0], g.origin) and np.array_equal(u32(before[1]), u32(g.values)) and np.array_equal(before[2], words)
+    assert np.array_equal(before[3], at.id) and np.array_equal(u32(before[4]), u32(at.velocity))
+    assert call(po, pv, pa, pi, pve) == k and not untouched()                                               # and the call itself is good
+    # a list out of order, an origin off the 8-grid; an empty list
+    g2, _ = lists_of(fs, "hi", n, R, w, dx)
+    o = g2.origin.copy(); o[[1, 2]] = o[[2, 1]]
+    with pytest.raises(fs.FluidError):
+        fs.sdf_filter_grown(fs.SdfGrid(n, o, g2.values, g2.active, g2.background, g2.radius, g2.half_width), filt, 3)
+    o = g2.origin.copy(); o[0, 1] += 4
+    with pytest.raises(fs.FluidError):
+        fs.sdf_filter_grown(fs.SdfGrid(n, o, g2.values, g2.active, g2.background, g2.radius, g2.half_width), filt, 3)
+    e = fs.SdfGrid(16, np.empty((0, 3)), np.empty((0, 512)), np.empty((0, 512)), 2.0, 2.0, 2.0)
+    assert fs.sdf_filter_grown(e, (2, 3, -0.5), 3).n_leaves == 0
+    # K = 0 with no offset runs nothing: the list as it is
+    same_list = fs.sdf_filter_grown(g2, (1, 0, 0.0), 3)
+    assert np.array_equal(same_list.origin, g2.origin) and np.array_equal(u32(same_list.values), u32(g2.values)) and np.array_equal(same_list.active, g2.active)
+
+
+def test_hand_made_lists_pin_the_inheritance_order_and_the_grid(fs):
+    """A random field on n = 20 (the grid ends inside a leaf on both sides): random masks, a different id on every voxel, every
+    second leaf taken off the list.  The host function equals the reference on the dense field, which pins the inheritance order on
+    every newly active voxel — among them voxels whose -x and +y neighbours carry different ids — and junk in the listed leaves'
+    voxels outside the grid is neither read nor a neighbour, and is copied unchanged."""
+    n, dx, w = 20, 1.0, 2.0
+    bg = np.float32(dx * w)
+    lo, hi, l0, nl = sdf_ref.geometry(n)
+    rng = np.random.default_rng(11)
+    act = rng.random((n, n, n)) < 0.08
+    val = np.where(act, rng.uniform(-0.9, 0.9, (n, n, n)) * bg, np.where(rng.random((n, n, n)) < 0.3, -bg, bg)).astype(np.float32)
+    org, v, a = sdf_ref.leaf_list(val, act, bg)
+    keep = np.arange(len(org)) % 2 == 0
+    org, v, a = org[keep], v[keep], a[keep]
+    g = fs.SdfGrid(n, org, v, a, bg, 2.0, w)
+    val, act = fs.sdf_to_dense(g)                                             # the field with the unlisted leaves blanked
+    ids = np.where(act, np.arange(n ** 3, dtype=np.uint32).reshape(n, n, n), NO_ID).astype(np.uint32)
+    vel = np.where(act[None], rng.uniform(-3, 3, (3, n, n, n)), 0.0).astype(np.float32)
+    li, lv = attr_ref.leaf_attr(ids, vel, org)
+    at = fs.SdfAttr(li, lv)
+    # one dilation by hand: a voxel whose -x and +y neighbours are active takes the -x one's id
+    a1, i1, _ = G.dilate_attr(act, ids, vel)
+    both = ~act[1:, :-1] & act[:-1, :-1] & act[1:, 1:]
+    assert both.sum() > 10 and np.array_equal(i1[1:, :-1][both], ids[:-1, :-1][both])
+    off = np.arange(512)
+    junk_v, junk_a, junk_i = g.values.copy(), g.active.copy(), li.copy()
+    inside = np.zeros((len(org), 512), bool)
+    for i, o in enumerate(org):
+        c = np.stack([o[0] + (off >> 6), o[1] + ((off >> 3) & 7), o[2] + (off & 7)], axis=1)
+        inside[i] = ((c >= lo) & (c <= hi)).all(axis=1)
+    junk_v[~inside] = rng.uniform(-9, 9, int((~inside).sum())).astype(np.float32)
+    junk_a[~inside] = rng.random(int((~inside).sum())) < 0.5
+    junk_i[~inside] = 12345
+    assert (~inside).sum() > 1000
+    gj, atj = fs.SdfGrid(n, org, junk_v, junk_a, bg, 2.0, w), fs.SdfAttr(junk_i, lv)
+    for case in [(1, 0, -1.0, 1), (1, 1, 0.0, 3), (1, 0, -3.0, 3), (2, 2, 1.0, 2)]:
+        W, K, units, N = case
+        vt, att, it, velt = G.grown(val, act, bg, dx, W, K, units * dx, N, ids, vel)
+        out, oa = fs.sdf_filter_grown(g, (W, K, units * dx), N, attr=at)
+        o2, v2, a2 = sdf_ref.leaf_list(vt, att, bg)
+        i2, l2 = attr_ref.leaf_attr(it, velt, o2)
+        assert same(out, oa, (o2, v2, a2, i2, l2)), case
+        outj, oaj = fs.sdf_filter_grown(gj, (W, K, units * dx), N, attr=atj)
+        assert np.array_equal(outj.origin, out.origin), case
+        was = {tuple(o): i for i, o in enumerate(org)}
+        for i, o in enumerate(outj.origin):
+            c = np.stack([o[0] + (off >> 6), o[1] + ((off >> 3) & 7), o[2] + (off & 7)], axis=1)
+            ins = ((c >= lo) & (c <= hi)).all(axis=1)
+            assert np.array_equal(u32(outj.values[i][ins]), u32(out.values[i][ins])) and np.array_equal(outj.active[i][ins], out.active[i][ins]), case
+            assert np.array_equal(oaj.id[i][ins], oa.id[i][ins]), case
+            if tuple(o) in was:                                               # a leaf of the input: its outside copied unchanged
+                k = was[tuple(o)]
+                assert np.array_equal(u32(outj.values[i][~ins]), u32(junk_v[k][~ins])) and np.array_equal(outj.active[i][~ins], junk_a[k][~ins]), case
+            else:                                                             # a leaf the dilation added: +bg, inactive, no id
+                assert (outj.values[i][~ins] == bg).all() and not outj.active[i][~ins].any() and (oaj.id[i][~ins] == NO_ID).all(), case
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_grown_filter_under_asan_ubsan(tmp_path):
+    exe = tmp_path / "host_san_grow"
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off",
+           "-fno-omit-frame-pointer", "-I", os.path.join(ROOT, "include"), os.path.join(CSRC, "sdf_filter_host.cpp"),
+           os.path.join(ROOT, "tests", "host_san_grow_main.cpp"), "-o", str(exe)]
+    b = subprocess.run(cmd, capture_output=True, text=True)
+    if b.returncode != 0 and "asan" in (b.stderr or "").lower() and "cannot find" in b.stderr.lower():
+        pytest.skip("sanitizer runtime not installed")
+    assert b.returncode == 0, b.stderr[-3000:]
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600,
+                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
+    assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
+    assert "host sanitizer run (grow): ok" in r.stdout
+
+
+@pytest.mark.parametrize("extra", [{"FLUID_OUT_TRACK": "3,1,2"}, {"FLUID_OUT_TRACK": "3,1,-1"}, {"FLUID_OUT_TRACK": "3,0,1"}, {"FLUID_OUT_TRACK": "0,1,1"},
+                                   {"FLUID_OUT_TRACK": "3,1,1,"}, {"FLUID_OUT_TRACK": "3,1,x"}, {"FLUID_OUT_TRACK": "3,1,1", "FLUID_OUT_SMOOTH": ""},
+                                   {"FLUID_OUT_MESH": "", "FLUID_BLOCKS": "2x1x1", "FLUID_BLOCKS_MESH": "1.5,2.5", "FLUID_BLOCKS_MESH_VEL": "1",
+                                    "FLUID_OUT_TRACK": "3,1,0"}])
+def test_driver_refuses_a_growing_it_would_not_apply(fs, tmp_path, extra):
+    """FLUID_OUT_TRACK=N,TRIM,GROW malformed, GROW outside 0 / 1, GROW = 1 without N >= 1 and the trim, without FLUID_OUT_SMOOTH, or
+    FLUID_BLOCKS_MESH_VEL with GROW = 0: refused before any handle is created — the message is the variable's own."""
+    env = dict(os.environ, FLUID_N="16", FLUID_PPC="1", FLUID_STEPS="1", FLUID_OUT=str(tmp_path / "simulation"), FLUID_OUT_MESH="1.5,2.5",
+               FLUID_OUT_SMOOTH="1,1")
+    for k in ("FLUID_OUT_DENSE", "FLUID_BLOCKS", "FLUID_SOURCE_EVERY", "FLUID_RAW", "FLUID_OUT_SURFACE", "FLUID_BLOCKS_SURFACE", "FLUID_BLOCKS_MESH",
+              "FLUID_BLOCKS_MESH_VEL", "FLUID_OUT_RENDER", "FLUID_BLOCKS_RENDER"):
+        env.pop(k, None)
+    env.update(extra)
+    r = subprocess.run([os.path.join(ROOT, "fluid-simulation_amd", "fluid")], capture_output=True, text=True, env=env, cwd=tmp_path, timeout=60)
+    assert r.returncode == 1 and "FLUID_OUT_TRACK" in r.stderr and "fluid_create" not in r.stderr, (r.returncode, r.stderr[-500:])
+    assert not list(tmp_path.rglob("*.ply")) and not list(tmp_path.rglob("*.vdb"))
