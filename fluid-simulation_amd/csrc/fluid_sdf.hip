@@ -21,7 +21,9 @@
 //
 // fluid_sdf_snapshot_filtered / fluid_mesh_snapshot_filtered ("liquid surface, smoothed"; kernels_sdf_filter.hip): the front half
 // ends with the filter's box passes, one launch each, 3 per iteration (x, z, y), from tv to tv2 and back; what follows reads
-// whichever buffer the last pass wrote.  tv2 exists from the handle's first filtered snapshot on.
+// whichever buffer the last pass wrote.  tv2 exists from the handle's first filtered snapshot on.  The order of passes, offset
+// steps and tracks of all three forms, and the limits of their arguments, are sdf_filter_plan.h's, shared with the host functions
+// (sdf_filter_host.cpp); sdf_front supplies what each of them launches.
 //
 // fluid_sdf_set_track ("liquid surface, renormalised"; kernels_sdf_track.hip): with the setting on, every filter of the front half
 // runs its tracked form: a track (N normalisation passes, one launch each, ping-pong like the box passes; the trim rides on the
@@ -51,7 +53,7 @@
 // decomposed handle; a dead entry is never scattered, so never a winner).  tmin exists from the handle's first such snapshot on; a
 // slot keeps room for the longest record per leaf it has held (wide = 0, 1, 2).
 #include "sim.h"
-#include "sdf_track_def.h"
+#include "sdf_filter_plan.h"
 
 using namespace fl;
 #define fail fluid_fail
@@ -74,8 +76,7 @@ struct SdfState {
     bool filtered = false;
     int* lflags = nullptr;     // the list flags after a trim, leaf_cap like flags: allocated once a tracked snapshot was asked for
     bool tracked = false;
-    int track_n = 0;           // fluid_sdf_set_track: passes per track and the trim (0 / false: off)
-    bool track_trim = false;
+    fluid_sdf_track_t track{0, 0, FLUID_SDF_TRACK_FIRST_BIAS};   // fluid_sdf_set_track: passes per track and the trim (0 / 0: off)
     int* flags2 = nullptr;     // the dilation's second flags and masks (leaf_cap, leaf_cap x 8): allocated once a grown snapshot was asked for
     uint64_t* tm2 = nullptr;
     bool grown = false;
@@ -219,8 +220,7 @@ static long sdf_count_flags(fluid_sim* s, const int* flags, long leaves)
 int fl::sdf_begin(fluid_sim* s, const fluid_sdf_params_t* p, SdfFront* f, const fluid_sdf_filter_t* filt)
 {
     if (!p) return fail(FLUID_ERR_ARG, "null argument");
-    if (filt && (filt->width < 1 || filt->width > 4 || filt->iterations < 0 || filt->iterations > 16 || !std::isfinite(filt->offset) ||
-                 !std::isfinite((float)filt->offset)))
+    if (filt && !plan::filter_ok(filt))
         return fail(FLUID_ERR_ARG, "level-set filter: width in 1..4, iterations in 0..16 and a finite offset are required");
     const float R = (float)p->radius, w = (float)p->half_width;
     const float mx = R + w;
@@ -239,13 +239,14 @@ int fl::sdf_begin(fluid_sim* s, const fluid_sdf_params_t* p, SdfFront* f, const 
     g.min2 = mn * mn;
     f->any = false;
     f->tv = nullptr, f->flags = nullptr, f->list = nullptr;
-    f->track_n = filt ? s->sdf->track_n : 0, f->track_trim = filt && s->sdf->track_trim;
+    const fluid_sdf_track_t* t = filt ? &s->sdf->track : nullptr;   // the argument rules: sdf_filter_plan.h
+    f->track_n = t ? t->normalize : 0, f->track_trim = t && t->trim != 0;
     f->grow = filt && s->sdf->track_grow;
-    if (f->grow && !(f->track_n >= 1 && f->track_trim))
+    if (f->grow && !plan::grow_ok(t))
         return fail(FLUID_ERR_ARG, "grown level-set filter: growing the band requires tracking with normalize >= 1 and trim = 1 (fluid_sdf_set_track)");
-    if (f->grow && std::fabs((float)filt->offset) > 4.0f * g.dxf)
+    if (f->grow && !plan::grown_offset_ok((float)filt->offset, g.dxf))
         return fail(FLUID_ERR_ARG, "grown level-set filter: an offset beyond 4 dx in magnitude is refused");
-    if (!f->grow && (f->track_n > 0 || f->track_trim) && std::fabs((float)filt->offset) > g.bg)
+    if (!f->grow && plan::tracking(t) && !plan::tracked_offset_ok((float)filt->offset, g.bg))
         return fail(FLUID_ERR_ARG, "tracked level-set filter: an offset beyond the background in magnitude leaves no surface");
     f->filt = filt, f->dilate = 4;
     f->attr = false, f->dist2 = false;
@@ -271,13 +272,8 @@ int fl::sdf_front(fluid_sim* s, SdfFront* f)
             if (box[a] < g.lo || box[3 + a] > g.hi || box[3 + a] < box[a]) return fail(FLUID_ERR_HIP, "level set: particle box out of range");
         g.bx0 = box[0], g.by0 = box[1], g.bz0 = box[2];
         g.bnx = box[3] - box[0] + 1, g.bny = box[4] - box[1] + 1, g.bnz = box[5] - box[2] + 1;
-        int dilate = f->dilate;
-        if (f->grow) {   // T grown tracks move the active set by at most T cells (Manhattan): one per iteration and per offset step
-            dilate += f->filt->iterations;
-            const float a = std::fabs((float)f->filt->offset);
-            float d = 0.0f;
-            for (float delta; (delta = tdef::offset_step(a, d, g.dxf)) != 0.0f;) d = d + delta, ++dilate;
-        }
+        // T grown tracks move the active set by at most T cells (Manhattan)
+        const int dilate = f->dilate + (f->grow ? plan::tracks(*f->filt, g.dxf) : 0);
         for (int a = 0; a < 3; ++a) {
             const int c0 = std::max(box[a] - dilate, g.lo), c1 = std::min(box[3 + a] + dilate, g.hi);
             g.l0[a] = (c0 - g.L0) >> 3;
@@ -300,18 +296,20 @@ int fl::sdf_front(fluid_sim* s, SdfFront* f)
         if (f->attr) f->tid = o->tid, f->tvel = o->tvel;
         if (f->dist2) f->tmin = o->tmin;
         if (f->filt) {
-            // iteration = x, z, y (the library's order); the offset rides on the last pass, or is a pass of its own without one
-            static const int axes[3] = {0, 2, 1};
-            const int W = f->filt->width, passes = 3 * f->filt->iterations;
-            const float off = (float)f->filt->offset;
+            // the schedule of passes, offset steps and tracks: sdf_filter_plan.h; here what each of them launches
             float *src = o->tv, *dst = o->tv2;
             int *flags = o->flags, *flags2 = o->flags2;   // grown: the dilation's ping-pong
-            const long flagged0 = o->grow_stats && tracked ? sdf_count_flags(s, o->flags, leaves) : 0;
             uint64_t *tm = o->tm, *tm2 = o->tm2;
-            if (tracked) {
-                // one track: N passes src -> dst, the trim on the last; without a pass the trim alone, in place
-                bool trimmed = false;
-                auto track = [&]() {
+            const long flagged0 = o->grow_stats && tracked ? sdf_count_flags(s, o->flags, leaves) : 0;
+            bool trimmed = false;
+            plan::run(
+                *f->filt, g.dxf, tracked,
+                [&](int axis, int W, float off) {
+                    launch_sdf_box(s->st, g, axis, W, off, flags, tm, src, dst);
+                    std::swap(src, dst);
+                },
+                [&](float step) { launch_sdf_offset(s->st, g, step, flags, tm, src); },
+                [&]() {   // one track: N passes src -> dst, the trim on the last; without a pass the trim alone, in place
                     if (f->grow) {   // a newly flagged leaf gets its +bg in src, which the first pass below reads
                         launch_sdf_grow(s->st, g, flags, tm, flags2, tm2, src, f->attr ? o->tid : nullptr, o->tvel);
                         std::swap(flags, flags2), std::swap(tm, tm2);
@@ -323,38 +321,16 @@ int fl::sdf_front(fluid_sim* s, SdfFront* f)
                     }
                     if (f->track_n == 0) launch_sdf_track(s->st, g, false, true, flags, tm, src, src, f->attr ? o->tid : nullptr, o->tvel);
                     trimmed = f->track_trim;
-                };
-                for (int k = 0; k < passes; ++k) {
-                    launch_sdf_box(s->st, g, axes[k % 3], W, 0.0f, flags, tm, src, dst);
-                    std::swap(src, dst);
-                    if (k % 3 == 2) track();
-                }
-                const float a = std::fabs(off);
-                float d = 0.0f;
-                for (float delta; (delta = tdef::offset_step(a, d, g.dxf)) != 0.0f;) {
-                    d = d + delta;
-                    launch_sdf_offset(s->st, g, std::copysign(delta, off), flags, tm, src);
-                    track();
-                }
-                if (trimmed) {   // what is listed is what the last trim left
-                    launch_sdf_relist(s->st, g, flags, tm, src, o->lflags);
-                    f->list = o->lflags;
-                } else f->list = flags;
-                f->flags = flags, f->tm = tm;
-                if (o->grow_stats) {
-                    const size_t per_leaf = 2 * 2048 + 64 + 3 * sizeof(int) + (o->tracked ? sizeof(int) : 0) + (o->grown ? 64 + sizeof(int) : 0) +
-                                            (o->attr ? 2048 + 6144 : 0) + (o->dist2 ? 2048 : 0);
-                    fprintf(stderr, "sdf grow: grow %d leaves_in_range %ld flagged_by_search %ld flagged_at_end %ld leaf_scratch_bytes %zu\n", f->grow ? 1 : 0, leaves,
-                            flagged0, sdf_count_flags(s, flags, leaves), (size_t)o->leaf_cap * per_leaf);
-                }
-            } else {
-                for (int k = 0; k < passes; ++k) {
-                    launch_sdf_box(s->st, g, axes[k % 3], W, k == passes - 1 ? off : 0.0f, o->flags, o->tm, src, dst);
-                    std::swap(src, dst);
-                }
-                if (passes == 0 && off != 0.0f) launch_sdf_offset(s->st, g, off, o->flags, o->tm, src);
+                });
+            if (trimmed) launch_sdf_relist(s->st, g, flags, tm, src, o->lflags);   // what is listed is what the last trim left
+            f->list = trimmed ? o->lflags : flags;
+            f->flags = flags, f->tm = tm, f->tv = src;
+            if (o->grow_stats && tracked) {
+                const size_t per_leaf = 2 * 2048 + 64 + 3 * sizeof(int) + (o->tracked ? sizeof(int) : 0) + (o->grown ? 64 + sizeof(int) : 0) +
+                                        (o->attr ? 2048 + 6144 : 0) + (o->dist2 ? 2048 : 0);
+                fprintf(stderr, "sdf grow: grow %d leaves_in_range %ld flagged_by_search %ld flagged_at_end %ld leaf_scratch_bytes %zu\n", f->grow ? 1 : 0, leaves,
+                        flagged0, sdf_count_flags(s, flags, leaves), (size_t)o->leaf_cap * per_leaf);
             }
-            f->tv = src;
         }
     }
     return FLUID_OK;
@@ -489,12 +465,11 @@ int fluid_sdf_snapshot_filtered(fluid_sim_t* s, const fluid_sdf_params_t* p, con
 int fluid_sdf_set_track(fluid_sim_t* s, const fluid_sdf_track_t* t)
 {
     if (int rc = snap_guard(s, SDF_TRACK_SINGLE)) return rc;
-    if (t && (t->normalize < 0 || t->normalize > tdef::MAX_PASSES || (t->trim != 0 && t->trim != 1) || t->scheme != FLUID_SDF_TRACK_FIRST_BIAS))
+    if (!plan::track_ok(t))
         return fail(FLUID_ERR_ARG, "level-set tracking: normalize in 0..8, trim 0 or 1 and scheme FLUID_SDF_TRACK_FIRST_BIAS are required");
     HIPCHK(hipSetDevice(s->prm.device));
     if (int rc = sdf_init(s)) return rc;
-    s->sdf->track_n = t ? t->normalize : 0;
-    s->sdf->track_trim = t && t->trim != 0;
+    s->sdf->track = t ? *t : fluid_sdf_track_t{0, 0, FLUID_SDF_TRACK_FIRST_BIAS};
     return FLUID_OK;
 }
 

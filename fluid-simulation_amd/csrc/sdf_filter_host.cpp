@@ -10,15 +10,19 @@
 // fluid_sdf_filter_grown ("liquid surface, grown band") is the tracked filter whose every track begins with a dilation of the
 // masks (the word arithmetic is sdf_grow_def.h's, shared with kernels_sdf_grow.hip): the list is a working copy that the dilation
 // lengthens by the unlisted face neighbours it activates voxels in, and the attributes travel with it.
+// All three run the one schedule of sdf_filter_plan.h (the order of passes, offset steps and tracks, and the arguments' limits,
+// shared with fluid_sdf.hip); the tracked and the grown function are one driver (run_tracked) on one working list (Band) with one
+// rule for which leaves stay listed (copy_out), and differ in their refusals, in the dilation and in what travels with the band.
 // Arithmetic: float, no contraction (x86-64 has none without -mfma; the builds state -ffp-contract=off).
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <initializer_list>
 #include <vector>
 
 #include "leaf_list.h"
+#include "sdf_filter_plan.h"
 #include "sdf_grow_def.h"
-#include "sdf_track_def.h"
 
 namespace {
 
@@ -75,19 +79,23 @@ void box_pass(const fluid_sdf_grid_t* g, int axis, int W, float off, const float
     }
 }
 
-bool filter_ok(const fluid_sdf_filter_t* f)
-{
-    return f && f->width >= 1 && f->width <= 4 && f->iterations >= 0 && f->iterations <= 16 && std::isfinite(f->offset) && std::isfinite((float)f->offset);
-}
-
-// ---- "liquid surface, renormalised": the arithmetic is sdf_track_def.h's; here the neighbours, the masks and the list ----------
 inline bool in_grid(const fluid_sdf_grid_t* g, const int32_t* o, int at)
 {
     const int lo = -(g->n / 2), hi = lo + g->n - 1;
     const int c[3] = {o[0] + (at >> 6), o[1] + ((at >> 3) & 7), o[2] + (at & 7)};
     return c[0] >= lo && c[0] <= hi && c[1] >= lo && c[1] <= hi && c[2] >= lo && c[2] <= hi;
 }
+inline bool is_active(const uint64_t* mask, size_t l, int at) { return (mask[8 * l + (at >> 6)] >> (at & 63)) & 1ull; }
 
+// the offset, or a step of it: added to the active voxels inside the grid (g->origin and g->active; val: 512 per leaf)
+void add_active(const fluid_sdf_grid_t* g, float step, float* val)
+{
+    for (size_t l = 0; l < (size_t)g->n_leaves; ++l)
+        for (int at = 0; at < 512; ++at)
+            if (is_active(g->active, l, at) && in_grid(g, g->origin + 3 * l, at)) val[512 * l + at] = val[512 * l + at] + step;
+}
+
+// ---- "liquid surface, renormalised": the arithmetic is sdf_track_def.h's; here the neighbours, the masks and the list ----------
 // one normalisation pass src -> dst (512 per leaf, the list's order); g->active is the mask as it is now
 void norm_pass(const fluid_sdf_grid_t* g, float dx, const float* src, float* dst)
 {
@@ -142,6 +150,9 @@ void trim_pass(const fluid_sdf_grid_t* g, float* val, uint64_t* mask)
         }
 }
 
+// a band to track in: a background and a half width to take dx from
+bool band_ok(const fluid_sdf_grid_t* g) { return g->background > 0.0f && g->half_width > 0.0f; }
+
 // the list carries bg = dx * half_width, not dx: the quotient, or its float neighbour whose product gives bg back
 float list_dx(const fluid_sdf_grid_t* g)
 {
@@ -151,22 +162,38 @@ float list_dx(const fluid_sdf_grid_t* g)
     return dx;
 }
 
-bool overlaps(const void* a, size_t na, const void* b, size_t nb)
+// does an input array (nl leaves) overlap an output array (cap leaves)?  {pointer, bytes per leaf}; a null pointer overlaps nothing
+struct Arr { const void* p; size_t per_leaf; };
+bool overlap(std::initializer_list<Arr> in, size_t nl, std::initializer_list<Arr> out, size_t cap)
 {
-    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + na, b0 = (uintptr_t)b, b1 = b0 + nb;
-    return a && b && na && nb && a0 < b1 && b0 < a1;
+    for (const Arr& a : in)
+        for (const Arr& b : out) {
+            const uintptr_t a0 = (uintptr_t)a.p, a1 = a0 + a.per_leaf * nl, b0 = (uintptr_t)b.p, b1 = b0 + b.per_leaf * cap;
+            if (a.p && b.p && nl && cap && a0 < b1 && b0 < a1) return true;
+        }
+    return false;
 }
 
-// ---- "liquid surface, grown band": the working list of the grown filter, which a dilation can lengthen ---------------------------
+// ---- the working list of the tracked and the grown filter, which a dilation can lengthen ------------------------------------------
 struct Band {
     std::vector<int32_t> org;      // 3 per leaf, ascending
+    std::vector<int32_t> from;     // per leaf: its index in the caller's list (`kept`), -1 for a leaf a dilation added
     std::vector<uint64_t> mask;    // 8 per leaf
     std::vector<float> val[2];     // 512 per leaf: the passes' ping-pong, `at` = the one that holds the values
     int at = 0;
-    bool attr = false;
+    bool attr = false;             // "liquid surface, grown band": the attributes travel with the band
     std::vector<uint32_t> id;      // 512 per leaf
     std::vector<float> vel;        // 3 x 512 per leaf
     size_t leaves() const { return org.size() / 3; }
+    Band() = default;
+    Band(const fluid_sdf_grid_t* g, const fluid_sdf_attr_t* a) : org(g->origin, g->origin + 3 * (size_t)g->n_leaves), from((size_t)g->n_leaves),
+        mask(g->active, g->active + 8 * (size_t)g->n_leaves), attr(a != nullptr)
+    {
+        const size_t nl = leaves();
+        for (size_t l = 0; l < nl; ++l) from[l] = (int32_t)l;
+        val[0].assign(g->values, g->values + 512 * nl), val[1].resize(512 * nl);
+        if (a) id.assign(a->id, a->id + 512 * nl), vel.assign(a->velocity, a->velocity + 1536 * nl);
+    }
 };
 
 // One dilation of the band's masks (the mask words: sdf_grow_def.h).  `cur` describes the band as it is (origin, active, n_leaves
@@ -245,13 +272,14 @@ void dilate(fluid_sdf_grid_t* cur, Band& b)
         Band m;
         m.at = b.at, m.attr = b.attr;
         const size_t total = nl + add.size();
-        m.org.reserve(3 * total), m.mask.reserve(8 * total), m.val[0].reserve(512 * total), m.val[1].resize(512 * total);
+        m.org.reserve(3 * total), m.from.reserve(total), m.mask.reserve(8 * total), m.val[0].reserve(512 * total), m.val[1].resize(512 * total);
         if (b.attr) m.id.reserve(512 * total), m.vel.reserve(1536 * total);
         const std::vector<float>& v = b.val[b.at];
         for (size_t i = 0, k = 0; i < nl || k < add.size();) {
             const bool old = k == add.size() || (i < nl && Org{b.org[3 * i], b.org[3 * i + 1], b.org[3 * i + 2]} < add[k]);
             if (old) {
                 m.org.insert(m.org.end(), &b.org[3 * i], &b.org[3 * i] + 3);
+                m.from.push_back(b.from[i]);
                 m.mask.insert(m.mask.end(), &b.mask[8 * i], &b.mask[8 * i] + 8);
                 m.val[0].insert(m.val[0].end(), &v[512 * i], &v[512 * i] + 512);
                 if (b.attr) m.id.insert(m.id.end(), &b.id[512 * i], &b.id[512 * i] + 512), m.vel.insert(m.vel.end(), &b.vel[1536 * i], &b.vel[1536 * i] + 1536);
@@ -259,6 +287,7 @@ void dilate(fluid_sdf_grid_t* cur, Band& b)
             } else {
                 const int32_t o[3] = {add[k].x, add[k].y, add[k].z};
                 m.org.insert(m.org.end(), o, o + 3);
+                m.from.push_back(-1);
                 m.mask.insert(m.mask.end(), &add_mask[8 * k], &add_mask[8 * k] + 8);
                 m.val[0].insert(m.val[0].end(), 512, cur->background);
                 if (b.attr) m.id.insert(m.id.end(), &add_id[512 * k], &add_id[512 * k] + 512), m.vel.insert(m.vel.end(), &add_vel[1536 * k], &add_vel[1536 * k] + 1536);
@@ -288,213 +317,123 @@ void trim_pass_attr(const fluid_sdf_grid_t* g, Band& b)
             }
 }
 
-}  // namespace
-
-extern "C" {
-
-int fluid_sdf_filter(const fluid_sdf_grid_t* g, const fluid_sdf_filter_t* f, float* values)
+// The tracked filter on a band (the schedule: sdf_filter_plan.h): a track is the dilation when growing, N normalisation passes and
+// the trim.  True when a trim ran, which is when leaves can have left the list.
+bool run_tracked(const fluid_sdf_grid_t* g, Band& b, const fluid_sdf_filter_t* f, int N, bool trim, bool grow)
 {
-    if (check_list(g) != FLUID_OK || !filter_ok(f)) return FLUID_ERR_ARG;
-    const size_t count = 512 * (size_t)g->n_leaves;
-    if (count == 0) return FLUID_OK;
-    if (!values) return FLUID_ERR_ARG;
-    const uintptr_t a0 = (uintptr_t)g->values, a1 = a0 + count * sizeof(float), b0 = (uintptr_t)values, b1 = b0 + count * sizeof(float);
-    if (a0 < b1 && b0 < a1) return FLUID_ERR_ARG;
-    const int lo = -(g->n / 2), hi = lo + g->n - 1;
-    const float off = (float)f->offset;
-    const int passes = 3 * f->iterations;
-    if (passes == 0) {
-        memcpy(values, g->values, count * sizeof(float));
-        if (off != 0.0f)
-            for (long l = 0; l < g->n_leaves; ++l) {
-                const int32_t* o = g->origin + 3 * (size_t)l;
-                for (int at = 0; at < 512; ++at) {
-                    const int c[3] = {o[0] + (at >> 6), o[1] + ((at >> 3) & 7), o[2] + (at & 7)};
-                    const bool in = c[0] >= lo && c[0] <= hi && c[1] >= lo && c[1] <= hi && c[2] >= lo && c[2] <= hi;
-                    if (in && ((g->active[8 * (size_t)l + (at >> 6)] >> (at & 63)) & 1ull)) values[512 * (size_t)l + at] = values[512 * (size_t)l + at] + off;
-                }
-            }
-        return FLUID_OK;
-    }
-    std::vector<float> scratch(count);
-    static const int axes[3] = {0, 2, 1};   // the library's order: x, z, y
-    const float* src = g->values;
-    for (int k = 0; k < passes; ++k) {
-        float* dst = ((passes - 1 - k) & 1) ? scratch.data() : values;   // the last pass writes `values`
-        box_pass(g, axes[k % 3], f->width, k == passes - 1 ? off : 0.0f, src, dst);
-        src = dst;
-    }
-    return FLUID_OK;
-}
-
-int64_t fluid_sdf_filter_tracked(const fluid_sdf_grid_t* g, const fluid_sdf_filter_t* f, const fluid_sdf_track_t* t, int64_t cap_leaves,
-                                 int32_t* origin, float* values, uint64_t* active, int32_t* kept)
-{
-    // first pass: everything that can be refused, and the result in arrays of our own; second pass: the copy
-    if (check_list(g) != FLUID_OK || !filter_ok(f)) return -FLUID_ERR_ARG;
-    if (t && (t->normalize < 0 || t->normalize > tdef::MAX_PASSES || (t->trim != 0 && t->trim != 1) || t->scheme != FLUID_SDF_TRACK_FIRST_BIAS))
-        return -FLUID_ERR_ARG;
-    const int N = t ? t->normalize : 0;
-    const bool trim = t && t->trim != 0, tracked = N > 0 || trim;
-    const float off = (float)f->offset, bg = g->background;
-    if (tracked && (std::fabs(off) > bg || !(bg > 0.0f) || !(g->half_width > 0.0f))) return -FLUID_ERR_ARG;
-    const bool count_only = !origin && !values && !active;
-    if (!count_only && (!origin || !values || !active || cap_leaves < 0)) return -FLUID_ERR_ARG;
-    const size_t nl = (size_t)g->n_leaves, count = 512 * nl;
-    if (!count_only) {
-        const size_t cap = (size_t)cap_leaves;
-        const void* in[3] = {g->origin, g->values, g->active};
-        const size_t nin[3] = {12 * nl, 2048 * nl, 64 * nl};
-        const void* out[4] = {origin, values, active, kept};
-        const size_t nout[4] = {12 * cap, 2048 * cap, 64 * cap, 4 * cap};
-        for (int i = 0; i < 3; ++i)
-            for (int k = 0; k < 4; ++k)
-                if (overlaps(in[i], nin[i], out[k], nout[k])) return -FLUID_ERR_ARG;
-    }
-    if (nl == 0) return 0;
-    std::vector<float> val(count);
-    std::vector<uint64_t> mask(g->active, g->active + 8 * nl);
-    std::vector<int32_t> keep(nl);
-    for (size_t l = 0; l < nl; ++l) keep[l] = (int32_t)l;
-    if (!tracked) {
-        if (!count_only && cap_leaves < g->n_leaves) return -FLUID_ERR_ARG;
-        if (count_only) return g->n_leaves;
-        if (fluid_sdf_filter(g, f, val.data()) != FLUID_OK) return -FLUID_ERR_ARG;
-    } else {
-        std::vector<float> other(count);
-        fluid_sdf_grid_t cur = *g;   // the list with the mask as it is now
-        cur.active = mask.data();
-        const float dx = list_dx(g);
-        memcpy(val.data(), g->values, count * sizeof(float));
-        float *src = val.data(), *dst = other.data();
-        bool trimmed = false;
-        auto track = [&]() {
-            for (int i = 0; i < N; ++i) {
-                norm_pass(&cur, dx, src, dst);
-                std::swap(src, dst);
-            }
-            if (trim) trim_pass(&cur, src, mask.data()), trimmed = true;
-        };
-        static const int axes[3] = {0, 2, 1};
-        for (int k = 0; k < 3 * f->iterations; ++k) {
-            box_pass(&cur, axes[k % 3], f->width, 0.0f, src, dst);
-            std::swap(src, dst);
-            if (k % 3 == 2) track();
-        }
-        const float a = std::fabs(off);
-        float d = 0.0f;
-        for (float delta; (delta = tdef::offset_step(a, d, dx)) != 0.0f;) {
-            d = d + delta;
-            const float step = std::copysign(delta, off);
-            for (size_t l = 0; l < nl; ++l)
-                for (int at = 0; at < 512; ++at)
-                    if (((mask[8 * l + (at >> 6)] >> (at & 63)) & 1ull) && in_grid(g, g->origin + 3 * l, at)) src[512 * l + at] = src[512 * l + at] + step;
-            track();
-        }
-        if (src != val.data()) memcpy(val.data(), src, count * sizeof(float));
-        if (trimmed) {   // listed: an in-grid voxel that is anything but inactive +bg
-            keep.clear();
-            for (size_t l = 0; l < nl; ++l) {
-                bool any = false;
-                for (int at = 0; at < 512 && !any; ++at)
-                    any = in_grid(g, g->origin + 3 * l, at) && (((mask[8 * l + (at >> 6)] >> (at & 63)) & 1ull) || val[512 * l + at] != bg);
-                if (any) keep.push_back((int32_t)l);
-            }
-        }
-        if (count_only) return (int64_t)keep.size();
-        if (cap_leaves < (int64_t)keep.size()) return -FLUID_ERR_ARG;
-    }
-    for (size_t i = 0; i < keep.size(); ++i) {
-        const size_t l = (size_t)keep[i];
-        memcpy(origin + 3 * i, g->origin + 3 * l, 3 * sizeof(int32_t));
-        memcpy(values + 512 * i, val.data() + 512 * l, 512 * sizeof(float));
-        memcpy(active + 8 * i, mask.data() + 8 * l, 8 * sizeof(uint64_t));
-        if (kept) kept[i] = keep[i];
-    }
-    return (int64_t)keep.size();
-}
-
-int64_t fluid_sdf_filter_grown(const fluid_sdf_grid_t* g, const fluid_sdf_attr_t* attr, const fluid_sdf_filter_t* f, const fluid_sdf_track_t* t,
-                               int64_t cap_leaves, int32_t* origin, float* values, uint64_t* active, uint32_t* id, float* velocity)
-{
-    // everything that can be refused first; the result is made in arrays of our own and copied last
-    if (check_list(g) != FLUID_OK || !filter_ok(f)) return -FLUID_ERR_ARG;
-    if (!t || t->normalize < 1 || t->normalize > tdef::MAX_PASSES || t->trim != 1 || t->scheme != FLUID_SDF_TRACK_FIRST_BIAS) return -FLUID_ERR_ARG;
-    const float off = (float)f->offset, bg = g->background;
-    if (!(bg > 0.0f) || !(g->half_width > 0.0f)) return -FLUID_ERR_ARG;
-    const float dx = list_dx(g);
-    if (std::fabs(off) > 4.0f * dx) return -FLUID_ERR_ARG;
-    const size_t nl = (size_t)g->n_leaves;
-    if (attr && (attr->n_leaves != g->n_leaves || (nl > 0 && (!attr->id || !attr->velocity)))) return -FLUID_ERR_ARG;
-    const bool count_only = !origin && !values && !active && !id && !velocity;
-    if (!count_only) {
-        if (!origin || !values || !active || cap_leaves < 0) return -FLUID_ERR_ARG;
-        if (attr ? (!id || !velocity) : (id || velocity)) return -FLUID_ERR_ARG;
-        const size_t cap = (size_t)cap_leaves;
-        const void* in[5] = {g->origin, g->values, g->active, attr ? attr->id : nullptr, attr ? attr->velocity : nullptr};
-        const size_t nin[5] = {12 * nl, 2048 * nl, 64 * nl, 2048 * nl, 6144 * nl};
-        const void* out[5] = {origin, values, active, id, velocity};
-        const size_t nout[5] = {12 * cap, 2048 * cap, 64 * cap, 2048 * cap, 6144 * cap};
-        for (int i = 0; i < 5; ++i)
-            for (int k = 0; k < 5; ++k)
-                if (overlaps(in[i], nin[i], out[k], nout[k])) return -FLUID_ERR_ARG;
-    }
-    if (nl == 0) return 0;
-    Band b;
-    b.org.assign(g->origin, g->origin + 3 * nl);
-    b.mask.assign(g->active, g->active + 8 * nl);
-    b.val[0].assign(g->values, g->values + 512 * nl);
-    b.val[1].resize(512 * nl);
-    b.attr = attr != nullptr;
-    if (attr) b.id.assign(attr->id, attr->id + 512 * nl), b.vel.assign(attr->velocity, attr->velocity + 1536 * nl);
-    fluid_sdf_grid_t cur = *g;   // the band as it is now
+    fluid_sdf_grid_t cur = *g;   // the band as it is now: dilate() keeps it pointing into b
     cur.origin = b.org.data(), cur.active = b.mask.data(), cur.values = nullptr;
-    const int N = t->normalize;
-    auto track = [&]() {
-        dilate(&cur, b);
-        for (int i = 0; i < N; ++i) {
-            norm_pass(&cur, dx, b.val[b.at].data(), b.val[1 - b.at].data());
+    const float dx = list_dx(g);
+    bool trimmed = false;
+    plan::run(
+        *f, dx, true,
+        [&](int axis, int W, float off) {
+            box_pass(&cur, axis, W, off, b.val[b.at].data(), b.val[1 - b.at].data());
             b.at = 1 - b.at;
-        }
-        trim_pass_attr(&cur, b);
-    };
-    static const int axes[3] = {0, 2, 1};
-    for (int k = 0; k < 3 * f->iterations; ++k) {
-        box_pass(&cur, axes[k % 3], f->width, 0.0f, b.val[b.at].data(), b.val[1 - b.at].data());
-        b.at = 1 - b.at;
-        if (k % 3 == 2) track();
-    }
-    const float a = std::fabs(off);
-    float d = 0.0f;
-    bool tracked = f->iterations > 0;
-    for (float delta; (delta = tdef::offset_step(a, d, dx)) != 0.0f;) {
-        d = d + delta;
-        const float step = std::copysign(delta, off);
-        float* v = b.val[b.at].data();
-        for (size_t l = 0; l < b.leaves(); ++l)
-            for (int at = 0; at < 512; ++at)
-                if (((b.mask[8 * l + (at >> 6)] >> (at & 63)) & 1ull) && in_grid(&cur, &b.org[3 * l], at)) v[512 * l + at] = v[512 * l + at] + step;
-        track();
-        tracked = true;
-    }
+        },
+        [&](float step) { add_active(&cur, step, b.val[b.at].data()); },
+        [&]() {
+            if (grow) dilate(&cur, b);
+            for (int i = 0; i < N; ++i) {
+                norm_pass(&cur, dx, b.val[b.at].data(), b.val[1 - b.at].data());
+                b.at = 1 - b.at;
+            }
+            if (trim) trim_pass_attr(&cur, b), trimmed = true;
+        });
+    return trimmed;
+}
+
+// The band into the caller's arrays (origin == nullptr: the count alone).  Listed: every leaf when no trim ran, else a leaf with an
+// in-grid voxel that is anything but inactive +bg.  The count, or -FLUID_ERR_ARG with nothing written when cap_leaves is too small.
+int64_t copy_out(const fluid_sdf_grid_t* g, const Band& b, bool trimmed, int64_t cap_leaves, int32_t* origin, float* values, uint64_t* active,
+                 int32_t* kept, uint32_t* id, float* velocity)
+{
     const float* v = b.val[b.at].data();
     std::vector<size_t> keep;
-    for (size_t l = 0; l < b.leaves(); ++l) {   // listed: an in-grid voxel that is anything but inactive +bg (with no track run: every leaf)
-        bool any = !tracked;
-        for (int at = 0; at < 512 && !any; ++at)
-            any = in_grid(&cur, &b.org[3 * l], at) && (((b.mask[8 * l + (at >> 6)] >> (at & 63)) & 1ull) || v[512 * l + at] != bg);
+    for (size_t l = 0; l < b.leaves(); ++l) {
+        bool any = !trimmed;
+        for (int at = 0; at < 512 && !any; ++at) any = in_grid(g, &b.org[3 * l], at) && (is_active(b.mask.data(), l, at) || v[512 * l + at] != g->background);
         if (any) keep.push_back(l);
     }
-    if (count_only) return (int64_t)keep.size();
+    if (!origin) return (int64_t)keep.size();
     if (cap_leaves < (int64_t)keep.size()) return -FLUID_ERR_ARG;
     for (size_t i = 0; i < keep.size(); ++i) {
         const size_t l = keep[i];
         memcpy(origin + 3 * i, &b.org[3 * l], 3 * sizeof(int32_t));
         memcpy(values + 512 * i, v + 512 * l, 512 * sizeof(float));
         memcpy(active + 8 * i, &b.mask[8 * l], 8 * sizeof(uint64_t));
-        if (attr) memcpy(id + 512 * i, &b.id[512 * l], 512 * sizeof(uint32_t)), memcpy(velocity + 1536 * i, &b.vel[1536 * l], 1536 * sizeof(float));
+        if (kept) kept[i] = b.from[l];
+        if (b.attr) memcpy(id + 512 * i, &b.id[512 * l], 512 * sizeof(uint32_t)), memcpy(velocity + 1536 * i, &b.vel[1536 * l], 1536 * sizeof(float));
     }
     return (int64_t)keep.size();
+}
+
+}  // namespace
+
+extern "C" {
+
+int fluid_sdf_filter(const fluid_sdf_grid_t* g, const fluid_sdf_filter_t* f, float* values)
+{
+    if (check_list(g) != FLUID_OK || !plan::filter_ok(f)) return FLUID_ERR_ARG;
+    const size_t count = 512 * (size_t)g->n_leaves;
+    if (count == 0) return FLUID_OK;
+    if (!values || overlap({{g->values, 2048}}, (size_t)g->n_leaves, {{values, 2048}}, (size_t)g->n_leaves)) return FLUID_ERR_ARG;
+    const int passes = 3 * f->iterations;
+    if (passes == 0) memcpy(values, g->values, count * sizeof(float));
+    std::vector<float> scratch(passes ? count : 0);
+    const float* src = g->values;
+    int k = 0;
+    plan::run(
+        *f, 0.0f, false,
+        [&](int axis, int W, float off) {
+            float* dst = ((passes - 1 - k++) & 1) ? scratch.data() : values;   // the last pass writes `values`
+            box_pass(g, axis, W, off, src, dst);
+            src = dst;
+        },
+        [&](float off) { add_active(g, off, values); }, [] {});
+    return FLUID_OK;
+}
+
+int64_t fluid_sdf_filter_tracked(const fluid_sdf_grid_t* g, const fluid_sdf_filter_t* f, const fluid_sdf_track_t* t, int64_t cap_leaves,
+                                 int32_t* origin, float* values, uint64_t* active, int32_t* kept)
+{
+    // everything that can be refused first; the result is made in a band of our own and copied last
+    if (check_list(g) != FLUID_OK || !plan::filter_ok(f) || !plan::track_ok(t)) return -FLUID_ERR_ARG;
+    const bool tracked = plan::tracking(t);
+    if (tracked && (!plan::tracked_offset_ok((float)f->offset, g->background) || !band_ok(g))) return -FLUID_ERR_ARG;
+    const bool count_only = !origin && !values && !active;
+    if (!count_only && (!origin || !values || !active || cap_leaves < 0)) return -FLUID_ERR_ARG;
+    const size_t nl = (size_t)g->n_leaves;
+    if (!count_only && overlap({{g->origin, 12}, {g->values, 2048}, {g->active, 64}}, nl, {{origin, 12}, {values, 2048}, {active, 64}, {kept, 4}}, (size_t)cap_leaves))
+        return -FLUID_ERR_ARG;
+    if (nl == 0) return 0;
+    if (!tracked && count_only) return g->n_leaves;
+    Band b(g, nullptr);
+    bool trimmed = false;
+    if (tracked) trimmed = run_tracked(g, b, f, t->normalize, t->trim != 0, false);
+    else if (fluid_sdf_filter(g, f, b.val[0].data()) != FLUID_OK) return -FLUID_ERR_ARG;
+    return copy_out(g, b, trimmed, cap_leaves, origin, values, active, kept, nullptr, nullptr);
+}
+
+int64_t fluid_sdf_filter_grown(const fluid_sdf_grid_t* g, const fluid_sdf_attr_t* attr, const fluid_sdf_filter_t* f, const fluid_sdf_track_t* t,
+                               int64_t cap_leaves, int32_t* origin, float* values, uint64_t* active, uint32_t* id, float* velocity)
+{
+    if (check_list(g) != FLUID_OK || !plan::filter_ok(f) || !plan::track_ok(t) || !plan::grow_ok(t)) return -FLUID_ERR_ARG;
+    if (!band_ok(g) || !plan::grown_offset_ok((float)f->offset, list_dx(g))) return -FLUID_ERR_ARG;
+    const size_t nl = (size_t)g->n_leaves;
+    if (attr && (attr->n_leaves != g->n_leaves || (nl > 0 && (!attr->id || !attr->velocity)))) return -FLUID_ERR_ARG;
+    const bool count_only = !origin && !values && !active && !id && !velocity;
+    if (!count_only) {
+        if (!origin || !values || !active || cap_leaves < 0) return -FLUID_ERR_ARG;
+        if (attr ? (!id || !velocity) : (id || velocity)) return -FLUID_ERR_ARG;
+        if (overlap({{g->origin, 12}, {g->values, 2048}, {g->active, 64}, {attr ? attr->id : nullptr, 2048}, {attr ? attr->velocity : nullptr, 6144}}, nl,
+                    {{origin, 12}, {values, 2048}, {active, 64}, {id, 2048}, {velocity, 6144}}, (size_t)cap_leaves))
+            return -FLUID_ERR_ARG;
+    }
+    if (nl == 0) return 0;
+    Band b(g, attr);
+    const bool trimmed = run_tracked(g, b, f, t->normalize, true, true);
+    return copy_out(g, b, trimmed, cap_leaves, origin, values, active, nullptr, id, velocity);
 }
 
 }  // extern "C"
