@@ -237,6 +237,9 @@ SYMBOLS = [
     ("fluid_sdf_set_track_grow", C.c_int, [_P, C.c_int32]),
     ("fluid_sdf_filter_grown", C.c_int64, [C.POINTER(SdfGridC), C.POINTER(SdfAttrC), C.POINTER(SdfFilter), C.POINTER(SdfTrack), C.c_int64, _P, _P, _P,
                                            _P, _P]),
+    ("fluid_sdf_set_filter_kind", C.c_int, [_P, C.c_int32]),
+    ("fluid_sdf_flow", C.c_int64, [C.POINTER(SdfGridC), C.POINTER(SdfAttrC), C.c_int32, C.POINTER(SdfFilter), C.POINTER(SdfTrack), C.c_int32, C.c_int64,
+                                   _P, _P, _P, _P, _P]),
     ("fluid_mesh_snapshot", C.c_int, [_P, C.POINTER(SdfParams)]),
     ("fluid_mesh_wait", C.c_int, [_P, C.POINTER(MeshC)]),
     ("fluid_mesh_stats", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -371,6 +371,10 @@ void launch_sdf_relist(hipStream_t st, const SdfGeom& g, const int* flags, const
 // newly active voxel inherits its first active face neighbour's id and velocity
 void launch_sdf_grow(hipStream_t st, const SdfGeom& g, const int* flags, const uint64_t* tm, int* flags2, uint64_t* tm2, float* val, uint32_t* tid,
                      float* tvel);
+// flows of that level set (kernels_sdf_flow.hip): one pass of a median (W = 1 or 2), Laplacian or mean-curvature flow (kind: a
+// FLUID_SDF_FILTER_* other than BOX) from src to dst, with launch_sdf_box's conventions; `off` is added to the active voxels' results
+void launch_sdf_flow(hipStream_t st, const SdfGeom& g, int kind, int W, float off, const int* flags, const uint64_t* tm, const float* src,
+                     float* dst);
 // surface nets of that level set (kernels_mesh.hip): per leaf of the range the mixed-cell mask (8 words), the exclusive prefix of the
 // words' popcounts, the vertex and the quad count; tot[2] = the two totals, saturating at 2^31 (a one-block sum of the counts)
 void launch_mesh_mark(hipStream_t st, const SdfGeom& g, const float* tv, const int* flags, uint64_t* cmask, int* cpre, int* vcnt, int* qcnt,

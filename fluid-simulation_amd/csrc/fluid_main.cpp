@@ -76,6 +76,11 @@
 // are fluid_sdf_snapshot_filtered / fluid_mesh_snapshot_filtered; a block run filters the merged list on the main thread
 // (fluid_sdf_filter, two buffers in turn) before it goes to the writer thread.  Refused malformed, outside the filter's limits, or
 // with none of the four set, before any handle is created.  Without it stdout and every file are what they were.
+//   FLUID_OUT_SMOOTH_KIND=box|median|laplacian|curvature (unset: box; with FLUID_OUT_SMOOTH only) — the filter FLUID_OUT_SMOOTH runs K
+// iterations of (include/fluid_hip.h, "liquid surface, flows"), for everything FLUID_OUT_SMOOTH applies to: a median takes W = 1 or 2,
+// laplacian and curvature W = 1.  One GPU through fluid_sdf_set_filter_kind, a block run through fluid_sdf_flow on the main thread
+// after the merge, tracked and grown as FLUID_OUT_TRACK says.  Refused with another name, without FLUID_OUT_SMOOTH or with a W the
+// kind does not admit, before any handle is created.
 //   FLUID_OUT_TRACK=N[,TRIM] (unset: off; with FLUID_OUT_SMOOTH only; TRIM defaults to 1) — the filter runs tracked: N normalisation
 // passes (0..8) and, with TRIM = 1, the trim after every box iteration and every offset step (include/fluid_hip.h, "liquid
 // surface, renormalised"), for everything FLUID_OUT_SMOOTH applies to: one GPU through fluid_sdf_set_track, a block run through
@@ -361,6 +366,7 @@ struct BlockCfg {
     fluid_sdf_params_t sp{};
     bool smooth = false;      // FLUID_OUT_SMOOTH
     fluid_sdf_filter_t sf{};
+    int32_t kind = FLUID_SDF_FILTER_BOX;   // FLUID_OUT_SMOOTH_KIND
     bool track = false;       // FLUID_OUT_TRACK
     bool grow = false;        // ... with GROW = 1
     fluid_sdf_track_t tk{};
@@ -586,10 +592,18 @@ static int run_blocks(const BlockCfg& cfg, const std::vector<double>& pos, int64
             sat = fluid_sdf_attr_t{(int32_t)ks, attr && ks ? si.data() : nullptr, attr && ks ? sw.data() : nullptr};
             sg = fluid_sdf_grid_t{n, (int32_t)ks, sp[0].background, sp[0].radius, sp[0].half_width, ks ? so.data() : nullptr, ks ? sv.data() : nullptr,
                                   ks ? sa.data() : nullptr};
-            if (cfg.smooth && cfg.track && cfg.grow && ks) {   // the grown list can be longer than the merged one: count, then fill
+            if (cfg.smooth && (cfg.kind != FLUID_SDF_FILTER_BOX || (cfg.track && cfg.grow)) && ks) {
+                // a flow (FLUID_OUT_SMOOTH_KIND) in any of its three forms, or the grown box filter; the grown list can be longer than
+                // the merged one: count, then fill
                 const fluid_sdf_attr_t* in = attr ? &sat : nullptr;
-                const int64_t kg = fluid_sdf_filter_grown(&sg, in, &cfg.sf, &cfg.tk, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
-                if (kg < 0) { sy.fail("fluid_sdf_filter_grown: the merged surface list, or an offset beyond 4 voxels, was refused"); break; }
+                const bool flow = cfg.kind != FLUID_SDF_FILTER_BOX;
+                const fluid_sdf_track_t* tk = cfg.track ? &cfg.tk : nullptr;
+                auto filter = [&](int64_t cap, int32_t* o, float* v, uint64_t* a, uint32_t* id, float* vel) {
+                    return flow ? fluid_sdf_flow(&sg, in, cfg.kind, &cfg.sf, tk, cfg.grow ? 1 : 0, cap, o, v, a, id, vel)
+                                : fluid_sdf_filter_grown(&sg, in, &cfg.sf, &cfg.tk, cap, o, v, a, id, vel);
+                };
+                const int64_t kg = filter(0, nullptr, nullptr, nullptr, nullptr, nullptr);
+                if (kg < 0) { sy.fail(flow ? "fluid_sdf_flow: the merged surface list, or the offset, was refused" : "fluid_sdf_filter_grown: the merged surface list, or an offset beyond 4 voxels, was refused"); break; }
                 auto& sm = s_smooth[i & 1];
                 auto& to = t_org[i & 1];
                 auto& ta = t_act[i & 1];
@@ -598,8 +612,10 @@ static int run_blocks(const BlockCfg& cfg, const std::vector<double>& pos, int64
                 if (to.size() < 3 * (size_t)kg) { to.resize(3 * ((size_t)kg + 64)); ta.resize(8 * ((size_t)kg + 64)); }
                 if (sm.size() < 512 * (size_t)kg) sm.resize(512 * ((size_t)kg + 64));
                 if (attr && ti.size() < 512 * (size_t)kg) { ti.resize(512 * ((size_t)kg + 64)); tv.resize(1536 * ((size_t)kg + 64)); }
-                if (kg && fluid_sdf_filter_grown(&sg, in, &cfg.sf, &cfg.tk, kg, to.data(), sm.data(), ta.data(), attr ? ti.data() : nullptr,
-                                                 attr ? tv.data() : nullptr) != kg) { sy.fail("fluid_sdf_filter_grown: the second call disagrees with the count"); break; }
+                if (kg && filter(kg, to.data(), sm.data(), ta.data(), attr ? ti.data() : nullptr, attr ? tv.data() : nullptr) != kg) {
+                    sy.fail("the level-set filter's second call disagrees with the count");
+                    break;
+                }
                 sg = fluid_sdf_grid_t{n, (int32_t)kg, sg.background, sg.radius, sg.half_width, kg ? to.data() : nullptr, kg ? sm.data() : nullptr,
                                       kg ? ta.data() : nullptr};
                 sat = fluid_sdf_attr_t{(int32_t)kg, attr && kg ? ti.data() : nullptr, attr && kg ? tv.data() : nullptr};
@@ -838,6 +854,24 @@ int main(int, char**)
         }
         bc.smooth = true, bc.sf = sf;
     }
+    int32_t smooth_kind = FLUID_SDF_FILTER_BOX;
+    if (const char* kenv = getenv("FLUID_OUT_SMOOTH_KIND"); kenv && *kenv) {
+        const std::string v = kenv;
+        if (v == "box") smooth_kind = FLUID_SDF_FILTER_BOX;
+        else if (v == "median") smooth_kind = FLUID_SDF_FILTER_MEDIAN;
+        else if (v == "laplacian") smooth_kind = FLUID_SDF_FILTER_LAPLACIAN;
+        else if (v == "curvature") smooth_kind = FLUID_SDF_FILTER_MEAN_CURVATURE;
+        else { std::cerr << "FLUID_OUT_SMOOTH_KIND must be box, median, laplacian or curvature" << std::endl; return 1; }
+        if (!smooth) {
+            std::cerr << "FLUID_OUT_SMOOTH_KIND chooses the filter FLUID_OUT_SMOOTH runs: FLUID_OUT_SMOOTH is not set" << std::endl;
+            return 1;
+        }
+        if (smooth_kind == FLUID_SDF_FILTER_MEDIAN ? sf.width > 2 : smooth_kind != FLUID_SDF_FILTER_BOX && sf.width != 1) {
+            std::cerr << "FLUID_OUT_SMOOTH_KIND: a median takes W = 1 or 2 in FLUID_OUT_SMOOTH, laplacian and curvature W = 1" << std::endl;
+            return 1;
+        }
+        bc.kind = smooth_kind;
+    }
     const char* tkenv = getenv("FLUID_OUT_TRACK");
     const bool track = tkenv && *tkenv;
     bool track_grow = false;
@@ -891,6 +925,10 @@ int main(int, char**)
     fluid_sim_t* sim = nullptr;
     if (!(blocks && *blocks) && fluid_create(&prm, &sim) != FLUID_OK) {
         std::cerr << "fluid_create: " << fluid_last_error() << std::endl;
+        return 1;
+    }
+    if (sim && smooth_kind != FLUID_SDF_FILTER_BOX && fluid_sdf_set_filter_kind(sim, smooth_kind) != FLUID_OK) {
+        std::cerr << "fluid_sdf_set_filter_kind: " << fluid_last_error() << std::endl;
         return 1;
     }
     if (sim && track && fluid_sdf_set_track(sim, &tk) != FLUID_OK) {

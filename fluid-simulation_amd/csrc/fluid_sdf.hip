@@ -40,6 +40,10 @@
 // again, every leaf of its range, so nothing of an earlier snapshot is read.  flags2 and tm2 exist from the handle's first grown
 // snapshot on.
 //
+// fluid_sdf_set_filter_kind ("liquid surface, flows"; kernels_sdf_flow.hip): with a kind other than BOX every filter of the front
+// half runs that kind's one pass per iteration in place of the three box passes: one launch, ping-pong between the same two value
+// buffers; tracks, growing and the offset follow it exactly as they follow a box iteration.
+//
 // fluid_sdf_snapshot_attr / fluid_mesh_snapshot_attr ("liquid surface, attributes"): the scatter also writes each sorted position's
 // index in the live arrays (ssrc), the search keeps the closest particle beside the minimum and writes its id and velocity per voxel
 // (tid, tvel), and the pack lists them.  ssrc, tid and tvel exist from the handle's first attribute snapshot on.  An attribute
@@ -81,6 +85,7 @@ struct SdfState {
     uint64_t* tm2 = nullptr;
     bool grown = false;
     bool track_grow = false;   // fluid_sdf_set_track_grow
+    int kind = FLUID_SDF_FILTER_BOX;   // fluid_sdf_set_filter_kind
     // attributes: index in the live arrays per sorted position (part_cap), winner's id (leaf_cap x 512) and velocity (leaf_cap x 3 x 512)
     // per voxel: allocated once an attribute snapshot was asked for
     int* ssrc = nullptr;
@@ -104,6 +109,7 @@ static const char* const SDF_SINGLE = "level-set snapshots are single-GPU only: 
 static const char* const SDF_FILT_SINGLE = "filtered level-set snapshots are single-GPU only: a mean of per-block minima is not the mean of the minimum; filter the merged list on the host (fluid_sdf_filter)";
 
 static const char* const SDF_GROW_SINGLE = "grown level-set snapshots are single-GPU only: a decomposed handle's filter runs on the merged list on the host (fluid_sdf_filter_grown)";
+static const char* const SDF_KIND_SINGLE = "level-set flows are single-GPU only: a decomposed handle's filter runs on the merged list on the host (fluid_sdf_flow)";
 static const char* const SDF_TRACK_SINGLE = "tracked level-set snapshots are single-GPU only: a decomposed handle's filter runs on the merged list on the host (fluid_sdf_filter_tracked)";
 
 static int sdf_init(fluid_sim* s)
@@ -242,6 +248,9 @@ int fl::sdf_begin(fluid_sim* s, const fluid_sdf_params_t* p, SdfFront* f, const 
     const fluid_sdf_track_t* t = filt ? &s->sdf->track : nullptr;   // the argument rules: sdf_filter_plan.h
     f->track_n = t ? t->normalize : 0, f->track_trim = t && t->trim != 0;
     f->grow = filt && s->sdf->track_grow;
+    f->kind = filt ? s->sdf->kind : FLUID_SDF_FILTER_BOX;
+    if (filt && !plan::width_ok(f->kind, filt->width))
+        return fail(FLUID_ERR_ARG, "level-set flow: a median takes width 1 or 2, a Laplacian or mean-curvature flow width 1 (fluid_sdf_set_filter_kind)");
     if (f->grow && !plan::grow_ok(t))
         return fail(FLUID_ERR_ARG, "grown level-set filter: growing the band requires tracking with normalize >= 1 and trim = 1 (fluid_sdf_set_track)");
     if (f->grow && !plan::grown_offset_ok((float)filt->offset, g.dxf))
@@ -303,9 +312,13 @@ int fl::sdf_front(fluid_sim* s, SdfFront* f)
             const long flagged0 = o->grow_stats && tracked ? sdf_count_flags(s, o->flags, leaves) : 0;
             bool trimmed = false;
             plan::run(
-                *f->filt, g.dxf, tracked,
+                f->kind, *f->filt, g.dxf, tracked,
                 [&](int axis, int W, float off) {
                     launch_sdf_box(s->st, g, axis, W, off, flags, tm, src, dst);
+                    std::swap(src, dst);
+                },
+                [&](int kind, int W, float off) {
+                    launch_sdf_flow(s->st, g, kind, W, off, flags, tm, src, dst);
                     std::swap(src, dst);
                 },
                 [&](float step) { launch_sdf_offset(s->st, g, step, flags, tm, src); },
@@ -480,6 +493,16 @@ int fluid_sdf_set_track_grow(fluid_sim_t* s, int32_t grow)
     HIPCHK(hipSetDevice(s->prm.device));
     if (int rc = sdf_init(s)) return rc;
     s->sdf->track_grow = grow != 0;
+    return FLUID_OK;
+}
+
+int fluid_sdf_set_filter_kind(fluid_sim_t* s, int32_t kind)
+{
+    if (int rc = snap_guard(s, SDF_KIND_SINGLE)) return rc;
+    if (!plan::kind_ok(kind)) return fail(FLUID_ERR_ARG, "level-set filter kind: one of FLUID_SDF_FILTER_BOX, _MEDIAN, _LAPLACIAN, _MEAN_CURVATURE is required");
+    HIPCHK(hipSetDevice(s->prm.device));
+    if (int rc = sdf_init(s)) return rc;
+    s->sdf->kind = kind;
     return FLUID_OK;
 }
 

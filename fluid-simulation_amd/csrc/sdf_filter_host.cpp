@@ -10,9 +10,13 @@
 // fluid_sdf_filter_grown ("liquid surface, grown band") is the tracked filter whose every track begins with a dilation of the
 // masks (the word arithmetic is sdf_grow_def.h's, shared with kernels_sdf_grow.hip): the list is a working copy that the dilation
 // lengthens by the unlisted face neighbours it activates voxels in, and the attributes travel with it.
-// All three run the one schedule of sdf_filter_plan.h (the order of passes, offset steps and tracks, and the arguments' limits,
-// shared with fluid_sdf.hip); the tracked and the grown function are one driver (run_tracked) on one working list (Band) with one
-// rule for which leaves stay listed (copy_out), and differ in their refusals, in the dilation and in what travels with the band.
+// fluid_sdf_flow ("liquid surface, flows") is all three forms for a filter kind: the box passes, or one pass per iteration of a
+// median, Laplacian or mean-curvature flow (the per-voxel arithmetic is sdf_flow_def.h's, shared with kernels_sdf_flow.hip) on the
+// leaf's (8 + 2H)^3 tile, the 26 neighbour leaves found by bisection.
+// All four run the one schedule of sdf_filter_plan.h (the order of passes, offset steps and tracks, and the arguments' limits,
+// shared with fluid_sdf.hip); the tracked, the grown and the flow function are one driver (run_band) on one working list (Band)
+// with one rule for which leaves stay listed (copy_out), and differ in their refusals, in the dilation and in what travels with
+// the band.
 // Arithmetic: float, no contraction (x86-64 has none without -mfma; the builds state -ffp-contract=off).
 #include <cmath>
 #include <cstdint>
@@ -22,6 +26,7 @@
 
 #include "leaf_list.h"
 #include "sdf_filter_plan.h"
+#include "sdf_flow_def.h"
 #include "sdf_grow_def.h"
 
 namespace {
@@ -93,6 +98,72 @@ void add_active(const fluid_sdf_grid_t* g, float step, float* val)
     for (size_t l = 0; l < (size_t)g->n_leaves; ++l)
         for (int at = 0; at < 512; ++at)
             if (is_active(g->active, l, at) && in_grid(g, g->origin + 3 * l, at)) val[512 * l + at] = val[512 * l + at] + step;
+}
+
+// ---- "liquid surface, flows": the arithmetic is sdf_flow_def.h's; here the 26 neighbour leaves and the (8 + 2H)^3 tile -------------
+// one pass of a median (width W), Laplacian or mean-curvature flow: src -> dst (512 per leaf, the list's order); `off` is added to
+// the active voxels' results
+void flow_pass(const fluid_sdf_grid_t* g, int kind, int W, float dx, float off, const float* src, float* dst)
+{
+    const int lo = -(g->n / 2), hi = lo + g->n - 1;
+    const float bg = g->background;
+    const fdef::Consts k = fdef::consts(dx);
+    const int H = kind == FLUID_SDF_FILTER_MEDIAN ? W : 1, S = LEAF + 2 * H;
+    std::vector<float> tile((size_t)S * S * S);
+    for (long l = 0; l < g->n_leaves; ++l) {
+        const int32_t* o = g->origin + 3 * (size_t)l;
+        const float* nb[27];   // the leaves around this one ((dx + 1) * 9 + (dy + 1) * 3 + dz + 1), nullptr where unlisted
+        for (int d = 0; d < 27; ++d) {
+            const long q = d == 13 ? l : find_leaf(g, Org{o[0] + (d / 9 - 1) * LEAF, o[1] + (d / 3 % 3 - 1) * LEAF, o[2] + (d % 3 - 1) * LEAF});
+            nb[d] = q >= 0 ? src + 512 * (size_t)q : nullptr;
+        }
+        // the tile: voxel o + (X - H, Y - H, Z - H) at (X * S + Y) * S + Z; +bg outside the grid and in unlisted leaves
+        for (int X = 0; X < S; ++X)
+            for (int Y = 0; Y < S; ++Y)
+                for (int Z = 0; Z < S; ++Z) {
+                    const int r[3] = {X - H, Y - H, Z - H};
+                    int d = 0, at = 0;
+                    bool in = true;
+                    for (int a = 0; a < 3; ++a) {
+                        const int side = r[a] < 0 ? -1 : r[a] >= LEAF ? 1 : 0, c = o[a] + r[a];
+                        in = in && c >= lo && c <= hi;
+                        d = d * 3 + side + 1;
+                        at = at * 8 + (r[a] - side * LEAF);
+                    }
+                    tile[((size_t)X * S + Y) * S + Z] = in && nb[d] ? nb[d][at] : bg;
+                }
+        const float* v = src + 512 * (size_t)l;
+        float* out = dst + 512 * (size_t)l;
+        for (int at = 0; at < 512; ++at) {
+            out[at] = v[at];
+            if (!is_active(g->active, (size_t)l, at) || !in_grid(g, o, at)) continue;
+            const int x = at >> 6, y = (at >> 3) & 7, z = at & 7;
+            auto T = [&](int i, int j, int m) { return tile[((size_t)(x + H + i) * S + (y + H + j)) * S + (z + H + m)]; };
+            float r;
+            if (kind == FLUID_SDF_FILTER_MEDIAN) {
+                uint32_t keys[fdef::median_count(2)];
+                int m = 0;
+                for (int i = -W; i <= W; ++i)
+                    for (int j = -W; j <= W; ++j)
+                        for (int q = -W; q <= W; ++q) {
+                            const float f = T(i, j, q);
+                            uint32_t bits;
+                            memcpy(&bits, &f, 4);
+                            keys[m++] = fdef::median_key(bits);
+                        }
+                const uint32_t bits = fdef::median_bits(fdef::median_select(m, (m - 1) >> 1, [&](int i) { return keys[i]; }));
+                memcpy(&r, &bits, 4);
+            } else if (kind == FLUID_SDF_FILTER_LAPLACIAN) {
+                r = fdef::laplacian_value(v[at], T(-1, 0, 0), T(1, 0, 0), T(0, -1, 0), T(0, 1, 0), T(0, 0, -1), T(0, 0, 1), k.invdx2, k.dt_lap);
+            } else {
+                const fdef::Edges e{T(1, 1, 0), T(1, -1, 0), T(-1, -1, 0), T(-1, 1, 0), T(1, 0, 1), T(1, 0, -1), T(-1, 0, -1), T(-1, 0, 1),
+                                    T(0, 1, 1), T(0, 1, -1), T(0, -1, -1), T(0, -1, 1)};
+                r = fdef::curvature_value(v[at], T(-1, 0, 0), T(1, 0, 0), T(0, -1, 0), T(0, 1, 0), T(0, 0, -1), T(0, 0, 1), e, k.invdx2, k.dt_curv);
+            }
+            if (off != 0.0f) r = r + off;
+            out[at] = r;
+        }
+    }
 }
 
 // ---- "liquid surface, renormalised": the arithmetic is sdf_track_def.h's; here the neighbours, the masks and the list ----------
@@ -317,18 +388,22 @@ void trim_pass_attr(const fluid_sdf_grid_t* g, Band& b)
             }
 }
 
-// The tracked filter on a band (the schedule: sdf_filter_plan.h): a track is the dilation when growing, N normalisation passes and
-// the trim.  True when a trim ran, which is when leaves can have left the list.
-bool run_tracked(const fluid_sdf_grid_t* g, Band& b, const fluid_sdf_filter_t* f, int N, bool trim, bool grow)
+// The filter of `kind` on a band (the schedule: sdf_filter_plan.h), tracked or not: a track is the dilation when growing, N
+// normalisation passes and the trim.  True when a trim ran, which is when leaves can have left the list.
+bool run_band(const fluid_sdf_grid_t* g, Band& b, int kind, const fluid_sdf_filter_t* f, bool tracked, int N, bool trim, bool grow)
 {
     fluid_sdf_grid_t cur = *g;   // the band as it is now: dilate() keeps it pointing into b
     cur.origin = b.org.data(), cur.active = b.mask.data(), cur.values = nullptr;
-    const float dx = list_dx(g);
+    const float dx = tracked || plan::kind_needs_dx(kind) ? list_dx(g) : 0.0f;
     bool trimmed = false;
     plan::run(
-        *f, dx, true,
+        kind, *f, dx, tracked,
         [&](int axis, int W, float off) {
             box_pass(&cur, axis, W, off, b.val[b.at].data(), b.val[1 - b.at].data());
+            b.at = 1 - b.at;
+        },
+        [&](int kd, int W, float off) {
+            flow_pass(&cur, kd, W, dx, off, b.val[b.at].data(), b.val[1 - b.at].data());
             b.at = 1 - b.at;
         },
         [&](float step) { add_active(&cur, step, b.val[b.at].data()); },
@@ -378,19 +453,19 @@ int fluid_sdf_filter(const fluid_sdf_grid_t* g, const fluid_sdf_filter_t* f, flo
     const size_t count = 512 * (size_t)g->n_leaves;
     if (count == 0) return FLUID_OK;
     if (!values || overlap({{g->values, 2048}}, (size_t)g->n_leaves, {{values, 2048}}, (size_t)g->n_leaves)) return FLUID_ERR_ARG;
-    const int passes = 3 * f->iterations;
+    const int passes = plan::passes(FLUID_SDF_FILTER_BOX, *f);
     if (passes == 0) memcpy(values, g->values, count * sizeof(float));
     std::vector<float> scratch(passes ? count : 0);
     const float* src = g->values;
     int k = 0;
     plan::run(
-        *f, 0.0f, false,
+        FLUID_SDF_FILTER_BOX, *f, 0.0f, false,
         [&](int axis, int W, float off) {
             float* dst = ((passes - 1 - k++) & 1) ? scratch.data() : values;   // the last pass writes `values`
             box_pass(g, axis, W, off, src, dst);
             src = dst;
         },
-        [&](float off) { add_active(g, off, values); }, [] {});
+        [](int, int, float) {}, [&](float off) { add_active(g, off, values); }, [] {});
     return FLUID_OK;
 }
 
@@ -410,7 +485,7 @@ int64_t fluid_sdf_filter_tracked(const fluid_sdf_grid_t* g, const fluid_sdf_filt
     if (!tracked && count_only) return g->n_leaves;
     Band b(g, nullptr);
     bool trimmed = false;
-    if (tracked) trimmed = run_tracked(g, b, f, t->normalize, t->trim != 0, false);
+    if (tracked) trimmed = run_band(g, b, FLUID_SDF_FILTER_BOX, f, true, t->normalize, t->trim != 0, false);
     else if (fluid_sdf_filter(g, f, b.val[0].data()) != FLUID_OK) return -FLUID_ERR_ARG;
     return copy_out(g, b, trimmed, cap_leaves, origin, values, active, kept, nullptr, nullptr);
 }
@@ -432,7 +507,34 @@ int64_t fluid_sdf_filter_grown(const fluid_sdf_grid_t* g, const fluid_sdf_attr_t
     }
     if (nl == 0) return 0;
     Band b(g, attr);
-    const bool trimmed = run_tracked(g, b, f, t->normalize, true, true);
+    const bool trimmed = run_band(g, b, FLUID_SDF_FILTER_BOX, f, true, t->normalize, true, true);
+    return copy_out(g, b, trimmed, cap_leaves, origin, values, active, nullptr, id, velocity);
+}
+
+int64_t fluid_sdf_flow(const fluid_sdf_grid_t* g, const fluid_sdf_attr_t* attr, int32_t kind, const fluid_sdf_filter_t* f, const fluid_sdf_track_t* t,
+                       int32_t grow, int64_t cap_leaves, int32_t* origin, float* values, uint64_t* active, uint32_t* id, float* velocity)
+{
+    // everything that can be refused first; the result is made in a band of our own and copied last
+    if (check_list(g) != FLUID_OK || !plan::filter_ok(f) || !plan::kind_ok(kind) || !plan::width_ok(kind, f->width)) return -FLUID_ERR_ARG;
+    if (!plan::track_ok(t) || (grow != 0 && grow != 1) || (grow && !plan::grow_ok(t))) return -FLUID_ERR_ARG;
+    const bool tracked = grow || plan::tracking(t);
+    if ((tracked || plan::kind_needs_dx(kind)) && !band_ok(g)) return -FLUID_ERR_ARG;
+    if (grow ? !plan::grown_offset_ok((float)f->offset, list_dx(g)) : tracked && !plan::tracked_offset_ok((float)f->offset, g->background))
+        return -FLUID_ERR_ARG;
+    const size_t nl = (size_t)g->n_leaves;
+    if (attr && (attr->n_leaves != g->n_leaves || (nl > 0 && (!attr->id || !attr->velocity)))) return -FLUID_ERR_ARG;
+    const bool count_only = !origin && !values && !active && !id && !velocity;
+    if (!count_only) {
+        if (!origin || !values || !active || cap_leaves < 0) return -FLUID_ERR_ARG;
+        if (attr ? (!id || !velocity) : (id || velocity)) return -FLUID_ERR_ARG;
+        if (overlap({{g->origin, 12}, {g->values, 2048}, {g->active, 64}, {attr ? attr->id : nullptr, 2048}, {attr ? attr->velocity : nullptr, 6144}}, nl,
+                    {{origin, 12}, {values, 2048}, {active, 64}, {id, 2048}, {velocity, 6144}}, (size_t)cap_leaves))
+            return -FLUID_ERR_ARG;
+    }
+    if (nl == 0) return 0;
+    if (!tracked && count_only) return g->n_leaves;
+    Band b(g, attr);
+    const bool trimmed = run_band(g, b, kind, f, tracked, tracked ? t->normalize : 0, tracked && t->trim != 0, grow != 0);
     return copy_out(g, b, trimmed, cap_leaves, origin, values, active, nullptr, id, velocity);
 }
 

@@ -312,6 +312,7 @@ struct SdfFront {
     int track_n;          // "liquid surface, renormalised": the handle's setting, copied by sdf_begin when a filter is given:
     bool track_trim;      // passes per track and the trim; 0 / false: the filter runs untracked
     bool grow;            // "liquid surface, grown band": every track begins with a dilation, and the range is dilate + T cells
+    int kind;             // "liquid surface, flows": the handle's FLUID_SDF_FILTER_* setting, copied by sdf_begin (width rule checked there)
     const fluid_sdf_filter_t* filt;   // nullptr: unfiltered.  Set by sdf_begin from its argument (limits checked there)
     int dilate;           // cells the base-cell box is dilated by for the range: 4; 5 for a filtered mesh (set by the caller after sdf_begin); with grow sdf_front adds T
     bool attr;            // "liquid surface, attributes": the search also keeps the closest particle (set by the caller after sdf_begin)

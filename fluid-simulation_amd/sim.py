@@ -267,6 +267,43 @@ def sdf_filter_grown(grid, filt, track, attr=None):
     return out if attr is None else (out, SdfAttr(ids, vel))
 
 
+SDF_FILTER_KINDS = {"box": 0, "median": 1, "laplacian": 2, "curvature": 3}   # FLUID_SDF_FILTER_*
+
+
+def _sdf_kind_of(kind):
+    """FLUID_SDF_FILTER_* of a name of SDF_FILTER_KINDS; an integer is passed on as it is (the library checks it)."""
+    return SDF_FILTER_KINDS[kind] if isinstance(kind, str) else int(kind)
+
+
+def sdf_flow(grid, kind, filt, track=None, grow=False, attr=None):
+    """The filter of `kind` ("box", "median", "laplacian", "curvature", or a FLUID_SDF_FILTER_* number) of an SdfGrid
+    (fluid_sdf_flow: host only; include/fluid_hip.h, "liquid surface, flows").  filt = (width, iterations[, offset]): a median
+    takes width 1 or 2, a Laplacian or mean-curvature flow width 1.  track = None (untracked), normalize or (normalize, trim);
+    grow=True: every track begins with a dilation of the band.  Returns the new SdfGrid, or with attr (an SdfAttr of `grid`'s
+    leaves) the pair (SdfGrid, SdfAttr).  A decomposed run filters the merged list."""
+    c, _keep = grid._c()
+    f, t = _sdf_filter_of(filt), _sdf_track_of(track)
+    pt = None if t is None else C.byref(t)
+    pa = None
+    if attr is not None:
+        ac = attr._c()
+        pa = C.byref(ac)
+    kd = _sdf_kind_of(kind)
+    k = lib.fluid_sdf_flow(C.byref(c), pa, kd, C.byref(f), pt, int(grow), 0, None, None, None, None, None)
+    if k < 0:
+        raise FluidError(-k, "fluid_sdf_flow: a bad leaf list or attributes, kind, filter (median: width 1..2; laplacian, curvature: "
+                             "width 1; iterations 0..16) or track (the offset's limit is that of the form that runs)")
+    org, val, words = np.empty((k, 3), np.int32), np.empty((k, 512), np.float32), np.zeros((k, 8), np.uint64)
+    ids = np.empty((k, 512), np.uint32) if attr is not None else None
+    vel = np.empty((k, 3, 512), np.float32) if attr is not None else None
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)   # noqa: E731
+    if k and lib.fluid_sdf_flow(C.byref(c), pa, kd, C.byref(f), pt, int(grow), k, p(org), p(val), p(words), p(ids), p(vel)) != k:
+        raise FluidError(1, "fluid_sdf_flow: the second call disagrees with the count")
+    act = np.unpackbits(words.view(np.uint8), axis=1, bitorder="little").astype(bool).reshape(k, 512)
+    out = SdfGrid(grid.n, org, val, act, grid.background, grid.radius, grid.half_width)
+    return out if attr is None else (out, SdfAttr(ids, vel))
+
+
 class Mesh:
     """fluid_mesh_t on the host: the surface nets of the level set (include/fluid_hip.h, "liquid surface as a mesh").  vertices
     (nv, 3) float32 in index space, quads (nq, 4) uint32 vertex numbers, counter-clockwise seen from outside the liquid."""
@@ -789,6 +826,12 @@ class FluidSim:
         t = None if normalize is None else SdfTrack(int(normalize), int(bool(trim)), 0)
         check(lib.fluid_sdf_set_track(self._h, None if t is None else C.byref(t)))
         check(lib.fluid_sdf_set_track_grow(self._h, int(grow)))
+
+    def sdf_set_filter_kind(self, kind):
+        """A setting of the handle: every later snapshot given smooth= runs the passes of `kind` ("box", the default; "median",
+        "laplacian", "curvature"; or a FLUID_SDF_FILTER_* number) in place of the box passes (include/fluid_hip.h, "liquid
+        surface, flows").  The width the kind admits is checked by the next filtered snapshot."""
+        check(lib.fluid_sdf_set_filter_kind(self._h, _sdf_kind_of(kind)))
 
     def sdf_wait(self):
         """The oldest level-set snapshot not yet waited for, as an SdfGrid (copied out of the handle's pinned buffer)."""

@@ -812,6 +812,82 @@ int64_t fluid_sdf_filter_grown(const fluid_sdf_grid_t* g, const struct fluid_sdf
                                const fluid_sdf_track_t* t, int64_t cap_leaves, int32_t* origin, float* values, uint64_t* active,
                                uint32_t* id /* NULL iff attr NULL */, float* velocity /* likewise */);
 
+/* ---- liquid surface, flows: median, Laplacian and mean-curvature flow of the level set --------------------------------------------
+ * The three other filters of the library's LevelSetFilter.  The box filter blurs: it rounds off thin sheets as fast as it removes
+ * the one-particle bumps of the sphere union.  median(width) removes the bumps and keeps edges, meanCurvature() is the standard
+ * fairing step before meshing, and laplacian() is its cheap equivalent once the field is renormalised (the library says so itself,
+ * tools/LevelSetFilter.h:411-417).  Restated from the library's arithmetic (tools/LevelSetFilter.h:256-268, 318-347, 380-409,
+ * 421-450, 481-507; math/Stencils.h:147-155, 1230-1238, 1283-1288, 1506-1540, 1596-1619, 1670-1680; math/Math.h:119) as an exact,
+ * order-free definition of its own: the kernels (kernels_sdf_flow.hip), fluid_sdf_flow below and the tests' numpy form give the
+ * same bytes; the arithmetic is stated once for both compilers in csrc/sdf_flow_def.h.
+ *
+ * Common rules.  Input val, act as in "liquid surface, smoothed": unlisted leaves and everything outside the grid read as +bg,
+ * inactive voxels as their stored +-bg.  Each pass is Jacobi (it reads only the complete result of the pass before).  Only ACTIVE
+ * voxels get a new value; topology does not change, inactive voxels keep their value, attributes are untouched.
+ * dx = (float)params.dx.  No FMA anywhere; IEEE division and square root, float and double.  Neighbours: xm = val(c - e_x),
+ * xp = val(c + e_x), likewise y and z; v(i,j,k) = val(c + (i,j,k)); p = val(c).
+ * Shared constants: inv2dx = (float)(0.5 / (double)dx);  invdx2 = (float)(4.0 * (double)inv2dx * (double)inv2dx).
+ *
+ * Laplacian (GradStencil).  All float.  dt = (dx * dx) / 6.0f;
+ *   L = invdx2 * ((((((xm + xp) + ym) + yp) + zm) + zp) - 6.0f * p);   val_new = p + dt * L.
+ *
+ * Mean curvature (CurvatureStencil::meanCurvatureNormGrad).  Differences are taken in FLOAT and then widened; everything after
+ * that is DOUBLE (the library's Real), and the term is narrowed once.  dt = (dx * dx) / 3.0f;
+ *   Dx = 0.5 * (double)(xp - xm), Dy, Dz likewise;  Dx2 = Dx * Dx, Dy2, Dz2 likewise;  ng = (Dx2 + Dy2) + Dz2.
+ *   ng <= 1e-15 (math::Tolerance<double>):  F = 0.0f.  Otherwise:
+ *   Dxx = (double)((xp - 2.0f * p) + xm), Dyy, Dzz likewise;
+ *   Dxy = 0.25 * (double)(((v(1,1,0) - v(1,-1,0)) + v(-1,-1,0)) - v(-1,1,0));
+ *   Dxz = 0.25 * (double)(((v(1,0,1) - v(1,0,-1)) + v(-1,0,-1)) - v(-1,0,1));
+ *   Dyz = 0.25 * (double)(((v(0,1,1) - v(0,1,-1)) + v(0,-1,-1)) - v(0,-1,1));
+ *   alpha = ((Dx2*(Dyy+Dzz) + Dy2*(Dxx+Dzz)) + Dz2*(Dxx+Dyy)) - 2.0*((Dx*((Dy*Dxy) + (Dz*Dxz))) + ((Dy*Dz)*Dyz));
+ *   beta = sqrt(ng);   F = (float)((alpha * (double)invdx2) / (2.0 * (beta * beta)));
+ *   val_new = p + dt * F in float.
+ * 19 points: the centre, the six faces and the twelve edges; no corners.
+ *
+ * Median (DenseStencil, width W).  Take the m = (2W+1)^3 values of the cube around c; val_new is the element at zero-based rank
+ * (m - 1) >> 1 in the order of the usual monotone 32-bit key: all bits of a negative float flipped, the sign bit of the others
+ * set.  Under it -0 sorts before +0 and equal keys are equal bytes, so the result is a function of the multiset alone and any
+ * selection method gives the same bytes.  Where this differs from the source: the library selects with std::nth_element under
+ * operator<, for which -0 and +0 are equivalent, so which of the two zeros it returns at the median rank is its implementation's
+ * choice; the key order decides it.  Values are always finite — the rasteriser's values lie in [-bg, bg], a box, Laplacian or
+ * curvature pass and the track's step are finite arithmetic on at most 16 iterations of bounded growth, an offset is finite, and
+ * the median returns one of its inputs — so no NaN ever reaches the key, whose order is total on everything else.
+ *
+ * Schedule.  One iteration of these three kinds is ONE pass (the box filter has three).  With tracking on each pass is followed by
+ * one track, as the library does (LevelSetFilter.h:256-268, 318-347), grown if growing is on.  After the iterations the offset,
+ * exactly as for the box filter: stepped under tracking, a single val + off otherwise.  T, the number of tracks, stays iterations
+ * + offset steps.  A flow changes only active voxels, so the range argument for the mesh and the image is unchanged: the
+ * particles' box dilated by 5, or by 5 + T when grown.
+ * Limits.  Median: width 1 or 2 (the 27- and 125-value cubes; the library's default is 1, and its own comment calls the filter
+ * "simple but slow").  Laplacian and mean curvature: width must be 1.  Iterations 0..16; the offset rules stay as they are.
+ *
+ * What this is not.  HJWENO5, the alpha masks of the library's filters and Filter::fill are not built.  Parity of the results
+ * with the library's own output is unpinned: the definitions are restated from its source. */
+#define FLUID_SDF_FILTER_BOX 0
+#define FLUID_SDF_FILTER_MEDIAN 1
+#define FLUID_SDF_FILTER_LAPLACIAN 2
+#define FLUID_SDF_FILTER_MEAN_CURVATURE 3
+/* A setting of the handle beside fluid_sdf_set_track and fluid_sdf_set_track_grow, and independent of them in order: every later
+ * snapshot that is given a filter — fluid_sdf_snapshot_filtered, fluid_sdf_snapshot_attr, fluid_mesh_snapshot_filtered,
+ * fluid_mesh_snapshot_attr, fluid_mesh_snapshot_ex and fluid_render_snapshot — runs the passes of that kind in place of the box
+ * passes.  The default is FLUID_SDF_FILTER_BOX, with which every byte of every entry point is what it was.  The width rule of the
+ * kind is checked where a filtered snapshot begins: FLUID_ERR_ARG from that snapshot.  One launch per pass; no scratch beyond the
+ * second value buffer of the filtered snapshots.  FLUID_ERR_ARG: an unknown kind.  FLUID_ERR_STATE on a decomposed handle: filter
+ * the merged list (fluid_sdf_flow). */
+int fluid_sdf_set_filter_kind(fluid_sim_t* s, int32_t kind);
+/* Host only: the filter of `kind` applied to a leaf list, how a block run gets the flows after fluid_sdf_grids_merge /
+ * fluid_sdf_attr_grids_merge.  t == NULL (and N = 0 with trim = 0): untracked, every leaf stays; t with grow = 0: the tracked
+ * filter; grow = 1: the grown filter.  Outputs, the count-only call, dx from background / half_width, the voxels of listed leaves
+ * outside the grid and the refusals follow fluid_sdf_filter_grown (the offset limit of the form that runs: none untracked, the
+ * background tracked, 4 dx grown; a background and a half width are required where dx is read: tracked, or a Laplacian or
+ * curvature pass), and beside them: an unknown kind, a width the kind does not admit, grow neither 0 nor 1.  With
+ * kind = FLUID_SDF_FILTER_BOX it returns the bytes of fluid_sdf_filter, fluid_sdf_filter_tracked or fluid_sdf_filter_grown for
+ * the same arguments.  Works leaf by leaf, the 26 neighbours found by bisection; no dense grid is made. */
+int64_t fluid_sdf_flow(const fluid_sdf_grid_t* g, const struct fluid_sdf_attr* attr /* may be NULL */, int32_t kind,
+                       const fluid_sdf_filter_t* f, const fluid_sdf_track_t* t /* NULL: untracked */, int32_t grow, int64_t cap_leaves,
+                       int32_t* origin, float* values, uint64_t* active, uint32_t* id /* NULL iff attr NULL */,
+                       float* velocity /* likewise */);
+
 /* ---- liquid surface as a mesh: surface nets of the level set ----------------------------------------------------------------
  * Polygons for everyone who is no volume renderer.  The reference names tools/VolumeToMesh.h, whose output depends on the library's
  * tree traversal; like the level set itself the mesh gets an exact, order-free definition of its own — naive surface nets on the
