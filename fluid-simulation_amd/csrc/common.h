@@ -365,6 +365,9 @@ void launch_sdf_offset(hipStream_t st, const SdfGeom& g, float off, const int* f
 // is flagged and holds anything but inactive +bg
 void launch_sdf_track(hipStream_t st, const SdfGeom& g, bool norm, bool trim, const int* flags, uint64_t* tm, const float* src, float* dst,
                       uint32_t* tid, float* tvel);
+// kernels_sdf_weno.hip: one normalisation pass of the HJWENO5 scheme src -> dst, with the same trim on the last pass
+void launch_sdf_track_weno(hipStream_t st, const SdfGeom& g, bool trim, const int* flags, uint64_t* tm, const float* src, float* dst, uint32_t* tid,
+                           float* tvel);
 void launch_sdf_relist(hipStream_t st, const SdfGeom& g, const int* flags, const uint64_t* tm, const float* tv, int* list);
 // band dilation of that level set (kernels_sdf_grow.hip): reads flags / tm, writes flags2 / tm2 for every leaf of the range (the
 // caller swaps the pairs); a leaf that becomes flagged gets +bg in val and, with tid / tvel non-NULL, NO_ID and +0; with them a

@@ -91,6 +91,10 @@
 // "liquid surface, grown band"; N >= 1 and TRIM = 1 are required, and |OFFSET| of FLUID_OUT_SMOOTH may reach 4 voxels): one GPU
 // through fluid_sdf_set_track_grow, a block run through fluid_sdf_filter_grown after the merge, which returns the attributes in
 // full — so FLUID_BLOCKS_MESH_VEL is accepted with GROW = 1.
+//   FLUID_OUT_TRACK_SCHEME=first|hjweno5 (default first; with FLUID_OUT_TRACK only) — the spatial scheme of the normalisation passes:
+// first-order upwind, or HJWENO5, the library's own default (include/fluid_hip.h, "liquid surface, renormalised: HJWENO5").  One GPU
+// through fluid_sdf_set_track, a block run through the scheme field of the track its host function is given.  Refused with another
+// word or without FLUID_OUT_TRACK, before any handle is created.
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -896,8 +900,21 @@ int main(int, char**)
             std::cerr << "FLUID_OUT_TRACK cannot be combined with FLUID_BLOCKS_MESH_VEL: the trim can shorten the merged list and the block driver does not gather the attributes (GROW = 1 returns them in full)" << std::endl;
             return 1;
         }
-        bc.track = true, bc.tk = tk, bc.grow = track_grow;
     }
+    const char* scenv = getenv("FLUID_OUT_TRACK_SCHEME");
+    if (scenv && *scenv) {
+        const std::string word = scenv;
+        if (!track) {
+            std::cerr << "FLUID_OUT_TRACK_SCHEME names the scheme FLUID_OUT_TRACK runs: FLUID_OUT_TRACK is not set" << std::endl;
+            return 1;
+        }
+        if (word != "first" && word != "hjweno5") {
+            std::cerr << "FLUID_OUT_TRACK_SCHEME must be first or hjweno5" << std::endl;
+            return 1;
+        }
+        tk.scheme = word == "hjweno5" ? FLUID_SDF_TRACK_HJWENO5 : FLUID_SDF_TRACK_FIRST_BIAS;
+    }
+    if (track) bc.track = true, bc.tk = tk, bc.grow = track_grow;
     if (blocks && *blocks) {
         char tail = 0;
         if (sscanf(blocks, "%dx%dx%d%c", &bc.dims[0], &bc.dims[1], &bc.dims[2], &tail) != 3 || bc.dims[0] < 1 || bc.dims[1] < 1 || bc.dims[2] < 1 ||

@@ -247,6 +247,7 @@ int fl::sdf_begin(fluid_sim* s, const fluid_sdf_params_t* p, SdfFront* f, const 
     f->tv = nullptr, f->flags = nullptr, f->list = nullptr;
     const fluid_sdf_track_t* t = filt ? &s->sdf->track : nullptr;   // the argument rules: sdf_filter_plan.h
     f->track_n = t ? t->normalize : 0, f->track_trim = t && t->trim != 0;
+    f->track_scheme = t ? t->scheme : FLUID_SDF_TRACK_FIRST_BIAS;
     f->grow = filt && s->sdf->track_grow;
     f->kind = filt ? s->sdf->kind : FLUID_SDF_FILTER_BOX;
     if (filt && !plan::width_ok(f->kind, filt->width))
@@ -329,7 +330,9 @@ int fl::sdf_front(fluid_sim* s, SdfFront* f)
                     }
                     for (int i = 0; i < f->track_n; ++i) {
                         const bool last = i == f->track_n - 1;
-                        launch_sdf_track(s->st, g, true, last && f->track_trim, flags, tm, src, dst, f->attr ? o->tid : nullptr, o->tvel);
+                        uint32_t* tid = f->attr ? o->tid : nullptr;
+                        if (f->track_scheme == FLUID_SDF_TRACK_HJWENO5) launch_sdf_track_weno(s->st, g, last && f->track_trim, flags, tm, src, dst, tid, o->tvel);
+                        else launch_sdf_track(s->st, g, true, last && f->track_trim, flags, tm, src, dst, tid, o->tvel);
                         std::swap(src, dst);
                     }
                     if (f->track_n == 0) launch_sdf_track(s->st, g, false, true, flags, tm, src, src, f->attr ? o->tid : nullptr, o->tvel);
@@ -479,7 +482,7 @@ int fluid_sdf_set_track(fluid_sim_t* s, const fluid_sdf_track_t* t)
 {
     if (int rc = snap_guard(s, SDF_TRACK_SINGLE)) return rc;
     if (!plan::track_ok(t))
-        return fail(FLUID_ERR_ARG, "level-set tracking: normalize in 0..8, trim 0 or 1 and scheme FLUID_SDF_TRACK_FIRST_BIAS are required");
+        return fail(FLUID_ERR_ARG, "level-set tracking: normalize in 0..8, trim 0 or 1 and scheme FLUID_SDF_TRACK_FIRST_BIAS or FLUID_SDF_TRACK_HJWENO5 are required");
     HIPCHK(hipSetDevice(s->prm.device));
     if (int rc = sdf_init(s)) return rc;
     s->sdf->track = t ? *t : fluid_sdf_track_t{0, 0, FLUID_SDF_TRACK_FIRST_BIAS};

@@ -6,7 +6,8 @@
 // the passes alternate between the caller's array and one scratch array of the same size, so that the last one writes the caller's.
 // fluid_sdf_filter_tracked ("liquid surface, renormalised") is the same for the tracked filter: the box passes above, a
 // normalisation pass that finds the six face neighbours by bisection (the per-voxel arithmetic is sdf_track_def.h's, shared with
-// kernels_sdf_track.hip), the trim on masks of its own, and the list compacted to the leaves that still hold something.
+// kernels_sdf_track.hip, or under FLUID_SDF_TRACK_HJWENO5 sdf_weno_def.h's, shared with kernels_sdf_weno.hip, the same six
+// neighbours read three planes deep), the trim on masks of its own, and the list compacted to the leaves that still hold something.
 // fluid_sdf_filter_grown ("liquid surface, grown band") is the tracked filter whose every track begins with a dilation of the
 // masks (the word arithmetic is sdf_grow_def.h's, shared with kernels_sdf_grow.hip): the list is a working copy that the dilation
 // lengthens by the unlisted face neighbours it activates voxels in, and the attributes travel with it.
@@ -28,6 +29,7 @@
 #include "sdf_filter_plan.h"
 #include "sdf_flow_def.h"
 #include "sdf_grow_def.h"
+#include "sdf_weno_def.h"
 
 namespace {
 
@@ -203,6 +205,46 @@ void norm_pass(const fluid_sdf_grid_t* g, float dx, const float* src, float* dst
                     n6[a][side] = x;
                 }
             out[at] = tdef::track_value(v[at], n6[0][0], n6[0][1], n6[1][0], n6[1][1], n6[2][0], n6[2][1], dt, inv);
+        }
+    }
+}
+
+// ---- "liquid surface, renormalised: HJWENO5": the arithmetic is sdf_weno_def.h's; the same neighbours, read three planes deep ----
+void norm_pass_weno(const fluid_sdf_grid_t* g, float dx, const float* src, float* dst)
+{
+    const int lo = -(g->n / 2), hi = lo + g->n - 1;
+    const float bg = g->background, dt = dx * 0.3f, inv = 1.0f / dx;
+    static const int stride[3] = {64, 8, 1};
+    for (long l = 0; l < g->n_leaves; ++l) {
+        const int32_t* o = g->origin + 3 * (size_t)l;
+        const float* nb[3][2];   // the face neighbours' values, nullptr where unlisted
+        for (int a = 0; a < 3; ++a)
+            for (int side = 0; side < 2; ++side) {
+                Org q{o[0], o[1], o[2]};
+                (a == 0 ? q.x : a == 1 ? q.y : q.z) += side ? LEAF : -LEAF;
+                const long k = find_leaf(g, q);
+                nb[a][side] = k >= 0 ? src + 512 * (size_t)k : nullptr;
+            }
+        const float* v = src + 512 * (size_t)l;
+        const uint64_t* mask = g->active + 8 * (size_t)l;
+        float* out = dst + 512 * (size_t)l;
+        for (int at = 0; at < 512; ++at) {
+            out[at] = v[at];
+            if (!((mask[at >> 6] >> (at & 63)) & 1ull) || !in_grid(g, o, at)) continue;
+            const int c[3] = {at >> 6, (at >> 3) & 7, at & 7};
+            float u[3][7];
+            for (int a = 0; a < 3; ++a)
+                for (int d = -3; d <= 3; ++d) {
+                    const int k = c[a] + d, ca = o[a] + k;
+                    float x = bg;
+                    if (ca >= lo && ca <= hi) {
+                        if (k < 0) x = nb[a][0] ? nb[a][0][at + (d + LEAF) * stride[a]] : bg;
+                        else if (k >= LEAF) x = nb[a][1] ? nb[a][1][at + (d - LEAF) * stride[a]] : bg;
+                        else x = v[at + d * stride[a]];
+                    }
+                    u[a][d + 3] = x;
+                }
+            out[at] = wdef::track_value_weno(u[0], u[1], u[2], dt, inv);
         }
     }
 }
@@ -390,7 +432,7 @@ void trim_pass_attr(const fluid_sdf_grid_t* g, Band& b)
 
 // The filter of `kind` on a band (the schedule: sdf_filter_plan.h), tracked or not: a track is the dilation when growing, N
 // normalisation passes and the trim.  True when a trim ran, which is when leaves can have left the list.
-bool run_band(const fluid_sdf_grid_t* g, Band& b, int kind, const fluid_sdf_filter_t* f, bool tracked, int N, bool trim, bool grow)
+bool run_band(const fluid_sdf_grid_t* g, Band& b, int kind, const fluid_sdf_filter_t* f, bool tracked, int N, bool trim, bool grow, int scheme)
 {
     fluid_sdf_grid_t cur = *g;   // the band as it is now: dilate() keeps it pointing into b
     cur.origin = b.org.data(), cur.active = b.mask.data(), cur.values = nullptr;
@@ -410,7 +452,8 @@ bool run_band(const fluid_sdf_grid_t* g, Band& b, int kind, const fluid_sdf_filt
         [&]() {
             if (grow) dilate(&cur, b);
             for (int i = 0; i < N; ++i) {
-                norm_pass(&cur, dx, b.val[b.at].data(), b.val[1 - b.at].data());
+                if (scheme == FLUID_SDF_TRACK_HJWENO5) norm_pass_weno(&cur, dx, b.val[b.at].data(), b.val[1 - b.at].data());
+                else norm_pass(&cur, dx, b.val[b.at].data(), b.val[1 - b.at].data());
                 b.at = 1 - b.at;
             }
             if (trim) trim_pass_attr(&cur, b), trimmed = true;
@@ -485,7 +528,7 @@ int64_t fluid_sdf_filter_tracked(const fluid_sdf_grid_t* g, const fluid_sdf_filt
     if (!tracked && count_only) return g->n_leaves;
     Band b(g, nullptr);
     bool trimmed = false;
-    if (tracked) trimmed = run_band(g, b, FLUID_SDF_FILTER_BOX, f, true, t->normalize, t->trim != 0, false);
+    if (tracked) trimmed = run_band(g, b, FLUID_SDF_FILTER_BOX, f, true, t->normalize, t->trim != 0, false, t->scheme);
     else if (fluid_sdf_filter(g, f, b.val[0].data()) != FLUID_OK) return -FLUID_ERR_ARG;
     return copy_out(g, b, trimmed, cap_leaves, origin, values, active, kept, nullptr, nullptr);
 }
@@ -507,7 +550,7 @@ int64_t fluid_sdf_filter_grown(const fluid_sdf_grid_t* g, const fluid_sdf_attr_t
     }
     if (nl == 0) return 0;
     Band b(g, attr);
-    const bool trimmed = run_band(g, b, FLUID_SDF_FILTER_BOX, f, true, t->normalize, true, true);
+    const bool trimmed = run_band(g, b, FLUID_SDF_FILTER_BOX, f, true, t->normalize, true, true, t->scheme);
     return copy_out(g, b, trimmed, cap_leaves, origin, values, active, nullptr, id, velocity);
 }
 
@@ -534,7 +577,7 @@ int64_t fluid_sdf_flow(const fluid_sdf_grid_t* g, const fluid_sdf_attr_t* attr, 
     if (nl == 0) return 0;
     if (!tracked && count_only) return g->n_leaves;
     Band b(g, attr);
-    const bool trimmed = run_band(g, b, kind, f, tracked, tracked ? t->normalize : 0, tracked && t->trim != 0, grow != 0);
+    const bool trimmed = run_band(g, b, kind, f, tracked, tracked ? t->normalize : 0, tracked && t->trim != 0, grow != 0, tracked ? t->scheme : FLUID_SDF_TRACK_FIRST_BIAS);
     return copy_out(g, b, trimmed, cap_leaves, origin, values, active, nullptr, id, velocity);
 }
 

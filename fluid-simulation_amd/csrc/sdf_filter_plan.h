@@ -25,7 +25,8 @@ inline bool kind_needs_dx(int kind) { return kind == FLUID_SDF_FILTER_LAPLACIAN 
 // (a null track: tracking off)
 inline bool track_ok(const fluid_sdf_track_t* t)
 {
-    return !t || (t->normalize >= 0 && t->normalize <= tdef::MAX_PASSES && (t->trim == 0 || t->trim == 1) && t->scheme == FLUID_SDF_TRACK_FIRST_BIAS);
+    return !t || (t->normalize >= 0 && t->normalize <= tdef::MAX_PASSES && (t->trim == 0 || t->trim == 1) &&
+                  (t->scheme == FLUID_SDF_TRACK_FIRST_BIAS || t->scheme == FLUID_SDF_TRACK_HJWENO5));
 }
 inline bool tracking(const fluid_sdf_track_t* t) { return t && (t->normalize > 0 || t->trim != 0); }
 // growing the band: every track normalises and trims

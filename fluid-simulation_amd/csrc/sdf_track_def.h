@@ -30,6 +30,16 @@ TDEF float axis_term(bool out, float dm, float dp)
     return fmax2(A * A, B * B);
 }
 
+// The step from the three axis terms, whatever scheme formed them (sdf_weno_def.h forms them from seven values per axis)
+TDEF float track_step(float p, float tx, float ty, float tz, float dt, float inv)
+{
+    float G = tx;
+    G = G + ty;
+    G = G + tz;
+    const float S = p / (sqrtf(p * p + G) + TOL);
+    return p - (dt * S) * (sqrtf(G) * inv - 1.0f);
+}
+
 // One pass on an active voxel with value p and the six neighbours' values of the pass before; dt = dx * 0.3f, inv = 1.0f / dx.
 TDEF float track_value(float p, float xm, float xp, float ym, float yp, float zm, float zp, float dt, float inv)
 {
@@ -37,11 +47,7 @@ TDEF float track_value(float p, float xm, float xp, float ym, float yp, float zm
     const float tx = axis_term(out, p - xm, xp - p);
     const float ty = axis_term(out, p - ym, yp - p);
     const float tz = axis_term(out, p - zm, zp - p);
-    float G = tx;
-    G = G + ty;
-    G = G + tz;
-    const float S = p / (sqrtf(p * p + G) + TOL);
-    return p - (dt * S) * (sqrtf(G) * inv - 1.0f);
+    return track_step(p, tx, ty, tz, dt, inv);
 }
 
 // The trim class of an active voxel's value: -1 = it becomes inactive -bg, +1 = inactive +bg, 0 = it stays as it is

@@ -311,6 +311,7 @@ struct SdfFront {
     const int* list;      // the leaf is listed: flags, or after a tracked filter's trim the flags derived from what the trim left
     int track_n;          // "liquid surface, renormalised": the handle's setting, copied by sdf_begin when a filter is given:
     bool track_trim;      // passes per track and the trim; 0 / false: the filter runs untracked
+    int track_scheme;     // FLUID_SDF_TRACK_FIRST_BIAS or FLUID_SDF_TRACK_HJWENO5: which kernel a normalisation pass launches
     bool grow;            // "liquid surface, grown band": every track begins with a dilation, and the range is dilate + T cells
     int kind;             // "liquid surface, flows": the handle's FLUID_SDF_FILTER_* setting, copied by sdf_begin (width rule checked there)
     const fluid_sdf_filter_t* filt;   // nullptr: unfiltered.  Set by sdf_begin from its argument (limits checked there)

@@ -16,7 +16,7 @@ import threading
 import numpy as np
 
 from ._lib import lib, check, Params, StepStats, LeafGridC, SdfParams, SdfGridC, SdfAttrPartC, SdfTrack
-from .sim import FluidSim, source_methods, grid_bounds, merge_leaf_grids, _leaf_grid_copy, merge_sdf_grids, _sdf_grid_copy, merge_sdf_attr_grids, _sdf_attr_part_copy  # noqa: F401
+from .sim import _sdf_scheme_of, FluidSim, source_methods, grid_bounds, merge_leaf_grids, _leaf_grid_copy, merge_sdf_grids, _sdf_grid_copy, merge_sdf_attr_grids, _sdf_attr_part_copy  # noqa: F401
 
 EXCHANGE_T = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                          C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p)
@@ -416,12 +416,12 @@ class DistFluidSim(FluidSim):
         p = SdfParams(float(radius), float(half_width))
         check((lib.fluid_dist_sdf_snapshot_attr if attr else lib.fluid_dist_sdf_snapshot)(self._h, C.byref(p)))
 
-    def sdf_set_track(self, normalize, trim=True, grow=False):
+    def sdf_set_track(self, normalize, trim=True, grow=False, scheme="first"):
         """Refused: a decomposed handle takes no tracked snapshots; track the merged list (sdf_filter_tracked, or with grow
         sdf_filter_grown: the library's FLUID_ERR_STATE names it)."""
         if grow:
             check(lib.fluid_sdf_set_track_grow(self._h, int(grow)))   # FLUID_ERR_STATE
-        t = None if normalize is None else SdfTrack(int(normalize), int(bool(trim)), 0)
+        t = None if normalize is None else SdfTrack(int(normalize), int(bool(trim)), _sdf_scheme_of(scheme))
         check(lib.fluid_sdf_set_track(self._h, None if t is None else C.byref(t)))   # FLUID_ERR_STATE: the library names the host function
 
     def sdf_wait(self):

@@ -208,21 +208,35 @@ def sdf_filter(grid, width, iterations, offset=0.0):
     return SdfGrid(grid.n, grid.origin, val, grid.active, grid.background, grid.radius, grid.half_width)
 
 
+SDF_TRACK_SCHEMES = {"first": 0, "hjweno5": 4}   # FLUID_SDF_TRACK_FIRST_BIAS, FLUID_SDF_TRACK_HJWENO5: the library's own numbers
+
+
+def _sdf_scheme_of(scheme):
+    """The scheme's number: "first" (the default), "hjweno5", or a number passed on as it is (the library refuses what it lacks)."""
+    if isinstance(scheme, str):
+        if scheme not in SDF_TRACK_SCHEMES:
+            raise ValueError(f"scheme must be one of {sorted(SDF_TRACK_SCHEMES)} or a number")
+        return SDF_TRACK_SCHEMES[scheme]
+    return int(scheme)
+
+
 def _sdf_track_of(track):
-    """fluid_sdf_track_t of None (off), a pass count, or (normalize[, trim]); the trim defaults to on."""
+    """fluid_sdf_track_t of None (off), a pass count, or (normalize[, trim[, scheme]]); the trim defaults to on, the scheme to
+    "first"."""
     if track is None:
         return None
     if isinstance(track, (tuple, list)):
-        if len(track) not in (1, 2):
-            raise ValueError("track must be None, normalize or (normalize, trim)")
-        return SdfTrack(int(track[0]), int(bool(track[1])) if len(track) == 2 else 1, 0)
+        if len(track) not in (1, 2, 3):
+            raise ValueError("track must be None, normalize, (normalize, trim) or (normalize, trim, scheme)")
+        return SdfTrack(int(track[0]), int(bool(track[1])) if len(track) >= 2 else 1, _sdf_scheme_of(track[2]) if len(track) == 3 else 0)
     return SdfTrack(int(track), 1, 0)
 
 
 def sdf_filter_tracked(grid, filt, track):
     """(SdfGrid, kept): the tracked filter of an SdfGrid (fluid_sdf_filter_tracked: host only).  filt = (width, iterations[,
-    offset]); track = None, normalize or (normalize, trim): after every box iteration and every offset step the level set is
-    renormalised and trimmed (include/fluid_hip.h, "liquid surface, renormalised").  The trim can unlist leaves: kept[i] is the
+    offset]); track = None, normalize, (normalize, trim) or (normalize, trim, scheme): after every box iteration and every offset
+    step the level set is renormalised and trimmed (include/fluid_hip.h, "liquid surface, renormalised"), with scheme "first"
+    (the default) or "hjweno5" ("liquid surface, renormalised: HJWENO5").  The trim can unlist leaves: kept[i] is the
     index in `grid` of leaf i of the result.  A decomposed run tracks sdf_filter_tracked(merge_sdf_grids(parts), ...)."""
     c, _keep = grid._c()
     f, t = _sdf_filter_of(filt), _sdf_track_of(track)
@@ -243,8 +257,8 @@ def sdf_filter_tracked(grid, filt, track):
 def sdf_filter_grown(grid, filt, track, attr=None):
     """The grown filter of an SdfGrid (fluid_sdf_filter_grown: host only): the tracked filter whose every track begins with a
     dilation of the band (include/fluid_hip.h, "liquid surface, grown band").  filt = (width, iterations[, offset]), |offset| <=
-    4 dx; track = normalize (1..8) or (normalize, True).  Returns the new SdfGrid, which can list leaves `grid` does not, or with
-    attr (an SdfAttr of `grid`'s leaves) the pair (SdfGrid, SdfAttr).  A decomposed run grows the merged list."""
+    4 dx; track = normalize (1..8), (normalize, True) or (normalize, True, scheme).  Returns the new SdfGrid, which can list leaves
+    `grid` does not, or with attr (an SdfAttr of `grid`'s leaves) the pair (SdfGrid, SdfAttr).  A decomposed run grows the merged list."""
     c, _keep = grid._c()
     f, t = _sdf_filter_of(filt), _sdf_track_of(track)
     pt = None if t is None else C.byref(t)
@@ -278,7 +292,7 @@ def _sdf_kind_of(kind):
 def sdf_flow(grid, kind, filt, track=None, grow=False, attr=None):
     """The filter of `kind` ("box", "median", "laplacian", "curvature", or a FLUID_SDF_FILTER_* number) of an SdfGrid
     (fluid_sdf_flow: host only; include/fluid_hip.h, "liquid surface, flows").  filt = (width, iterations[, offset]): a median
-    takes width 1 or 2, a Laplacian or mean-curvature flow width 1.  track = None (untracked), normalize or (normalize, trim);
+    takes width 1 or 2, a Laplacian or mean-curvature flow width 1.  track = None (untracked), normalize, (normalize, trim) or (normalize, trim, scheme);
     grow=True: every track begins with a dilation of the band.  Returns the new SdfGrid, or with attr (an SdfAttr of `grid`'s
     leaves) the pair (SdfGrid, SdfAttr).  A decomposed run filters the merged list."""
     c, _keep = grid._c()
@@ -817,13 +831,15 @@ class FluidSim:
         else:
             check(lib.fluid_sdf_snapshot_filtered(self._h, C.byref(p), C.byref(_sdf_filter_of(smooth))))
 
-    def sdf_set_track(self, normalize, trim=True, grow=False):
+    def sdf_set_track(self, normalize, trim=True, grow=False, scheme="first"):
         """A setting of the handle: every later snapshot given smooth= renormalises (`normalize` passes, 0..8; the library's
         default is 3) and, with `trim`, trims the level set after every box iteration and every offset step (include/fluid_hip.h,
         "liquid surface, renormalised").  sdf_set_track(None): off, the default.  grow=True: every track begins with a dilation of
         the band ("liquid surface, grown band"; it needs normalize >= 1 and the trim, which the next filtered snapshot checks);
-        grow is passed on as it is, so an integer other than 0 / 1 is the library's FLUID_ERR_ARG."""
-        t = None if normalize is None else SdfTrack(int(normalize), int(bool(trim)), 0)
+        grow is passed on as it is, so an integer other than 0 / 1 is the library's FLUID_ERR_ARG.  scheme: "first" (first-order
+        upwind, the default), "hjweno5" (the library's own default, "liquid surface, renormalised: HJWENO5") or a number, passed
+        on as it is."""
+        t = None if normalize is None else SdfTrack(int(normalize), int(bool(trim)), _sdf_scheme_of(scheme))
         check(lib.fluid_sdf_set_track(self._h, None if t is None else C.byref(t)))
         check(lib.fluid_sdf_set_track_grow(self._h, int(grow)))
 

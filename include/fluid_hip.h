@@ -724,12 +724,14 @@ int fluid_sdf_filter(const fluid_sdf_grid_t* g, const fluid_sdf_filter_t* f, flo
  *
  * What this is not.  By itself the band never grows: dilateActiveValues, the first line of track(), is run only with growing
  * switched on ("liquid surface, grown band" below); without it a surface that leaves the band is lost to the trim instead of
- * followed.  HJWENO5, the library's default spatial scheme, and TVD_RK2/3 are not built;
- * neither are the tracker's dilate / erode / resize.  Decomposed handles take no tracked snapshots: track the merged list. */
-#define FLUID_SDF_TRACK_FIRST_BIAS 0
+ * followed.  The library's default spatial scheme, HJWENO5, is the scheme FLUID_SDF_TRACK_HJWENO5 ("liquid surface, renormalised:
+ * HJWENO5" below); the other spatial schemes (SECOND_BIAS, THIRD_BIAS, WENO5_BIAS) and TVD_RK2/3 are not built; neither are the
+ * tracker's dilate / erode / resize.  Decomposed handles take no tracked snapshots: track the merged list. */
+#define FLUID_SDF_TRACK_FIRST_BIAS 0   /* the library's own BiasedGradientScheme numbers (math/FiniteDifference.h:192-199) */
+#define FLUID_SDF_TRACK_HJWENO5 4      /* "liquid surface, renormalised: HJWENO5" below; 1, 2, 3 and everything else: FLUID_ERR_ARG */
 typedef struct fluid_sdf_track { int32_t normalize; /* passes per track: 0..8; the library's default is 3 */
                                  int32_t trim;      /* 0 or 1 */
-                                 int32_t scheme;    /* FLUID_SDF_TRACK_FIRST_BIAS only */ } fluid_sdf_track_t;
+                                 int32_t scheme;    /* FLUID_SDF_TRACK_FIRST_BIAS or FLUID_SDF_TRACK_HJWENO5 */ } fluid_sdf_track_t;
 /* A setting of the handle, like fluid_set_dt: every later snapshot that is given a filter runs the tracked form of it —
  * fluid_sdf_snapshot_filtered, fluid_sdf_snapshot_attr, fluid_mesh_snapshot_filtered, fluid_mesh_snapshot_attr,
  * fluid_mesh_snapshot_ex and fluid_render_snapshot; unfiltered snapshots are untouched.  NULL: off (the default).  One launch per
@@ -749,8 +751,56 @@ int fluid_sdf_set_track(fluid_sim_t* s, const fluid_sdf_track_t* t);
 int64_t fluid_sdf_filter_tracked(const fluid_sdf_grid_t* g, const fluid_sdf_filter_t* f, const fluid_sdf_track_t* t,
                                  int64_t cap_leaves, int32_t* origin, float* values, uint64_t* active, int32_t* kept /* may be NULL */);
 
+/* ---- liquid surface, renormalised: HJWENO5 -------------------------------------------------------------------------------------------
+ * The library's tracker defaults to HJWENO5_BIAS with TVD_RK1 (tools/LevelSetTracker.h:83-86); FIRST_BIAS above is what it runs
+ * only when asked.  The first-order Godunov step is diffusive on curved surfaces: it moves an EXACT signed distance of a sphere of
+ * radius 4 to 9 voxels by 0.05 to 0.1 voxel per track, HJWENO5 by about a thousandth (profiles/track/NOTES.md), so "an offset moves
+ * the surface by the offset" holds only to that accuracy under FIRST_BIAS.  With scheme = FLUID_SDF_TRACK_HJWENO5 every
+ * normalisation pass of every track forms its gradient term from seven values per axis.  Nothing else changes: the same launches
+ * per pass, the same two value buffers, the same trim, dilation, offset steps, listing and attributes, the schedule of
+ * sdf_filter_plan.h.  Restated from the library's arithmetic (tools/LevelSetTracker.h:596-609; math/Operators.h:252-284;
+ * math/FiniteDifference.h:331-349, 352-374, 1224-1233, 1428-1435) as an exact, order-free definition of its own: the kernel
+ * (kernels_sdf_weno.hip), the host functions below and the tests' numpy form give the same bytes; the arithmetic is stated once
+ * for both compilers in csrc/sdf_weno_def.h.  Where this text and the cited lines differ the lines win.
+ *
+ * Only the gradient term of "liquid surface, renormalised" changes.  For an ACTIVE voxel c with p = val(c), and per axis a in the
+ * order x, y, z, let u(k) = val(c + k e_a) for k = -3..3.  Reads follow the rule above: unlisted leaves and everything outside the
+ * grid read +bg, inactive voxels their stored +-bg.  All differences are float subtractions.
+ *   dp =  W5(u(3)-u(2),   u(2)-u(1),   u(1)-u(0),  u(0)-u(-1), u(-1)-u(-2))
+ *   dm = -W5(u(-3)-u(-2), u(-2)-u(-1), u(-1)-u(0), u(0)-u(1),  u(1)-u(2))
+ *   t_a from (out, dm, dp) exactly as above (A, B, max(A*A, B*B)); G, S and val_new exactly as above.
+ * W5(v1..v5) takes floats and returns a float; it works in double where the library's expression promotes (WENO5<float> with its
+ * default scale2 = 0.01f).  sqf is a float product, sqd a double product:
+ *   C = 13.0/12.0;  eps = 1.0e-6 * (double)0.01f
+ *   s1 = (C*(double)sqf((v1 - 2.0f*v2) + v3) + 0.25*sqd((double)(v1 - 4.0f*v2) + 3.0*(double)v3)) + eps
+ *   s2 = (C*(double)sqf((v2 - 2.0f*v3) + v4) + 0.25*(double)sqf(v2 - v4)) + eps
+ *   s3 = (C*(double)sqf((v3 - 2.0f*v4) + v5) + 0.25*sqd((3.0*(double)v3 - (double)(4.0f*v4)) + (double)v5)) + eps
+ *   A1 = 0.1/(s1*s1);  A2 = 0.6/(s2*s2);  A3 = 0.3/(s3*s3)
+ *   num = (A1*((2.0*v1 - 7.0*v2) + 11.0*v3) + A2*((5.0*v3 - v2) + 2.0*v4)) + A3*((2.0*v3 + 5.0*v4) - v5)      (double)
+ *   W5  = (float)( (double)(float)num / (6.0*((A1 + A2) + A3)) )
+ * No FMA, in float or in double; IEEE division and square root, in float and in double; denormals kept.
+ *
+ * What still holds.
+ * Signs: G >= 0 whatever formed it, and the step is the one above, so where sqrtf(G) * inv >= 1 the correction is at most 0.3 |p|
+ * and directed towards 0, elsewhere it moves p away from 0, and p = 0 gives S = 0: a pass changes no sign (up to rounding).  With
+ * K = 1 and no offset the mesh of the tracked level set has the untracked mesh's vertex and quad counts.
+ * Finite: eps > 0 keeps s1, s2, s3 positive, so A1, A2, A3 and their sum are positive and finite for finite input, and G is finite.
+ * Range: a stencil of depth 3 along the axes still needs face neighbours only (a leaf is 8 deep), and everything outside the
+ * device's range of leaves is inactive +bg in truth, so the ranges of "grown band" (4 + T, 5 + T for the mesh and the image) and
+ * of fluid_mesh_snapshot_filtered need no change.
+ * Symmetries of the definition (checked on the reference, tests/test_sdf_weno_ref.py): negating the seven values negates dm and dp
+ * bit for bit; reversing them gives (-dp, -dm) bit for bit.
+ *
+ * Where it applies.  fluid_sdf_set_track takes the scheme, and with it every entry point that takes a filter on a one-GPU handle
+ * (the list at fluid_sdf_set_track), grown tracks and every filter kind included.  On the host fluid_sdf_filter_tracked,
+ * fluid_sdf_filter_grown and fluid_sdf_flow run the scheme their fluid_sdf_track_t names, the six face neighbours read three
+ * planes deep.  Schemes 1, 2, 3, anything >= 5 and negatives stay FLUID_ERR_ARG; decomposed handles stay FLUID_ERR_STATE.
+ *
+ * What this is not.  TVD_RK2 / TVD_RK3 (they need a third buffer); SECOND_BIAS, THIRD_BIAS, WENO5_BIAS; fused passes.  Parity of the
+ * results with the library's own output is unpinned, as for the other surface sections: the definition is restated from its source. */
+
 /* ---- liquid surface, grown band: dilate, normalise, trim ---------------------------------------------------------------------------
- * The section above stops one line short of the library's track(), which is dilateActiveValues(leafs, 1, NN_FACE, IGNORE_TILES),
+ * "Liquid surface, renormalised" stops one line short of the library's track(), which is dilateActiveValues(leafs, 1, NN_FACE, IGNORE_TILES),
  * normalize(), prune() (tools/LevelSetTracker.h:299, 302, 305).  Without the dilation the band stays where the rasteriser put it:
  * a tracked offset cannot exceed bg, and within bg the surface runs into the rim of a band that does not follow it.  With growing
  * on every track begins with one dilation, so the band walks with the surface — outwards through +bg, inwards through the
@@ -786,7 +836,7 @@ int64_t fluid_sdf_filter_tracked(const fluid_sdf_grid_t* g, const fluid_sdf_filt
  * handle that has taken a grown snapshot pays for it.
  * With growing off every byte of every entry point is what it was.
  *
- * What this is not.  LevelSetTracker::dilate(n) / erode / resize, which change the half width and the background; HJWENO5; tracked
+ * What this is not.  LevelSetTracker::dilate(n) / erode / resize, which change the half width and the background; tracked
  * rank snapshots of decomposed handles; a two-offset "closing" entry point — a caller composes one on the host with two
  * fluid_sdf_filter_grown calls. */
 /* A setting of the handle like fluid_sdf_set_track, and independent of it in order: grow = 1 makes every later filtered snapshot
@@ -861,7 +911,7 @@ int64_t fluid_sdf_filter_grown(const fluid_sdf_grid_t* g, const struct fluid_sdf
  * Limits.  Median: width 1 or 2 (the 27- and 125-value cubes; the library's default is 1, and its own comment calls the filter
  * "simple but slow").  Laplacian and mean curvature: width must be 1.  Iterations 0..16; the offset rules stay as they are.
  *
- * What this is not.  HJWENO5, the alpha masks of the library's filters and Filter::fill are not built.  Parity of the results
+ * What this is not.  The alpha masks of the library's filters and Filter::fill are not built.  Parity of the results
  * with the library's own output is unpinned: the definitions are restated from its source. */
 #define FLUID_SDF_FILTER_BOX 0
 #define FLUID_SDF_FILTER_MEDIAN 1
