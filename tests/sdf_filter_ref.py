@@ -8,6 +8,7 @@ to the active voxels after the last iteration unless float32(offset) == 0.
   box_pass()  one pass along one axis
   smooth()    K iterations and the offset; `order` is a parameter only so that a test can show that it matters
   FILTERS     the (width, iterations, offset) the host and GPU tests share
+Pinned: tests/test_vdb_ref.py holds box_pass() and ORDER bit for bit to OpenVDB's own Avg and box(), compiled in place (oracle/vdb_ref.cpp).
 """
 import numpy as np
 

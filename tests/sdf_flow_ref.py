@@ -11,6 +11,9 @@ and narrowed once; the median is np.partition over the monotone uint32 keys of t
   keys() / unkeys() the median's order
   flow()            the filter of a kind: K iterations, tracks, the offset; untracked, tracked or grown; with ids / vel the attributes
   CASES             the (kind, W) the host and GPU tests share
+Pinned: tests/test_vdb_ref.py holds consts() and the three passes bit for bit to OpenVDB's own GradStencil, CurvatureStencil and
+DenseStencil::median and the filter's two time steps, compiled in place (oracle/vdb_ref.cpp), on inputs without -0.0: between
+signed zeros keys() is this project's own order.
 """
 import numpy as np
 

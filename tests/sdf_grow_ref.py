@@ -10,6 +10,8 @@ is float32 (asserted in those files and here).
   grown_track()   one dilation, N normalisation passes, the trim; grow=False is sdf_track_ref.track with the trim
   grown()         the tracked filter (W, K, offset; N) with every track a grown one; with ids / vel the attribute form
   GROWS           the (W, K, offset / dx, N) the host and GPU tests share, all with the trim
+Pinned: the passes this file composes (sdf_track_ref, sdf_filter_ref) are held to OpenVDB's own lines by tests/test_vdb_ref.py; the
+dilation (tools/Morphology.h) is still this file's reading alone.
 """
 import numpy as np
 

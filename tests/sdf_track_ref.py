@@ -10,6 +10,8 @@ offset of tools/LevelSetFilter.h:352-368, on a dense (val, act) (n, n, n) of tes
   track()      N passes, then the trim
   tracked()    the tracked filter (W, K, offset; N, trim); N = 0 without trim is sdf_filter_ref.smooth()
   TRACKS       the (W, K, offset / dx, N, trim) the host and GPU tests share
+Pinned: tests/test_vdb_ref.py holds norm_pass() and offset_steps() bit for bit to OpenVDB's own Normalizer::eval and offset(), compiled in
+place (oracle/vdb_ref.cpp); trim() is restated there in three lines from tools/LevelSetTracker.h:469-472.
 """
 import numpy as np
 

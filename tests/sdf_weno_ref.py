@@ -13,6 +13,8 @@ themselves, run with this file's pass in place of the first-order one (hjweno5()
   norm_pass_weno()  one normalisation pass
   track()  tracked()  grown()  flow()   sdf_track_ref.track / tracked, sdf_grow_ref.grown, sdf_flow_ref.flow under HJWENO5
   CASES             the (W, K, offset / dx, N, trim) the host and GPU tests share
+Pinned: tests/test_vdb_ref.py holds weno5(), axis_diffs(), voxel_value() and norm_pass_weno() bit for bit to OpenVDB's own WENO5, D1 and
+Normalizer::eval over the NineteenPointStencil, compiled in place (oracle/vdb_ref.cpp).
 """
 import contextlib
 
