@@ -1,8 +1,5 @@
 // Box filter and offset of the particles' level set for gfx950 (wave64) (include/fluid_hip.h, "liquid surface, smoothed";
-// fluid_sdf.hip).  The kernels work on what k_sdf_search (kernels_sdf.hip) leaves on the device: tv (512 values), tm (8 mask words)
-// and a listed flag per leaf j = (jx * nl[1] + jy) * nl[2] + jz of the range.  A leaf whose flag is 0 is inactive +bg everywhere
-// WHATEVER its tv and tm hold (they may be those of an earlier snapshot), and so is every leaf outside the range and everything
-// outside the grid: only flagged leaves are ever read, and only flagged leaves are written.
+// fluid_sdf.hip).  The leaves, their flags and what an unflagged leaf reads as: sdf_leaf.h.
 //
 //   box     one launch per axis pass, one 512-thread block per leaf of the range, thread t = the voxel ((x&7)*8 + (y&7))*8 + (z&7).
 //           The block of an unflagged leaf leaves at once.  A flagged leaf stages its 8 x 8 x (8 + 2W) values along the axis in LDS
@@ -15,16 +12,11 @@
 // LDS index of plane k (0 .. 8 + 2W - 1) and in-plane position uv (0 .. 63): k * 64 + ((uv + 8 k) & 63).  A wave is an x plane of
 // the leaf; for either in-plane numbering below its 64 lanes then fall into 64 different banks on every axis.
 #include "common.h"
+#include "sdf_leaf.h"
 
 namespace fl {
 
 __device__ __forceinline__ int box_lds(int k, int uv) { return k * 64 + ((uv + 8 * k) & 63); }
-
-// offset in the leaf of the voxel at plane kc of the axis and in-plane position uv: uv = y*8+z (axis x), x*8+z (y), x*8+y (z)
-__device__ __forceinline__ int box_voxel(int axis, int kc, int uv)
-{
-    return axis == 0 ? kc * 64 + uv : axis == 1 ? (uv >> 3) * 64 + kc * 8 + (uv & 7) : uv * 8 + kc;
-}
 
 __global__ __launch_bounds__(512) void k_sdf_box(SdfGeom g, int axis, int W, float frac, float off, const int* __restrict__ flags,
                                                  const unsigned long long* __restrict__ tm, const float* __restrict__ src,
@@ -42,19 +34,11 @@ __global__ __launch_bounds__(512) void k_sdf_box(SdfGeom g, int axis, int W, flo
     if (t < 2 * W * 64) {
         // halo plane i (0 .. W-1) of the leaf at -1 (its planes 8-W ..) or +1 (its planes 0 ..) on the axis
         const int side = t >= W * 64, r = t - side * W * 64, i = r >> 6, huv = r & 63;
-        const int ja = axis == 0 ? (int)(j / ((long)g.nl[1] * g.nl[2])) : axis == 1 ? (int)((j / g.nl[2]) % g.nl[1]) : (int)(j % g.nl[2]);
-        const long stride = axis == 0 ? (long)g.nl[1] * g.nl[2] : axis == 1 ? g.nl[2] : 1;
-        const int jn = ja + (side ? 1 : -1);
-        float v = g.bg;
-        if (jn >= 0 && jn < g.nl[axis]) {
-            const long q = side ? j + stride : j - stride;
-            if (flags[q]) v = src[q * 512 + box_voxel(axis, side ? i : 8 - W + i, huv)];
-        }
-        T[box_lds(side ? 8 + W + i : i, huv)] = v;
+        T[box_lds(side ? 8 + W + i : i, huv)] = face_value(g, flags, src, j, axis, side, side ? i : 8 - W + i, huv);
     }
     __syncthreads();
     float val = own;
-    if ((tm[j * 8 + x] >> (t & 63)) & 1ull) {
+    if (leaf_active(tm, j, t)) {
         float s = 0.0f;
         for (int i = 0; i <= 2 * W; ++i) s = s + T[box_lds(kc + i, uv)];
         val = s * frac;
@@ -69,7 +53,7 @@ __global__ __launch_bounds__(512) void k_sdf_offset(float off, const int* __rest
     const long j = blockIdx.x;
     if (!flags[j]) return;
     const int t = threadIdx.x;
-    if ((tm[j * 8 + (t >> 6)] >> (t & 63)) & 1ull) tv[j * 512 + t] = tv[j * 512 + t] + off;
+    if (leaf_active(tm, j, t)) tv[j * 512 + t] = tv[j * 512 + t] + off;
 }
 
 void launch_sdf_box(hipStream_t st, const SdfGeom& g, int axis, int W, float off, const int* flags, const uint64_t* tm, const float* src,

@@ -1,8 +1,6 @@
 // Median, Laplacian and mean-curvature flow of the particles' level set for gfx950 (wave64) (include/fluid_hip.h, "liquid surface,
-// flows"; fluid_sdf.hip).  The kernel works on what k_sdf_search, the box passes and the tracks leave on the device, with the
-// conventions of kernels_sdf_track.hip: tv (512 values), tm (8 mask words) and a flag per leaf j = (jx * nl[1] + jy) * nl[2] + jz of
-// the range; a leaf whose flag is 0 is inactive +bg everywhere whatever its tv and tm hold, and so is everything outside the range.
-// Only flagged leaves are read or written; the flag is never changed here.
+// flows"; fluid_sdf.hip).  The kernel works on what k_sdf_search, the box passes and the tracks leave on the device; the leaves, their
+// flags and what an unflagged leaf reads as: sdf_leaf.h.
 //
 //   flow    one launch per pass, one 512-thread block per leaf of the range, thread t = the voxel ((x&7)*8 + (y&7))*8 + (z&7).  The
 //           block of an unflagged leaf leaves at once.  A flagged leaf stages its (8 + 2H)^3 tile in LDS, H = 1 (Laplacian,
@@ -25,6 +23,7 @@
 #include "../../include/fluid_hip.h"
 #include "common.h"
 #include "sdf_flow_def.h"
+#include "sdf_leaf.h"
 
 namespace fl {
 
@@ -41,18 +40,16 @@ __global__ __launch_bounds__(512) void k_sdf_flow(SdfGeom g, float invdx2, float
     const long j = blockIdx.x;
     if (!flags[j]) return;   // (the whole block alike)
     const int t = threadIdx.x;
-    const int jz = (int)(j % g.nl[2]), jy = (int)((j / g.nl[2]) % g.nl[1]), jx = (int)(j / ((long)g.nl[1] * g.nl[2]));
+    int jx, jy, jz;
+    leaf_coords(g, j, jx, jy, jz);
     const uint32_t bg = __float_as_uint(g.bg);
     for (int i = t; i < S * S * S; i += 512) {
         const int X = i / (S * S), Y = (i / S) % S, Z = i % S;
         const int rx = X - H, ry = Y - H, rz = Z - H;   // the voxel in this leaf's frame: -H .. 7 + H
         const int sx = rx < 0 ? -1 : rx >= 8 ? 1 : 0, sy = ry < 0 ? -1 : ry >= 8 ? 1 : 0, sz = rz < 0 ? -1 : rz >= 8 ? 1 : 0;
-        const int qx = jx + sx, qy = jy + sy, qz = jz + sz;
         uint32_t v = bg;
-        if (qx >= 0 && qx < g.nl[0] && qy >= 0 && qy < g.nl[1] && qz >= 0 && qz < g.nl[2]) {
-            const long q = ((long)qx * g.nl[1] + qy) * g.nl[2] + qz;
-            if (flags[q]) v = __float_as_uint(src[q * 512 + ((rx - 8 * sx) * 8 + (ry - 8 * sy)) * 8 + (rz - 8 * sz)]);
-        }
+        leaf_or_none(g, flags, jx + sx, jy + sy, jz + sz,
+                     [&](long q) { v = __float_as_uint(src[q * 512 + ((rx - 8 * sx) * 8 + (ry - 8 * sy)) * 8 + (rz - 8 * sz)]); });
         T[(X * S + Y) * P + Z] = MEDIAN ? fdef::median_key(v) : v;
     }
     __syncthreads();
@@ -60,7 +57,7 @@ __global__ __launch_bounds__(512) void k_sdf_flow(SdfGeom g, float invdx2, float
     const int c = ((x + H) * S + (y + H)) * P + (z + H);
     const float own = src[j * 512 + t];
     float val = own;
-    if ((tm[j * 8 + x] >> (t & 63)) & 1ull) {
+    if (leaf_active(tm, j, t)) {
         auto at = [&](int a, int b, int d) { return __uint_as_float(T[c + (a * S + b) * P + d]); };
         if (MEDIAN) {
             constexpr int n = 2 * H + 1, m = n * n * n;

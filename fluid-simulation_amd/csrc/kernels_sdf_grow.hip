@@ -1,6 +1,5 @@
 // The band dilation at the head of a grown track for gfx950 (wave64) (include/fluid_hip.h, "liquid surface, grown band";
-// fluid_sdf.hip), with the conventions of kernels_sdf_track.hip: tv (512 values), tm (8 mask words) and a flag per leaf j of the
-// range; a leaf whose flag is 0 is inactive +bg everywhere whatever its tv and tm hold, and so is everything outside the range.
+// fluid_sdf.hip).  The leaves, their flags and what an unflagged leaf reads as: sdf_leaf.h.
 //
 //   grow    one launch per track, one 512-thread block per leaf of the range, wave x = the mask word of the (y, z) plane at x, lane =
 //           the bit y * 8 + z.  Everything that decides is wave-uniform word arithmetic (sdf_grow_def.h): the in-plane neighbours are
@@ -17,6 +16,7 @@
 //           active are read, so the two sets are disjoint across the whole launch.
 #include "common.h"
 #include "sdf_grow_def.h"
+#include "sdf_leaf.h"
 
 namespace fl {
 
@@ -28,8 +28,10 @@ __global__ __launch_bounds__(512) void k_sdf_grow(SdfGeom g, const int* __restri
     const long j = blockIdx.x;
     const int t = threadIdx.x, x = t >> 6, bit = t & 63;
     const long sx = (long)g.nl[1] * g.nl[2], sy = g.nl[2];
-    const int jx = (int)(j / sx), jy = (int)((j / sy) % g.nl[1]), jz = (int)(j % g.nl[2]);
-    // the six face neighbours in the range, -1 where the range ends or the leaf is not flagged
+    int jx, jy, jz;
+    leaf_coords(g, j, jx, jy, jz);
+    // the six face neighbours in the range, -1 where the range ends or the leaf is not flagged: sdf_leaf.h's face_or_none rule written
+    // out for all six at once, from the three coordinates (six calls of the helper cost 0.6 us a launch: profiles/track/NOTES.md)
     long nb[6];
     nb[0] = jx > 0 ? j - sx : -1, nb[1] = jx < g.nl[0] - 1 ? j + sx : -1;
     nb[2] = jy > 0 ? j - sy : -1, nb[3] = jy < g.nl[1] - 1 ? j + sy : -1;
@@ -55,11 +57,7 @@ __global__ __launch_bounds__(512) void k_sdf_grow(SdfGeom g, const int* __restri
     if (bit == 0) tm2[j * 8 + x] = own | fresh;
     if (!flagged) {
         val[j * 512 + t] = g.bg;
-        if (ATTR) {
-            tid[j * 512 + t] = 0xffffffffu;
-            float* tw = tvel + j * 1536 + t;
-            tw[0] = 0.0f, tw[512] = 0.0f, tw[1024] = 0.0f;
-        }
+        if (ATTR) attr_clear(tid, tvel, j, t);
     }
     if (ATTR && ((fresh >> bit) & 1ull)) {
         int d = 5;   // (fresh is a subset of the union of c: some direction has the bit)

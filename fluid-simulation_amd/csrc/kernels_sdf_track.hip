@@ -1,18 +1,13 @@
 // Renormalisation and trim of the particles' level set for gfx950 (wave64) (include/fluid_hip.h, "liquid surface, renormalised";
-// fluid_sdf.hip).  The kernels work on what k_sdf_search and the box passes leave on the device, with the conventions of
-// kernels_sdf_filter.hip: tv (512 values), tm (8 mask words) and a flag per leaf j of the range; a leaf whose flag is 0 is inactive
-// +bg everywhere whatever its tv and tm hold, and so is everything outside the range.  Here the flag means "this leaf's values are
-// valid": it is never cleared, because the neighbour blocks of the same launch read it to choose between src and +bg.  A flagged
-// leaf that the trim left all inactive +bg reads correctly; whether a leaf is LISTED is derived afterwards, into an array of its own.
+// fluid_sdf.hip).  The kernels work on what k_sdf_search and the box passes leave on the device; the leaves, their flags and why no
+// pass clears a flag: sdf_leaf.h.
 //
 //   track   one launch per normalisation pass, one 512-thread block per leaf of the range, thread t = the voxel
 //           ((x&7)*8 + (y&7))*8 + (z&7).  The block of an unflagged leaf leaves at once.  A flagged leaf stages its own 512 values and
 //           the six 64-value faces of its face neighbours in LDS (896 floats; a 7-point stencil needs no edges or corners), +bg where
 //           the neighbour is unflagged or outside the range.  Every thread writes its voxel to the OTHER buffer: an active voxel
 //           tdef::track_value of its seven values (sdf_track_def.h), an inactive one its value unchanged.  Jacobi by construction.
-//           TRIM (the last pass of a track): an active result at or beyond +-bg becomes inactive +-bg; the wave's ballot of "still
-//           active" is the new mask word x, written over tm[j*8 + x] — only this wave reads that word.  With attributes the
-//           deactivated voxel's id and velocity become NO_ID and +0.
+//           TRIM (the last pass of a track): sdf_leaf.h's trim_store.
 //           NORM = false: the trim alone, in place, no tile.
 //   relist  list[j] = the leaf is flagged and holds anything but inactive +bg: what the scan and the pack run off after a trim.
 // Arithmetic: float, no FMA (-ffp-contract=off), IEEE division and square root (-fhip-fp32-correctly-rounded-divide-sqrt).
@@ -20,15 +15,10 @@
 // A wave is an x plane: its x neighbours are 64 consecutive floats (own plane x -+ 1, or a whole x face), one bank each.  Along y
 // and z 56 lanes read own values and 8 lanes a face row, which can share banks with them two ways; see DESIGN f13.
 #include "common.h"
+#include "sdf_leaf.h"
 #include "sdf_track_def.h"
 
 namespace fl {
-
-// offset in the leaf of the voxel at plane k of the axis and in-plane position uv
-__device__ __forceinline__ int track_voxel(int axis, int k, int uv)
-{
-    return axis == 0 ? k * 64 + uv : axis == 1 ? (uv >> 3) * 64 + k * 8 + (uv & 7) : uv * 8 + k;
-}
 
 template <bool NORM, bool TRIM, bool ATTR>
 __global__ __launch_bounds__(512) void k_sdf_track(SdfGeom g, float dt, float inv, const int* __restrict__ flags, unsigned long long* tm,
@@ -45,19 +35,11 @@ __global__ __launch_bounds__(512) void k_sdf_track(SdfGeom g, float dt, float in
         if (t < 6 * 64) {
             // face f: the plane of the leaf at -1 (its plane 7) or +1 (its plane 0) on the axis that touches this leaf
             const int f = t >> 6, uv = t & 63, axis = f >> 1, side = f & 1;
-            const int ja = axis == 0 ? (int)(j / ((long)g.nl[1] * g.nl[2])) : axis == 1 ? (int)((j / g.nl[2]) % g.nl[1]) : (int)(j % g.nl[2]);
-            const long stride = axis == 0 ? (long)g.nl[1] * g.nl[2] : axis == 1 ? g.nl[2] : 1;
-            const int jn = ja + (side ? 1 : -1);
-            float v = g.bg;
-            if (jn >= 0 && jn < g.nl[axis]) {
-                const long q = side ? j + stride : j - stride;
-                if (flags[q]) v = src[q * 512 + track_voxel(axis, side ? 0 : 7, uv)];
-            }
-            T[512 + t] = v;
+            T[512 + t] = face_value(g, flags, src, j, axis, side, side ? 0 : 7, uv);
         }
         __syncthreads();
     }
-    bool act = (tm[j * 8 + x] >> (t & 63)) & 1ull;
+    const bool act = leaf_active(tm, j, t);
     float val = own;
     if (NORM && act) {
         const int yz = t & 63, xz = x * 8 + z, xy = t >> 3;
@@ -66,20 +48,7 @@ __global__ __launch_bounds__(512) void k_sdf_track(SdfGeom g, float dt, float in
         const float zm = z > 0 ? T[t - 1] : T[512 + 256 + xy], zp = z < 7 ? T[t + 1] : T[512 + 320 + xy];
         val = tdef::track_value(own, xm, xp, ym, yp, zm, zp, dt, inv);
     }
-    if (TRIM) {
-        const int cls = act ? tdef::trim_class(val, g.bg) : 0;
-        if (cls != 0) {
-            val = cls < 0 ? -g.bg : g.bg;
-            act = false;
-            if (ATTR) {
-                tid[j * 512 + t] = 0xffffffffu;
-                float* tw = tvel + j * 1536 + t;
-                tw[0] = 0.0f, tw[512] = 0.0f, tw[1024] = 0.0f;
-            }
-        }
-        const unsigned long long b = __ballot(act);   // (every lane of the wave is here: the branches above have rejoined)
-        if ((t & 63) == 0) tm[j * 8 + x] = b;
-    }
+    if (TRIM) val = trim_store<ATTR>(g, j, t, x, act, val, tm, tid, tvel);   // (every lane of the wave is here: the branches above have rejoined)
     if (NORM || TRIM) dst[j * 512 + t] = val;
 }
 
@@ -92,7 +61,7 @@ __global__ __launch_bounds__(512) void k_sdf_relist(float bg, const int* __restr
         if (t == 0) list[j] = 0;
         return;
     }
-    const bool act = (tm[j * 8 + (t >> 6)] >> (t & 63)) & 1ull;
+    const bool act = leaf_active(tm, j, t);
     const int listed = __syncthreads_or(act || tv[j * 512 + t] != bg);
     if (t == 0) list[j] = listed ? 1 : 0;
 }

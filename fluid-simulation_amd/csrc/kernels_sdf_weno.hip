@@ -1,7 +1,6 @@
 // HJWENO5 renormalisation of the particles' level set for gfx950 (wave64) (include/fluid_hip.h, "liquid surface, renormalised:
-// HJWENO5"; fluid_sdf.hip).  The conventions are kernels_sdf_track.hip's: tv (512 values), tm (8 mask words) and a flag per leaf j
-// of the range; a leaf whose flag is 0 is inactive +bg everywhere, and so is everything outside the range; the flag is never
-// cleared.  The trim alone (no pass) and the relisting are scheme-independent and stay with k_sdf_track / k_sdf_relist.
+// HJWENO5"; fluid_sdf.hip).  The leaves, their flags and what an unflagged leaf reads as: sdf_leaf.h.  The trim alone (no pass) and the
+// relisting are scheme-independent and stay with k_sdf_track / k_sdf_relist.
 //
 //   track_weno  one launch per normalisation pass, one 512-thread block per leaf of the range, thread t = the voxel
 //           ((x&7)*8 + (y&7))*8 + (z&7).  The block of an unflagged leaf leaves at once.  A flagged leaf stages its own 512 values and,
@@ -11,7 +10,7 @@
 //           rounds of 512 threads, at most three per thread; the 64 threads of a wave fetch one plane, so the flag test is uniform.
 //           Every thread writes its voxel to the OTHER buffer: an active voxel wdef::track_value_weno of its 19 values
 //           (sdf_weno_def.h), an inactive one its value unchanged and without the arithmetic.  Jacobi by construction.
-//           TRIM and ATTR: exactly as in k_sdf_track — the wave's ballot of "still active" is the new mask word.
+//           TRIM and ATTR: sdf_leaf.h's trim_store, as in k_sdf_track.
 // Arithmetic: float and double as sdf_weno_def.h types them, no FMA (-ffp-contract=off), IEEE division and square root.
 // LDS: the x axis is laid out as one column of 14 planes, T[(x + 3) * 64 + yz] for x = -3..10: the minus neighbour's planes 5, 6, 7,
 // the leaf's own eight, the plus neighbour's planes 0, 1, 2.  So the voxel's own value is T[192 + t], a wave (an x plane) reads
@@ -20,15 +19,10 @@
 // uv = x*8+z for y and x*8+y for z.  Along y and z some lanes of a wave read own values and some a halo row, which can share banks;
 // not measured, see DESIGN f16.
 #include "common.h"
+#include "sdf_leaf.h"
 #include "sdf_weno_def.h"
 
 namespace fl {
-
-// offset in the leaf of the voxel at plane k of the axis and in-plane position uv (as kernels_sdf_track.hip's track_voxel)
-__device__ __forceinline__ int weno_voxel(int axis, int k, int uv)
-{
-    return axis == 0 ? k * 64 + uv : axis == 1 ? (uv >> 3) * 64 + k * 8 + (uv & 7) : uv * 8 + k;
-}
 
 // where the tile keeps the halo value of face (axis, side) at depth d (0 = the plane that touches the leaf) and position uv
 __device__ __forceinline__ int weno_halo(int axis, int side, int d, int uv)
@@ -60,19 +54,11 @@ __global__ __launch_bounds__(512) void k_sdf_track_weno(SdfGeom g, float dt, flo
         const int h = t + 512 * r;   // halo value h: plane h >> 6 = 3 * face + depth, position h & 63
         if (h < 18 * 64) {
             const int pl = h >> 6, uv = h & 63, f = pl / 3, d = pl - 3 * f, axis = f >> 1, side = f & 1;
-            const int ja = axis == 0 ? (int)(j / ((long)g.nl[1] * g.nl[2])) : axis == 1 ? (int)((j / g.nl[2]) % g.nl[1]) : (int)(j % g.nl[2]);
-            const long stride = axis == 0 ? (long)g.nl[1] * g.nl[2] : axis == 1 ? g.nl[2] : 1;
-            const int jn = ja + (side ? 1 : -1);
-            float v = g.bg;
-            if (jn >= 0 && jn < g.nl[axis]) {
-                const long q = side ? j + stride : j - stride;
-                if (flags[q]) v = src[q * 512 + weno_voxel(axis, side ? d : 7 - d, uv)];
-            }
-            T[weno_halo(axis, side, d, uv)] = v;
+            T[weno_halo(axis, side, d, uv)] = face_value(g, flags, src, j, axis, side, side ? d : 7 - d, uv);
         }
     }
     __syncthreads();
-    bool act = (tm[j * 8 + x] >> (t & 63)) & 1ull;
+    const bool act = leaf_active(tm, j, t);
     float val = own;
     if (act) {
         const int xz = x * 8 + z, xy = t >> 3;
@@ -85,20 +71,7 @@ __global__ __launch_bounds__(512) void k_sdf_track_weno(SdfGeom g, float dt, flo
         }
         val = wdef::track_value_weno(ux, uy, uz, dt, inv);
     }
-    if (TRIM) {
-        const int cls = act ? tdef::trim_class(val, g.bg) : 0;
-        if (cls != 0) {
-            val = cls < 0 ? -g.bg : g.bg;
-            act = false;
-            if (ATTR) {
-                tid[j * 512 + t] = 0xffffffffu;
-                float* tw = tvel + j * 1536 + t;
-                tw[0] = 0.0f, tw[512] = 0.0f, tw[1024] = 0.0f;
-            }
-        }
-        const unsigned long long b = __ballot(act);   // (every lane of the wave is here: the branches above have rejoined)
-        if ((t & 63) == 0) tm[j * 8 + x] = b;
-    }
+    if (TRIM) val = trim_store<ATTR>(g, j, t, x, act, val, tm, tid, tvel);   // (every lane of the wave is here: the branches above have rejoined)
     dst[j * 512 + t] = val;
 }
 

@@ -15,9 +15,10 @@
 // median, Laplacian or mean-curvature flow (the per-voxel arithmetic is sdf_flow_def.h's, shared with kernels_sdf_flow.hip) on the
 // leaf's (8 + 2H)^3 tile, the 26 neighbour leaves found by bisection.
 // All four run the one schedule of sdf_filter_plan.h (the order of passes, offset steps and tracks, and the arguments' limits,
-// shared with fluid_sdf.hip); the tracked, the grown and the flow function are one driver (run_band) on one working list (Band)
-// with one rule for which leaves stay listed (copy_out), and differ in their refusals, in the dilation and in what travels with
-// the band.
+// shared with fluid_sdf.hip); the tracked, the grown and the flow function are one entry path (band_filter: the refusals, then
+// run_band on one working list, Band, then copy_out's one rule for which leaves stay listed) and differ in the arguments they fix:
+// the kind, the dilation and what travels with the band.  A leaf's face neighbours in the list are found in one place
+// (face_neighbours).
 // Arithmetic: float, no contraction (x86-64 has none without -mfma; the builds state -ffp-contract=off).
 #include <cmath>
 #include <cstdint>
@@ -33,6 +34,21 @@
 
 namespace {
 
+// the origin of the face neighbour of the leaf at o on axis a: side 0 = -1, 1 = +1
+inline Org face_org(const Org& o, int a, int side)
+{
+    Org q = o;
+    (a == 0 ? q.x : a == 1 ? q.y : q.z) += side ? LEAF : -LEAF;
+    return q;
+}
+
+// the six face neighbours of the leaf at o as indices in g's list, -1 where unlisted: such a leaf reads as +bg
+void face_neighbours(const fluid_sdf_grid_t* g, const Org& o, long nb[3][2])
+{
+    for (int a = 0; a < 3; ++a)
+        for (int side = 0; side < 2; ++side) nb[a][side] = find_leaf(g, face_org(o, a, side));
+}
+
 // one pass of width W along `axis`: src -> dst (512 per leaf, the list's order); `off` is added to the active voxels' results
 void box_pass(const fluid_sdf_grid_t* g, int axis, int W, float off, const float* src, float* dst)
 {
@@ -43,10 +59,9 @@ void box_pass(const fluid_sdf_grid_t* g, int axis, int W, float off, const float
     float line[LEAF + 8];
     for (long l = 0; l < g->n_leaves; ++l) {
         const int32_t* o = g->origin + 3 * (size_t)l;
-        Org om{o[0], o[1], o[2]}, op = om;
-        (axis == 0 ? om.x : axis == 1 ? om.y : om.z) -= LEAF;
-        (axis == 0 ? op.x : axis == 1 ? op.y : op.z) += LEAF;
-        const long lm = find_leaf(g, om), lp = find_leaf(g, op);
+        long nb[3][2];
+        face_neighbours(g, org_of(g, l), nb);
+        const long lm = nb[axis][0], lp = nb[axis][1];
         const float* v = src + 512 * (size_t)l;
         const float* vm = lm >= 0 ? src + 512 * (size_t)lm : nullptr;
         const float* vp = lp >= 0 ? src + 512 * (size_t)lp : nullptr;
@@ -168,83 +183,39 @@ void flow_pass(const fluid_sdf_grid_t* g, int kind, int W, float dx, float off, 
     }
 }
 
-// ---- "liquid surface, renormalised": the arithmetic is sdf_track_def.h's; here the neighbours, the masks and the list ----------
-// one normalisation pass src -> dst (512 per leaf, the list's order); g->active is the mask as it is now
-void norm_pass(const fluid_sdf_grid_t* g, float dx, const float* src, float* dst)
+// ---- "liquid surface, renormalised": the arithmetic is sdf_track_def.h's, or three planes deep ("HJWENO5") sdf_weno_def.h's; here
+// the neighbours, the masks and the list ------------------------------------------------------------------------------------------
+// one normalisation pass src -> dst (512 per leaf, the list's order) that reads D values either way on every axis: D = 1
+// tdef::track_value, D = 3 wdef::track_value_weno; g->active is the mask as it is now
+template <int D> void norm_pass(const fluid_sdf_grid_t* g, float dx, const float* src, float* dst)
 {
     const int lo = -(g->n / 2), hi = lo + g->n - 1;
     const float bg = g->background, dt = dx * 0.3f, inv = 1.0f / dx;
     static const int stride[3] = {64, 8, 1};
     for (long l = 0; l < g->n_leaves; ++l) {
         const int32_t* o = g->origin + 3 * (size_t)l;
-        const float* nb[3][2];   // the face neighbours' values, nullptr where unlisted
-        for (int a = 0; a < 3; ++a)
-            for (int side = 0; side < 2; ++side) {
-                Org q{o[0], o[1], o[2]};
-                (a == 0 ? q.x : a == 1 ? q.y : q.z) += side ? LEAF : -LEAF;
-                const long k = find_leaf(g, q);
-                nb[a][side] = k >= 0 ? src + 512 * (size_t)k : nullptr;
-            }
+        long nb[3][2];
+        face_neighbours(g, org_of(g, l), nb);
         const float* v = src + 512 * (size_t)l;
-        const uint64_t* mask = g->active + 8 * (size_t)l;
         float* out = dst + 512 * (size_t)l;
         for (int at = 0; at < 512; ++at) {
             out[at] = v[at];
-            if (!((mask[at >> 6] >> (at & 63)) & 1ull) || !in_grid(g, o, at)) continue;
+            if (!is_active(g->active, (size_t)l, at) || !in_grid(g, o, at)) continue;
             const int c[3] = {at >> 6, (at >> 3) & 7, at & 7};
-            float n6[3][2];
+            float u[3][2 * D + 1];
             for (int a = 0; a < 3; ++a)
-                for (int side = 0; side < 2; ++side) {
-                    const int k = c[a] + (side ? 1 : -1), ca = o[a] + k;
-                    float x = bg;
-                    if (ca >= lo && ca <= hi) {
-                        if (k < 0) x = nb[a][0] ? nb[a][0][at + 7 * stride[a]] : bg;
-                        else if (k >= LEAF) x = nb[a][1] ? nb[a][1][at - 7 * stride[a]] : bg;
-                        else x = v[at + (side ? stride[a] : -stride[a])];
-                    }
-                    n6[a][side] = x;
-                }
-            out[at] = tdef::track_value(v[at], n6[0][0], n6[0][1], n6[1][0], n6[1][1], n6[2][0], n6[2][1], dt, inv);
-        }
-    }
-}
-
-// ---- "liquid surface, renormalised: HJWENO5": the arithmetic is sdf_weno_def.h's; the same neighbours, read three planes deep ----
-void norm_pass_weno(const fluid_sdf_grid_t* g, float dx, const float* src, float* dst)
-{
-    const int lo = -(g->n / 2), hi = lo + g->n - 1;
-    const float bg = g->background, dt = dx * 0.3f, inv = 1.0f / dx;
-    static const int stride[3] = {64, 8, 1};
-    for (long l = 0; l < g->n_leaves; ++l) {
-        const int32_t* o = g->origin + 3 * (size_t)l;
-        const float* nb[3][2];   // the face neighbours' values, nullptr where unlisted
-        for (int a = 0; a < 3; ++a)
-            for (int side = 0; side < 2; ++side) {
-                Org q{o[0], o[1], o[2]};
-                (a == 0 ? q.x : a == 1 ? q.y : q.z) += side ? LEAF : -LEAF;
-                const long k = find_leaf(g, q);
-                nb[a][side] = k >= 0 ? src + 512 * (size_t)k : nullptr;
-            }
-        const float* v = src + 512 * (size_t)l;
-        const uint64_t* mask = g->active + 8 * (size_t)l;
-        float* out = dst + 512 * (size_t)l;
-        for (int at = 0; at < 512; ++at) {
-            out[at] = v[at];
-            if (!((mask[at >> 6] >> (at & 63)) & 1ull) || !in_grid(g, o, at)) continue;
-            const int c[3] = {at >> 6, (at >> 3) & 7, at & 7};
-            float u[3][7];
-            for (int a = 0; a < 3; ++a)
-                for (int d = -3; d <= 3; ++d) {
+                for (int d = -D; d <= D; ++d) {
                     const int k = c[a] + d, ca = o[a] + k;
                     float x = bg;
                     if (ca >= lo && ca <= hi) {
-                        if (k < 0) x = nb[a][0] ? nb[a][0][at + (d + LEAF) * stride[a]] : bg;
-                        else if (k >= LEAF) x = nb[a][1] ? nb[a][1][at + (d - LEAF) * stride[a]] : bg;
+                        if (k < 0) x = nb[a][0] >= 0 ? src[512 * (size_t)nb[a][0] + at + (d + LEAF) * stride[a]] : bg;
+                        else if (k >= LEAF) x = nb[a][1] >= 0 ? src[512 * (size_t)nb[a][1] + at + (d - LEAF) * stride[a]] : bg;
                         else x = v[at + d * stride[a]];
                     }
-                    u[a][d + 3] = x;
+                    u[a][d + D] = x;
                 }
-            out[at] = wdef::track_value_weno(u[0], u[1], u[2], dt, inv);
+            if constexpr (D == 1) out[at] = tdef::track_value(v[at], u[0][0], u[0][2], u[1][0], u[1][2], u[2][0], u[2][2], dt, inv);
+            else out[at] = wdef::track_value_weno(u[0], u[1], u[2], dt, inv);
         }
     }
 }
@@ -322,12 +293,9 @@ void dilate(fluid_sdf_grid_t* cur, Band& b)
             eff[8 * l + x] = b.mask[8 * l + x] & gdef::grid_word(b.org[3 * l] + x, b.org[3 * l + 1], b.org[3 * l + 2], lo, hi);
     // the new bits of the leaf at o (self = its index, -1: unlisted), and for each its id and velocity (into id512 / vel1536)
     auto grow_leaf = [&](const Org& o, long self, uint64_t fresh[8], uint32_t* id512, float* vel1536) {
-        long nb[6];
-        for (int d = 0; d < 6; ++d) {
-            Org q = o;
-            (d < 2 ? q.x : d < 4 ? q.y : q.z) += (d & 1) ? LEAF : -LEAF;
-            nb[d] = find_leaf(cur, q);
-        }
+        long nb3[3][2];
+        face_neighbours(cur, o, nb3);
+        const long* nb = &nb3[0][0];   // direction d = 2 * axis + side: -x +x -y +y -z +z
         auto word = [&](long l, int x) { return l >= 0 ? eff[8 * (size_t)l + x] : 0ull; };
         bool any = false;
         for (int x = 0; x < 8; ++x) {
@@ -351,13 +319,17 @@ void dilate(fluid_sdf_grid_t* cur, Band& b)
     };
     // the unlisted face neighbours of the listed leaves, inside the grid's leaves
     std::vector<Org> cand;
-    for (size_t l = 0; l < nl; ++l)
-        for (int d = 0; d < 6; ++d) {
-            Org q{b.org[3 * l], b.org[3 * l + 1], b.org[3 * l + 2]};
-            int32_t& k = d < 2 ? q.x : d < 4 ? q.y : q.z;
-            k += (d & 1) ? LEAF : -LEAF;
-            if (k >= L0 && k <= L1 && find_leaf(cur, q) < 0) cand.push_back(q);
-        }
+    for (size_t l = 0; l < nl; ++l) {
+        const Org o = org_of(cur, (long)l);
+        long nb[3][2];
+        face_neighbours(cur, o, nb);
+        for (int a = 0; a < 3; ++a)
+            for (int side = 0; side < 2; ++side) {
+                const Org q = face_org(o, a, side);
+                const int32_t k = a == 0 ? q.x : a == 1 ? q.y : q.z;
+                if (k >= L0 && k <= L1 && nb[a][side] < 0) cand.push_back(q);
+            }
+    }
     std::sort(cand.begin(), cand.end());
     cand.erase(std::unique(cand.begin(), cand.end()), cand.end());
     std::vector<Org> add;
@@ -452,8 +424,8 @@ bool run_band(const fluid_sdf_grid_t* g, Band& b, int kind, const fluid_sdf_filt
         [&]() {
             if (grow) dilate(&cur, b);
             for (int i = 0; i < N; ++i) {
-                if (scheme == FLUID_SDF_TRACK_HJWENO5) norm_pass_weno(&cur, dx, b.val[b.at].data(), b.val[1 - b.at].data());
-                else norm_pass(&cur, dx, b.val[b.at].data(), b.val[1 - b.at].data());
+                if (scheme == FLUID_SDF_TRACK_HJWENO5) norm_pass<3>(&cur, dx, b.val[b.at].data(), b.val[1 - b.at].data());
+                else norm_pass<1>(&cur, dx, b.val[b.at].data(), b.val[1 - b.at].data());
                 b.at = 1 - b.at;
             }
             if (trim) trim_pass_attr(&cur, b), trimmed = true;
@@ -486,6 +458,34 @@ int64_t copy_out(const fluid_sdf_grid_t* g, const Band& b, bool trimmed, int64_t
     return (int64_t)keep.size();
 }
 
+// The tracked, the grown and the flow entry point: everything that can be refused first; the result is made in a band of our own
+// and copied last.  The count of listed leaves, or -FLUID_ERR_ARG with nothing written.
+int64_t band_filter(const fluid_sdf_grid_t* g, const fluid_sdf_attr_t* attr, int32_t kind, const fluid_sdf_filter_t* f, const fluid_sdf_track_t* t,
+                    int32_t grow, int64_t cap_leaves, int32_t* origin, float* values, uint64_t* active, int32_t* kept, uint32_t* id, float* velocity)
+{
+    if (check_list(g) != FLUID_OK || !plan::filter_ok(f) || !plan::kind_ok(kind) || !plan::width_ok(kind, f->width)) return -FLUID_ERR_ARG;
+    if (!plan::track_ok(t) || (grow != 0 && grow != 1) || (grow && !plan::grow_ok(t))) return -FLUID_ERR_ARG;
+    const bool tracked = grow || plan::tracking(t);
+    if ((tracked || plan::kind_needs_dx(kind)) && !band_ok(g)) return -FLUID_ERR_ARG;
+    if (grow ? !plan::grown_offset_ok((float)f->offset, list_dx(g)) : tracked && !plan::tracked_offset_ok((float)f->offset, g->background))
+        return -FLUID_ERR_ARG;
+    const size_t nl = (size_t)g->n_leaves;
+    if (attr && (attr->n_leaves != g->n_leaves || (nl > 0 && (!attr->id || !attr->velocity)))) return -FLUID_ERR_ARG;
+    const bool count_only = !origin && !values && !active && !id && !velocity;
+    if (!count_only) {
+        if (!origin || !values || !active || cap_leaves < 0) return -FLUID_ERR_ARG;
+        if (attr ? (!id || !velocity) : (id || velocity)) return -FLUID_ERR_ARG;
+        if (overlap({{g->origin, 12}, {g->values, 2048}, {g->active, 64}, {attr ? attr->id : nullptr, 2048}, {attr ? attr->velocity : nullptr, 6144}}, nl,
+                    {{origin, 12}, {values, 2048}, {active, 64}, {kept, 4}, {id, 2048}, {velocity, 6144}}, (size_t)cap_leaves))
+            return -FLUID_ERR_ARG;
+    }
+    if (nl == 0) return 0;
+    if (!tracked && count_only) return g->n_leaves;
+    Band b(g, attr);
+    const bool trimmed = run_band(g, b, kind, f, tracked, tracked ? t->normalize : 0, tracked && t->trim != 0, grow != 0, tracked ? t->scheme : FLUID_SDF_TRACK_FIRST_BIAS);
+    return copy_out(g, b, trimmed, cap_leaves, origin, values, active, kept, id, velocity);
+}
+
 }  // namespace
 
 extern "C" {
@@ -515,70 +515,19 @@ int fluid_sdf_filter(const fluid_sdf_grid_t* g, const fluid_sdf_filter_t* f, flo
 int64_t fluid_sdf_filter_tracked(const fluid_sdf_grid_t* g, const fluid_sdf_filter_t* f, const fluid_sdf_track_t* t, int64_t cap_leaves,
                                  int32_t* origin, float* values, uint64_t* active, int32_t* kept)
 {
-    // everything that can be refused first; the result is made in a band of our own and copied last
-    if (check_list(g) != FLUID_OK || !plan::filter_ok(f) || !plan::track_ok(t)) return -FLUID_ERR_ARG;
-    const bool tracked = plan::tracking(t);
-    if (tracked && (!plan::tracked_offset_ok((float)f->offset, g->background) || !band_ok(g))) return -FLUID_ERR_ARG;
-    const bool count_only = !origin && !values && !active;
-    if (!count_only && (!origin || !values || !active || cap_leaves < 0)) return -FLUID_ERR_ARG;
-    const size_t nl = (size_t)g->n_leaves;
-    if (!count_only && overlap({{g->origin, 12}, {g->values, 2048}, {g->active, 64}}, nl, {{origin, 12}, {values, 2048}, {active, 64}, {kept, 4}}, (size_t)cap_leaves))
-        return -FLUID_ERR_ARG;
-    if (nl == 0) return 0;
-    if (!tracked && count_only) return g->n_leaves;
-    Band b(g, nullptr);
-    bool trimmed = false;
-    if (tracked) trimmed = run_band(g, b, FLUID_SDF_FILTER_BOX, f, true, t->normalize, t->trim != 0, false, t->scheme);
-    else if (fluid_sdf_filter(g, f, b.val[0].data()) != FLUID_OK) return -FLUID_ERR_ARG;
-    return copy_out(g, b, trimmed, cap_leaves, origin, values, active, kept, nullptr, nullptr);
+    return band_filter(g, nullptr, FLUID_SDF_FILTER_BOX, f, t, 0, cap_leaves, origin, values, active, kept, nullptr, nullptr);
 }
 
 int64_t fluid_sdf_filter_grown(const fluid_sdf_grid_t* g, const fluid_sdf_attr_t* attr, const fluid_sdf_filter_t* f, const fluid_sdf_track_t* t,
                                int64_t cap_leaves, int32_t* origin, float* values, uint64_t* active, uint32_t* id, float* velocity)
 {
-    if (check_list(g) != FLUID_OK || !plan::filter_ok(f) || !plan::track_ok(t) || !plan::grow_ok(t)) return -FLUID_ERR_ARG;
-    if (!band_ok(g) || !plan::grown_offset_ok((float)f->offset, list_dx(g))) return -FLUID_ERR_ARG;
-    const size_t nl = (size_t)g->n_leaves;
-    if (attr && (attr->n_leaves != g->n_leaves || (nl > 0 && (!attr->id || !attr->velocity)))) return -FLUID_ERR_ARG;
-    const bool count_only = !origin && !values && !active && !id && !velocity;
-    if (!count_only) {
-        if (!origin || !values || !active || cap_leaves < 0) return -FLUID_ERR_ARG;
-        if (attr ? (!id || !velocity) : (id || velocity)) return -FLUID_ERR_ARG;
-        if (overlap({{g->origin, 12}, {g->values, 2048}, {g->active, 64}, {attr ? attr->id : nullptr, 2048}, {attr ? attr->velocity : nullptr, 6144}}, nl,
-                    {{origin, 12}, {values, 2048}, {active, 64}, {id, 2048}, {velocity, 6144}}, (size_t)cap_leaves))
-            return -FLUID_ERR_ARG;
-    }
-    if (nl == 0) return 0;
-    Band b(g, attr);
-    const bool trimmed = run_band(g, b, FLUID_SDF_FILTER_BOX, f, true, t->normalize, true, true, t->scheme);
-    return copy_out(g, b, trimmed, cap_leaves, origin, values, active, nullptr, id, velocity);
+    return band_filter(g, attr, FLUID_SDF_FILTER_BOX, f, t, 1, cap_leaves, origin, values, active, nullptr, id, velocity);
 }
 
 int64_t fluid_sdf_flow(const fluid_sdf_grid_t* g, const fluid_sdf_attr_t* attr, int32_t kind, const fluid_sdf_filter_t* f, const fluid_sdf_track_t* t,
                        int32_t grow, int64_t cap_leaves, int32_t* origin, float* values, uint64_t* active, uint32_t* id, float* velocity)
 {
-    // everything that can be refused first; the result is made in a band of our own and copied last
-    if (check_list(g) != FLUID_OK || !plan::filter_ok(f) || !plan::kind_ok(kind) || !plan::width_ok(kind, f->width)) return -FLUID_ERR_ARG;
-    if (!plan::track_ok(t) || (grow != 0 && grow != 1) || (grow && !plan::grow_ok(t))) return -FLUID_ERR_ARG;
-    const bool tracked = grow || plan::tracking(t);
-    if ((tracked || plan::kind_needs_dx(kind)) && !band_ok(g)) return -FLUID_ERR_ARG;
-    if (grow ? !plan::grown_offset_ok((float)f->offset, list_dx(g)) : tracked && !plan::tracked_offset_ok((float)f->offset, g->background))
-        return -FLUID_ERR_ARG;
-    const size_t nl = (size_t)g->n_leaves;
-    if (attr && (attr->n_leaves != g->n_leaves || (nl > 0 && (!attr->id || !attr->velocity)))) return -FLUID_ERR_ARG;
-    const bool count_only = !origin && !values && !active && !id && !velocity;
-    if (!count_only) {
-        if (!origin || !values || !active || cap_leaves < 0) return -FLUID_ERR_ARG;
-        if (attr ? (!id || !velocity) : (id || velocity)) return -FLUID_ERR_ARG;
-        if (overlap({{g->origin, 12}, {g->values, 2048}, {g->active, 64}, {attr ? attr->id : nullptr, 2048}, {attr ? attr->velocity : nullptr, 6144}}, nl,
-                    {{origin, 12}, {values, 2048}, {active, 64}, {id, 2048}, {velocity, 6144}}, (size_t)cap_leaves))
-            return -FLUID_ERR_ARG;
-    }
-    if (nl == 0) return 0;
-    if (!tracked && count_only) return g->n_leaves;
-    Band b(g, attr);
-    const bool trimmed = run_band(g, b, kind, f, tracked, tracked ? t->normalize : 0, tracked && t->trim != 0, grow != 0, tracked ? t->scheme : FLUID_SDF_TRACK_FIRST_BIAS);
-    return copy_out(g, b, trimmed, cap_leaves, origin, values, active, nullptr, id, velocity);
+    return band_filter(g, attr, kind, f, t, grow, cap_leaves, origin, values, active, nullptr, id, velocity);
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@ import mesh_ref
 import render_ref as rr
 import sdf_filter_ref
 import sdf_ref
+from sdf_testlib import u32
 
 SETS = mesh_ref.SETS
 EYE = (-30.0, 10.0, -40.0)                                      # outside every grid used here
@@ -82,10 +83,6 @@ def reference(key, val, bg, cam, shade=SHADE):
 def leaf_grid(fs, n, val, act, bg, R, w):
     org, v, a = sdf_ref.leaf_list(val, act, bg)
     return fs.SdfGrid(n, org, v, a, bg, R, w)
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def same(got, ref, what=7, note=""):

@@ -14,6 +14,7 @@ import attr_ref
 import mesh_ref
 import sdf_filter_ref
 import sdf_ref
+from sdf_testlib import u32
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "fluid-simulation_amd", "csrc")
@@ -23,10 +24,6 @@ FILTERS = [None] + sdf_filter_ref.FILTERS + [(1, 0, -0.9)]
 HEADER = ("ply\nformat binary_little_endian 1.0\nelement vertex {nv}\nproperty float x\nproperty float y\nproperty float z\n"
           "{vel}element face {nq}\nproperty list uchar uint vertex_indices\nend_header\n")
 VEL = "property float vx\nproperty float vy\nproperty float vz\n"
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def lists_of(fs, val, act, ids, v32, n, R, w, dx):

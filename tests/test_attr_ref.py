@@ -7,13 +7,10 @@ import pytest
 import attr_ref
 import mesh_ref
 import sdf_ref
+from sdf_testlib import u32
 
 SETS = mesh_ref.SETS
 NO_ID = attr_ref.NO_ID
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 @pytest.mark.parametrize("R,w,dx", SETS)

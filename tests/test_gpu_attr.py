@@ -13,6 +13,7 @@ import attr_ref
 import mesh_ref
 import sdf_filter_ref
 import sdf_ref
+from sdf_testlib import u32
 
 pytestmark = pytest.mark.gpu
 
@@ -20,10 +21,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SETS = mesh_ref.SETS
 ERR_ARG, ERR_STATE = 1, 3
 LEAF, ATTR = 2048 + 64 + 12, 2048 + 6144
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def reference(pos, vel, n, R, w, dx, filt=None):

@@ -12,16 +12,13 @@ import pytest
 import leaf_ref
 import vdb_reader
 from conftest import rel_l2, ROOT
+from sdf_testlib import fluid_env, u32
 
 pytestmark = pytest.mark.gpu
 
 LEAF_BYTES, HEADER_BYTES = 2048 + 12, 4      # FLUID_OUTPUT_LEAF_BYTES, FLUID_OUTPUT_HEADER_BYTES
 ERR_STATE = 3
 REBALANCED = 32                              # FLUID_PATH_DIST_REBALANCED
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def keys_of(origin):
@@ -318,10 +315,7 @@ FLUID = os.path.join(ROOT, "fluid-simulation_amd", "fluid")
 
 
 def run_fluid(fs, out, **env):
-    e = dict(os.environ, FLUID_N="32", FLUID_PPC="4", FLUID_STEPS="4", FLUID_RAW="1", FLUID_OUT=str(out / "simulation"))
-    for k in ("FLUID_OUT_DENSE", "FLUID_BLOCKS", "FLUID_DIST_SOLVE", "FLUID_SOURCE_EVERY", "FLUID_REBALANCE_EVERY", "FLUID_DEVICES"):
-        e.pop(k, None)
-    e.update(env)
+    e = fluid_env(out, 32, 4, 4, **dict({"FLUID_RAW": "1"}, **env))
     out.mkdir(exist_ok=True)
     return subprocess.run([FLUID], capture_output=True, text=True, env=e, timeout=600)
 

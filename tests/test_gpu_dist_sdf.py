@@ -14,6 +14,7 @@ import leaf_ref
 import sdf_ref
 import vdb_reader
 from conftest import ROOT
+from sdf_testlib import fluid_env, u32
 
 pytestmark = pytest.mark.gpu
 
@@ -22,10 +23,6 @@ LEAF_BYTES = 2048 + 64 + 12                               # FLUID_SDF_LEAF_BYTES
 ERR_ARG, ERR_STATE = 1, 3
 REBALANCED = 32                                           # FLUID_PATH_DIST_REBALANCED
 MODES = ["decomposed", "replicated"]
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def check_grid(g, pos, n, R, w, dx):
@@ -312,11 +309,7 @@ FLUID = os.path.join(ROOT, "fluid-simulation_amd", "fluid")
 
 
 def run_fluid(out, **env):
-    e = dict(os.environ, FLUID_N="32", FLUID_PPC="2", FLUID_STEPS="3", FLUID_OUT=str(out / "simulation"))
-    for k in ("FLUID_OUT_DENSE", "FLUID_OUT_SURFACE", "FLUID_BLOCKS", "FLUID_BLOCKS_SURFACE", "FLUID_DIST_SOLVE", "FLUID_SOURCE_EVERY",
-              "FLUID_REBALANCE_EVERY", "FLUID_DEVICES", "FLUID_RAW"):
-        e.pop(k, None)
-    e.update(env)
+    e = fluid_env(out, 32, 2, 3, **env)
     out.mkdir(exist_ok=True)
     return subprocess.run([FLUID], capture_output=True, text=True, env=e, cwd=out, timeout=600)
 

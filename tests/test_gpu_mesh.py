@@ -10,16 +10,13 @@ import pytest
 
 import mesh_ref
 import sdf_ref
+from sdf_testlib import read_ply, u32
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SETS = mesh_ref.SETS
 ERR_ARG, ERR_STATE = 1, 3
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def same(got, vert, quads, what=""):
@@ -207,18 +204,6 @@ def test_snapshots_do_not_disturb_the_steps_or_each_other(fs):
         s.close()
 
 
-def read_ply(path):
-    raw = open(path, "rb").read()
-    end = raw.index(b"end_header\n") + len(b"end_header\n")
-    head = raw[:end].decode("ascii")
-    nv = int(head.split("element vertex ")[1].split("\n")[0])
-    nq = int(head.split("element face ")[1].split("\n")[0])
-    v = np.frombuffer(raw, "<f4", 3 * nv, end).reshape(nv, 3)
-    f = np.frombuffer(raw, np.dtype([("k", "u1"), ("i", "<u4", 4)]), nq, end + 12 * nv)
-    assert end + 12 * nv + 17 * nq == len(raw)
-    return v, f
-
-
 def test_driver_writes_the_mesh(fs, tmp_path):
     """The `fluid` program with FLUID_OUT_MESH=R,W: mesh<i>.ply holds the handle's mesh of the particles of step i (taken from a
     handle that runs the same scene here) times the voxel size, and stdout and the other files are what they are without it."""
@@ -248,8 +233,8 @@ def test_driver_writes_the_mesh(fs, tmp_path):
         sim.step()
         sim.mesh_snapshot(R, w)
         v, q = sim.mesh_wait()
-        fv, ff = read_ply(tmp_path / "mesh" / f"simulation/mesh{i}.ply")
-        assert len(q) > 0 and np.array_equal(u32(fv), u32(v * np.float32(dx))) and np.array_equal(ff["i"], q) and (ff["k"] == 4).all(), i
+        fv, fq, _ = read_ply(tmp_path / "mesh" / f"simulation/mesh{i}.ply")
+        assert len(q) > 0 and np.array_equal(u32(fv), u32(v * np.float32(dx))) and np.array_equal(fq, q), i
     ref = ref_of(sim.download_particles()[0], n, R, w, dx)                      # ... and the last one is the reference's
     same((v, q), ref[0], ref[1])
     sim.close()

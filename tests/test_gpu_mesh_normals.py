@@ -14,6 +14,7 @@ import mesh_normals_ref as mn
 import mesh_ref
 import sdf_filter_ref
 import sdf_ref
+from sdf_testlib import u32
 
 pytestmark = pytest.mark.gpu
 
@@ -21,10 +22,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SETS = mesh_ref.SETS
 ERR_ARG, ERR_STATE = 1, 3
 VELOCITY, NORMALS, TRIANGLES = 1, 2, 4
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def bytes_to_host(nv, nq, what):

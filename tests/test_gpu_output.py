@@ -9,15 +9,12 @@ import numpy as np
 import pytest
 
 import leaf_ref
+from sdf_testlib import u32
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LEAF_BYTES, HEADER_BYTES = 2048 + 12, 4      # FLUID_OUTPUT_LEAF_BYTES, FLUID_OUTPUT_HEADER_BYTES
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def check_snapshot(fs, sim, lg, dense, strictly_sparse=True):

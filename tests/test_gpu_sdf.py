@@ -10,6 +10,7 @@ import pytest
 
 import sdf_ref
 import vdb_reader
+from sdf_testlib import u32
 
 pytestmark = pytest.mark.gpu
 
@@ -17,10 +18,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SETS = [(1.5, 2.5, 1.0), (3.0, 1.0, 1.0), (1.0, 2.0, 0.5), (2.0, 2.0, 1.0)]      # (R, w, dx)
 LEAF_BYTES = 2048 + 64 + 12                                                    # FLUID_SDF_LEAF_BYTES
 ERR_ARG, ERR_STATE = 1, 3
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def check_grid(g, pos, n, R, w, dx):

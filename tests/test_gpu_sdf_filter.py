@@ -2,8 +2,6 @@
 In every comparison the device list equals tests/sdf_filter_ref.py of tests/sdf_ref.py closed() — origins, masks, values as bit
 patterns — and the device mesh equals tests/mesh_ref.py of that filtered field: vertices as bit patterns, quads exactly."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,19 +9,15 @@ import pytest
 import mesh_ref
 import sdf_filter_ref
 import sdf_ref
+from sdf_testlib import read_ply, run_fluid, same_grid, u32
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SETS = mesh_ref.SETS
 FILTERS = sdf_filter_ref.FILTERS
 SCENES = ["one", "corner", "lo", "hi", "cloud"]
 ERR_ARG, ERR_STATE = 1, 3
 LEAF_BYTES = 2048 + 64 + 12
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def same_mesh(got, vert, quads, what=""):
@@ -32,12 +26,6 @@ def same_mesh(got, vert, quads, what=""):
     assert v.dtype == np.float32 and q.dtype == np.uint32
     assert np.array_equal(u32(v), u32(vert)), what
     assert np.array_equal(q, quads), what
-
-
-def same_grid(g, other, what=""):
-    assert g.n_leaves == other.n_leaves and np.array_equal(g.origin, other.origin), what
-    assert np.array_equal(g.active, other.active), what
-    assert np.array_equal(u32(g.values), u32(other.values)), what
 
 
 def ref_of(pos, n, R, w, dx, filt):
@@ -280,30 +268,6 @@ def test_blocks_filter_the_merged_list(fs, dims):
     one.close()
 
 
-def read_ply(path):
-    raw = open(path, "rb").read()
-    end = raw.index(b"end_header\n") + len(b"end_header\n")
-    head = raw[:end].decode("ascii")
-    nv = int(head.split("element vertex ")[1].split("\n")[0])
-    nq = int(head.split("element face ")[1].split("\n")[0])
-    v = np.frombuffer(raw, "<f4", 3 * nv, end).reshape(nv, 3)
-    f = np.frombuffer(raw, np.dtype([("k", "u1"), ("i", "<u4", 4)]), nq, end + 12 * nv)
-    assert end + 12 * nv + 17 * nq == len(raw)
-    return v, f
-
-
-def run_fluid(d, n, ppc, steps, **extra):
-    d.mkdir()
-    env = dict(os.environ, FLUID_N=str(n), FLUID_PPC=str(ppc), FLUID_STEPS=str(steps), FLUID_OUT=str(d / "simulation"))
-    for k in ("FLUID_OUT_MESH", "FLUID_OUT_SURFACE", "FLUID_OUT_SMOOTH", "FLUID_OUT_DENSE", "FLUID_BLOCKS", "FLUID_BLOCKS_SURFACE", "FLUID_SOURCE_EVERY",
-              "FLUID_RAW", "FLUID_DIST_SOLVE", "FLUID_REBALANCE_EVERY", "FLUID_DEVICES"):
-        env.pop(k, None)
-    env.update(extra)
-    r = subprocess.run([os.path.join(ROOT, "fluid-simulation_amd", "fluid")], capture_output=True, text=True, env=env, cwd=d, timeout=300)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
-    return [ln for ln in r.stdout.splitlines() if not ln.startswith("Time Taken")]
-
-
 def test_driver_writes_the_smoothed_mesh(fs, tmp_path):
     """The `fluid` program with FLUID_OUT_MESH and FLUID_OUT_SMOOTH=1,2,-0.25: mesh<i>.ply holds the handle's filtered mesh of the
     particles of step i times the voxel size; stdout and the other files are what they are without FLUID_OUT_SMOOTH."""
@@ -323,9 +287,9 @@ def test_driver_writes_the_smoothed_mesh(fs, tmp_path):
         sim.step()
         sim.mesh_snapshot(R, w, smooth=filt)
         v, q = sim.mesh_wait()
-        fv, ff = read_ply(tmp_path / "smooth" / f"simulation/mesh{i}.ply")
-        assert len(q) > 0 and np.array_equal(u32(fv), u32(v * np.float32(dx))) and np.array_equal(ff["i"], q) and (ff["k"] == 4).all(), i
-        pv, _ = read_ply(tmp_path / "plain" / f"simulation/mesh{i}.ply")
+        fv, fq, _ = read_ply(tmp_path / "smooth" / f"simulation/mesh{i}.ply")
+        assert len(q) > 0 and np.array_equal(u32(fv), u32(v * np.float32(dx))) and np.array_equal(fq, q), i
+        pv, _, _ = read_ply(tmp_path / "plain" / f"simulation/mesh{i}.ply")
         assert pv.shape != fv.shape or not np.array_equal(u32(pv), u32(fv))       # the smoothing did something
     _, ref = ref_of(sim.download_particles()[0], n, R, w, dx, filt)              # ... and the last one is the reference's
     same_mesh((v, q), ref[0], ref[1])

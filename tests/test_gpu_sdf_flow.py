@@ -11,22 +11,13 @@ import attr_ref
 import mesh_ref
 import sdf_flow_ref as R
 import sdf_ref
+from sdf_testlib import run_fluid, same_grid, u32
 
 pytestmark = pytest.mark.gpu
 
 SET = (2.0, 2.0, 1.0)                                     # R, w, dx
 FORMS = [("untracked", 0, False, False), ("tracked", 3, True, False), ("grown", 3, True, True)]   # name, N, trim, grow
 ERR_ARG, ERR_STATE = 1, 3
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def same_grid(g, other, what=""):
-    assert g.n_leaves == other.n_leaves and np.array_equal(g.origin, other.origin), (what, g.n_leaves, other.n_leaves)
-    assert np.array_equal(g.active, other.active), what
-    assert np.array_equal(u32(g.values), u32(other.values)), what
 
 
 def is_dense(g, dense, bg, what=""):
@@ -191,22 +182,6 @@ def test_decomposed_handle_refuses(fs):
         assert "fluid_sdf_flow" in fs.lib.fluid_last_error().decode()
     sim.close()
     grp.close()
-
-
-def run_fluid(d, n, ppc, steps, **extra):
-    import os
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    d.mkdir()
-    env = dict(os.environ, FLUID_N=str(n), FLUID_PPC=str(ppc), FLUID_STEPS=str(steps), FLUID_OUT=str(d / "simulation"))
-    for k in ("FLUID_OUT_MESH", "FLUID_OUT_SURFACE", "FLUID_OUT_SMOOTH", "FLUID_OUT_SMOOTH_KIND", "FLUID_OUT_TRACK", "FLUID_OUT_DENSE", "FLUID_BLOCKS",
-              "FLUID_BLOCKS_SURFACE", "FLUID_BLOCKS_MESH", "FLUID_BLOCKS_MESH_VEL", "FLUID_SOURCE_EVERY", "FLUID_RAW", "FLUID_DIST_SOLVE", "FLUID_REBALANCE_EVERY",
-              "FLUID_DEVICES", "FLUID_OUT_RENDER", "FLUID_BLOCKS_RENDER", "FLUID_OUT_MESH_VEL", "FLUID_OUT_MESH_NORMALS", "FLUID_OUT_MESH_TRIS"):
-        env.pop(k, None)
-    env.update(extra)
-    r = subprocess.run([os.path.join(root, "fluid-simulation_amd", "fluid")], capture_output=True, text=True, env=env, cwd=d, timeout=300)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
-    return [ln for ln in r.stdout.splitlines() if not ln.startswith("Time Taken")]
 
 
 def test_driver_writes_the_curvature_flow_on_one_gpu_and_on_blocks(fs, tmp_path):

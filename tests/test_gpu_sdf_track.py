@@ -13,6 +13,7 @@ import mesh_ref
 import sdf_filter_ref
 import sdf_ref
 import sdf_track_ref
+from sdf_testlib import fluid_env, read_ply, run_fluid, same_grid, same_mesh, u32
 
 pytestmark = pytest.mark.gpu
 
@@ -23,23 +24,6 @@ SCENES = ["one", "corner", "lo", "hi", "cloud"]
 ERR_ARG, ERR_STATE = 1, 3
 LEAF_BYTES = 2048 + 64 + 12
 NO_ID = 0xFFFFFFFF
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def same_mesh(got, vert, quads, what=""):
-    v, q = got[0], got[1]
-    assert v.shape == vert.shape and q.shape == quads.shape, (what, v.shape, vert.shape, q.shape, quads.shape)
-    assert np.array_equal(u32(v), u32(vert)), what
-    assert np.array_equal(q, quads), what
-
-
-def same_grid(g, other, what=""):
-    assert g.n_leaves == other.n_leaves and np.array_equal(g.origin, other.origin), what
-    assert np.array_equal(g.active, other.active), what
-    assert np.array_equal(u32(g.values), u32(other.values)), what
 
 
 def args_of(case, dx):
@@ -360,35 +344,6 @@ def test_blocks_track_the_merged_list(fs, dims):
     one.close()
 
 
-def read_ply(path):
-    raw = open(path, "rb").read()
-    end = raw.index(b"end_header\n") + len(b"end_header\n")
-    head = raw[:end].decode("ascii")
-    nv = int(head.split("element vertex ")[1].split("\n")[0])
-    nq = int(head.split("element face ")[1].split("\n")[0])
-    v = np.frombuffer(raw, "<f4", 3 * nv, end).reshape(nv, 3)
-    f = np.frombuffer(raw, np.dtype([("k", "u1"), ("i", "<u4", 4)]), nq, end + 12 * nv)
-    assert end + 12 * nv + 17 * nq == len(raw)
-    return v, f
-
-
-def fluid_env(d, n, ppc, steps, **extra):
-    env = dict(os.environ, FLUID_N=str(n), FLUID_PPC=str(ppc), FLUID_STEPS=str(steps), FLUID_OUT=str(d / "simulation"))
-    for k in ("FLUID_OUT_MESH", "FLUID_OUT_SURFACE", "FLUID_OUT_SMOOTH", "FLUID_OUT_TRACK", "FLUID_OUT_DENSE", "FLUID_BLOCKS", "FLUID_BLOCKS_SURFACE",
-              "FLUID_BLOCKS_MESH", "FLUID_BLOCKS_MESH_VEL", "FLUID_SOURCE_EVERY", "FLUID_RAW", "FLUID_DIST_SOLVE", "FLUID_REBALANCE_EVERY", "FLUID_DEVICES"):
-        env.pop(k, None)
-    env.update(extra)
-    return env
-
-
-def run_fluid(d, n, ppc, steps, **extra):
-    d.mkdir()
-    r = subprocess.run([os.path.join(ROOT, "fluid-simulation_amd", "fluid")], capture_output=True, text=True, env=fluid_env(d, n, ppc, steps, **extra),
-                       cwd=d, timeout=300)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
-    return [ln for ln in r.stdout.splitlines() if not ln.startswith("Time Taken")]
-
-
 def test_driver_writes_the_tracked_mesh(fs, tmp_path):
     """The `fluid` program with FLUID_OUT_MESH, FLUID_OUT_SMOOTH=1,2,-0.25 and FLUID_OUT_TRACK=3: mesh<i>.ply holds the handle's
     tracked mesh of the particles of step i times the voxel size; stdout and the other files are what they are without it."""
@@ -409,9 +364,9 @@ def test_driver_writes_the_tracked_mesh(fs, tmp_path):
         sim.step()
         sim.mesh_snapshot(R, w, smooth=(1, 2, -0.25))
         v, q = sim.mesh_wait()
-        fv, ff = read_ply(tmp_path / "track" / f"simulation/mesh{i}.ply")
-        assert len(q) > 0 and np.array_equal(u32(fv), u32(v * np.float32(dx))) and np.array_equal(ff["i"], q) and (ff["k"] == 4).all(), i
-        pv, _ = read_ply(tmp_path / "smooth" / f"simulation/mesh{i}.ply")
+        fv, fq, _ = read_ply(tmp_path / "track" / f"simulation/mesh{i}.ply")
+        assert len(q) > 0 and np.array_equal(u32(fv), u32(v * np.float32(dx))) and np.array_equal(fq, q), i
+        pv, _, _ = read_ply(tmp_path / "smooth" / f"simulation/mesh{i}.ply")
         assert pv.shape != fv.shape or not np.array_equal(u32(pv), u32(fv))       # the tracking did something
     _, ref, _ = ref_of(sim.download_particles()[0], n, R, w, dx, case)           # ... and the last one is the reference's
     same_mesh((v, q), ref[0], ref[1])
@@ -454,9 +409,9 @@ def test_driver_on_blocks_writes_the_tracked_mesh(fs, tmp_path):
         merged = fs.merge_sdf_grids([r[i][0] for r in res])
         host, _ = fs.sdf_filter_tracked(merged, filt, tr)
         hm = fs.sdf_mesh(host)
-        fv, ff = read_ply(tmp_path / "track" / f"simulation/mesh{i}.ply")
-        assert len(hm.quads) > 0 and np.array_equal(u32(fv), u32(hm.vertices * np.float32(dx))) and np.array_equal(ff["i"], hm.quads), i
-        pv, _ = read_ply(tmp_path / "plain" / f"simulation/mesh{i}.ply")
+        fv, fq, _ = read_ply(tmp_path / "track" / f"simulation/mesh{i}.ply")
+        assert len(hm.quads) > 0 and np.array_equal(u32(fv), u32(hm.vertices * np.float32(dx))) and np.array_equal(fq, hm.quads), i
+        pv, _, _ = read_ply(tmp_path / "plain" / f"simulation/mesh{i}.ply")
         assert pv.shape != fv.shape or not np.array_equal(u32(pv), u32(fv))       # the tracking did something
         _, ref, _ = ref_of(np.concatenate([r[i][1] for r in res]), n, R, w, dx, case)
         same_mesh((hm.vertices, hm.quads), ref[0], ref[1], f"step {i}")

@@ -15,6 +15,7 @@ import sdf_flow_ref
 import sdf_grow_ref
 import sdf_ref
 import sdf_weno_ref as W
+from sdf_testlib import same_grid, same_mesh, u32
 
 pytestmark = pytest.mark.gpu
 
@@ -24,23 +25,6 @@ ERR_ARG, ERR_STATE = 1, 3
 LEAF_BYTES = 2048 + 64 + 12
 NO_ID = 0xFFFFFFFF
 HJ = W.HJWENO5
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def same_mesh(got, vert, quads, what=""):
-    v, q = got[0], got[1]
-    assert v.shape == vert.shape and q.shape == quads.shape, (what, v.shape, vert.shape, q.shape, quads.shape)
-    assert np.array_equal(u32(v), u32(vert)), what
-    assert np.array_equal(q, quads), what
-
-
-def same_grid(g, other, what=""):
-    assert g.n_leaves == other.n_leaves and np.array_equal(g.origin, other.origin), (what, g.n_leaves, other.n_leaves)
-    assert np.array_equal(g.active, other.active), what
-    assert np.array_equal(u32(g.values), u32(other.values)), what
 
 
 def same_leaves(g, leaves, what=""):

@@ -10,15 +10,12 @@ import numpy as np
 import pytest
 
 import leaf_ref
+from sdf_testlib import u32
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "fluid-simulation_amd", "csrc")
 DIMS = {1: (1, 1, 1), 2: (2, 1, 1), 4: (1, 2, 2), 8: (2, 2, 2)}
 ERR_ARG = 1
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def cut_of(n):

@@ -8,13 +8,10 @@ import pytest
 import mesh_normals_ref as mn
 import mesh_ref
 import sdf_ref
+from sdf_testlib import u32
 
 SETS = mesh_ref.SETS
 N = 32
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 @pytest.fixture(autouse=True)

@@ -12,24 +12,13 @@ import pytest
 import mesh_ref
 import sdf_filter_ref
 import sdf_ref
+from sdf_testlib import grid_of, u32
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "fluid-simulation_amd", "csrc")
 ERR_ARG = 1
 SCENES = ["one", "corner", "lo", "hi", "cloud"]
 FILTERS = sdf_filter_ref.FILTERS
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def grid_of(fs, name, n, R, w, dx):
-    """The unfiltered scene as an SdfGrid."""
-    _, val, act, bg, _ = sdf_filter_ref.scene(name, n, R, w, dx, (1, 0, 0.0))     # (1, 0, 0) is the identity
-    fR, fw = sdf_ref.constants(R, w, dx)[:2]
-    org, v, a = sdf_ref.leaf_list(val, act, bg)
-    return fs.SdfGrid(n, org, v, a, bg, fR, fw)
 
 
 @pytest.mark.parametrize("R,w,dx", mesh_ref.SETS)

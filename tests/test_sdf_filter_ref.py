@@ -4,12 +4,9 @@ import numpy as np
 
 import mesh_ref
 import sdf_filter_ref as R
+from sdf_testlib import u32
 
 F = np.float32
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def cloud():

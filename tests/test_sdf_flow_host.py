@@ -14,6 +14,7 @@ import pytest
 import attr_ref
 import sdf_flow_ref as R
 import sdf_ref
+from sdf_testlib import lists_of, u32
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "fluid-simulation_amd", "csrc")
@@ -21,19 +22,6 @@ ERR_ARG = 1
 SET = (2.0, 2.0, 1.0)                                     # R, w, dx
 FORMS = [("untracked", 0, False, False, -0.25), ("tracked", 3, True, False, 0.6), ("grown", 3, True, True, -0.6)]   # name, N, trim, grow, offset / dx
 KS = [0, 1, 2, 3]
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def lists_of(fs, name, n, Rad, w, dx):
-    """The unfiltered scene as (SdfGrid, SdfAttr)."""
-    _, val, act, ids, v32, bg = R.base(name, n, Rad, w, dx)
-    fR, fw = sdf_ref.constants(Rad, w, dx)[:2]
-    org, v, a = sdf_ref.leaf_list(val, act, bg)
-    li, lv = attr_ref.leaf_attr(ids, v32, org)
-    return fs.SdfGrid(n, org, v, a, bg, fR, fw), fs.SdfAttr(li, lv)
 
 
 def expected(name, n, Rad, w, dx, kind, W, K, units, N, trim, grow):
@@ -53,7 +41,7 @@ def same(out, oa, exp):
 
 
 def run_forms(fs, name, n, Rad, w, dx, kind, W):
-    g, at = lists_of(fs, name, n, Rad, w, dx)
+    g, at = lists_of(fs, R.base, name, n, Rad, w, dx)
     assert g.n_leaves > 0
     for form, N, trim, grow, units in FORMS:
         track = (N, trim) if N else None
@@ -108,7 +96,7 @@ def test_the_leaf_corner_scene_feeds_edge_and_corner_leaves():
 
 def test_kind_box_is_the_three_host_functions(fs):
     n, (Rad, w, dx) = 16, SET
-    g, at = lists_of(fs, "cloud", n, Rad, w, dx)
+    g, at = lists_of(fs, R.base, "cloud", n, Rad, w, dx)
     for filt in [(1, 1, 0.0), (2, 2, 0.5), (1, 0, -0.25), (4, 3, 0.0), (1, 0, 0.0)]:
         a = fs.sdf_filter(g, *filt)
         b = fs.sdf_flow(g, "box", filt)
@@ -135,7 +123,7 @@ def raw_call(fs, g, attr, kind, filt, track, grow, cap, org, val, act, ids, vel)
 
 def test_count_only_and_refusals(fs):
     n, (Rad, w, dx) = 32, SET
-    g, at = lists_of(fs, "leafcorner", n, Rad, w, dx)
+    g, at = lists_of(fs, R.base, "leafcorner", n, Rad, w, dx)
     nl = g.n_leaves
     tr = (3, 1, 0)
     none5 = (None,) * 5

@@ -8,12 +8,9 @@ import sdf_flow_ref as R
 import sdf_grow_ref as G
 import sdf_ref
 import sdf_track_ref
+from sdf_testlib import u32
 
 F = np.float32
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=F).view(np.uint32)
 
 
 def test_a_dyadic_plane_is_a_fixed_point_of_laplacian_and_curvature():

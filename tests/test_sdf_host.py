@@ -11,14 +11,11 @@ import pytest
 
 import sdf_ref
 import vdb_reader
+from sdf_testlib import u32
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "fluid-simulation_amd", "csrc")
 ERR_ARG = 1
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def hand_made(fs, n, bg=np.float32(2.5)):

@@ -10,15 +10,12 @@ import numpy as np
 import pytest
 
 import sdf_ref
+from sdf_testlib import u32
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "fluid-simulation_amd", "csrc")
 SETS = [(1.5, 2.5, 1.0), (3.0, 1.0, 1.0), (1.0, 2.0, 0.5), (2.0, 2.0, 1.0)]      # (R, w, dx): those of test_gpu_sdf.py
 ERR_ARG = 1
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def particles(n):

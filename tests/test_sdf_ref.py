@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import sdf_ref
+from sdf_testlib import u32
 
 # (R, w, dx); the first has R + w > 4: refused by the C ABI, valid for the reference
 SETS = [(1.5, 3.0, 1.0), (1.5, 2.5, 1.0), (3.0, 1.0, 1.0), (1.0, 2.0, 0.5), (2.0, 2.0, 1.0)]
@@ -17,10 +18,6 @@ def particles():
     p = rng.uniform(lo - 1.0, hi + 1.0, size=(60, 3))      # a few have their base cell outside the grid
     p[:20] = rng.uniform(-3.0, 3.0, size=(20, 3))           # a clump: voxels deep inside (m <= min2 when R > w)
     return np.vstack([p, [[2.0, -3.0, 1.0]]])                # one exactly on a voxel
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 @pytest.mark.parametrize("R,w,dx", SETS)

@@ -9,13 +9,10 @@ import mesh_ref
 import sdf_filter_ref
 import sdf_ref
 import sdf_track_ref as T
+from sdf_testlib import u32
 
 F = np.float32
 SCENES = ["one", "corner", "lo", "hi", "cloud"]
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def leaves(val, act, bg):

@@ -17,12 +17,9 @@ import mesh_ref
 import sdf_filter_ref
 import sdf_track_ref
 import sdf_weno_ref as W
+from sdf_testlib import u32
 
 F = np.float32
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=F).view(np.uint32)
 
 
 def septuples(count, seed):
