@@ -73,6 +73,11 @@ class SdfTrack(C.Structure):
     _fields_ = [("normalize", C.c_int32), ("trim", C.c_int32), ("scheme", C.c_int32)]
 
 
+class SdfSurface(C.Structure):
+    """fluid_sdf_surface_t: which level set the particles give (include/fluid_hip.h, "liquid surface, averaged positions")."""
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("influence", C.c_double)]
+
+
 class MeshC(C.Structure):
     """fluid_mesh_t: the surface nets of the level set (include/fluid_hip.h, "liquid surface as a mesh")."""
     _fields_ = [("n", C.c_int32), ("n_vertices", C.c_int64), ("n_quads", C.c_int64), ("radius", C.c_float),
@@ -240,6 +245,8 @@ SYMBOLS = [
     ("fluid_sdf_set_filter_kind", C.c_int, [_P, C.c_int32]),
     ("fluid_sdf_flow", C.c_int64, [C.POINTER(SdfGridC), C.POINTER(SdfAttrC), C.c_int32, C.POINTER(SdfFilter), C.POINTER(SdfTrack), C.c_int32, C.c_int64,
                                    _P, _P, _P, _P, _P]),
+    ("fluid_sdf_set_surface", C.c_int, [_P, C.POINTER(SdfSurface)]),
+    ("fluid_particles_surface", C.c_int, [C.c_int32, C.c_double, C.c_int64, _P, C.POINTER(SdfParams), C.POINTER(SdfSurface), _P, _P]),
     ("fluid_mesh_snapshot", C.c_int, [_P, C.POINTER(SdfParams)]),
     ("fluid_mesh_wait", C.c_int, [_P, C.POINTER(MeshC)]),
     ("fluid_mesh_stats", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

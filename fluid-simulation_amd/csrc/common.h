@@ -354,6 +354,10 @@ void launch_sdf_search_attr(hipStream_t st, const SdfGeom& g, const int* start, 
 void launch_sdf_pack_attr(hipStream_t st, const SdfGeom& g, const int* flags, const int* slot, const float* tv, const uint64_t* tm, float* values,
                           uint64_t* active, int* origin, const uint32_t* tid, const float* tvel, uint32_t* ids, float* vel,
                           const float* tmin = nullptr, float* dist2 = nullptr);   // tmin / dist2: nullptr, or the squared distances as well
+// "liquid surface, averaged positions" (kernels_sdf_avg.hip): the search whose values come from the minimum and the weighted integer
+// sums of the particles within hf; h2 = hf * hf, ih2 = 1.0f / h2.  Same inputs and outputs as launch_sdf_search
+void launch_sdf_search_avg(hipStream_t st, const SdfGeom& g, float h2, float ih2, const int* start, const double* sx, const double* sy,
+                           const double* sz, float* tv, uint64_t* tm, int* flags);
 // box filter of that level set (kernels_sdf_filter.hip): one pass of width W along `axis` from src to dst (both 512 values per leaf of
 // the range; only flagged leaves are read or written), `off` added to the active voxels' results (0.0f: none); and the offset alone
 void launch_sdf_box(hipStream_t st, const SdfGeom& g, int axis, int W, float off, const int* flags, const uint64_t* tm, const float* src,

@@ -95,6 +95,12 @@
 // first-order upwind, or HJWENO5, the library's own default (include/fluid_hip.h, "liquid surface, renormalised: HJWENO5").  One GPU
 // through fluid_sdf_set_track, a block run through the scheme field of the track its host function is given.  Refused with another
 // word or without FLUID_OUT_TRACK, before any handle is created.
+//   FLUID_OUT_SURFACE_KIND=spheres|averaged[,H] (unset: spheres; H defaults to 3) — the level set FLUID_OUT_SURFACE, FLUID_OUT_MESH and
+// FLUID_OUT_RENDER take from the particles: the union of spheres, or the distance to the weighted average of the particle positions
+// within H voxels, 0 < H <= 4 (include/fluid_hip.h, "liquid surface, averaged positions"), through fluid_sdf_set_surface; the
+// filters of FLUID_OUT_SMOOTH follow it as they follow the spheres.  One GPU only.  Refused with another word, an H outside the
+// limits, none of the three set, with FLUID_BLOCKS (a rank record of the averaged surface and its merge are not built) or with
+// FLUID_OUT_MESH_VEL (an average of positions has no closest particle), before any handle is created.
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -914,6 +920,32 @@ int main(int, char**)
         }
         tk.scheme = word == "hjweno5" ? FLUID_SDF_TRACK_HJWENO5 : FLUID_SDF_TRACK_FIRST_BIAS;
     }
+    fluid_sdf_surface_t skind{FLUID_SDF_SURFACE_SPHERES, 0, 0.0};
+    if (const char* senv = getenv("FLUID_OUT_SURFACE_KIND"); senv && *senv) {
+        const std::string v = senv;
+        const size_t comma = v.find(',');
+        const std::string word = v.substr(0, comma);
+        double H = 3.0;
+        char tail = 0;
+        if ((word != "spheres" && word != "averaged") || (comma != std::string::npos && (word != "averaged" || sscanf(v.c_str() + comma + 1, "%lf%c", &H, &tail) != 1)) ||
+            !(H > 0) || !((float)H > 0.0f) || !((float)H <= 4.0f)) {
+            std::cerr << "FLUID_OUT_SURFACE_KIND must be spheres or averaged[,H] (influence radius in voxels, 0 < H <= 4), e.g. averaged,3" << std::endl;
+            return 1;
+        }
+        if (blocks && *blocks) {
+            std::cerr << "FLUID_OUT_SURFACE_KIND cannot be combined with FLUID_BLOCKS: the averaged surface is one-GPU only (a rank record would carry the minimum and the four sums; that merge is not built)" << std::endl;
+            return 1;
+        }
+        if (mesh_vel) {
+            std::cerr << "FLUID_OUT_SURFACE_KIND cannot be combined with FLUID_OUT_MESH_VEL: an average of positions has no closest particle to take a velocity from" << std::endl;
+            return 1;
+        }
+        if (!surface && !mesh && !render) {
+            std::cerr << "FLUID_OUT_SURFACE_KIND chooses the level set FLUID_OUT_SURFACE, FLUID_OUT_MESH or FLUID_OUT_RENDER take: none of them is set" << std::endl;
+            return 1;
+        }
+        if (word == "averaged") skind = fluid_sdf_surface_t{FLUID_SDF_SURFACE_AVERAGED, 0, H};
+    }
     if (track) bc.track = true, bc.tk = tk, bc.grow = track_grow;
     if (blocks && *blocks) {
         char tail = 0;
@@ -946,6 +978,10 @@ int main(int, char**)
     }
     if (sim && smooth_kind != FLUID_SDF_FILTER_BOX && fluid_sdf_set_filter_kind(sim, smooth_kind) != FLUID_OK) {
         std::cerr << "fluid_sdf_set_filter_kind: " << fluid_last_error() << std::endl;
+        return 1;
+    }
+    if (sim && skind.kind != FLUID_SDF_SURFACE_SPHERES && fluid_sdf_set_surface(sim, &skind) != FLUID_OK) {
+        std::cerr << "fluid_sdf_set_surface: " << fluid_last_error() << std::endl;
         return 1;
     }
     if (sim && track && fluid_sdf_set_track(sim, &tk) != FLUID_OK) {

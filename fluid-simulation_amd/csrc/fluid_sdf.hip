@@ -44,6 +44,11 @@
 // half runs that kind's one pass per iteration in place of the three box passes: one launch, ping-pong between the same two value
 // buffers; tracks, growing and the offset follow it exactly as they follow a box iteration.
 //
+// fluid_sdf_set_surface ("liquid surface, averaged positions"; kernels_sdf_avg.hip): with kind AVERAGED the front half launches
+// k_sdf_search_avg in place of k_sdf_search, behind the same bin, scan and scatter; tv / tm / flags mean what they meant, so filters,
+// tracks, growth, pack, mesh and ray caster follow unchanged.  Attribute snapshots and the rank records of decomposed runs are
+// refused under it (FLUID_ERR_STATE).
+//
 // fluid_sdf_snapshot_attr / fluid_mesh_snapshot_attr ("liquid surface, attributes"): the scatter also writes each sorted position's
 // index in the live arrays (ssrc), the search keeps the closest particle beside the minimum and writes its id and velocity per voxel
 // (tid, tvel), and the pack lists them.  ssrc, tid and tvel exist from the handle's first attribute snapshot on.  An attribute
@@ -58,6 +63,7 @@
 // slot keeps room for the longest record per leaf it has held (wide = 0, 1, 2).
 #include "sim.h"
 #include "sdf_filter_plan.h"
+#include "sdf_avg_def.h"
 
 using namespace fl;
 #define fail fluid_fail
@@ -86,6 +92,7 @@ struct SdfState {
     bool grown = false;
     bool track_grow = false;   // fluid_sdf_set_track_grow
     int kind = FLUID_SDF_FILTER_BOX;   // fluid_sdf_set_filter_kind
+    fluid_sdf_surface_t surface{FLUID_SDF_SURFACE_SPHERES, 0, 0.0};   // fluid_sdf_set_surface
     // attributes: index in the live arrays per sorted position (part_cap), winner's id (leaf_cap x 512) and velocity (leaf_cap x 3 x 512)
     // per voxel: allocated once an attribute snapshot was asked for
     int* ssrc = nullptr;
@@ -110,6 +117,9 @@ static const char* const SDF_FILT_SINGLE = "filtered level-set snapshots are sin
 
 static const char* const SDF_GROW_SINGLE = "grown level-set snapshots are single-GPU only: a decomposed handle's filter runs on the merged list on the host (fluid_sdf_filter_grown)";
 static const char* const SDF_KIND_SINGLE = "level-set flows are single-GPU only: a decomposed handle's filter runs on the merged list on the host (fluid_sdf_flow)";
+static const char* const SDF_AVG_SINGLE = "the averaged-position surface is single-GPU only: a rank record would carry the minimum and the four sums, and that merge is not built";
+static const char* const SDF_AVG_ATTR = "the averaged-position surface carries no attributes: an average of positions has no closest particle (fluid_sdf_set_surface)";
+static const char* const SDF_AVG_DIST = "fluid_dist_sdf_snapshot gives the spheres' rank record: the averaged-position surface has none (fluid_sdf_set_surface)";
 static const char* const SDF_TRACK_SINGLE = "tracked level-set snapshots are single-GPU only: a decomposed handle's filter runs on the merged list on the host (fluid_sdf_filter_tracked)";
 
 static int sdf_init(fluid_sim* s)
@@ -261,6 +271,10 @@ int fl::sdf_begin(fluid_sim* s, const fluid_sdf_params_t* p, SdfFront* f, const 
     f->filt = filt, f->dilate = 4;
     f->attr = false, f->dist2 = false;
     f->tm = nullptr, f->tid = nullptr, f->tvel = nullptr, f->tmin = nullptr;
+    const fluid_sdf_surface_t& sf = s->sdf->surface;
+    f->averaged = sf.kind == FLUID_SDF_SURFACE_AVERAGED;
+    const adef::Consts hc = f->averaged ? adef::consts(sf.influence) : adef::Consts{0.0f, 0.0f};
+    f->h2 = hc.h2, f->ih2 = hc.ih2;
     return FLUID_OK;
 }
 
@@ -269,6 +283,7 @@ int fl::sdf_front(fluid_sim* s, SdfFront* f)
     SdfState* o = s->sdf;
     SdfGeom& g = f->g;
     int rc;
+    if (f->averaged && f->attr) return fail(FLUID_ERR_STATE, SDF_AVG_ATTR);
     const Particles live = s->pa.shifted(s->p_off);
     int* box = o->h_small;
     if (s->np > 0) {
@@ -298,7 +313,8 @@ int fl::sdf_front(fluid_sim* s, SdfFront* f)
         launch_sdf_count(s->st, s->np, live, g, o->cnt, o->place, s->dist);
         launch_exclusive_scan(s->st, o->cnt, o->start, cells + 1, o->cell_sums, o->d_small + 6);   // start[cells] = the counted particles
         launch_sdf_scatter(s->st, s->np, live, g, o->start, o->place, sx, sy, sz, f->attr ? o->ssrc : nullptr);
-        if (f->attr) launch_sdf_search_attr(s->st, g, o->start, sx, sy, sz, o->tv, o->tm, o->flags, o->ssrc, live, o->tid, o->tvel, f->dist2 ? o->tmin : nullptr);
+        if (f->averaged) launch_sdf_search_avg(s->st, g, f->h2, f->ih2, o->start, sx, sy, sz, o->tv, o->tm, o->flags);
+        else if (f->attr) launch_sdf_search_attr(s->st, g, o->start, sx, sy, sz, o->tv, o->tm, o->flags, o->ssrc, live, o->tid, o->tvel, f->dist2 ? o->tmin : nullptr);
         else launch_sdf_search(s->st, g, o->start, sx, sy, sz, o->tv, o->tm, o->flags, o->count_visits ? o->visits : nullptr);
         f->any = true;
         f->tv = o->tv, f->flags = o->flags, f->list = o->flags;
@@ -456,6 +472,8 @@ static int sdf_stats(fluid_sim* s, int64_t* leaves_in_grid, int64_t* leaves_list
     return FLUID_OK;
 }
 
+static bool sdf_averaged(const fluid_sim* s) { return s->sdf && s->sdf->surface.kind == FLUID_SDF_SURFACE_AVERAGED; }
+
 void fl::sdf_move(fluid_sim* from, fluid_sim* to)
 {
     sdf_free(to);
@@ -509,6 +527,20 @@ int fluid_sdf_set_filter_kind(fluid_sim_t* s, int32_t kind)
     return FLUID_OK;
 }
 
+int fluid_sdf_set_surface(fluid_sim_t* s, const fluid_sdf_surface_t* sf)
+{
+    if (int rc = snap_guard(s, SDF_AVG_SINGLE)) return rc;
+    if (sf && sf->kind != FLUID_SDF_SURFACE_SPHERES) {
+        if (sf->kind != FLUID_SDF_SURFACE_AVERAGED || sf->reserved != 0 || !adef::influence_ok(sf->influence))
+            return fail(FLUID_ERR_ARG, "level-set surface: kind FLUID_SDF_SURFACE_SPHERES or _AVERAGED, reserved 0 and 0 < influence <= 4 (voxels) are required");
+    }
+    HIPCHK(hipSetDevice(s->prm.device));
+    if (int rc = sdf_init(s)) return rc;
+    const bool avg = sf && sf->kind == FLUID_SDF_SURFACE_AVERAGED;
+    s->sdf->surface = avg ? *sf : fluid_sdf_surface_t{FLUID_SDF_SURFACE_SPHERES, 0, 0.0};
+    return FLUID_OK;
+}
+
 int fluid_sdf_wait(fluid_sim_t* s, fluid_sdf_grid_t* out)
 {
     int rc = snap_guard(s, SDF_SINGLE);
@@ -536,6 +568,7 @@ int fluid_sdf_stats(fluid_sim_t* s, int64_t* leaves_in_grid, int64_t* leaves_lis
 int fluid_dist_sdf_snapshot(fluid_sim_t* s, const fluid_sdf_params_t* p)
 {
     if (!s) return fail(FLUID_ERR_ARG, "null handle");
+    if (sdf_averaged(s)) return fail(FLUID_ERR_STATE, SDF_AVG_DIST);
     return sdf_capture(s, p);
 }
 
@@ -548,6 +581,7 @@ int fluid_dist_sdf_wait(fluid_sim_t* s, fluid_sdf_grid_t* out)
 int fluid_dist_sdf_snapshot_attr(fluid_sim_t* s, const fluid_sdf_params_t* p)
 {
     if (!s) return fail(FLUID_ERR_ARG, "null handle");
+    if (sdf_averaged(s)) return fail(FLUID_ERR_STATE, SDF_AVG_DIST);
     return sdf_capture(s, p, nullptr, 2);
 }
 

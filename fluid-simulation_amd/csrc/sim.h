@@ -322,6 +322,8 @@ struct SdfFront {
     const float* tvel;    // [leaf][axis][512] velocities (both stale where flags[j] == 0; nullptr without attr)
     bool dist2;           // with attr: the search also writes m per voxel (set by the caller after sdf_begin)
     const float* tmin;    // dist2: 512 per leaf of the range, m where active and +inf elsewhere (stale where flags[j] == 0)
+    bool averaged;        // "liquid surface, averaged positions": the handle's fluid_sdf_set_surface setting, copied by sdf_begin,
+    float h2, ih2;        // and its constants; sdf_front refuses it together with attr
 };
 // limits of the parameters (and of the filter, when one is given), the state, the constants of g
 int sdf_begin(fluid_sim* s, const fluid_sdf_params_t* p, SdfFront* f, const fluid_sdf_filter_t* filt = nullptr);

@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 
-from ._lib import lib, check, FluidError, Params, StepStats, FIELD, Source, LeafGridC, SdfParams, SdfGridC, SdfFilter, SdfTrack, MeshC, SdfAttrC, MeshAttrC, SdfAttrPartC, MeshExC, MESH, Camera, Shade, ImageC, RENDER
+from ._lib import lib, check, FluidError, Params, StepStats, FIELD, Source, LeafGridC, SdfParams, SdfGridC, SdfFilter, SdfTrack, SdfSurface, MeshC, SdfAttrC, MeshAttrC, SdfAttrPartC, MeshExC, MESH, Camera, Shade, ImageC, RENDER
 
 _FIELD_DTYPE = {
     FIELD.CONTAINER: (np.float32, 1), FIELD.WEIGHTS: (np.float32, 1), FIELD.OUTPUT: (np.float32, 1),
@@ -279,6 +279,30 @@ def sdf_filter_grown(grid, filt, track, attr=None):
     act = np.unpackbits(words.view(np.uint8), axis=1, bitorder="little").astype(bool).reshape(k, 512)
     out = SdfGrid(grid.n, org, val, act, grid.background, grid.radius, grid.half_width)
     return out if attr is None else (out, SdfAttr(ids, vel))
+
+
+SDF_SURFACE_KINDS = {"spheres": 0, "averaged": 1}   # FLUID_SDF_SURFACE_*
+
+
+def _sdf_surface_of(kind, influence):
+    """fluid_sdf_surface_t of a name of SDF_SURFACE_KINDS (or a number, passed on as it is) and an influence radius in voxels."""
+    k = SDF_SURFACE_KINDS[kind] if isinstance(kind, str) else int(kind)
+    if k != 0 and influence is None:
+        raise ValueError("the averaged surface needs an influence radius (voxels)")
+    return SdfSurface(k, 0, 0.0 if influence is None else float(influence))
+
+
+def particles_surface(pos, n, R, w, dx, kind="spheres", influence=None):
+    """(values float32 (n, n, n), active bool (n, n, n)): the dense level set of the particles `pos` (k, 3) on the grid of n^3
+    voxels of size dx, spheres of radius R and a band of half width w (voxels); kind "spheres" or "averaged" with its influence
+    radius (include/fluid_hip.h, "liquid surface, averaged positions"; fluid_particles_surface: host only, brute force)."""
+    p = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
+    val = np.empty((n,) * 3, dtype=np.float32)
+    act = np.empty((n,) * 3, dtype=np.uint8)
+    prm, sf = SdfParams(float(R), float(w)), _sdf_surface_of(kind, influence)
+    check(lib.fluid_particles_surface(int(n), float(dx), len(p), p.ctypes.data_as(C.c_void_p), C.byref(prm), C.byref(sf),
+                                      val.ctypes.data_as(C.c_void_p), act.ctypes.data_as(C.c_void_p)))
+    return val, act.astype(bool)
 
 
 SDF_FILTER_KINDS = {"box": 0, "median": 1, "laplacian": 2, "curvature": 3}   # FLUID_SDF_FILTER_*
@@ -848,6 +872,17 @@ class FluidSim:
         "laplacian", "curvature"; or a FLUID_SDF_FILTER_* number) in place of the box passes (include/fluid_hip.h, "liquid
         surface, flows").  The width the kind admits is checked by the next filtered snapshot."""
         check(lib.fluid_sdf_set_filter_kind(self._h, _sdf_kind_of(kind)))
+
+    def sdf_set_surface(self, kind="spheres", influence=None):
+        """A setting of the handle: every later level-set, mesh and render snapshot takes the level set of `kind`: "spheres" (the
+        default: the union of spheres) or "averaged" (the distance to the weighted average of the particle positions within
+        `influence` voxels, 0 < influence <= 4, never outside the spheres; include/fluid_hip.h, "liquid surface, averaged
+        positions").  A number is passed on as it is.  Under "averaged" attr=True snapshots are the library's FLUID_ERR_STATE."""
+        if kind is None:
+            check(lib.fluid_sdf_set_surface(self._h, None))
+            return
+        sf = _sdf_surface_of(kind, influence)
+        check(lib.fluid_sdf_set_surface(self._h, C.byref(sf)))
 
     def sdf_wait(self):
         """The oldest level-set snapshot not yet waited for, as an SdfGrid (copied out of the handle's pinned buffer)."""

@@ -938,6 +938,55 @@ int64_t fluid_sdf_flow(const fluid_sdf_grid_t* g, const struct fluid_sdf_attr* a
                        int32_t* origin, float* values, uint64_t* active, uint32_t* id /* NULL iff attr NULL */,
                        float* velocity /* likewise */);
 
+/* ---- liquid surface, averaged positions: the distance to a weighted average of the nearby particles -------------------------------
+ * Every section above works on the bumps of the union of spheres after they are made; this one does not make them.  It is the
+ * surface FLIP users know from Zhu and Bridson (the distance to a kernel-weighted average of the nearby particle positions: flat
+ * over a flat pool), which OpenVDB does not have: a definition of the project's own, in the style of "liquid surface".  Unchanged
+ * from there: the constants R, w, dxf, bg, max2, min2, which particles count, x2y2z2 (x2 below) exactly as stated there, m = the
+ * minimum of x2 over the counted particles, and the leaf and list rules.  New, with hf = (float)influence:
+ *   h2 = hf * hf, ih2 = 1.0f / h2 (float, the division correctly rounded).
+ *   Weight of particle P at voxel c: W = 0 unless x2 < h2; otherwise t = 1.0f - x2 * ih2, wt = (t * t) * t (float, no FMA) and
+ *     W = (int64)rintf(wt * 16777216.0f) — the product is exact, the rounding half to even, and W may be 0.
+ *   Offset: O_a = (int64)rint((P_a - (double)c_a) * 262144.0) per axis a: one double subtraction, an exact scaling; |O_a| < 2^20.
+ *   Sums over the counted particles: SW = sum of W, SX = sum of W * O_x, SY, SZ likewise: 64-bit integers added with wrap-around
+ *     (unsigned arithmetic).  They are exact while fewer than 2^19 particles lie within hf of one voxel: that is the limit, and it
+ *     is not checked.
+ *   Averaged distance (SW > 0 only): den = (double)SW * 262144.0; ax = (double)SX / den, ay, az likewise (double divisions);
+ *     a2 = (float)(ax * ax); a2 = (float)((double)a2 + ay * ay); a2 = (float)((double)a2 + az * az); da = dxf * (sqrtf(a2) - R).
+ *   The voxel: no particle or m >= max2: inactive +bg.  m <= min2: inactive -bg.  Otherwise ds = dxf * (sqrtf(m) - R),
+ *     d = SW > 0 ? fmaxf(da, ds) : ds; active with value d if d < bg, else inactive +bg.
+ * The maximum with the spheres' distance is what keeps air gaps narrower than 2 hf open (the plain average fills them), and it
+ * leaves a lone droplet a sphere.  Three things follow:
+ *   d >= ds everywhere: the averaged liquid lies inside the union of spheres, its active set is a subset of the spheres' active set
+ *     and its listed leaves a subset of theirs, so every range argument downstream (4 or 5 cells of dilation, growth) holds as it is.
+ *   A particle whose base cell is k + 1 cells away has x2 >= (k + 0.5)^2 as computed (the ring argument of kernels_sdf.hip), so its
+ *     weight is exactly 0 once (k + 0.5)^2 >= h2: with hf <= 4, ring 4 is the last.
+ *   The sums need EVERY ring up to that one; m has earlier stops of its own, or simply rides along.
+ * A value is a function of integer sums and a minimum over the particle set: order-free and bit-reproducible.
+ * Limits: 0 < hf <= 4, else FLUID_ERR_ARG.  With hf < R + w the band voxels further than hf from every particle keep the spheres'
+ * value (SW == 0): that is legal.
+ * Decomposed runs are out of scope: a rank record would carry m and the four sums, and the merge would be a minimum and integer
+ * additions, which is exact; none of it is built.  Neither are attributes, radii per particle or anisotropic kernels. */
+#define FLUID_SDF_SURFACE_SPHERES  0
+#define FLUID_SDF_SURFACE_AVERAGED 1
+typedef struct fluid_sdf_surface { int32_t kind; int32_t reserved; double influence; /* voxels; read with AVERAGED only */ } fluid_sdf_surface_t;
+/* A setting of the handle beside fluid_sdf_set_track, fluid_sdf_set_track_grow and fluid_sdf_set_filter_kind, and independent of
+ * them in order: every later fluid_sdf_snapshot, fluid_sdf_snapshot_filtered, fluid_mesh_snapshot, fluid_mesh_snapshot_filtered,
+ * fluid_mesh_snapshot_ex (without FLUID_MESH_VELOCITY) and fluid_render_snapshot takes the level set defined above in place of the
+ * spheres'; filters, tracks, growth, meshes and images work on it as they work on the spheres'.  NULL or kind
+ * FLUID_SDF_SURFACE_SPHERES (the default): the spheres, every byte of every entry point what it was.  Under AVERAGED the attribute
+ * entry points (fluid_sdf_snapshot_attr, fluid_mesh_snapshot_attr, FLUID_MESH_VELOCITY) and fluid_dist_sdf_snapshot /
+ * fluid_dist_sdf_snapshot_attr (also on a plain handle) return FLUID_ERR_STATE.  FLUID_ERR_ARG: a kind other than the two, or
+ * under AVERAGED reserved != 0 or an influence outside (0, 4].  FLUID_ERR_STATE on a decomposed handle. */
+int fluid_sdf_set_surface(fluid_sim_t* s, const fluid_sdf_surface_t* sf);
+/* Host only, no handle: the dense level set of np particles (pos: x, y, z per particle, index-space coordinates) on the grid of
+ * n^3 voxels of size dx, for either kind (sf NULL or SPHERES: "liquid surface"), brute force over the base cells within 4 of each
+ * voxel: values[n^3] and active[n^3] (z fastest; active may be NULL).  The limits of p and sf are those of fluid_sdf_snapshot and
+ * fluid_sdf_set_surface; n >= 1, dx > 0 and non-NULL pos (np > 0), p, values are required: FLUID_ERR_ARG.  It is how the definition
+ * above is checked where there is no device, and what the search on the device is pinned to bit for bit. */
+int fluid_particles_surface(int32_t n, double dx, int64_t np, const double* pos, const fluid_sdf_params_t* p, const fluid_sdf_surface_t* sf,
+                            float* values, uint8_t* active);
+
 /* ---- liquid surface as a mesh: surface nets of the level set ----------------------------------------------------------------
  * Polygons for everyone who is no volume renderer.  The reference names tools/VolumeToMesh.h, whose output depends on the library's
  * tree traversal; like the level set itself the mesh gets an exact, order-free definition of its own — naive surface nets on the
