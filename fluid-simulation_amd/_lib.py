@@ -94,6 +94,12 @@ class SdfAttrPartC(C.Structure):
     _fields_ = [("n_leaves", C.c_int32), ("id", C.c_void_p), ("velocity", C.c_void_p), ("dist2", C.c_void_p)]
 
 
+class SdfAvgPartC(C.Structure):
+    """fluid_sdf_avg_part_t: a rank's record of squared distances and weighted sums ("liquid surface, averaged positions (decomposed runs)")."""
+    _fields_ = [("n", C.c_int32), ("n_leaves", C.c_int32), ("background", C.c_float), ("radius", C.c_float), ("half_width", C.c_float),
+                ("dx", C.c_float), ("influence", C.c_float), ("origin", C.c_void_p), ("dist2", C.c_void_p), ("sums", C.c_void_p)]
+
+
 class MeshAttrC(C.Structure):
     """fluid_mesh_attr_t: a velocity per mesh vertex."""
     _fields_ = [("n_vertices", C.c_int64), ("velocity", C.c_void_p)]
@@ -262,6 +268,9 @@ SYMBOLS = [
     ("fluid_dist_sdf_snapshot_attr", C.c_int, [_P, C.POINTER(SdfParams)]),
     ("fluid_dist_sdf_wait_attr", C.c_int, [_P, C.POINTER(SdfGridC), C.POINTER(SdfAttrPartC)]),
     ("fluid_sdf_attr_grids_merge", C.c_int64, [C.POINTER(SdfGridC), C.POINTER(SdfAttrPartC), C.c_int32, C.c_int64, _P, _P, _P, _P, _P]),
+    ("fluid_dist_sdf_snapshot_avg", C.c_int, [_P, C.POINTER(SdfParams), C.POINTER(SdfSurface)]),
+    ("fluid_dist_sdf_wait_avg", C.c_int, [_P, C.POINTER(SdfAvgPartC)]),
+    ("fluid_sdf_avg_grids_merge", C.c_int64, [C.POINTER(SdfAvgPartC), C.c_int32, C.c_int64, _P, _P, _P]),
     ("fluid_mesh_snapshot_ex", C.c_int, [_P, C.POINTER(SdfParams), C.POINTER(SdfFilter), C.c_uint32]),
     ("fluid_mesh_wait_ex", C.c_int, [_P, C.POINTER(MeshC), C.POINTER(MeshExC)]),
     ("fluid_sdf_mesh_normals", C.c_int64, [C.POINTER(SdfGridC), C.c_int64, _P]),

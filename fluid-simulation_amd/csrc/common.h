@@ -358,6 +358,13 @@ void launch_sdf_pack_attr(hipStream_t st, const SdfGeom& g, const int* flags, co
 // sums of the particles within hf; h2 = hf * hf, ih2 = 1.0f / h2.  Same inputs and outputs as launch_sdf_search
 void launch_sdf_search_avg(hipStream_t st, const SdfGeom& g, float h2, float ih2, const int* start, const double* sx, const double* sy,
                            const double* sz, float* tv, uint64_t* tm, int* flags);
+// "liquid surface, averaged positions (decomposed runs)": the same search writing a rank record in place of values and masks: tdist2
+// (512 per leaf of the range: m inside (min2, max(max2, h2)), +0 at or below min2, +inf elsewhere) and tsum ([leaf][4][512]: SW, SX,
+// SY, SZ, 0 where dist2 is +0 or +inf); flags: some in-grid voxel of the leaf has m < max(max2, h2).  And the pack of the flagged leaves
+void launch_sdf_search_avg_record(hipStream_t st, const SdfGeom& g, float h2, float ih2, const int* start, const double* sx, const double* sy,
+                                  const double* sz, float* tdist2, uint64_t* tsum, int* flags);
+void launch_sdf_pack_avg(hipStream_t st, const SdfGeom& g, const int* flags, const int* slot, const float* tdist2, const uint64_t* tsum,
+                         float* dist2, uint64_t* sums, int* origin);
 // box filter of that level set (kernels_sdf_filter.hip): one pass of width W along `axis` from src to dst (both 512 values per leaf of
 // the range; only flagged leaves are read or written), `off` added to the active voxels' results (0.0f: none); and the offset alone
 void launch_sdf_box(hipStream_t st, const SdfGeom& g, int axis, int W, float off, const int* flags, const uint64_t* tm, const float* src,

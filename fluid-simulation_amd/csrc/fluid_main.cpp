@@ -99,8 +99,15 @@
 // FLUID_OUT_RENDER take from the particles: the union of spheres, or the distance to the weighted average of the particle positions
 // within H voxels, 0 < H <= 4 (include/fluid_hip.h, "liquid surface, averaged positions"), through fluid_sdf_set_surface; the
 // filters of FLUID_OUT_SMOOTH follow it as they follow the spheres.  One GPU only.  Refused with another word, an H outside the
-// limits, none of the three set, with FLUID_BLOCKS (a rank record of the averaged surface and its merge are not built) or with
+// limits, none of the three set, with FLUID_BLOCKS (a block run takes FLUID_BLOCKS_SURFACE_KIND) or with
 // FLUID_OUT_MESH_VEL (an average of positions has no closest particle), before any handle is created.
+//   FLUID_BLOCKS_SURFACE_KIND=spheres|averaged[,H] (unset: spheres; H defaults to 3; read with FLUID_BLOCKS only) — the same choice for
+// what FLUID_BLOCKS_SURFACE, FLUID_BLOCKS_MESH and FLUID_BLOCKS_RENDER take: with averaged every block thread takes the rank record
+// of its live particles (fluid_dist_sdf_snapshot_avg: minimum and weighted integer sums per voxel) and the main thread merges the
+// records (fluid_sdf_avg_grids_merge; include/fluid_hip.h, "liquid surface, averaged positions (decomposed runs)"): the merged list
+// is byte for byte the one-GPU list, and everything after the merge — FLUID_OUT_SMOOTH*, mesh, normals, triangles, image, file —
+// goes on as after fluid_sdf_grids_merge.  Refused with another word, an H outside the limits, none of the three set, or with
+// FLUID_BLOCKS_MESH_VEL (an average of positions has no closest particle), before any handle is created.
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -386,6 +393,8 @@ struct BlockCfg {
     double mesh_vel_scale = 1.0;
     bool render = false;      // FLUID_BLOCKS_RENDER (its R,W are in sp as well)
     fluid_camera_t cam{};
+    bool averaged = false;    // FLUID_BLOCKS_SURFACE_KIND=averaged: the blocks take rank records of the averaged surface
+    fluid_sdf_surface_t surf{FLUID_SDF_SURFACE_SPHERES, 0, 0.0};
 };
 
 // What the main thread and the block threads share: `go` = steps released so far, done[i & 1] = blocks that finished step i.
@@ -448,6 +457,8 @@ static int run_blocks(const BlockCfg& cfg, const std::vector<double>& pos, int64
     const bool level = surface || mesh || render;   // one level-set snapshot per block and step serves all of them
     std::vector<fluid_sdf_grid_t> spart[2] = {std::vector<fluid_sdf_grid_t>(R), std::vector<fluid_sdf_grid_t>(R)};
     std::vector<fluid_sdf_attr_part_t> apart[2] = {std::vector<fluid_sdf_attr_part_t>(R), std::vector<fluid_sdf_attr_part_t>(R)};
+    const bool avg = level && cfg.averaged;         // ... of the averaged surface: rank records of the minimum and the sums
+    std::vector<fluid_sdf_avg_part_t> vpart[2] = {std::vector<fluid_sdf_avg_part_t>(R), std::vector<fluid_sdf_avg_part_t>(R)};
     std::vector<fluid_step_stats_t> st0(2);   // rank 0's stats of step i in st0[i & 1]
     auto block = [&](int r) {
         fluid_sim_t* sim = nullptr;
@@ -479,8 +490,10 @@ static int run_blocks(const BlockCfg& cfg, const std::vector<double>& pos, int64
             // (the copy of this step's list is the only thing waited for here: the next step starts when the main thread says so)
             if (output && fluid_dist_output_wait(sim, &part[i & 1][r]) != FLUID_OK) { err("fluid_dist_output_wait"); break; }
             // the surface of this block's live particles as the step left them (exact whether or not the step moved the planes)
-            if (level && (attr ? fluid_dist_sdf_snapshot_attr(sim, &cfg.sp) : fluid_dist_sdf_snapshot(sim, &cfg.sp)) != FLUID_OK) { err("fluid_dist_sdf_snapshot"); break; }
-            if (level && (attr ? fluid_dist_sdf_wait_attr(sim, &spart[i & 1][r], &apart[i & 1][r]) : fluid_dist_sdf_wait(sim, &spart[i & 1][r])) != FLUID_OK) { err("fluid_dist_sdf_wait"); break; }
+            if (avg && fluid_dist_sdf_snapshot_avg(sim, &cfg.sp, &cfg.surf) != FLUID_OK) { err("fluid_dist_sdf_snapshot_avg"); break; }
+            if (avg && fluid_dist_sdf_wait_avg(sim, &vpart[i & 1][r]) != FLUID_OK) { err("fluid_dist_sdf_wait_avg"); break; }
+            if (level && !avg && (attr ? fluid_dist_sdf_snapshot_attr(sim, &cfg.sp) : fluid_dist_sdf_snapshot(sim, &cfg.sp)) != FLUID_OK) { err("fluid_dist_sdf_snapshot"); break; }
+            if (level && !avg && (attr ? fluid_dist_sdf_wait_attr(sim, &spart[i & 1][r], &apart[i & 1][r]) : fluid_dist_sdf_wait(sim, &spart[i & 1][r])) != FLUID_OK) { err("fluid_dist_sdf_wait"); break; }
             {
                 std::lock_guard<std::mutex> lk(sy.m);
                 if (r == 0) st0[i & 1] = st;
@@ -587,9 +600,11 @@ static int run_blocks(const BlockCfg& cfg, const std::vector<double>& pos, int64
         if (level) {
             const auto& sp = spart[i & 1];
             const auto& ap = apart[i & 1];
-            const int64_t ks = attr ? fluid_sdf_attr_grids_merge(sp.data(), ap.data(), R, 0, nullptr, nullptr, nullptr, nullptr, nullptr)
-                                    : fluid_sdf_grids_merge(sp.data(), R, 0, nullptr, nullptr, nullptr);
-            if (ks < 0) { sy.fail("fluid_sdf_grids_merge: the blocks' surface lists do not merge"); break; }
+            const auto& vp = vpart[i & 1];
+            const int64_t ks = avg    ? fluid_sdf_avg_grids_merge(vp.data(), R, 0, nullptr, nullptr, nullptr)
+                               : attr ? fluid_sdf_attr_grids_merge(sp.data(), ap.data(), R, 0, nullptr, nullptr, nullptr, nullptr, nullptr)
+                                      : fluid_sdf_grids_merge(sp.data(), R, 0, nullptr, nullptr, nullptr);
+            if (ks < 0) { sy.fail(avg ? "fluid_sdf_avg_grids_merge: the blocks' rank records do not merge" : "fluid_sdf_grids_merge: the blocks' surface lists do not merge"); break; }
             auto& so = s_org[i & 1];
             auto& sv = s_val[i & 1];
             auto& sa = s_act[i & 1];
@@ -597,11 +612,12 @@ static int run_blocks(const BlockCfg& cfg, const std::vector<double>& pos, int64
             auto& sw = s_vel[i & 1];
             if (so.size() < 3 * (size_t)ks) { so.resize(3 * ((size_t)ks + 64)); sv.resize(512 * ((size_t)ks + 64)); sa.resize(8 * ((size_t)ks + 64)); }
             if (attr && si.size() < 512 * (size_t)ks) { si.resize(512 * ((size_t)ks + 64)); sw.resize(1536 * ((size_t)ks + 64)); }
-            if (ks && (attr ? fluid_sdf_attr_grids_merge(sp.data(), ap.data(), R, ks, so.data(), sv.data(), sa.data(), si.data(), sw.data())
-                            : fluid_sdf_grids_merge(sp.data(), R, ks, so.data(), sv.data(), sa.data())) != ks) { sy.fail("fluid_sdf_grids_merge: the blocks' surface lists do not merge"); break; }
+            if (ks && (avg    ? fluid_sdf_avg_grids_merge(vp.data(), R, ks, so.data(), sv.data(), sa.data())
+                       : attr ? fluid_sdf_attr_grids_merge(sp.data(), ap.data(), R, ks, so.data(), sv.data(), sa.data(), si.data(), sw.data())
+                              : fluid_sdf_grids_merge(sp.data(), R, ks, so.data(), sv.data(), sa.data())) != ks) { sy.fail("the blocks' surface lists do not merge: the second call disagrees with the count"); break; }
             sat = fluid_sdf_attr_t{(int32_t)ks, attr && ks ? si.data() : nullptr, attr && ks ? sw.data() : nullptr};
-            sg = fluid_sdf_grid_t{n, (int32_t)ks, sp[0].background, sp[0].radius, sp[0].half_width, ks ? so.data() : nullptr, ks ? sv.data() : nullptr,
-                                  ks ? sa.data() : nullptr};
+            sg = fluid_sdf_grid_t{n, (int32_t)ks, avg ? vp[0].background : sp[0].background, avg ? vp[0].radius : sp[0].radius,
+                                  avg ? vp[0].half_width : sp[0].half_width, ks ? so.data() : nullptr, ks ? sv.data() : nullptr, ks ? sa.data() : nullptr};
             if (cfg.smooth && (cfg.kind != FLUID_SDF_FILTER_BOX || (cfg.track && cfg.grow)) && ks) {
                 // a flow (FLUID_OUT_SMOOTH_KIND) in any of its three forms, or the grown box filter; the grown list can be longer than
                 // the merged one: count, then fill
@@ -933,7 +949,7 @@ int main(int, char**)
             return 1;
         }
         if (blocks && *blocks) {
-            std::cerr << "FLUID_OUT_SURFACE_KIND cannot be combined with FLUID_BLOCKS: the averaged surface is one-GPU only (a rank record would carry the minimum and the four sums; that merge is not built)" << std::endl;
+            std::cerr << "FLUID_OUT_SURFACE_KIND cannot be combined with FLUID_BLOCKS: it is a setting of a one-GPU handle (a block run takes FLUID_BLOCKS_SURFACE_KIND: rank records of the minimum and the four sums, merged on the host)" << std::endl;
             return 1;
         }
         if (mesh_vel) {
@@ -945,6 +961,27 @@ int main(int, char**)
             return 1;
         }
         if (word == "averaged") skind = fluid_sdf_surface_t{FLUID_SDF_SURFACE_AVERAGED, 0, H};
+    }
+    if (const char* benv = getenv("FLUID_BLOCKS_SURFACE_KIND"); blocks && *blocks && benv && *benv) {
+        const std::string v = benv;
+        const size_t comma = v.find(',');
+        const std::string word = v.substr(0, comma);
+        double H = 3.0;
+        char tail = 0;
+        if ((word != "spheres" && word != "averaged") || (comma != std::string::npos && (word != "averaged" || sscanf(v.c_str() + comma + 1, "%lf%c", &H, &tail) != 1)) ||
+            !(H > 0) || !((float)H > 0.0f) || !((float)H <= 4.0f)) {
+            std::cerr << "FLUID_BLOCKS_SURFACE_KIND must be spheres or averaged[,H] (influence radius in voxels, 0 < H <= 4), e.g. averaged,3" << std::endl;
+            return 1;
+        }
+        if (word == "averaged" && bc.mesh_vel) {
+            std::cerr << "FLUID_BLOCKS_SURFACE_KIND=averaged cannot be combined with FLUID_BLOCKS_MESH_VEL: an average of positions has no closest particle to take a velocity from" << std::endl;
+            return 1;
+        }
+        if (!bc.surface && !bc.mesh && !bc.render) {
+            std::cerr << "FLUID_BLOCKS_SURFACE_KIND chooses the level set FLUID_BLOCKS_SURFACE, FLUID_BLOCKS_MESH or FLUID_BLOCKS_RENDER take: none of them is set" << std::endl;
+            return 1;
+        }
+        if (word == "averaged") bc.averaged = true, bc.surf = fluid_sdf_surface_t{FLUID_SDF_SURFACE_AVERAGED, 0, H};
     }
     if (track) bc.track = true, bc.tk = tk, bc.grow = track_grow;
     if (blocks && *blocks) {

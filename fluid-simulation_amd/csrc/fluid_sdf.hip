@@ -49,6 +49,13 @@
 // tracks, growth, pack, mesh and ray caster follow unchanged.  Attribute snapshots and the rank records of decomposed runs are
 // refused under it (FLUID_ERR_STATE).
 //
+// fluid_dist_sdf_snapshot_avg ("liquid surface, averaged positions (decomposed runs)"): the rank record of the averaged surface is a
+// fourth kind of snapshot in the same ring.  The surface comes with the call, not from the handle's setting; the front half launches
+// k_sdf_search_avg<true>, which writes dist2 into tmin and the four sums into tsum (32 B per voxel of the range, allocated by the
+// handle's first such snapshot) and flags the leaves with m < max(max2, h2); k_sdf_pack_avg lists them:
+// [n x 2048 B of dist2 | n x 16384 B of sums | n x 12 B of origins].  No values, no masks: the merge on the host
+// (fluid_sdf_avg_grids_merge, sdf_avg_host.cpp) makes them.  Only fluid_dist_sdf_wait_avg takes such a snapshot, and it takes no other.
+//
 // fluid_sdf_snapshot_attr / fluid_mesh_snapshot_attr ("liquid surface, attributes"): the scatter also writes each sorted position's
 // index in the live arrays (ssrc), the search keeps the closest particle beside the minimum and writes its id and velocity per voxel
 // (tid, tvel), and the pack lists them.  ssrc, tid and tvel exist from the handle's first attribute snapshot on.  An attribute
@@ -71,10 +78,12 @@ using namespace fl;
 constexpr size_t SDF_REC = FLUID_SDF_LEAF_BYTES;
 struct SdfMeta {               // per slot of the ring
     int wide = 0;              // the slot is sized for leaves of this kind (the longest it has held)
-    int attr = 0;              // the snapshot in the slot: 0 plain, 1 with attributes, 2 with attributes and dist2
+    int attr = 0;              // the snapshot in the slot: 0 plain, 1 with attributes, 2 with attributes and dist2, 3 an averaged rank record
     int n_leaves = 0;
     float bg = 0, R = 0, w = 0;
+    float dxf = 0, hf = 0;     // kind 3: what the merge needs beside them
 };
+constexpr int SDF_AVG_RECORD = 3;
 struct SdfState {
     // scratch: cells of the particles' box, particles, leaves of the dilated box
     long cell_cap = 0, part_cap = 0, leaf_cap = 0;
@@ -101,6 +110,8 @@ struct SdfState {
     bool attr = false;
     float* tmin = nullptr;     // m per voxel (leaf_cap x 512): allocated once a snapshot with dist2 was asked for
     bool dist2 = false;
+    uint64_t* tsum = nullptr;  // SW, SX, SY, SZ per voxel ([leaf_cap][4][512]): allocated once an averaged rank record was asked for
+    bool avgrec = false;
     uint64_t* tm = nullptr;
     int *flags = nullptr, *slot = nullptr, *leaf_sums = nullptr;
     unsigned* visits = nullptr;   // FLUID_SDF_VISITS=1 only
@@ -117,9 +128,9 @@ static const char* const SDF_FILT_SINGLE = "filtered level-set snapshots are sin
 
 static const char* const SDF_GROW_SINGLE = "grown level-set snapshots are single-GPU only: a decomposed handle's filter runs on the merged list on the host (fluid_sdf_filter_grown)";
 static const char* const SDF_KIND_SINGLE = "level-set flows are single-GPU only: a decomposed handle's filter runs on the merged list on the host (fluid_sdf_flow)";
-static const char* const SDF_AVG_SINGLE = "the averaged-position surface is single-GPU only: a rank record would carry the minimum and the four sums, and that merge is not built";
+static const char* const SDF_AVG_SINGLE = "the averaged-position surface as a handle's setting is single-GPU only: a decomposed handle gives the rank record of the minimum and the four sums (fluid_dist_sdf_snapshot_avg), merged on the host (fluid_sdf_avg_grids_merge)";
 static const char* const SDF_AVG_ATTR = "the averaged-position surface carries no attributes: an average of positions has no closest particle (fluid_sdf_set_surface)";
-static const char* const SDF_AVG_DIST = "fluid_dist_sdf_snapshot gives the spheres' rank record: the averaged-position surface has none (fluid_sdf_set_surface)";
+static const char* const SDF_AVG_DIST = "fluid_dist_sdf_snapshot gives the spheres' rank record: the averaged-position surface has a rank record of its own, which takes the surface as an argument (fluid_dist_sdf_snapshot_avg)";
 static const char* const SDF_TRACK_SINGLE = "tracked level-set snapshots are single-GPU only: a decomposed handle's filter runs on the merged list on the host (fluid_sdf_filter_tracked)";
 
 static int sdf_init(fluid_sim* s)
@@ -139,7 +150,7 @@ void fl::sdf_free(fluid_sim* s)
     SdfState* o = s->sdf;
     if (!o) return;
     snap_free(o->ring);
-    for (void* p : {(void*)o->cnt, (void*)o->start, (void*)o->cell_sums, (void*)o->place, (void*)o->spos, (void*)o->tv, (void*)o->tv2, (void*)o->lflags, (void*)o->flags2, (void*)o->tm2, (void*)o->ssrc, (void*)o->tid, (void*)o->tvel, (void*)o->tmin, (void*)o->tm, (void*)o->flags,
+    for (void* p : {(void*)o->cnt, (void*)o->start, (void*)o->cell_sums, (void*)o->place, (void*)o->spos, (void*)o->tv, (void*)o->tv2, (void*)o->lflags, (void*)o->flags2, (void*)o->tm2, (void*)o->ssrc, (void*)o->tid, (void*)o->tvel, (void*)o->tmin, (void*)o->tsum, (void*)o->tm, (void*)o->flags,
                     (void*)o->slot, (void*)o->leaf_sums, (void*)o->visits, (void*)o->d_small})
         if (p) hipFree(p);
     if (o->h_small) hipHostFree(o->h_small);
@@ -148,8 +159,12 @@ void fl::sdf_free(fluid_sim* s)
 }
 
 // (the handle's stream is idle here: every caller has just waited for a read-back on it)
-static int sdf_scratch(SdfState* o, long cells, long parts, long leaves, bool filtered, bool attr, bool dist2, bool tracked, bool grown)
+static int sdf_scratch(SdfState* o, long cells, long parts, long leaves, bool filtered, bool attr, bool dist2, bool tracked, bool grown, bool avgrec)
 {
+    if (avgrec && !o->avgrec) {   // the first averaged rank record of the handle: tsum beside whatever there is
+        o->avgrec = true;
+        if (o->leaf_cap > 0) HIPCHK(regrow(o->tsum, (size_t)o->leaf_cap * 2048));
+    }
     if (grown && !o->grown) {   // the first grown snapshot of the handle: flags2 and tm2 beside whatever flags and tm there are
         o->grown = true;
         if (o->leaf_cap > 0) {
@@ -203,6 +218,7 @@ static int sdf_scratch(SdfState* o, long cells, long parts, long leaves, bool fi
             HIPCHK(regrow(o->tvel, (size_t)cap * 1536));
         }
         if (o->dist2) HIPCHK(regrow(o->tmin, (size_t)cap * 512));
+        if (o->avgrec) HIPCHK(regrow(o->tsum, (size_t)cap * 2048));
         HIPCHK(regrow(o->tm, (size_t)cap * 8));
         HIPCHK(regrow(o->flags, (size_t)cap));
         if (o->tracked) HIPCHK(regrow(o->lflags, (size_t)cap));
@@ -233,7 +249,7 @@ static long sdf_count_flags(fluid_sim* s, const int* flags, long leaves)
 // on the handle's stream; a decomposed handle (s->dist) bins its live entries only.  f->any = some particle counts; then f->g holds
 // the box and the range, and tv / flags are the search's: 512 values and a listed flag per leaf of the range (the values of a leaf
 // whose flag is 0 may be stale: kernels_sdf.hip).  The scratch is one per handle: whoever calls next overwrites it, in stream order.
-int fl::sdf_begin(fluid_sim* s, const fluid_sdf_params_t* p, SdfFront* f, const fluid_sdf_filter_t* filt)
+int fl::sdf_begin(fluid_sim* s, const fluid_sdf_params_t* p, SdfFront* f, const fluid_sdf_filter_t* filt, const fluid_sdf_surface_t* sf_arg)
 {
     if (!p) return fail(FLUID_ERR_ARG, "null argument");
     if (filt && !plan::filter_ok(filt))
@@ -271,7 +287,8 @@ int fl::sdf_begin(fluid_sim* s, const fluid_sdf_params_t* p, SdfFront* f, const 
     f->filt = filt, f->dilate = 4;
     f->attr = false, f->dist2 = false;
     f->tm = nullptr, f->tid = nullptr, f->tvel = nullptr, f->tmin = nullptr;
-    const fluid_sdf_surface_t& sf = s->sdf->surface;
+    const fluid_sdf_surface_t& sf = sf_arg ? *sf_arg : s->sdf->surface;
+    f->record = false;
     f->averaged = sf.kind == FLUID_SDF_SURFACE_AVERAGED;
     const adef::Consts hc = f->averaged ? adef::consts(sf.influence) : adef::Consts{0.0f, 0.0f};
     f->h2 = hc.h2, f->ih2 = hc.ih2;
@@ -307,20 +324,21 @@ int fl::sdf_front(fluid_sim* s, SdfFront* f)
         const long cells = g.cells(), leaves = g.leaves();
         const bool tracked = f->track_n > 0 || f->track_trim;
         if (cells + 1 > 0x7fffffffL || leaves > 0x7fffffffL) return fail(FLUID_ERR_ARG, "level set: the particles' box is too large");
-        if ((rc = sdf_scratch(o, cells + 1, s->np, leaves, f->filt != nullptr, f->attr, f->dist2, tracked, f->grow))) return rc;
+        if ((rc = sdf_scratch(o, cells + 1, s->np, leaves, f->filt != nullptr, f->attr, f->dist2 || f->record, tracked, f->grow, f->record))) return rc;
         double *sx = o->spos, *sy = o->spos + o->part_cap, *sz = o->spos + 2 * o->part_cap;
         HIPCHK(hipMemsetAsync(o->cnt, 0, (size_t)(cells + 1) * sizeof(int), s->st));
         launch_sdf_count(s->st, s->np, live, g, o->cnt, o->place, s->dist);
         launch_exclusive_scan(s->st, o->cnt, o->start, cells + 1, o->cell_sums, o->d_small + 6);   // start[cells] = the counted particles
         launch_sdf_scatter(s->st, s->np, live, g, o->start, o->place, sx, sy, sz, f->attr ? o->ssrc : nullptr);
-        if (f->averaged) launch_sdf_search_avg(s->st, g, f->h2, f->ih2, o->start, sx, sy, sz, o->tv, o->tm, o->flags);
+        if (f->record) launch_sdf_search_avg_record(s->st, g, f->h2, f->ih2, o->start, sx, sy, sz, o->tmin, o->tsum, o->flags);
+        else if (f->averaged) launch_sdf_search_avg(s->st, g, f->h2, f->ih2, o->start, sx, sy, sz, o->tv, o->tm, o->flags);
         else if (f->attr) launch_sdf_search_attr(s->st, g, o->start, sx, sy, sz, o->tv, o->tm, o->flags, o->ssrc, live, o->tid, o->tvel, f->dist2 ? o->tmin : nullptr);
         else launch_sdf_search(s->st, g, o->start, sx, sy, sz, o->tv, o->tm, o->flags, o->count_visits ? o->visits : nullptr);
         f->any = true;
         f->tv = o->tv, f->flags = o->flags, f->list = o->flags;
         f->tm = o->tm;
         if (f->attr) f->tid = o->tid, f->tvel = o->tvel;
-        if (f->dist2) f->tmin = o->tmin;
+        if (f->dist2 || f->record) f->tmin = o->tmin;
         if (f->filt) {
             // the schedule of passes, offset steps and tracks: sdf_filter_plan.h; here what each of them launches
             float *src = o->tv, *dst = o->tv2;
@@ -369,18 +387,21 @@ int fl::sdf_front(fluid_sim* s, SdfFront* f)
 }
 
 // front half -> scan of the flags -> pack -> copy
-static constexpr size_t sdf_rec(int kind)   // bytes per listed leaf of a record: plain, with attributes, with attributes and dist2
+static constexpr size_t sdf_rec(int kind)   // bytes per listed leaf of a record: plain, with attributes, with attributes and dist2, averaged rank record
 {
+    if (kind == SDF_AVG_RECORD) return FLUID_SDF_AVG_PART_LEAF_BYTES;   // (the longest of the four: `wide` stays ordered)
     return SDF_REC + (kind >= 1 ? (size_t)FLUID_SDF_ATTR_LEAF_BYTES : 0) + (kind >= 2 ? (size_t)2048 : 0);
 }
 static constexpr size_t sdf_between(int kind) { return sdf_rec(kind) - SDF_REC; }   // per leaf, between the values and the masks
 
-static int sdf_capture(fluid_sim* s, const fluid_sdf_params_t* p, const fluid_sdf_filter_t* filt = nullptr, int attr = 0)
+static int sdf_capture(fluid_sim* s, const fluid_sdf_params_t* p, const fluid_sdf_filter_t* filt = nullptr, int attr = 0,
+                       const fluid_sdf_surface_t* sf = nullptr)
 {
     SdfFront f;
-    int rc = sdf_begin(s, p, &f, filt);
+    int rc = sdf_begin(s, p, &f, filt, sf);
     if (rc) return rc;
-    f.attr = attr >= 1, f.dist2 = attr >= 2;
+    const bool record = attr == SDF_AVG_RECORD;
+    f.attr = attr >= 1 && !record, f.dist2 = attr == 2, f.record = record;
     SdfState* o = s->sdf;
     if (snap_full(o->ring)) return fail(FLUID_ERR_STATE, "two level-set snapshots are waiting for fluid_sdf_wait");
     SnapSlot& q = o->ring.s[snap_slot(o->ring)];
@@ -412,7 +433,12 @@ static int sdf_capture(fluid_sim* s, const fluid_sdf_params_t* p, const fluid_sd
     m.attr = attr;
     const size_t rec = sdf_rec(attr);
     m.bg = g.bg, m.R = R, m.w = w;
-    if (n > 0) {
+    m.dxf = g.dxf, m.hf = record ? (float)sf->influence : 0.0f;
+    if (n > 0 && record) {
+        launch_sdf_pack_avg(s->st, g, f.list, o->slot, f.tmin, o->tsum, (float*)q.dev, (uint64_t*)(q.dev + (size_t)n * 2048),
+                            (int*)(q.dev + (size_t)n * (2048 + 16384)));
+        HIPCHK(hipGetLastError());
+    } else if (n > 0) {
         const size_t a = (size_t)n * sdf_between(attr);   // the attributes lie between the values and the masks
         float* values = (float*)q.dev;
         uint64_t* active = (uint64_t*)(q.dev + (size_t)n * 2048 + a);
@@ -429,10 +455,22 @@ static int sdf_capture(fluid_sim* s, const fluid_sdf_params_t* p, const fluid_sd
     return FLUID_OK;
 }
 
+// The oldest outstanding snapshot is (avg) / is not (!avg) an averaged rank record, or there is none: FLUID_OK.  Asked before
+// snap_next_wait, so that a refused wait leaves the snapshot outstanding.
+static int sdf_wait_kind(const SdfState* o, bool avg)
+{
+    if (!o || o->ring.n_wait >= o->ring.n_snap) return FLUID_OK;
+    const bool is = o->m[o->ring.n_wait & 1].attr == SDF_AVG_RECORD;
+    if (is == avg) return FLUID_OK;
+    return fail(FLUID_ERR_STATE, avg ? "the oldest level-set snapshot is no averaged rank record: fluid_dist_sdf_wait_avg takes those of fluid_dist_sdf_snapshot_avg alone"
+                                     : "the oldest level-set snapshot is an averaged rank record, which holds no values: fluid_dist_sdf_wait_avg takes it");
+}
+
 static int sdf_wait(fluid_sim* s, fluid_sdf_grid_t* out, fluid_sdf_attr_t* at = nullptr, fluid_sdf_attr_part_t* part = nullptr)
 {
     if (!out) return fail(FLUID_ERR_ARG, "null argument");
     SdfState* o = s->sdf;
+    if (int rk = sdf_wait_kind(o, false)) return rk;
     int k = -1, rc = o ? snap_next_wait(o->ring, &k) : FLUID_OK;
     if (rc) return rc;
     if (k < 0) return fail(FLUID_ERR_STATE, "no level-set snapshot is outstanding");
@@ -460,6 +498,26 @@ static int sdf_wait(fluid_sim* s, fluid_sdf_grid_t* out, fluid_sdf_attr_t* at = 
         part->velocity = has ? (const float*)(host + n * 4096) : nullptr;
         part->dist2 = has ? (const float*)(host + n * 10240) : nullptr;
     }
+    return FLUID_OK;
+}
+
+static int sdf_wait_avg(fluid_sim* s, fluid_sdf_avg_part_t* out)
+{
+    if (!out) return fail(FLUID_ERR_ARG, "null argument");
+    SdfState* o = s->sdf;
+    if (int rk = sdf_wait_kind(o, true)) return rk;
+    int k = -1, rc = o ? snap_next_wait(o->ring, &k) : FLUID_OK;
+    if (rc) return rc;
+    if (k < 0) return fail(FLUID_ERR_STATE, "no level-set snapshot is outstanding");
+    const char* host = o->ring.s[k].host;
+    const SdfMeta& m = o->m[k];
+    const size_t n = (size_t)m.n_leaves;
+    out->n = s->g.N;
+    out->n_leaves = m.n_leaves;
+    out->background = m.bg, out->radius = m.R, out->half_width = m.w, out->dx = m.dxf, out->influence = m.hf;
+    out->dist2 = n ? (const float*)host : nullptr;
+    out->sums = n ? (const uint64_t*)(host + n * 2048) : nullptr;
+    out->origin = n ? (const int32_t*)(host + n * (2048 + 16384)) : nullptr;
     return FLUID_OK;
 }
 
@@ -589,6 +647,20 @@ int fluid_dist_sdf_wait_attr(fluid_sim_t* s, fluid_sdf_grid_t* out, fluid_sdf_at
 {
     if (!s) return fail(FLUID_ERR_ARG, "null handle");
     return sdf_wait(s, out, nullptr, part);
+}
+
+int fluid_dist_sdf_snapshot_avg(fluid_sim_t* s, const fluid_sdf_params_t* p, const fluid_sdf_surface_t* sf)
+{
+    if (!s) return fail(FLUID_ERR_ARG, "null handle");
+    if (!sf || sf->kind != FLUID_SDF_SURFACE_AVERAGED || sf->reserved != 0 || !adef::influence_ok(sf->influence))
+        return fail(FLUID_ERR_ARG, "averaged rank record: kind FLUID_SDF_SURFACE_AVERAGED, reserved 0 and 0 < influence <= 4 (voxels) are required");
+    return sdf_capture(s, p, nullptr, SDF_AVG_RECORD, sf);
+}
+
+int fluid_dist_sdf_wait_avg(fluid_sim_t* s, fluid_sdf_avg_part_t* out)
+{
+    if (!s) return fail(FLUID_ERR_ARG, "null handle");
+    return sdf_wait_avg(s, out);
 }
 
 int fluid_dist_sdf_stats(fluid_sim_t* s, int64_t* leaves_in_grid, int64_t* leaves_listed, int64_t* bytes_to_host)

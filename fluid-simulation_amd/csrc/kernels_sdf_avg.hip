@@ -17,11 +17,18 @@
 // search: profiles/avg/NOTES.md.
 // A plane whose in-grid voxels all have m <= min2 (they are inactive -bg whatever follows) stops; x planes are taken from the
 // voxel's own outwards so that a deep interior gets there early.
+// RECORD ("liquid surface, averaged positions (decomposed runs)"): same walk, LDS and early stops; the finish writes what a merge
+// over ranks needs in place of the value: the canonical dist2 (m inside (min2, reach2), +0 at or below min2, +inf elsewhere) where
+// tv would go, and the four sums as four planes of 512 uint64 per leaf (a wave's 64 stores of a plane are 512 contiguous bytes),
+// zero wherever dist2 is +0 or +inf.  The leaf's flag is m < reach2 over its in-grid voxels, reach2 = max(max2, h2): a particle
+// can weigh on a voxel that lies outside its own band.  No tv / tm.  k_sdf_pack_avg lists the flagged leaves' records.
 #include "common.h"
 #include "sdf_avg_def.h"
 
 namespace fl {
 
+// RECORD: tv is the range's dist2 (512 per leaf) and tm its sums ([leaf][4][512])
+template <bool RECORD>
 __global__ __launch_bounds__(512) void k_sdf_search_avg(SdfGeom g, adef::Consts hc, int K, const int* __restrict__ start,
                                                         const double* __restrict__ sx, const double* __restrict__ sy,
                                                         const double* __restrict__ sz, float* __restrict__ tv,
@@ -82,6 +89,20 @@ __global__ __launch_bounds__(512) void k_sdf_search_avg(SdfGeom g, adef::Consts 
         }
         if (__all(!in || m <= g.min2)) break;
     }
+    if (RECORD) {
+        const float reach2 = fmaxf(g.max2, hc.h2);
+        const bool reached = in && m < reach2;
+        const bool keep = reached && m > g.min2;   // the sums of every other voxel are never read: 0, so that the record is canonical
+        tv[j * 512 + t] = keep ? m : (reached ? 0.0f : INFINITY);
+        unsigned long long* sums = tm + j * 2048 + t;
+        sums[0] = keep ? sum.w : 0ull;
+        sums[512] = keep ? sum.x : 0ull;
+        sums[1024] = keep ? sum.y : 0ull;
+        sums[1536] = keep ? sum.z : 0ull;
+        const int listed = __syncthreads_or(reached);
+        if (t == 0) flags[j] = listed ? 1 : 0;
+        return;
+    }
     float val = g.bg;
     bool act = false;
     if (in) adef::finish(m, sum, true, g.R, g.dxf, g.bg, g.max2, g.min2, val, act);
@@ -97,8 +118,48 @@ void launch_sdf_search_avg(hipStream_t st, const SdfGeom& g, float h2, float ih2
 {
     adef::Consts hc;
     hc.h2 = h2, hc.ih2 = ih2;
-    hipLaunchKernelGGL(k_sdf_search_avg, dim3((unsigned)g.leaves()), dim3(512), 0, st, g, hc, adef::last_ring(h2, g.max2), start, sx, sy, sz, tv,
+    hipLaunchKernelGGL(k_sdf_search_avg<false>, dim3((unsigned)g.leaves()), dim3(512), 0, st, g, hc, adef::last_ring(h2, g.max2), start, sx, sy, sz, tv,
                        (unsigned long long*)tm, flags);
+}
+
+void launch_sdf_search_avg_record(hipStream_t st, const SdfGeom& g, float h2, float ih2, const int* start, const double* sx, const double* sy,
+                                  const double* sz, float* tdist2, uint64_t* tsum, int* flags)
+{
+    adef::Consts hc;
+    hc.h2 = h2, hc.ih2 = ih2;
+    hipLaunchKernelGGL(k_sdf_search_avg<true>, dim3((unsigned)g.leaves()), dim3(512), 0, st, g, hc, adef::last_ring(h2, g.max2), start, sx, sy, sz, tdist2,
+                       (unsigned long long*)tsum, flags);
+}
+
+// One wave per leaf of the range, as k_sdf_pack (kernels_sdf.hip); the waves of unlisted leaves leave at once.  The leaf's 2048 bytes
+// of dist2 and 16384 bytes of sums go to slot[j] of the record in 16-byte copies (every base is a multiple of 2048 bytes from
+// hipMalloc's), its origin behind them.
+__global__ __launch_bounds__(256) void k_sdf_pack_avg(SdfGeom g, long nrange, const int* __restrict__ flags, const int* __restrict__ slot,
+                                                      const float* __restrict__ tdist2, const unsigned long long* __restrict__ tsum,
+                                                      float* __restrict__ dist2, unsigned long long* __restrict__ sums, int* __restrict__ origin)
+{
+    const long j = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= nrange || !flags[j]) return;
+    const int lane = threadIdx.x & 63;
+    const int jz = (int)(j % g.nl[2]), jy = (int)((j / g.nl[2]) % g.nl[1]), jx = (int)(j / ((long)g.nl[1] * g.nl[2]));
+    const long s = slot[j];
+    const float4* ms = (const float4*)(tdist2 + j * 512);
+    float4* md = (float4*)(dist2 + s * 512);
+    md[lane] = ms[lane];
+    md[lane + 64] = ms[lane + 64];
+    const uint4* ss = (const uint4*)(tsum + j * 2048);
+    uint4* sd = (uint4*)(sums + s * 2048);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) sd[lane + 64 * k] = ss[lane + 64 * k];
+    if (lane < 3) origin[s * 3 + lane] = g.L0 + 8 * (g.l0[lane] + (lane == 0 ? jx : lane == 1 ? jy : jz));
+}
+
+void launch_sdf_pack_avg(hipStream_t st, const SdfGeom& g, const int* flags, const int* slot, const float* tdist2, const uint64_t* tsum,
+                         float* dist2, uint64_t* sums, int* origin)
+{
+    const long nrange = g.leaves();
+    hipLaunchKernelGGL(k_sdf_pack_avg, dim3((unsigned)((nrange + 3) / 4)), dim3(256), 0, st, g, nrange, flags, slot, tdist2,
+                       (const unsigned long long*)tsum, dist2, (unsigned long long*)sums, origin);
 }
 
 }  // namespace fl

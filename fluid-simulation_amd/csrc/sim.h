@@ -324,9 +324,13 @@ struct SdfFront {
     const float* tmin;    // dist2: 512 per leaf of the range, m where active and +inf elsewhere (stale where flags[j] == 0)
     bool averaged;        // "liquid surface, averaged positions": the handle's fluid_sdf_set_surface setting, copied by sdf_begin,
     float h2, ih2;        // and its constants; sdf_front refuses it together with attr
+    bool record;          // "averaged positions (decomposed runs)": the search writes the rank record (dist2 into tmin, the sums) and no
+                          // tv / tm; set by the caller after an sdf_begin that was handed the surface
 };
-// limits of the parameters (and of the filter, when one is given), the state, the constants of g
-int sdf_begin(fluid_sim* s, const fluid_sdf_params_t* p, SdfFront* f, const fluid_sdf_filter_t* filt = nullptr);
+// limits of the parameters (and of the filter, when one is given), the state, the constants of g.  sf: nullptr = the handle's
+// fluid_sdf_set_surface setting; otherwise the surface is this one (checked by the caller) and the setting is not read
+int sdf_begin(fluid_sim* s, const fluid_sdf_params_t* p, SdfFront* f, const fluid_sdf_filter_t* filt = nullptr,
+              const fluid_sdf_surface_t* sf = nullptr);
 int sdf_front(fluid_sim* s, SdfFront* f);   // bbox (waits for the stream) -> count, scan, scatter -> search -> the filter's passes and tracks
 
 // fluid_mesh.hip

@@ -15,8 +15,8 @@ import threading
 
 import numpy as np
 
-from ._lib import lib, check, Params, StepStats, LeafGridC, SdfParams, SdfGridC, SdfAttrPartC, SdfTrack
-from .sim import _sdf_scheme_of, FluidSim, source_methods, grid_bounds, merge_leaf_grids, _leaf_grid_copy, merge_sdf_grids, _sdf_grid_copy, merge_sdf_attr_grids, _sdf_attr_part_copy  # noqa: F401
+from ._lib import lib, check, Params, StepStats, LeafGridC, SdfParams, SdfGridC, SdfAttrPartC, SdfAvgPartC, SdfSurface, SdfTrack
+from .sim import _sdf_scheme_of, FluidSim, source_methods, grid_bounds, merge_leaf_grids, _leaf_grid_copy, merge_sdf_grids, _sdf_grid_copy, merge_sdf_attr_grids, _sdf_attr_part_copy, merge_sdf_avg_grids, _sdf_avg_part_copy  # noqa: F401
 
 EXCHANGE_T = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                          C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p)
@@ -436,6 +436,20 @@ class DistFluidSim(FluidSim):
         g, a = SdfGridC(), SdfAttrPartC()
         check(lib.fluid_dist_sdf_wait_attr(self._h, C.byref(g), C.byref(a)))
         return _sdf_grid_copy(g), _sdf_attr_part_copy(a)
+
+    def sdf_snapshot_avg(self, radius, half_width, influence):
+        """Enqueue the rank record of the averaged-position surface of this rank's live particles as they are now: squared distances and
+        weighted sums per voxel, the surface given here and not by a setting (include/fluid_hip.h, "liquid surface, averaged
+        positions (decomposed runs)").  Shares the level set's two slots with sdf_snapshot."""
+        p, sf = SdfParams(float(radius), float(half_width)), SdfSurface(1, 0, float(influence))
+        check(lib.fluid_dist_sdf_snapshot_avg(self._h, C.byref(p), C.byref(sf)))
+
+    def sdf_wait_avg(self):
+        """The oldest level-set snapshot not yet waited for, which must be one of sdf_snapshot_avg, as an SdfAvgPart
+        (merge_sdf_avg_grids joins the ranks')."""
+        a = SdfAvgPartC()
+        check(lib.fluid_dist_sdf_wait_avg(self._h, C.byref(a)))
+        return _sdf_avg_part_copy(a)
 
     def sdf_stats(self):
         v = [C.c_int64() for _ in range(3)]

@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 
-from ._lib import lib, check, FluidError, Params, StepStats, FIELD, Source, LeafGridC, SdfParams, SdfGridC, SdfFilter, SdfTrack, SdfSurface, MeshC, SdfAttrC, MeshAttrC, SdfAttrPartC, MeshExC, MESH, Camera, Shade, ImageC, RENDER
+from ._lib import lib, check, FluidError, Params, StepStats, FIELD, Source, LeafGridC, SdfParams, SdfGridC, SdfFilter, SdfTrack, SdfSurface, MeshC, SdfAttrC, MeshAttrC, SdfAttrPartC, SdfAvgPartC, MeshExC, MESH, Camera, Shade, ImageC, RENDER
 
 _FIELD_DTYPE = {
     FIELD.CONTAINER: (np.float32, 1), FIELD.WEIGHTS: (np.float32, 1), FIELD.OUTPUT: (np.float32, 1),
@@ -487,6 +487,61 @@ def merge_sdf_attr_grids(parts, attrs):
     return SdfGrid(p0.n, org, val, act, p0.background, p0.radius, p0.half_width), SdfAttr(ids, vel)
 
 
+class SdfAvgPart:
+    """fluid_sdf_avg_part_t on the host ("liquid surface, averaged positions (decomposed runs)"): a rank's record of its live
+    particles, owning its arrays.  origin (k, 3) int32 ascending; dist2 (k, 512) float32: the squared distance to the closest
+    particle inside (min2, max(max2, h2)), +0 at or below min2, +inf elsewhere; sums (k, 4, 512) uint64: SW, SX, SY, SZ."""
+
+    def __init__(self, n, origin, dist2, sums, background, radius, half_width, dx, influence):
+        self.n = int(n)
+        self.origin = np.ascontiguousarray(origin, dtype=np.int32).reshape(-1, 3)
+        self.dist2 = np.ascontiguousarray(dist2, dtype=np.float32).reshape(-1, 512)
+        self.sums = np.ascontiguousarray(sums, dtype=np.uint64).reshape(-1, 4, 512)
+        assert self.origin.shape[0] == self.dist2.shape[0] == self.sums.shape[0]
+        self.background, self.radius, self.half_width = np.float32(background), np.float32(radius), np.float32(half_width)
+        self.dx, self.influence = np.float32(dx), np.float32(influence)
+
+    @property
+    def n_leaves(self):
+        return self.origin.shape[0]
+
+    def _c(self):
+        k = self.n_leaves
+        return SdfAvgPartC(self.n, k, self.background, self.radius, self.half_width, self.dx, self.influence,
+                           self.origin.ctypes.data if k else None, self.dist2.ctypes.data if k else None,
+                           self.sums.ctypes.data if k else None)
+
+
+def _sdf_avg_part_copy(a):
+    """SdfAvgPart copied out of the buffers a fluid_sdf_avg_part_t points into."""
+    k = a.n_leaves
+    if k == 0:
+        org, d2, sums = np.empty((0, 3), np.int32), np.empty((0, 512), np.float32), np.empty((0, 4, 512), np.uint64)
+    else:
+        org = np.ctypeslib.as_array(C.cast(a.origin, C.POINTER(C.c_int32)), shape=(k, 3)).copy()
+        d2 = np.ctypeslib.as_array(C.cast(a.dist2, C.POINTER(C.c_float)), shape=(k, 512)).copy()
+        sums = np.ctypeslib.as_array(C.cast(a.sums, C.POINTER(C.c_uint64)), shape=(k, 4, 512)).copy()
+    return SdfAvgPart(a.n, org, d2, sums, a.background, a.radius, a.half_width, a.dx, a.influence)
+
+
+def merge_sdf_avg_grids(parts):
+    """The SdfGrid of the averaged-position surface of the whole particle set from the ranks' SdfAvgParts (sdf_wait_avg of every
+    rank): per voxel the minimum of dist2 and the wrapping sums of the sums, finished as on one GPU
+    (fluid_sdf_avg_grids_merge: host only)."""
+    parts = list(parts)
+    arr = (SdfAvgPartC * max(len(parts), 1))(*[p._c() for p in parts])
+    k = lib.fluid_sdf_avg_grids_merge(arr, len(parts), 0, None, None, None)
+    if k < 0:
+        raise FluidError(-k, "fluid_sdf_avg_grids_merge: the parts do not merge (no part, records of different parameters, a bad "
+                             "leaf list, a dist2 that is NaN or negative, or sums beside a dist2 of +0 or +inf)")
+    org, val, words = np.empty((k, 3), np.int32), np.empty((k, 512), np.float32), np.zeros((k, 8), np.uint64)
+    if k and lib.fluid_sdf_avg_grids_merge(arr, len(parts), k, *[x.ctypes.data_as(C.c_void_p) for x in (org, val, words)]) != k:
+        raise FluidError(1, "fluid_sdf_avg_grids_merge: the second call disagrees with the count")
+    act = np.unpackbits(words.view(np.uint8), axis=1, bitorder="little").astype(bool).reshape(k, 512)
+    p0 = parts[0]
+    return SdfGrid(p0.n, org, val, act, p0.background, p0.radius, p0.half_width)
+
+
 def sdf_mesh_attr(grid, attr):
     """velocity (nv, 3) float32: the vertex velocities of sdf_mesh(grid), in its vertex order (fluid_sdf_mesh_attr: host only)."""
     c, _keep = grid._c()
@@ -883,6 +938,20 @@ class FluidSim:
             return
         sf = _sdf_surface_of(kind, influence)
         check(lib.fluid_sdf_set_surface(self._h, C.byref(sf)))
+
+    def sdf_snapshot_avg(self, radius, half_width, influence):
+        """Enqueue the rank record of the averaged-position surface of the particles as they are now: squared distances and
+        weighted sums per voxel, the surface given here and not by a setting (include/fluid_hip.h, "liquid surface, averaged
+        positions (decomposed runs)").  Shares the level set's two slots with sdf_snapshot."""
+        p, sf = SdfParams(float(radius), float(half_width)), SdfSurface(1, 0, float(influence))
+        check(lib.fluid_dist_sdf_snapshot_avg(self._h, C.byref(p), C.byref(sf)))
+
+    def sdf_wait_avg(self):
+        """The oldest level-set snapshot not yet waited for, which must be one of sdf_snapshot_avg, as an SdfAvgPart
+        (merge_sdf_avg_grids joins the ranks')."""
+        a = SdfAvgPartC()
+        check(lib.fluid_dist_sdf_wait_avg(self._h, C.byref(a)))
+        return _sdf_avg_part_copy(a)
 
     def sdf_wait(self):
         """The oldest level-set snapshot not yet waited for, as an SdfGrid (copied out of the handle's pinned buffer)."""

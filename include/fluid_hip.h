@@ -965,8 +965,8 @@ int64_t fluid_sdf_flow(const fluid_sdf_grid_t* g, const struct fluid_sdf_attr* a
  * A value is a function of integer sums and a minimum over the particle set: order-free and bit-reproducible.
  * Limits: 0 < hf <= 4, else FLUID_ERR_ARG.  With hf < R + w the band voxels further than hf from every particle keep the spheres'
  * value (SW == 0): that is legal.
- * Decomposed runs are out of scope: a rank record would carry m and the four sums, and the merge would be a minimum and integer
- * additions, which is exact; none of it is built.  Neither are attributes, radii per particle or anisotropic kernels. */
+ * Decomposed runs: a rank record carries m and the four sums, and the merge is a minimum and integer additions, which is exact:
+ * "liquid surface, averaged positions (decomposed runs)" below.  Attributes, radii per particle and anisotropic kernels are not built. */
 #define FLUID_SDF_SURFACE_SPHERES  0
 #define FLUID_SDF_SURFACE_AVERAGED 1
 typedef struct fluid_sdf_surface { int32_t kind; int32_t reserved; double influence; /* voxels; read with AVERAGED only */ } fluid_sdf_surface_t;
@@ -977,7 +977,8 @@ typedef struct fluid_sdf_surface { int32_t kind; int32_t reserved; double influe
  * FLUID_SDF_SURFACE_SPHERES (the default): the spheres, every byte of every entry point what it was.  Under AVERAGED the attribute
  * entry points (fluid_sdf_snapshot_attr, fluid_mesh_snapshot_attr, FLUID_MESH_VELOCITY) and fluid_dist_sdf_snapshot /
  * fluid_dist_sdf_snapshot_attr (also on a plain handle) return FLUID_ERR_STATE.  FLUID_ERR_ARG: a kind other than the two, or
- * under AVERAGED reserved != 0 or an influence outside (0, 4].  FLUID_ERR_STATE on a decomposed handle. */
+ * under AVERAGED reserved != 0 or an influence outside (0, 4].  FLUID_ERR_STATE on a decomposed handle, whose rank record takes the
+ * surface as an argument instead (fluid_dist_sdf_snapshot_avg). */
 int fluid_sdf_set_surface(fluid_sim_t* s, const fluid_sdf_surface_t* sf);
 /* Host only, no handle: the dense level set of np particles (pos: x, y, z per particle, index-space coordinates) on the grid of
  * n^3 voxels of size dx, for either kind (sf NULL or SPHERES: "liquid surface"), brute force over the base cells within 4 of each
@@ -986,6 +987,67 @@ int fluid_sdf_set_surface(fluid_sim_t* s, const fluid_sdf_surface_t* sf);
  * above is checked where there is no device, and what the search on the device is pinned to bit for bit. */
 int fluid_particles_surface(int32_t n, double dx, int64_t np, const double* pos, const fluid_sdf_params_t* p, const fluid_sdf_surface_t* sf,
                             float* values, uint8_t* active);
+
+/* ---- liquid surface, averaged positions (decomposed runs) --------------------------------------------------------------------------
+ * Everything not restated here is that of "liquid surface" and "liquid surface, averaged positions".  A voxel of the averaged surface
+ * is a function of a minimum and of four wrapping 64-bit integer sums over the particle set, and both split exactly over a partition
+ * of the set: every rank records (m, SW, SX, SY, SZ) of its own live particles, and a host merge finishes the voxels.  No ghost
+ * particles, no halo, no transport call.  Let reach2 = max(max2, h2) in float.
+ *
+ * Which leaves a rank lists.  The spheres' list is not enough: with hf > R + w a particle weighs on voxels outside its own band, and
+ * such a voxel may lie inside the band of another rank's particle while this rank lists nothing there.  A rank lists a leaf iff
+ * some in-grid voxel of it has m < reach2, m taken over this rank's live particles.
+ *
+ * What a rank stores per voxel of a listed leaf:
+ *   min2 < m < reach2:                                            dist2 = m; SW, SX, SY, SZ over this rank's live particles
+ *   m <= min2:                                                    dist2 = +0.0f; the four sums 0
+ *   m >= reach2, no particle, or the voxel outside [lo,hi]^3:     dist2 = +inf (0x7f800000); the four sums 0
+ * A voxel with m <= min2 on any rank is inactive -bg in every union, whatever the sums: that is why the record (and the search's
+ * early stop of a plane, which leaves m and the sums of such voxels unfinished) may drop them.  The record is canonical: a function
+ * of the rank's live particle set alone.  m is exact whenever m < reach2 (the ring argument above: a particle beyond the last ring
+ * has x2 >= reach2).
+ *
+ * Merge, per voxel over the parts that list its leaf: m = the minimum of the parts' dist2 (+inf if none lists it); the sums = the
+ * wrapping 64-bit sums of the parts' sums; the voxel = the rule of "liquid surface, averaged positions" applied to (m, sums).  A part
+ * whose dist2 is +inf adds zero sums, rightly: its particles are further than hf.  Where some part holds +0 the result is inactive
+ * -bg and the sums are not read.  The merged list holds the leaves with anything but inactive +bg, ascending, under the rules of
+ * fluid_sdf_to_dense.  For the records the ranks of a run give, the result is byte for byte the list fluid_sdf_snapshot gives under
+ * AVERAGED on one handle that holds the union of their live particles.
+ *
+ *   per step, every rank:    fluid_step(s, &st);  fluid_dist_sdf_snapshot_avg(s, &sp, &sf);  fluid_dist_sdf_wait_avg(s, &part[rank]);
+ *   one place:               k = fluid_sdf_avg_grids_merge(part, R, cap, origin, values, active);
+ *                            g = {n, k, bg, radius, half_width, origin, values, active};  filter / mesh / render / write as on one GPU.
+ * The rank record is unfiltered and carries no attributes: a block run filters after the merge. */
+#define FLUID_SDF_AVG_PART_LEAF_BYTES (2048 + 4 * 4096 + 12)   /* a listed leaf of a rank record on the way to the host */
+typedef struct fluid_sdf_avg_part {
+    int32_t n, n_leaves;
+    float background, radius, half_width, dx, influence;   /* dx = (float)dx of the handle, influence = hf */
+    const int32_t* origin;      /* 3 per leaf, ascending */
+    const float* dist2;         /* 512 per leaf */
+    const uint64_t* sums;       /* [leaf][4][512]: SW, SX, SY, SZ */
+} fluid_sdf_avg_part_t;
+/* fluid_dist_sdf_snapshot in every respect (live particles only, global coordinates, no transport call, the surface's own two slots
+ * and their shared count of outstanding snapshots, survival of a re-balance) but the record, and the surface comes with the call:
+ * sf must be of kind AVERAGED within the limits of fluid_sdf_set_surface, else FLUID_ERR_ARG; the handle's own surface setting is
+ * neither read nor changed.  A plain fluid_create handle is accepted.  The record is [n x 2048 B dist2 | n x 16384 B sums |
+ * n x 12 B origins]; fluid_dist_sdf_stats reports bytes_to_host = leaves_listed * FLUID_SDF_AVG_PART_LEAF_BYTES + 4.  The extra
+ * scratch (32 B per voxel of the range for the sums, 4 B for dist2) is allocated by the handle's first such snapshot, never inside
+ * a step; a slot keeps room for the longest record it has held. */
+int fluid_dist_sdf_snapshot_avg(fluid_sim_t* s, const fluid_sdf_params_t* p, const fluid_sdf_surface_t* sf);
+/* The oldest snapshot not yet waited for, which must be an averaged rank record: on one of another kind FLUID_ERR_STATE, and the
+ * snapshot stays outstanding.  Likewise fluid_sdf_wait, fluid_sdf_wait_attr, fluid_dist_sdf_wait and fluid_dist_sdf_wait_attr on an
+ * averaged rank record.  A rank with no counted particle gets n_leaves = 0 and NULL pointers.  Lifetime of the pointers: that of
+ * fluid_dist_sdf_wait's. */
+int fluid_dist_sdf_wait_avg(fluid_sim_t* s, fluid_sdf_avg_part_t* out);
+/* Host only.  The merge defined above into origin[3 * cap_leaves] / values[512 * cap_leaves] / active[8 * cap_leaves].  Returns the
+ * merged leaf count (all three outputs NULL: the count only, cap_leaves is ignored), or -FLUID_ERR_ARG with nothing written:
+ * n_parts < 1; parts whose n, background, radius, half_width, dx or influence differ as bit patterns, or are not what a snapshot
+ * gives (the limits of p and sf, background = dx * half_width); a part that breaks the list rules of fluid_sdf_to_dense; a part with
+ * n_leaves > 0 and a NULL array; a dist2 that is NaN or negative (-0 included); a voxel whose dist2 is +0 or +inf while one of its
+ * sums is not 0; cap_leaves too small.  Parts with n_leaves == 0 and NULL pointers are valid.  A k-way walk of the ascending lists;
+ * no dense grid. */
+int64_t fluid_sdf_avg_grids_merge(const fluid_sdf_avg_part_t* parts, int32_t n_parts, int64_t cap_leaves, int32_t* origin, float* values,
+                                  uint64_t* active);
 
 /* ---- liquid surface as a mesh: surface nets of the level set ----------------------------------------------------------------
  * Polygons for everyone who is no volume renderer.  The reference names tools/VolumeToMesh.h, whose output depends on the library's
