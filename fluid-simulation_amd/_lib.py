@@ -78,6 +78,12 @@ class SdfSurface(C.Structure):
     _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("influence", C.c_double)]
 
 
+class SdfTrails(C.Structure):
+    """fluid_sdf_trails_t: shutter time, spacing factor, end radius (voxels) and the most instances of a particle (include/fluid_hip.h,
+    "liquid surface, velocity trails")."""
+    _fields_ = [("shutter", C.c_double), ("delta", C.c_double), ("radius_min", C.c_double), ("max_instances", C.c_int32), ("reserved", C.c_int32)]
+
+
 class MeshC(C.Structure):
     """fluid_mesh_t: the surface nets of the level set (include/fluid_hip.h, "liquid surface as a mesh")."""
     _fields_ = [("n", C.c_int32), ("n_vertices", C.c_int64), ("n_quads", C.c_int64), ("radius", C.c_float),
@@ -253,6 +259,10 @@ SYMBOLS = [
                                    _P, _P, _P, _P, _P]),
     ("fluid_sdf_set_surface", C.c_int, [_P, C.POINTER(SdfSurface)]),
     ("fluid_particles_surface", C.c_int, [C.c_int32, C.c_double, C.c_int64, _P, C.POINTER(SdfParams), C.POINTER(SdfSurface), _P, _P]),
+    ("fluid_sdf_set_trails", C.c_int, [_P, C.POINTER(SdfTrails)]),
+    ("fluid_sdf_trails_stats", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("fluid_particles_trails", C.c_int64, [C.c_int64, _P, _P, C.POINTER(SdfParams), C.POINTER(SdfTrails), C.c_int64, _P, _P]),
+    ("fluid_spheres_surface", C.c_int, [C.c_int32, C.c_double, C.c_int64, _P, _P, C.POINTER(SdfParams), _P, _P]),
     ("fluid_mesh_snapshot", C.c_int, [_P, C.POINTER(SdfParams)]),
     ("fluid_mesh_wait", C.c_int, [_P, C.POINTER(MeshC)]),
     ("fluid_mesh_stats", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -3,6 +3,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+namespace tdef {
+struct Consts;   // sdf_trail_def.h
+}
+
 namespace fl {
 
 // ---- cell flag byte ---------------------------------------------------------------------
@@ -365,6 +369,17 @@ void launch_sdf_search_avg_record(hipStream_t st, const SdfGeom& g, float h2, fl
                                   const double* sz, float* tdist2, uint64_t* tsum, int* flags);
 void launch_sdf_pack_avg(hipStream_t st, const SdfGeom& g, const int* flags, const int* slot, const float* tdist2, const uint64_t* tsum,
                          float* dist2, uint64_t* sums, int* origin);
+// "liquid surface, velocity trails" (kernels_sdf_trail.hip; tc: sdf_trail_def.h).  count: icnt[i] = instances of live particle i,
+// small[0..5] = min, max of the base cells of the instances that lie in the grid, small[8..9] = the 64-bit total of icnt.  expand:
+// instance k of particle i to slot ioff[i] + k of ix, iy, iz, ir (cap slots).  scatter: launch_sdf_scatter with the radius (sr)
+// beside the position.  search_rad: launch_sdf_search over items that carry their own radius <= g.R
+void launch_trail_count(hipStream_t st, long n, Particles p, const tdef::Consts& tc, int lo, int hi, int* icnt, int* small);
+void launch_trail_expand(hipStream_t st, long n, Particles p, const tdef::Consts& tc, const int* ioff, long cap, double* ix, double* iy,
+                         double* iz, float* ir);
+void launch_trail_scatter(hipStream_t st, long n, const double* ix, const double* iy, const double* iz, const float* ir, const SdfGeom& g,
+                          const int* start, const int* place, double* sx, double* sy, double* sz, float* sr);
+void launch_sdf_search_rad(hipStream_t st, const SdfGeom& g, const int* start, const double* sx, const double* sy, const double* sz,
+                           const float* sr, float* tv, uint64_t* tm, int* flags);
 // box filter of that level set (kernels_sdf_filter.hip): one pass of width W along `axis` from src to dst (both 512 values per leaf of
 // the range; only flagged leaves are read or written), `off` added to the active voxels' results (0.0f: none); and the offset alone
 void launch_sdf_box(hipStream_t st, const SdfGeom& g, int axis, int W, float off, const int* flags, const uint64_t* tm, const float* src,

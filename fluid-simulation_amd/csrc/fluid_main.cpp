@@ -108,6 +108,14 @@
 // is byte for byte the one-GPU list, and everything after the merge — FLUID_OUT_SMOOTH*, mesh, normals, triangles, image, file —
 // goes on as after fluid_sdf_grids_merge.  Refused with another word, an H outside the limits, none of the three set, or with
 // FLUID_BLOCKS_MESH_VEL (an average of positions has no closest particle), before any handle is created.
+//   FLUID_OUT_SURFACE_TRAILS=SHUTTER[,DELTA[,RMIN[,MAX]]] (unset: off) — the level set FLUID_OUT_SURFACE, FLUID_OUT_MESH and
+// FLUID_OUT_RENDER take from the particles is that of their velocity trails (include/fluid_hip.h, "liquid surface, velocity trails"),
+// through fluid_sdf_set_trails: SHUTTER is the time a trail covers, a finite number >= 0 or the word dt, the dt FLIPadvect wrote in
+// the step the snapshot follows (fluid_step_stats_t.dt_out; the setting is renewed every step); DELTA > 0 the spacing factor
+// (default 1); RMIN > 0 the radius at the trail's end in voxels (default: half the smallest R of the three outputs), at most every
+// such R; MAX in 1..32 the most instances of a particle (default 16).  One GPU only.  Refused outside these limits, with none of
+// the three set, with FLUID_OUT_SURFACE_KIND=averaged, FLUID_OUT_MESH_VEL (trails carry no attributes) or FLUID_BLOCKS (the rank
+// record of instances is not built), before any handle is created.
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -962,6 +970,60 @@ int main(int, char**)
         }
         if (word == "averaged") skind = fluid_sdf_surface_t{FLUID_SDF_SURFACE_AVERAGED, 0, H};
     }
+    bool trails = false, trails_dt = false;
+    fluid_sdf_trails_t trl{0.0, 1.0, 0.0, 16, 0};
+    if (const char* tenv = getenv("FLUID_OUT_SURFACE_TRAILS"); tenv && *tenv) {
+        const char* const usage = "FLUID_OUT_SURFACE_TRAILS must be SHUTTER[,DELTA[,RMIN[,MAX]]]: SHUTTER a finite time >= 0 or the word dt, DELTA > 0, RMIN > 0 (voxels), MAX in 1..32, e.g. dt,1,0.5,16";
+        std::string v = tenv;
+        std::vector<std::string> part;
+        for (size_t at = 0;;) {
+            const size_t comma = v.find(',', at);
+            part.push_back(v.substr(at, comma == std::string::npos ? comma : comma - at));
+            if (comma == std::string::npos) break;
+            at = comma + 1;
+        }
+        double Rsmall = INFINITY;
+        if (surface) Rsmall = std::fmin(Rsmall, (double)(float)sp.radius);
+        if (mesh) Rsmall = std::fmin(Rsmall, (double)(float)mp.radius);
+        if (render) Rsmall = std::fmin(Rsmall, (double)(float)rp.radius);
+        trl.radius_min = std::isfinite(Rsmall) ? 0.5 * Rsmall : 0.5;
+        char tail = 0;
+        long maxi = 16;
+        bool ok = part.size() >= 1 && part.size() <= 4;
+        if (ok && part[0] == "dt") trails_dt = true;
+        else ok = ok && sscanf(part[0].c_str(), "%lf%c", &trl.shutter, &tail) == 1;
+        ok = ok && (part.size() < 2 || sscanf(part[1].c_str(), "%lf%c", &trl.delta, &tail) == 1);
+        ok = ok && (part.size() < 3 || sscanf(part[2].c_str(), "%lf%c", &trl.radius_min, &tail) == 1);
+        ok = ok && (part.size() < 4 || sscanf(part[3].c_str(), "%ld%c", &maxi, &tail) == 1);
+        ok = ok && maxi >= 1 && maxi <= 32;
+        trl.max_instances = (int32_t)(ok ? maxi : 16);
+        if (!ok || !(trl.shutter >= 0) || !std::isfinite(trl.shutter) || !(trl.delta > 0) || !std::isfinite(trl.delta) || !(trl.radius_min > 0) ||
+            !std::isfinite(trl.radius_min)) {
+            std::cerr << usage << std::endl;
+            return 1;
+        }
+        if (blocks && *blocks) {
+            std::cerr << "FLUID_OUT_SURFACE_TRAILS cannot be combined with FLUID_BLOCKS: it is a setting of a one-GPU handle (the rank record of instances is not built)" << std::endl;
+            return 1;
+        }
+        if (skind.kind == FLUID_SDF_SURFACE_AVERAGED) {
+            std::cerr << "FLUID_OUT_SURFACE_TRAILS cannot be combined with FLUID_OUT_SURFACE_KIND=averaged: the two surfaces exclude each other" << std::endl;
+            return 1;
+        }
+        if (mesh_vel) {
+            std::cerr << "FLUID_OUT_SURFACE_TRAILS cannot be combined with FLUID_OUT_MESH_VEL: trails carry no attributes" << std::endl;
+            return 1;
+        }
+        if (!surface && !mesh && !render) {
+            std::cerr << "FLUID_OUT_SURFACE_TRAILS chooses the level set FLUID_OUT_SURFACE, FLUID_OUT_MESH or FLUID_OUT_RENDER take: none of them is set" << std::endl;
+            return 1;
+        }
+        if (!((double)(float)trl.radius_min <= Rsmall)) {
+            std::cerr << "FLUID_OUT_SURFACE_TRAILS: RMIN must not exceed the radius R of FLUID_OUT_SURFACE, FLUID_OUT_MESH and FLUID_OUT_RENDER" << std::endl;
+            return 1;
+        }
+        trails = true;
+    }
     if (const char* benv = getenv("FLUID_BLOCKS_SURFACE_KIND"); blocks && *blocks && benv && *benv) {
         const std::string v = benv;
         const size_t comma = v.find(',');
@@ -1019,6 +1081,10 @@ int main(int, char**)
     }
     if (sim && skind.kind != FLUID_SDF_SURFACE_SPHERES && fluid_sdf_set_surface(sim, &skind) != FLUID_OK) {
         std::cerr << "fluid_sdf_set_surface: " << fluid_last_error() << std::endl;
+        return 1;
+    }
+    if (sim && trails && fluid_sdf_set_trails(sim, &trl) != FLUID_OK) {
+        std::cerr << "fluid_sdf_set_trails: " << fluid_last_error() << std::endl;
         return 1;
     }
     if (sim && track && fluid_sdf_set_track(sim, &tk) != FLUID_OK) {
@@ -1136,6 +1202,14 @@ int main(int, char**)
                 std::cerr << "fluid_output_snapshot: " << fluid_last_error() << std::endl;
                 lw.stop();
                 return 1;
+            }
+            if (trails_dt) {   // SHUTTER = dt: the path of the step just taken
+                trl.shutter = st.dt_out;
+                if (fluid_sdf_set_trails(sim, &trl) != FLUID_OK) {
+                    std::cerr << "fluid_sdf_set_trails: " << fluid_last_error() << std::endl;
+                    lw.stop();
+                    return 1;
+                }
             }
             if (surface && (smooth ? fluid_sdf_snapshot_filtered(sim, &sp, &sf) : fluid_sdf_snapshot(sim, &sp)) != FLUID_OK) {
                 std::cerr << "fluid_sdf_snapshot: " << fluid_last_error() << std::endl;

@@ -56,6 +56,13 @@
 // [n x 2048 B of dist2 | n x 16384 B of sums | n x 12 B of origins].  No values, no masks: the merge on the host
 // (fluid_sdf_avg_grids_merge, sdf_avg_host.cpp) makes them.  Only fluid_dist_sdf_wait_avg takes such a snapshot, and it takes no other.
 //
+// fluid_sdf_set_trails ("liquid surface, velocity trails"; kernels_sdf_trail.hip): with the setting on the front half first expands
+// the live particles into instances (count pass with the instances' base-cell box and their total, 24 + 8 bytes read back; scan;
+// write pass), then bins the INSTANCES behind the same count and scan, with a scatter that carries the radius, and launches
+// k_sdf_search_rad in place of k_sdf_search; tv / tm / flags mean what they meant.  Scratch of its own: icnt / ioff per particle, and
+// per instance 60 bytes: ipos and ir (28), place and spos, which are the spheres' arrays sized for the instances (28), and sr (4);
+// allocated by the handle's first snapshot under the setting.  Attribute snapshots and the spheres' rank records are refused under it.
+//
 // fluid_sdf_snapshot_attr / fluid_mesh_snapshot_attr ("liquid surface, attributes"): the scatter also writes each sorted position's
 // index in the live arrays (ssrc), the search keeps the closest particle beside the minimum and writes its id and velocity per voxel
 // (tid, tvel), and the pack lists them.  ssrc, tid and tvel exist from the handle's first attribute snapshot on.  An attribute
@@ -71,6 +78,7 @@
 #include "sim.h"
 #include "sdf_filter_plan.h"
 #include "sdf_avg_def.h"
+#include "sdf_trail_def.h"
 
 using namespace fl;
 #define fail fluid_fail
@@ -112,12 +120,21 @@ struct SdfState {
     bool dist2 = false;
     uint64_t* tsum = nullptr;  // SW, SX, SY, SZ per voxel ([leaf_cap][4][512]): allocated once an averaged rank record was asked for
     bool avgrec = false;
+    // velocity trails (fluid_sdf_set_trails): instances per particle and their scan (tpart_cap), the instances and their radii,
+    // unsorted and sorted (inst_cap): allocated once a snapshot under the setting was asked for
+    fluid_sdf_trails_t trails{0.0, 0.0, 0.0, 0, 0};
+    bool trails_on = false;
+    long tpart_cap = 0, inst_cap = 0;
+    int *icnt = nullptr, *ioff = nullptr, *isums = nullptr;
+    double* ipos = nullptr;    // x | y | z, inst_cap each
+    float *ir = nullptr, *sr = nullptr;
+    int64_t trail_particles = 0, trail_instances = 0;   // of the last snapshot under the setting
     uint64_t* tm = nullptr;
     int *flags = nullptr, *slot = nullptr, *leaf_sums = nullptr;
     unsigned* visits = nullptr;   // FLUID_SDF_VISITS=1 only
     bool count_visits = false;
     bool grow_stats = false;      // FLUID_SDF_GROW_STATS=1 only
-    int *d_small = nullptr, *h_small = nullptr;   // box[6], cell total, listed count
+    int *d_small = nullptr, *h_small = nullptr;   // box[6], cell total, listed count, the trails' 64-bit instance total
     SnapRing ring;
     SdfMeta m[2];
     long last_leaves = 0, last_bytes = 0;
@@ -131,6 +148,10 @@ static const char* const SDF_KIND_SINGLE = "level-set flows are single-GPU only:
 static const char* const SDF_AVG_SINGLE = "the averaged-position surface as a handle's setting is single-GPU only: a decomposed handle gives the rank record of the minimum and the four sums (fluid_dist_sdf_snapshot_avg), merged on the host (fluid_sdf_avg_grids_merge)";
 static const char* const SDF_AVG_ATTR = "the averaged-position surface carries no attributes: an average of positions has no closest particle (fluid_sdf_set_surface)";
 static const char* const SDF_AVG_DIST = "fluid_dist_sdf_snapshot gives the spheres' rank record: the averaged-position surface has a rank record of its own, which takes the surface as an argument (fluid_dist_sdf_snapshot_avg)";
+static const char* const SDF_TRAIL_SINGLE = "velocity trails are single-GPU only: the union splits exactly over ranks, but the rank record of instances is not built (fluid_sdf_set_trails)";
+static const char* const SDF_TRAIL_ATTR = "velocity trails carry no attributes (fluid_sdf_set_trails)";
+static const char* const SDF_TRAIL_DIST = "fluid_dist_sdf_snapshot gives the spheres' rank record: it is refused while velocity trails are set (fluid_sdf_set_trails)";
+static const char* const SDF_TRAIL_AVG = "velocity trails and the averaged-position surface exclude each other (fluid_sdf_set_trails, fluid_sdf_set_surface)";
 static const char* const SDF_TRACK_SINGLE = "tracked level-set snapshots are single-GPU only: a decomposed handle's filter runs on the merged list on the host (fluid_sdf_filter_tracked)";
 
 static int sdf_init(fluid_sim* s)
@@ -140,8 +161,8 @@ static int sdf_init(fluid_sim* s)
     s->sdf = o;   // from here on sdf_free releases whatever the lines below got
     if (const char* e = getenv("FLUID_SDF_VISITS")) o->count_visits = atoi(e) != 0;   // developer knob (tools/sdf_cost.py)
     if (const char* e = getenv("FLUID_SDF_GROW_STATS")) o->grow_stats = atoi(e) != 0;   // developer knob (tools/grow_cost.py)
-    HIPCHK(hipMalloc((void**)&o->d_small, 8 * sizeof(int)));
-    HIPCHK(hipHostMalloc((void**)&o->h_small, 8 * sizeof(int)));
+    HIPCHK(hipMalloc((void**)&o->d_small, 10 * sizeof(int)));
+    HIPCHK(hipHostMalloc((void**)&o->h_small, 10 * sizeof(int)));
     return snap_init(o->ring);
 }
 
@@ -151,7 +172,7 @@ void fl::sdf_free(fluid_sim* s)
     if (!o) return;
     snap_free(o->ring);
     for (void* p : {(void*)o->cnt, (void*)o->start, (void*)o->cell_sums, (void*)o->place, (void*)o->spos, (void*)o->tv, (void*)o->tv2, (void*)o->lflags, (void*)o->flags2, (void*)o->tm2, (void*)o->ssrc, (void*)o->tid, (void*)o->tvel, (void*)o->tmin, (void*)o->tsum, (void*)o->tm, (void*)o->flags,
-                    (void*)o->slot, (void*)o->leaf_sums, (void*)o->visits, (void*)o->d_small})
+                    (void*)o->icnt, (void*)o->ioff, (void*)o->isums, (void*)o->ipos, (void*)o->ir, (void*)o->sr, (void*)o->slot, (void*)o->leaf_sums, (void*)o->visits, (void*)o->d_small})
         if (p) hipFree(p);
     if (o->h_small) hipHostFree(o->h_small);
     delete o;
@@ -234,6 +255,28 @@ static int sdf_scratch(SdfState* o, long cells, long parts, long leaves, bool fi
     return FLUID_OK;
 }
 
+// The trails' scratch: per particle before the count pass, per instance once the total is known (the stream is idle at both places)
+static int trail_scratch(SdfState* o, long parts, long inst)
+{
+    if (parts > o->tpart_cap) {
+        o->tpart_cap = 0;
+        const long cap = parts + parts / 8 + 64;
+        HIPCHK(regrow(o->icnt, (size_t)cap));
+        HIPCHK(regrow(o->ioff, (size_t)cap));
+        HIPCHK(regrow(o->isums, (size_t)cap / 2048 + 16));
+        o->tpart_cap = cap;
+    }
+    if (inst > o->inst_cap) {
+        o->inst_cap = 0;
+        const long cap = inst + inst / 8 + 64;
+        HIPCHK(regrow(o->ipos, (size_t)3 * cap));
+        HIPCHK(regrow(o->ir, (size_t)cap));
+        HIPCHK(regrow(o->sr, (size_t)cap));
+        o->inst_cap = cap;
+    }
+    return FLUID_OK;
+}
+
 // FLUID_SDF_GROW_STATS=1: how many leaves of the range are flagged (two host waits: a figure for tools/grow_cost.py, never a default)
 static long sdf_count_flags(fluid_sim* s, const int* flags, long leaves)
 {
@@ -292,6 +335,9 @@ int fl::sdf_begin(fluid_sim* s, const fluid_sdf_params_t* p, SdfFront* f, const 
     f->averaged = sf.kind == FLUID_SDF_SURFACE_AVERAGED;
     const adef::Consts hc = f->averaged ? adef::consts(sf.influence) : adef::Consts{0.0f, 0.0f};
     f->h2 = hc.h2, f->ih2 = hc.ih2;
+    f->trails = !sf_arg && s->sdf->trails_on;   // (a surface handed in is the averaged rank record's: the setting is not read)
+    if (f->trails && !tdef::radius_ok(s->sdf->trails.radius_min, R))
+        return fail(FLUID_ERR_ARG, "velocity trails: radius_min <= radius is required (fluid_sdf_set_trails)");
     return FLUID_OK;
 }
 
@@ -301,9 +347,30 @@ int fl::sdf_front(fluid_sim* s, SdfFront* f)
     SdfGeom& g = f->g;
     int rc;
     if (f->averaged && f->attr) return fail(FLUID_ERR_STATE, SDF_AVG_ATTR);
+    if (f->trails && f->attr) return fail(FLUID_ERR_STATE, SDF_TRAIL_ATTR);
     const Particles live = s->pa.shifted(s->p_off);
     int* box = o->h_small;
-    if (s->np > 0) {
+    long items = s->np;   // what is binned: the live particles, or their instances
+    tdef::Consts tc{};
+    if (f->trails) {
+        const fluid_sdf_trails_t& t = o->trails;
+        tc = tdef::consts(t.shutter, t.delta, t.radius_min, t.max_instances, g.R);
+        o->trail_particles = s->np, o->trail_instances = 0;
+    }
+    if (s->np > 0 && f->trails) {
+        if ((rc = trail_scratch(o, s->np, 0))) return rc;
+        launch_trail_count(s->st, s->np, live, tc, g.lo, g.hi, o->icnt, o->d_small);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(o->h_small, o->d_small, 6 * sizeof(int), hipMemcpyDeviceToHost, s->st));
+        HIPCHK(hipMemcpyAsync(o->h_small + 8, o->d_small + 8, 2 * sizeof(int), hipMemcpyDeviceToHost, s->st));
+        HIPCHK(hipStreamSynchronize(s->st));
+        uint64_t total;
+        memcpy(&total, o->h_small + 8, sizeof total);
+        if (total < (uint64_t)s->np || total > (uint64_t)s->np * tdef::MAX_INSTANCES) return fail(FLUID_ERR_HIP, "velocity trails: instance total out of range");
+        if (total > 0x7fffffffull) return fail(FLUID_ERR_ARG, "velocity trails: more than 2^31 - 1 instances");
+        o->trail_instances = (int64_t)total;
+        items = (long)total;
+    } else if (s->np > 0) {
         launch_sdf_bbox(s->st, s->np, live, g.lo, g.hi, o->d_small, s->dist);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(o->h_small, o->d_small, 6 * sizeof(int), hipMemcpyDeviceToHost, s->st));
@@ -324,13 +391,22 @@ int fl::sdf_front(fluid_sim* s, SdfFront* f)
         const long cells = g.cells(), leaves = g.leaves();
         const bool tracked = f->track_n > 0 || f->track_trim;
         if (cells + 1 > 0x7fffffffL || leaves > 0x7fffffffL) return fail(FLUID_ERR_ARG, "level set: the particles' box is too large");
-        if ((rc = sdf_scratch(o, cells + 1, s->np, leaves, f->filt != nullptr, f->attr, f->dist2 || f->record, tracked, f->grow, f->record))) return rc;
+        if ((rc = sdf_scratch(o, cells + 1, items, leaves, f->filt != nullptr, f->attr, f->dist2 || f->record, tracked, f->grow, f->record))) return rc;
         double *sx = o->spos, *sy = o->spos + o->part_cap, *sz = o->spos + 2 * o->part_cap;
+        Particles inst{};   // trails: the instances stand where the particles stood (positions only)
+        if (f->trails) {
+            if ((rc = trail_scratch(o, s->np, items))) return rc;
+            inst.px = o->ipos, inst.py = o->ipos + o->inst_cap, inst.pz = o->ipos + 2 * o->inst_cap;
+            launch_exclusive_scan(s->st, o->icnt, o->ioff, s->np, o->isums, o->d_small + 6);   // (the total is known; d_small[6] is rewritten below)
+            launch_trail_expand(s->st, s->np, live, tc, o->ioff, items, inst.px, inst.py, inst.pz, o->ir);
+        }
         HIPCHK(hipMemsetAsync(o->cnt, 0, (size_t)(cells + 1) * sizeof(int), s->st));
-        launch_sdf_count(s->st, s->np, live, g, o->cnt, o->place, s->dist);
+        launch_sdf_count(s->st, items, f->trails ? inst : live, g, o->cnt, o->place, s->dist);
         launch_exclusive_scan(s->st, o->cnt, o->start, cells + 1, o->cell_sums, o->d_small + 6);   // start[cells] = the counted particles
-        launch_sdf_scatter(s->st, s->np, live, g, o->start, o->place, sx, sy, sz, f->attr ? o->ssrc : nullptr);
-        if (f->record) launch_sdf_search_avg_record(s->st, g, f->h2, f->ih2, o->start, sx, sy, sz, o->tmin, o->tsum, o->flags);
+        if (f->trails) launch_trail_scatter(s->st, items, inst.px, inst.py, inst.pz, o->ir, g, o->start, o->place, sx, sy, sz, o->sr);
+        else launch_sdf_scatter(s->st, s->np, live, g, o->start, o->place, sx, sy, sz, f->attr ? o->ssrc : nullptr);
+        if (f->trails) launch_sdf_search_rad(s->st, g, o->start, sx, sy, sz, o->sr, o->tv, o->tm, o->flags);
+        else if (f->record) launch_sdf_search_avg_record(s->st, g, f->h2, f->ih2, o->start, sx, sy, sz, o->tmin, o->tsum, o->flags);
         else if (f->averaged) launch_sdf_search_avg(s->st, g, f->h2, f->ih2, o->start, sx, sy, sz, o->tv, o->tm, o->flags);
         else if (f->attr) launch_sdf_search_attr(s->st, g, o->start, sx, sy, sz, o->tv, o->tm, o->flags, o->ssrc, live, o->tid, o->tvel, f->dist2 ? o->tmin : nullptr);
         else launch_sdf_search(s->st, g, o->start, sx, sy, sz, o->tv, o->tm, o->flags, o->count_visits ? o->visits : nullptr);
@@ -531,6 +607,7 @@ static int sdf_stats(fluid_sim* s, int64_t* leaves_in_grid, int64_t* leaves_list
 }
 
 static bool sdf_averaged(const fluid_sim* s) { return s->sdf && s->sdf->surface.kind == FLUID_SDF_SURFACE_AVERAGED; }
+static bool sdf_trails(const fluid_sim* s) { return s->sdf && s->sdf->trails_on; }
 
 void fl::sdf_move(fluid_sim* from, fluid_sim* to)
 {
@@ -592,10 +669,32 @@ int fluid_sdf_set_surface(fluid_sim_t* s, const fluid_sdf_surface_t* sf)
         if (sf->kind != FLUID_SDF_SURFACE_AVERAGED || sf->reserved != 0 || !adef::influence_ok(sf->influence))
             return fail(FLUID_ERR_ARG, "level-set surface: kind FLUID_SDF_SURFACE_SPHERES or _AVERAGED, reserved 0 and 0 < influence <= 4 (voxels) are required");
     }
+    const bool avg = sf && sf->kind == FLUID_SDF_SURFACE_AVERAGED;
+    if (avg && sdf_trails(s)) return fail(FLUID_ERR_STATE, SDF_TRAIL_AVG);
     HIPCHK(hipSetDevice(s->prm.device));
     if (int rc = sdf_init(s)) return rc;
-    const bool avg = sf && sf->kind == FLUID_SDF_SURFACE_AVERAGED;
     s->sdf->surface = avg ? *sf : fluid_sdf_surface_t{FLUID_SDF_SURFACE_SPHERES, 0, 0.0};
+    return FLUID_OK;
+}
+
+int fluid_sdf_set_trails(fluid_sim_t* s, const fluid_sdf_trails_t* t)
+{
+    if (int rc = snap_guard(s, SDF_TRAIL_SINGLE)) return rc;
+    if (t && !tdef::settings_ok(t->shutter, t->delta, t->radius_min, t->max_instances, t->reserved))
+        return fail(FLUID_ERR_ARG, "velocity trails: a finite shutter >= 0, delta > 0 and radius_min > 0 (voxels), max_instances in 1..32 and reserved 0 are required");
+    if (t && sdf_averaged(s)) return fail(FLUID_ERR_STATE, SDF_TRAIL_AVG);
+    HIPCHK(hipSetDevice(s->prm.device));
+    if (int rc = sdf_init(s)) return rc;
+    s->sdf->trails_on = t != nullptr;
+    s->sdf->trails = t ? *t : fluid_sdf_trails_t{0.0, 0.0, 0.0, 0, 0};
+    return FLUID_OK;
+}
+
+int fluid_sdf_trails_stats(fluid_sim_t* s, int64_t* particles, int64_t* instances)
+{
+    if (int rc = snap_guard(s, SDF_TRAIL_SINGLE)) return rc;
+    if (particles) *particles = s->sdf ? s->sdf->trail_particles : 0;
+    if (instances) *instances = s->sdf ? s->sdf->trail_instances : 0;
     return FLUID_OK;
 }
 
@@ -627,6 +726,7 @@ int fluid_dist_sdf_snapshot(fluid_sim_t* s, const fluid_sdf_params_t* p)
 {
     if (!s) return fail(FLUID_ERR_ARG, "null handle");
     if (sdf_averaged(s)) return fail(FLUID_ERR_STATE, SDF_AVG_DIST);
+    if (sdf_trails(s)) return fail(FLUID_ERR_STATE, SDF_TRAIL_DIST);
     return sdf_capture(s, p);
 }
 
@@ -640,6 +740,7 @@ int fluid_dist_sdf_snapshot_attr(fluid_sim_t* s, const fluid_sdf_params_t* p)
 {
     if (!s) return fail(FLUID_ERR_ARG, "null handle");
     if (sdf_averaged(s)) return fail(FLUID_ERR_STATE, SDF_AVG_DIST);
+    if (sdf_trails(s)) return fail(FLUID_ERR_STATE, SDF_TRAIL_DIST);
     return sdf_capture(s, p, nullptr, 2);
 }
 

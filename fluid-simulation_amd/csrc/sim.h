@@ -326,6 +326,8 @@ struct SdfFront {
     float h2, ih2;        // and its constants; sdf_front refuses it together with attr
     bool record;          // "averaged positions (decomposed runs)": the search writes the rank record (dist2 into tmin, the sums) and no
                           // tv / tm; set by the caller after an sdf_begin that was handed the surface
+    bool trails;          // "liquid surface, velocity trails": the handle's fluid_sdf_set_trails setting is on, copied by sdf_begin (never
+                          // with a surface handed in); sdf_front bins the particles' instances and refuses it together with attr
 };
 // limits of the parameters (and of the filter, when one is given), the state, the constants of g.  sf: nullptr = the handle's
 // fluid_sdf_set_surface setting; otherwise the surface is this one (checked by the caller) and the setting is not read

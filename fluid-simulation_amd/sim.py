@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 
-from ._lib import lib, check, FluidError, Params, StepStats, FIELD, Source, LeafGridC, SdfParams, SdfGridC, SdfFilter, SdfTrack, SdfSurface, MeshC, SdfAttrC, MeshAttrC, SdfAttrPartC, SdfAvgPartC, MeshExC, MESH, Camera, Shade, ImageC, RENDER
+from ._lib import lib, check, FluidError, Params, StepStats, FIELD, Source, LeafGridC, SdfParams, SdfGridC, SdfFilter, SdfTrack, SdfSurface, SdfTrails, MeshC, SdfAttrC, MeshAttrC, SdfAttrPartC, SdfAvgPartC, MeshExC, MESH, Camera, Shade, ImageC, RENDER
 
 _FIELD_DTYPE = {
     FIELD.CONTAINER: (np.float32, 1), FIELD.WEIGHTS: (np.float32, 1), FIELD.OUTPUT: (np.float32, 1),
@@ -302,6 +302,43 @@ def particles_surface(pos, n, R, w, dx, kind="spheres", influence=None):
     prm, sf = SdfParams(float(R), float(w)), _sdf_surface_of(kind, influence)
     check(lib.fluid_particles_surface(int(n), float(dx), len(p), p.ctypes.data_as(C.c_void_p), C.byref(prm), C.byref(sf),
                                       val.ctypes.data_as(C.c_void_p), act.ctypes.data_as(C.c_void_p)))
+    return val, act.astype(bool)
+
+
+def particles_trails(pos, vel, R, w, shutter, delta=1.0, radius_min=None, max_instances=16):
+    """(positions float64 (k, 3), radii float32 (k,)): the particles `pos` (np, 3) with velocities `vel` (voxels per time) expanded
+    into the instances of their velocity trails, in particle order; radius_min None: R / 2 (include/fluid_hip.h, "liquid surface,
+    velocity trails"; fluid_particles_trails: host only)."""
+    p = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
+    v = np.ascontiguousarray(vel, dtype=np.float64).reshape(-1, 3)
+    if v.shape != p.shape:
+        raise ValueError("one velocity per particle")
+    prm = SdfParams(float(R), float(w))
+    t = SdfTrails(float(shutter), float(delta), float(R) / 2 if radius_min is None else float(radius_min), int(max_instances), 0)
+    pp, vp = p.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p)
+    k = lib.fluid_particles_trails(len(p), pp, vp, C.byref(prm), C.byref(t), 0, None, None)
+    if k < 0:
+        check(int(-k))
+    out, rad = np.empty((k, 3), dtype=np.float64), np.empty(k, dtype=np.float32)
+    got = lib.fluid_particles_trails(len(p), pp, vp, C.byref(prm), C.byref(t), k, out.ctypes.data_as(C.c_void_p), rad.ctypes.data_as(C.c_void_p))
+    if got != k:
+        check(int(-got) if got < 0 else 1)
+    return out, rad
+
+
+def spheres_surface(pos, radius, n, R, w, dx):
+    """(values float32 (n, n, n), active bool (n, n, n)): the dense level set of the spheres at `pos` (k, 3) with their own radii
+    `radius` (k,), each in (0, R], and a band of half width w (voxels), on the grid of n^3 voxels of size dx (include/fluid_hip.h,
+    "liquid surface, velocity trails"; fluid_spheres_surface: host only, brute force)."""
+    p = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
+    r = np.ascontiguousarray(radius, dtype=np.float32).reshape(-1)
+    if len(r) != len(p):
+        raise ValueError("one radius per position")
+    val = np.empty((n,) * 3, dtype=np.float32)
+    act = np.empty((n,) * 3, dtype=np.uint8)
+    prm = SdfParams(float(R), float(w))
+    check(lib.fluid_spheres_surface(int(n), float(dx), len(p), p.ctypes.data_as(C.c_void_p), r.ctypes.data_as(C.c_void_p), C.byref(prm),
+                                    val.ctypes.data_as(C.c_void_p), act.ctypes.data_as(C.c_void_p)))
     return val, act.astype(bool)
 
 
@@ -938,6 +975,24 @@ class FluidSim:
             return
         sf = _sdf_surface_of(kind, influence)
         check(lib.fluid_sdf_set_surface(self._h, C.byref(sf)))
+
+    def sdf_set_trails(self, shutter, delta=1.0, radius_min=0.5, max_instances=16):
+        """A setting of the handle: every later level-set, mesh and render snapshot stamps each particle as a chain of at most
+        `max_instances` spheres along -velocity over the time `shutter` (the step's dt: the path of the last step), spaced by
+        `delta` radii / 2 and shrinking from the snapshot's radius to `radius_min` voxels, which must not exceed it
+        (include/fluid_hip.h, "liquid surface, velocity trails").  sdf_set_trails(None): off, the default.  Under trails attr=True
+        snapshots are the library's FLUID_ERR_STATE."""
+        if shutter is None:
+            check(lib.fluid_sdf_set_trails(self._h, None))
+            return
+        t = SdfTrails(float(shutter), float(delta), float(radius_min), int(max_instances), 0)
+        check(lib.fluid_sdf_set_trails(self._h, C.byref(t)))
+
+    def sdf_trails_stats(self):
+        """Of the last snapshot under sdf_set_trails: the live particles expanded and the instances made (before the in-grid test)."""
+        a, b = C.c_int64(), C.c_int64()
+        check(lib.fluid_sdf_trails_stats(self._h, C.byref(a), C.byref(b)))
+        return {"particles": a.value, "instances": b.value}
 
     def sdf_snapshot_avg(self, radius, half_width, influence):
         """Enqueue the rank record of the averaged-position surface of the particles as they are now: squared distances and

@@ -966,7 +966,8 @@ int64_t fluid_sdf_flow(const fluid_sdf_grid_t* g, const struct fluid_sdf_attr* a
  * Limits: 0 < hf <= 4, else FLUID_ERR_ARG.  With hf < R + w the band voxels further than hf from every particle keep the spheres'
  * value (SW == 0): that is legal.
  * Decomposed runs: a rank record carries m and the four sums, and the merge is a minimum and integer additions, which is exact:
- * "liquid surface, averaged positions (decomposed runs)" below.  Attributes, radii per particle and anisotropic kernels are not built. */
+ * "liquid surface, averaged positions (decomposed runs)" below.  Attributes and anisotropic kernels are not built; radii per particle are those of
+ * "liquid surface, velocity trails" below, a surface of its own. */
 #define FLUID_SDF_SURFACE_SPHERES  0
 #define FLUID_SDF_SURFACE_AVERAGED 1
 typedef struct fluid_sdf_surface { int32_t kind; int32_t reserved; double influence; /* voxels; read with AVERAGED only */ } fluid_sdf_surface_t;
@@ -1048,6 +1049,70 @@ int fluid_dist_sdf_wait_avg(fluid_sim_t* s, fluid_sdf_avg_part_t* out);
  * no dense grid. */
 int64_t fluid_sdf_avg_grids_merge(const fluid_sdf_avg_part_t* parts, int32_t n_parts, int64_t cap_leaves, int32_t* origin, float* values,
                                   uint64_t* active);
+
+/* ---- liquid surface, velocity trails: every particle a chain of shrinking spheres along -velocity ----------------------------------
+ * In a splash, spray and thin sheets come out of "liquid surface" as separate round blobs.  OpenVDB's answer is
+ * ParticlesToLevelSet::rasterizeTrails (tools/ParticlesToLevelSet.h:649-683, on makeSphere, :713-749): every particle is stamped as
+ * a short chain of spheres of decreasing radius behind it, so a fast droplet becomes a tapered streak and a sheet closes up.  This
+ * is that loop restated as a function of the particle set, with the trail length accumulated directly in place of |P - P0| and
+ * without the library's Rmin / Rmax rejection.  Unchanged from "liquid surface": the constants R, w, dxf, bg, the squared distance
+ * x2y2z2 (x2 below) exactly as stated there, and the leaf and list rules.  Float arithmetic unless stated, every operation rounded
+ * to float, no FMA; sqrtf and the float division correctly rounded.
+ * Settings (fluid_sdf_trails_t): shutter >= 0 and finite, the time the trail covers (shutter = dt: the path of the last step);
+ *   delta > 0 and finite, the spacing factor (the library's default: 1); radius_min > 0 and finite, in voxels, the radius at the
+ *   trail's end; 1 <= max_instances <= 32; reserved == 0.  Anything else: FLUID_ERR_ARG.  At a snapshot Rm = (float)radius_min must
+ *   satisfy Rm <= R, else FLUID_ERR_ARG from the snapshot: R belongs to the call, not to the setting.
+ * Instances of a particle with position P0 and velocity v (the handle's doubles; velocities are in the units positions advance in,
+ *   x += dt * v: voxels per time, no division by dx):
+ *   vf_a = (float)(shutter * v_a) per axis (a double product, one narrowing); s2 = (vf_x*vf_x + vf_y*vf_y) + vf_z*vf_z;
+ *   speed = sqrtf(s2).  Instance 0 is (P0, R), always, with P0 untouched.  Unless speed > 0.0f && speed <= FLT_MAX there is no
+ *   further instance.  Otherwise inv = 1.0f / speed, n_a = -(vf_a * inv), c = 0.5f * (float)delta, dR = R - Rm, and from t = 0,
+ *   r = R, k = 0:  t = t + c * r;  stop unless t <= speed and k + 1 < max_instances;  k = k + 1;  r = R - (dR * t) * inv;  emit the
+ *   instance at P_a = P0_a + (double)(t * n_a) (one float product, one double sum) with radius r;  repeat.
+ *   Every r <= R (the subtrahend is non-negative).  The loop is bounded by max_instances alone: t may stop growing in float.
+ * The voxel.  An instance counts iff its own base cell round(P) lies in [lo,hi]^3: a particle outside the grid can contribute
+ *   instances inside it.  For an instance of radius r: mx = r + w, max2 = mx * mx, mn = max(0.0f, r - w), min2 = mn * mn.  Against
+ *   voxel c it says nothing if x2 >= max2, INSIDE if x2 <= min2, and otherwise gives the candidate d = dxf * (sqrtf(x2) - r).  The
+ *   voxel is inactive -bg if any counted instance says inside; otherwise, with d* the minimum candidate, active with value d* if
+ *   d* < bg; inactive +bg in every other case.  An OR and a minimum of floats: order-free, and what makeSphere's order-dependent
+ *   sequence leaves in any order (a setValueOff(inside) wins whether it comes before or after a setValue).
+ *   When every radius equals R this is "liquid surface" bit for bit: sqrtf, the subtraction of a constant and the product with
+ *   dxf > 0 are monotone, so min d = d(min x2).
+ * Limits: R + w <= 4 as before; since r <= R an instance within its own mx of a voxel has its base cell within Chebyshev distance 4.
+ * Not built: trails on decomposed runs (the union splits exactly over ranks: an OR and a minimum; the rank record is the next step),
+ * radii given per particle on the device (fluid_spheres_surface has them on the host), attributes, anisotropic kernels. */
+typedef struct fluid_sdf_trails {
+    double shutter, delta, radius_min;
+    int32_t max_instances, reserved;
+} fluid_sdf_trails_t;
+/* A setting of the handle beside fluid_sdf_set_surface; NULL clears it.  While it is set, fluid_sdf_snapshot,
+ * fluid_sdf_snapshot_filtered, fluid_mesh_snapshot, fluid_mesh_snapshot_filtered, fluid_mesh_snapshot_ex (without
+ * FLUID_MESH_VELOCITY) and fluid_render_snapshot take the level set defined above in place of the spheres'; tracks, growth, filter
+ * kinds, pack, mesh and ray caster run unchanged.  The range is the box of the counted INSTANCES' base cells, dilated as before;
+ * fluid_sdf_grid_t.radius reports R.  Before the kernels are sized the instances' total is read back with their box (8 bytes beside
+ * the 24); scratch of 60 bytes per instance is allocated by the first snapshot under the setting.  Cleared: every byte of every
+ * entry point what it was.  FLUID_ERR_STATE: on a decomposed handle; while the handle's surface kind is AVERAGED (and
+ * fluid_sdf_set_surface(AVERAGED) while trails are set).  Under trails the attribute entry points (fluid_sdf_snapshot_attr,
+ * fluid_mesh_snapshot_attr, FLUID_MESH_VELOCITY) and fluid_dist_sdf_snapshot / fluid_dist_sdf_snapshot_attr (on a plain handle)
+ * return FLUID_ERR_STATE, as under AVERAGED.  fluid_dist_sdf_snapshot_avg takes its surface as an argument: it neither reads nor is
+ * changed by this setting. */
+int fluid_sdf_set_trails(fluid_sim_t* s, const fluid_sdf_trails_t* t);
+/* Of the last snapshot taken under the setting (either pointer may be NULL): the live particles expanded and the instances made,
+ * before the in-grid test. */
+int fluid_sdf_trails_stats(fluid_sim_t* s, int64_t* particles, int64_t* instances);
+/* Host only, no handle: the expansion above in particle order (pos, vel: x, y, z per particle; vel NULL: all zero) into
+ * out_pos[3 * cap] / out_radius[cap].  Returns the instance count (both outputs NULL: the count only, cap is ignored), or
+ * -FLUID_ERR_ARG with nothing written: np < 0, a NULL pos with np > 0, p or t NULL or outside their limits, Rm > R, one output NULL
+ * alone, cap too small. */
+int64_t fluid_particles_trails(int64_t np, const double* pos, const double* vel, const fluid_sdf_params_t* p, const fluid_sdf_trails_t* t,
+                               int64_t cap, double* out_pos, float* out_radius);
+/* Host only, no handle: the dense level set of n_items arbitrary (position, radius) items by the voxel rule above on the grid of
+ * n^3 voxels of size dx: values[n^3] and active[n^3] (z fastest; active may be NULL), brute force over the base cells within 4 of
+ * each voxel.  p->radius is the bound R (the limits of p are fluid_sdf_snapshot's); an item with !(0 < radius <= R) is
+ * FLUID_ERR_ARG, as are n < 1, !(dx > 0) and a NULL pos or radius (n_items > 0), p or values.  It is how radii per particle are
+ * available today, and what k_sdf_search_rad is pinned to bit for bit. */
+int fluid_spheres_surface(int32_t n, double dx, int64_t n_items, const double* pos, const float* radius, const fluid_sdf_params_t* p,
+                          float* values, uint8_t* active);
 
 /* ---- liquid surface as a mesh: surface nets of the level set ----------------------------------------------------------------
  * Polygons for everyone who is no volume renderer.  The reference names tools/VolumeToMesh.h, whose output depends on the library's
