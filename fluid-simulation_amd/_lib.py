@@ -281,6 +281,8 @@ SYMBOLS = [
     ("fluid_dist_sdf_snapshot_avg", C.c_int, [_P, C.POINTER(SdfParams), C.POINTER(SdfSurface)]),
     ("fluid_dist_sdf_wait_avg", C.c_int, [_P, C.POINTER(SdfAvgPartC)]),
     ("fluid_sdf_avg_grids_merge", C.c_int64, [C.POINTER(SdfAvgPartC), C.c_int32, C.c_int64, _P, _P, _P]),
+    ("fluid_dist_sdf_snapshot_trails", C.c_int, [_P, C.POINTER(SdfParams), C.POINTER(SdfTrails)]),
+    ("fluid_dist_sdf_trails_stats", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("fluid_mesh_snapshot_ex", C.c_int, [_P, C.POINTER(SdfParams), C.POINTER(SdfFilter), C.c_uint32]),
     ("fluid_mesh_wait_ex", C.c_int, [_P, C.POINTER(MeshC), C.POINTER(MeshExC)]),
     ("fluid_sdf_mesh_normals", C.c_int64, [C.POINTER(SdfGridC), C.c_int64, _P]),

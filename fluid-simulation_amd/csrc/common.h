@@ -371,11 +371,12 @@ void launch_sdf_pack_avg(hipStream_t st, const SdfGeom& g, const int* flags, con
                          float* dist2, uint64_t* sums, int* origin);
 // "liquid surface, velocity trails" (kernels_sdf_trail.hip; tc: sdf_trail_def.h).  count: icnt[i] = instances of live particle i,
 // small[0..5] = min, max of the base cells of the instances that lie in the grid, small[8..9] = the 64-bit total of icnt.  expand:
-// instance k of particle i to slot ioff[i] + k of ix, iy, iz, ir (cap slots).  scatter: launch_sdf_scatter with the radius (sr)
+// instance k of particle i to slot ioff[i] + k of ix, iy, iz, ir (cap slots).  live (as for launch_sdf_bbox): an entry with
+// pid == PID_DEAD has no instance (icnt 0), and small[10..11] = the 64-bit count of the live entries (0 with live = false).  scatter: launch_sdf_scatter with the radius (sr)
 // beside the position.  search_rad: launch_sdf_search over items that carry their own radius <= g.R
-void launch_trail_count(hipStream_t st, long n, Particles p, const tdef::Consts& tc, int lo, int hi, int* icnt, int* small);
+void launch_trail_count(hipStream_t st, long n, Particles p, const tdef::Consts& tc, int lo, int hi, int* icnt, int* small, bool live = false);
 void launch_trail_expand(hipStream_t st, long n, Particles p, const tdef::Consts& tc, const int* ioff, long cap, double* ix, double* iy,
-                         double* iz, float* ir);
+                         double* iz, float* ir, bool live = false);
 void launch_trail_scatter(hipStream_t st, long n, const double* ix, const double* iy, const double* iz, const float* ir, const SdfGeom& g,
                           const int* start, const int* place, double* sx, double* sy, double* sz, float* sr);
 void launch_sdf_search_rad(hipStream_t st, const SdfGeom& g, const int* start, const double* sx, const double* sy, const double* sz,

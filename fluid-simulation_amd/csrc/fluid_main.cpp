@@ -114,8 +114,16 @@
 // the step the snapshot follows (fluid_step_stats_t.dt_out; the setting is renewed every step); DELTA > 0 the spacing factor
 // (default 1); RMIN > 0 the radius at the trail's end in voxels (default: half the smallest R of the three outputs), at most every
 // such R; MAX in 1..32 the most instances of a particle (default 16).  One GPU only.  Refused outside these limits, with none of
-// the three set, with FLUID_OUT_SURFACE_KIND=averaged, FLUID_OUT_MESH_VEL (trails carry no attributes) or FLUID_BLOCKS (the rank
-// record of instances is not built), before any handle is created.
+// the three set, with FLUID_OUT_SURFACE_KIND=averaged, FLUID_OUT_MESH_VEL (trails carry no attributes) or FLUID_BLOCKS (a block run
+// takes FLUID_BLOCKS_SURFACE_TRAILS), before any handle is created.
+//   FLUID_BLOCKS_SURFACE_TRAILS=SHUTTER[,DELTA[,RMIN[,MAX]]] (unset: off; read with FLUID_BLOCKS only) — the same choice, with the same
+// grammar, defaults and word dt, for what FLUID_BLOCKS_SURFACE, FLUID_BLOCKS_MESH[_NORMALS|_TRIS] and FLUID_BLOCKS_RENDER take: every
+// block thread takes the rank record of its live particles' instances (fluid_dist_sdf_snapshot_trails, the trails an argument; with
+// dt the shutter is the block's own dt_out of the step just taken, the same double on every block) in the place of
+// fluid_dist_sdf_snapshot, and the main thread merges the plain lists as before (fluid_sdf_grids_merge; include/fluid_hip.h, "liquid
+// surface, velocity trails (decomposed runs)"): the merged list is byte for byte the one-GPU list of all particles, and
+// FLUID_OUT_SMOOTH*, FLUID_OUT_TRACK*, mesh, image and file go on unchanged.  Refused malformed, with RMIN > R, with none of the three
+// set, with FLUID_BLOCKS_SURFACE_KIND=averaged or with FLUID_BLOCKS_MESH_VEL (trails carry no attributes), before any handle is created.
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -152,6 +160,40 @@ static int env_option(const char* name, const char* base, bool base_set, const c
         return -1;
     }
     return t == "1";
+}
+
+// "SHUTTER[,DELTA[,RMIN[,MAX]]]" of FLUID_OUT_SURFACE_TRAILS / FLUID_BLOCKS_SURFACE_TRAILS into *t; *dt: SHUTTER is the word dt.  Rsmall: the
+// smallest (float) R of the outputs that are set, +inf if none is (RMIN defaults to half of it).  false: malformed or outside the
+// limits, and the usage is printed under the variable's name
+static bool parse_trails(const char* name, const char* value, double Rsmall, fluid_sdf_trails_t* t, bool* dt)
+{
+    const std::string v = value;
+    std::vector<std::string> part;
+    for (size_t at = 0;;) {
+        const size_t comma = v.find(',', at);
+        part.push_back(v.substr(at, comma == std::string::npos ? comma : comma - at));
+        if (comma == std::string::npos) break;
+        at = comma + 1;
+    }
+    *t = fluid_sdf_trails_t{0.0, 1.0, 0.0, 16, 0};
+    *dt = false;
+    t->radius_min = std::isfinite(Rsmall) ? 0.5 * Rsmall : 0.5;
+    char tail = 0;
+    long maxi = 16;
+    bool ok = part.size() >= 1 && part.size() <= 4;
+    if (ok && part[0] == "dt") *dt = true;
+    else ok = ok && sscanf(part[0].c_str(), "%lf%c", &t->shutter, &tail) == 1;
+    ok = ok && (part.size() < 2 || sscanf(part[1].c_str(), "%lf%c", &t->delta, &tail) == 1);
+    ok = ok && (part.size() < 3 || sscanf(part[2].c_str(), "%lf%c", &t->radius_min, &tail) == 1);
+    ok = ok && (part.size() < 4 || sscanf(part[3].c_str(), "%ld%c", &maxi, &tail) == 1);
+    ok = ok && maxi >= 1 && maxi <= 32;
+    t->max_instances = (int32_t)(ok ? maxi : 16);
+    if (!ok || !(t->shutter >= 0) || !std::isfinite(t->shutter) || !(t->delta > 0) || !std::isfinite(t->delta) || !(t->radius_min > 0) ||
+        !std::isfinite(t->radius_min)) {
+        std::cerr << name << " must be SHUTTER[,DELTA[,RMIN[,MAX]]]: SHUTTER a finite time >= 0 or the word dt, DELTA > 0, RMIN > 0 (voxels), MAX in 1..32, e.g. dt,1,0.5,16" << std::endl;
+        return false;
+    }
+    return true;
 }
 
 // "R,W[,WIDTHxHEIGHT]" of FLUID_OUT_RENDER / FLUID_BLOCKS_RENDER
@@ -403,6 +445,9 @@ struct BlockCfg {
     fluid_camera_t cam{};
     bool averaged = false;    // FLUID_BLOCKS_SURFACE_KIND=averaged: the blocks take rank records of the averaged surface
     fluid_sdf_surface_t surf{FLUID_SDF_SURFACE_SPHERES, 0, 0.0};
+    bool trails = false;      // FLUID_BLOCKS_SURFACE_TRAILS: the blocks take rank records of their instances
+    bool trails_dt = false;   // ... with SHUTTER = dt: every block's own dt_out of the step just taken
+    fluid_sdf_trails_t trl{0.0, 1.0, 0.0, 16, 0};
 };
 
 // What the main thread and the block threads share: `go` = steps released so far, done[i & 1] = blocks that finished step i.
@@ -467,6 +512,7 @@ static int run_blocks(const BlockCfg& cfg, const std::vector<double>& pos, int64
     std::vector<fluid_sdf_attr_part_t> apart[2] = {std::vector<fluid_sdf_attr_part_t>(R), std::vector<fluid_sdf_attr_part_t>(R)};
     const bool avg = level && cfg.averaged;         // ... of the averaged surface: rank records of the minimum and the sums
     std::vector<fluid_sdf_avg_part_t> vpart[2] = {std::vector<fluid_sdf_avg_part_t>(R), std::vector<fluid_sdf_avg_part_t>(R)};
+    const bool trails = level && cfg.trails;        // ... of the velocity trails: plain lists of every block's instances
     std::vector<fluid_step_stats_t> st0(2);   // rank 0's stats of step i in st0[i & 1]
     auto block = [&](int r) {
         fluid_sim_t* sim = nullptr;
@@ -500,7 +546,12 @@ static int run_blocks(const BlockCfg& cfg, const std::vector<double>& pos, int64
             // the surface of this block's live particles as the step left them (exact whether or not the step moved the planes)
             if (avg && fluid_dist_sdf_snapshot_avg(sim, &cfg.sp, &cfg.surf) != FLUID_OK) { err("fluid_dist_sdf_snapshot_avg"); break; }
             if (avg && fluid_dist_sdf_wait_avg(sim, &vpart[i & 1][r]) != FLUID_OK) { err("fluid_dist_sdf_wait_avg"); break; }
-            if (level && !avg && (attr ? fluid_dist_sdf_snapshot_attr(sim, &cfg.sp) : fluid_dist_sdf_snapshot(sim, &cfg.sp)) != FLUID_OK) { err("fluid_dist_sdf_snapshot"); break; }
+            if (trails) {   // a plain record like the spheres': fluid_dist_sdf_wait below takes it
+                fluid_sdf_trails_t t = cfg.trl;
+                if (cfg.trails_dt) t.shutter = st.dt_out;   // the path of the step just taken (one double on every block)
+                if (fluid_dist_sdf_snapshot_trails(sim, &cfg.sp, &t) != FLUID_OK) { err("fluid_dist_sdf_snapshot_trails"); break; }
+            }
+            if (level && !avg && !trails && (attr ? fluid_dist_sdf_snapshot_attr(sim, &cfg.sp) : fluid_dist_sdf_snapshot(sim, &cfg.sp)) != FLUID_OK) { err("fluid_dist_sdf_snapshot"); break; }
             if (level && !avg && (attr ? fluid_dist_sdf_wait_attr(sim, &spart[i & 1][r], &apart[i & 1][r]) : fluid_dist_sdf_wait(sim, &spart[i & 1][r])) != FLUID_OK) { err("fluid_dist_sdf_wait"); break; }
             {
                 std::lock_guard<std::mutex> lk(sy.m);
@@ -973,37 +1024,13 @@ int main(int, char**)
     bool trails = false, trails_dt = false;
     fluid_sdf_trails_t trl{0.0, 1.0, 0.0, 16, 0};
     if (const char* tenv = getenv("FLUID_OUT_SURFACE_TRAILS"); tenv && *tenv) {
-        const char* const usage = "FLUID_OUT_SURFACE_TRAILS must be SHUTTER[,DELTA[,RMIN[,MAX]]]: SHUTTER a finite time >= 0 or the word dt, DELTA > 0, RMIN > 0 (voxels), MAX in 1..32, e.g. dt,1,0.5,16";
-        std::string v = tenv;
-        std::vector<std::string> part;
-        for (size_t at = 0;;) {
-            const size_t comma = v.find(',', at);
-            part.push_back(v.substr(at, comma == std::string::npos ? comma : comma - at));
-            if (comma == std::string::npos) break;
-            at = comma + 1;
-        }
         double Rsmall = INFINITY;
         if (surface) Rsmall = std::fmin(Rsmall, (double)(float)sp.radius);
         if (mesh) Rsmall = std::fmin(Rsmall, (double)(float)mp.radius);
         if (render) Rsmall = std::fmin(Rsmall, (double)(float)rp.radius);
-        trl.radius_min = std::isfinite(Rsmall) ? 0.5 * Rsmall : 0.5;
-        char tail = 0;
-        long maxi = 16;
-        bool ok = part.size() >= 1 && part.size() <= 4;
-        if (ok && part[0] == "dt") trails_dt = true;
-        else ok = ok && sscanf(part[0].c_str(), "%lf%c", &trl.shutter, &tail) == 1;
-        ok = ok && (part.size() < 2 || sscanf(part[1].c_str(), "%lf%c", &trl.delta, &tail) == 1);
-        ok = ok && (part.size() < 3 || sscanf(part[2].c_str(), "%lf%c", &trl.radius_min, &tail) == 1);
-        ok = ok && (part.size() < 4 || sscanf(part[3].c_str(), "%ld%c", &maxi, &tail) == 1);
-        ok = ok && maxi >= 1 && maxi <= 32;
-        trl.max_instances = (int32_t)(ok ? maxi : 16);
-        if (!ok || !(trl.shutter >= 0) || !std::isfinite(trl.shutter) || !(trl.delta > 0) || !std::isfinite(trl.delta) || !(trl.radius_min > 0) ||
-            !std::isfinite(trl.radius_min)) {
-            std::cerr << usage << std::endl;
-            return 1;
-        }
+        if (!parse_trails("FLUID_OUT_SURFACE_TRAILS", tenv, Rsmall, &trl, &trails_dt)) return 1;
         if (blocks && *blocks) {
-            std::cerr << "FLUID_OUT_SURFACE_TRAILS cannot be combined with FLUID_BLOCKS: it is a setting of a one-GPU handle (the rank record of instances is not built)" << std::endl;
+            std::cerr << "FLUID_OUT_SURFACE_TRAILS cannot be combined with FLUID_BLOCKS: it is a setting of a one-GPU handle (a block run takes FLUID_BLOCKS_SURFACE_TRAILS: the rank record of every block's instances, merged on the host)" << std::endl;
             return 1;
         }
         if (skind.kind == FLUID_SDF_SURFACE_AVERAGED) {
@@ -1044,6 +1071,28 @@ int main(int, char**)
             return 1;
         }
         if (word == "averaged") bc.averaged = true, bc.surf = fluid_sdf_surface_t{FLUID_SDF_SURFACE_AVERAGED, 0, H};
+    }
+    if (const char* tenv = getenv("FLUID_BLOCKS_SURFACE_TRAILS"); blocks && *blocks && tenv && *tenv) {
+        const bool any = bc.surface || bc.mesh || bc.render;   // (their R,W are the same numbers: bc.sp)
+        const double Rsmall = any ? (double)(float)bc.sp.radius : INFINITY;
+        if (!parse_trails("FLUID_BLOCKS_SURFACE_TRAILS", tenv, Rsmall, &bc.trl, &bc.trails_dt)) return 1;
+        if (bc.averaged) {
+            std::cerr << "FLUID_BLOCKS_SURFACE_TRAILS cannot be combined with FLUID_BLOCKS_SURFACE_KIND=averaged: the two surfaces exclude each other" << std::endl;
+            return 1;
+        }
+        if (bc.mesh_vel) {
+            std::cerr << "FLUID_BLOCKS_SURFACE_TRAILS cannot be combined with FLUID_BLOCKS_MESH_VEL: trails carry no attributes" << std::endl;
+            return 1;
+        }
+        if (!any) {
+            std::cerr << "FLUID_BLOCKS_SURFACE_TRAILS chooses the level set FLUID_BLOCKS_SURFACE, FLUID_BLOCKS_MESH or FLUID_BLOCKS_RENDER take: none of them is set" << std::endl;
+            return 1;
+        }
+        if (!((double)(float)bc.trl.radius_min <= Rsmall)) {
+            std::cerr << "FLUID_BLOCKS_SURFACE_TRAILS: RMIN must not exceed the radius R of FLUID_BLOCKS_SURFACE, FLUID_BLOCKS_MESH and FLUID_BLOCKS_RENDER" << std::endl;
+            return 1;
+        }
+        bc.trails = true;
     }
     if (track) bc.track = true, bc.tk = tk, bc.grow = track_grow;
     if (blocks && *blocks) {

@@ -63,6 +63,12 @@
 // per instance 60 bytes: ipos and ir (28), place and spos, which are the spheres' arrays sized for the instances (28), and sr (4);
 // allocated by the handle's first snapshot under the setting.  Attribute snapshots and the spheres' rank records are refused under it.
 //
+// fluid_dist_sdf_snapshot_trails ("liquid surface, velocity trails (decomposed runs)"): the same front half with the trails handed in
+// (spheres and these trails: no setting of the handle is read or changed) and, on a decomposed handle, the <true> forms of the two
+// expansion passes, which pass over the dead entries and count the live ones (8 more bytes read back).  The instances have no pid: they
+// are binned by k_sdf_count<false>.  The record is a plain one (kind 0), taken by fluid_dist_sdf_wait; the counters are its own
+// (dist_trail_*), so that fluid_sdf_trails_stats keeps meaning "of the last snapshot under the setting".
+//
 // fluid_sdf_snapshot_attr / fluid_mesh_snapshot_attr ("liquid surface, attributes"): the scatter also writes each sorted position's
 // index in the live arrays (ssrc), the search keeps the closest particle beside the minimum and writes its id and velocity per voxel
 // (tid, tvel), and the pack lists them.  ssrc, tid and tvel exist from the handle's first attribute snapshot on.  An attribute
@@ -129,12 +135,13 @@ struct SdfState {
     double* ipos = nullptr;    // x | y | z, inst_cap each
     float *ir = nullptr, *sr = nullptr;
     int64_t trail_particles = 0, trail_instances = 0;   // of the last snapshot under the setting
+    int64_t dist_trail_particles = 0, dist_trail_instances = 0;   // of the last fluid_dist_sdf_snapshot_trails
     uint64_t* tm = nullptr;
     int *flags = nullptr, *slot = nullptr, *leaf_sums = nullptr;
     unsigned* visits = nullptr;   // FLUID_SDF_VISITS=1 only
     bool count_visits = false;
     bool grow_stats = false;      // FLUID_SDF_GROW_STATS=1 only
-    int *d_small = nullptr, *h_small = nullptr;   // box[6], cell total, listed count, the trails' 64-bit instance total
+    int *d_small = nullptr, *h_small = nullptr;   // box[6], cell total, listed count, the trails' 64-bit instance total and live count
     SnapRing ring;
     SdfMeta m[2];
     long last_leaves = 0, last_bytes = 0;
@@ -148,9 +155,9 @@ static const char* const SDF_KIND_SINGLE = "level-set flows are single-GPU only:
 static const char* const SDF_AVG_SINGLE = "the averaged-position surface as a handle's setting is single-GPU only: a decomposed handle gives the rank record of the minimum and the four sums (fluid_dist_sdf_snapshot_avg), merged on the host (fluid_sdf_avg_grids_merge)";
 static const char* const SDF_AVG_ATTR = "the averaged-position surface carries no attributes: an average of positions has no closest particle (fluid_sdf_set_surface)";
 static const char* const SDF_AVG_DIST = "fluid_dist_sdf_snapshot gives the spheres' rank record: the averaged-position surface has a rank record of its own, which takes the surface as an argument (fluid_dist_sdf_snapshot_avg)";
-static const char* const SDF_TRAIL_SINGLE = "velocity trails are single-GPU only: the union splits exactly over ranks, but the rank record of instances is not built (fluid_sdf_set_trails)";
+static const char* const SDF_TRAIL_SINGLE = "velocity trails as a handle's setting are single-GPU only: a decomposed handle gives the rank record of its live particles' instances, which takes the trails as an argument (fluid_dist_sdf_snapshot_trails), merged on the host (fluid_sdf_grids_merge)";
 static const char* const SDF_TRAIL_ATTR = "velocity trails carry no attributes (fluid_sdf_set_trails)";
-static const char* const SDF_TRAIL_DIST = "fluid_dist_sdf_snapshot gives the spheres' rank record: it is refused while velocity trails are set (fluid_sdf_set_trails)";
+static const char* const SDF_TRAIL_DIST = "fluid_dist_sdf_snapshot gives the spheres' rank record: it is refused while velocity trails are set (fluid_sdf_set_trails); the trails' rank record takes them as an argument (fluid_dist_sdf_snapshot_trails)";
 static const char* const SDF_TRAIL_AVG = "velocity trails and the averaged-position surface exclude each other (fluid_sdf_set_trails, fluid_sdf_set_surface)";
 static const char* const SDF_TRACK_SINGLE = "tracked level-set snapshots are single-GPU only: a decomposed handle's filter runs on the merged list on the host (fluid_sdf_filter_tracked)";
 
@@ -161,8 +168,8 @@ static int sdf_init(fluid_sim* s)
     s->sdf = o;   // from here on sdf_free releases whatever the lines below got
     if (const char* e = getenv("FLUID_SDF_VISITS")) o->count_visits = atoi(e) != 0;   // developer knob (tools/sdf_cost.py)
     if (const char* e = getenv("FLUID_SDF_GROW_STATS")) o->grow_stats = atoi(e) != 0;   // developer knob (tools/grow_cost.py)
-    HIPCHK(hipMalloc((void**)&o->d_small, 10 * sizeof(int)));
-    HIPCHK(hipHostMalloc((void**)&o->h_small, 10 * sizeof(int)));
+    HIPCHK(hipMalloc((void**)&o->d_small, 12 * sizeof(int)));
+    HIPCHK(hipHostMalloc((void**)&o->h_small, 12 * sizeof(int)));
     return snap_init(o->ring);
 }
 
@@ -292,7 +299,8 @@ static long sdf_count_flags(fluid_sim* s, const int* flags, long leaves)
 // on the handle's stream; a decomposed handle (s->dist) bins its live entries only.  f->any = some particle counts; then f->g holds
 // the box and the range, and tv / flags are the search's: 512 values and a listed flag per leaf of the range (the values of a leaf
 // whose flag is 0 may be stale: kernels_sdf.hip).  The scratch is one per handle: whoever calls next overwrites it, in stream order.
-int fl::sdf_begin(fluid_sim* s, const fluid_sdf_params_t* p, SdfFront* f, const fluid_sdf_filter_t* filt, const fluid_sdf_surface_t* sf_arg)
+int fl::sdf_begin(fluid_sim* s, const fluid_sdf_params_t* p, SdfFront* f, const fluid_sdf_filter_t* filt, const fluid_sdf_surface_t* sf_arg,
+                  const fluid_sdf_trails_t* tr_arg)
 {
     if (!p) return fail(FLUID_ERR_ARG, "null argument");
     if (filt && !plan::filter_ok(filt))
@@ -330,13 +338,16 @@ int fl::sdf_begin(fluid_sim* s, const fluid_sdf_params_t* p, SdfFront* f, const 
     f->filt = filt, f->dilate = 4;
     f->attr = false, f->dist2 = false;
     f->tm = nullptr, f->tid = nullptr, f->tvel = nullptr, f->tmin = nullptr;
-    const fluid_sdf_surface_t& sf = sf_arg ? *sf_arg : s->sdf->surface;
+    const fluid_sdf_surface_t spheres{FLUID_SDF_SURFACE_SPHERES, 0, 0.0};
+    const fluid_sdf_surface_t& sf = sf_arg ? *sf_arg : tr_arg ? spheres : s->sdf->surface;   // (trails handed in: spheres and these trails)
     f->record = false;
     f->averaged = sf.kind == FLUID_SDF_SURFACE_AVERAGED;
     const adef::Consts hc = f->averaged ? adef::consts(sf.influence) : adef::Consts{0.0f, 0.0f};
     f->h2 = hc.h2, f->ih2 = hc.ih2;
-    f->trails = !sf_arg && s->sdf->trails_on;   // (a surface handed in is the averaged rank record's: the setting is not read)
-    if (f->trails && !tdef::radius_ok(s->sdf->trails.radius_min, R))
+    f->trails_arg = tr_arg != nullptr;
+    f->trails = tr_arg || (!sf_arg && s->sdf->trails_on);   // (a surface handed in is the averaged rank record's: the setting is not read)
+    f->tr = tr_arg ? *tr_arg : s->sdf->trails;
+    if (f->trails && !tdef::radius_ok(f->tr.radius_min, R))
         return fail(FLUID_ERR_ARG, "velocity trails: radius_min <= radius is required (fluid_sdf_set_trails)");
     return FLUID_OK;
 }
@@ -352,24 +363,30 @@ int fl::sdf_front(fluid_sim* s, SdfFront* f)
     int* box = o->h_small;
     long items = s->np;   // what is binned: the live particles, or their instances
     tdef::Consts tc{};
+    // the entries of a decomposed handle that are dead have no instance; the trails handed in keep counters of their own
+    const bool tlive = f->trails && s->dist;
+    int64_t& t_particles = f->trails_arg ? o->dist_trail_particles : o->trail_particles;
+    int64_t& t_instances = f->trails_arg ? o->dist_trail_instances : o->trail_instances;
     if (f->trails) {
-        const fluid_sdf_trails_t& t = o->trails;
+        const fluid_sdf_trails_t& t = f->tr;
         tc = tdef::consts(t.shutter, t.delta, t.radius_min, t.max_instances, g.R);
-        o->trail_particles = s->np, o->trail_instances = 0;
+        t_particles = tlive ? 0 : s->np, t_instances = 0;
     }
     if (s->np > 0 && f->trails) {
         if ((rc = trail_scratch(o, s->np, 0))) return rc;
-        launch_trail_count(s->st, s->np, live, tc, g.lo, g.hi, o->icnt, o->d_small);
+        launch_trail_count(s->st, s->np, live, tc, g.lo, g.hi, o->icnt, o->d_small, tlive);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(o->h_small, o->d_small, 6 * sizeof(int), hipMemcpyDeviceToHost, s->st));
-        HIPCHK(hipMemcpyAsync(o->h_small + 8, o->d_small + 8, 2 * sizeof(int), hipMemcpyDeviceToHost, s->st));
+        HIPCHK(hipMemcpyAsync(o->h_small + 8, o->d_small + 8, (tlive ? 4 : 2) * sizeof(int), hipMemcpyDeviceToHost, s->st));
         HIPCHK(hipStreamSynchronize(s->st));
-        uint64_t total;
+        uint64_t total, alive = (uint64_t)s->np;   // every instance total lies in [live particles, MAX_INSTANCES x live particles]
         memcpy(&total, o->h_small + 8, sizeof total);
-        if (total < (uint64_t)s->np || total > (uint64_t)s->np * tdef::MAX_INSTANCES) return fail(FLUID_ERR_HIP, "velocity trails: instance total out of range");
+        if (tlive) memcpy(&alive, o->h_small + 10, sizeof alive);
+        if (alive > (uint64_t)s->np) return fail(FLUID_ERR_HIP, "velocity trails: live count out of range");
+        if (total < alive || total > alive * tdef::MAX_INSTANCES) return fail(FLUID_ERR_HIP, "velocity trails: instance total out of range");
         if (total > 0x7fffffffull) return fail(FLUID_ERR_ARG, "velocity trails: more than 2^31 - 1 instances");
-        o->trail_instances = (int64_t)total;
-        items = (long)total;
+        t_particles = (int64_t)alive, t_instances = (int64_t)total;
+        items = (long)total;   // (0: nothing live, and the box read back is k_trail_init's empty one)
     } else if (s->np > 0) {
         launch_sdf_bbox(s->st, s->np, live, g.lo, g.hi, o->d_small, s->dist);
         HIPCHK(hipGetLastError());
@@ -398,10 +415,10 @@ int fl::sdf_front(fluid_sim* s, SdfFront* f)
             if ((rc = trail_scratch(o, s->np, items))) return rc;
             inst.px = o->ipos, inst.py = o->ipos + o->inst_cap, inst.pz = o->ipos + 2 * o->inst_cap;
             launch_exclusive_scan(s->st, o->icnt, o->ioff, s->np, o->isums, o->d_small + 6);   // (the total is known; d_small[6] is rewritten below)
-            launch_trail_expand(s->st, s->np, live, tc, o->ioff, items, inst.px, inst.py, inst.pz, o->ir);
+            launch_trail_expand(s->st, s->np, live, tc, o->ioff, items, inst.px, inst.py, inst.pz, o->ir, tlive);
         }
         HIPCHK(hipMemsetAsync(o->cnt, 0, (size_t)(cells + 1) * sizeof(int), s->st));
-        launch_sdf_count(s->st, items, f->trails ? inst : live, g, o->cnt, o->place, s->dist);
+        launch_sdf_count(s->st, items, f->trails ? inst : live, g, o->cnt, o->place, s->dist && !f->trails);   // (the instances have no pid: none is dead)
         launch_exclusive_scan(s->st, o->cnt, o->start, cells + 1, o->cell_sums, o->d_small + 6);   // start[cells] = the counted particles
         if (f->trails) launch_trail_scatter(s->st, items, inst.px, inst.py, inst.pz, o->ir, g, o->start, o->place, sx, sy, sz, o->sr);
         else launch_sdf_scatter(s->st, s->np, live, g, o->start, o->place, sx, sy, sz, f->attr ? o->ssrc : nullptr);
@@ -471,10 +488,10 @@ static constexpr size_t sdf_rec(int kind)   // bytes per listed leaf of a record
 static constexpr size_t sdf_between(int kind) { return sdf_rec(kind) - SDF_REC; }   // per leaf, between the values and the masks
 
 static int sdf_capture(fluid_sim* s, const fluid_sdf_params_t* p, const fluid_sdf_filter_t* filt = nullptr, int attr = 0,
-                       const fluid_sdf_surface_t* sf = nullptr)
+                       const fluid_sdf_surface_t* sf = nullptr, const fluid_sdf_trails_t* tr = nullptr)
 {
     SdfFront f;
-    int rc = sdf_begin(s, p, &f, filt, sf);
+    int rc = sdf_begin(s, p, &f, filt, sf, tr);
     if (rc) return rc;
     const bool record = attr == SDF_AVG_RECORD;
     f.attr = attr >= 1 && !record, f.dist2 = attr == 2, f.record = record;
@@ -762,6 +779,22 @@ int fluid_dist_sdf_wait_avg(fluid_sim_t* s, fluid_sdf_avg_part_t* out)
 {
     if (!s) return fail(FLUID_ERR_ARG, "null handle");
     return sdf_wait_avg(s, out);
+}
+
+int fluid_dist_sdf_snapshot_trails(fluid_sim_t* s, const fluid_sdf_params_t* p, const fluid_sdf_trails_t* t)
+{
+    if (!s) return fail(FLUID_ERR_ARG, "null handle");
+    if (!t || !tdef::settings_ok(t->shutter, t->delta, t->radius_min, t->max_instances, t->reserved))
+        return fail(FLUID_ERR_ARG, "trails' rank record: a finite shutter >= 0, delta > 0 and radius_min > 0 (voxels), max_instances in 1..32 and reserved 0 are required");
+    return sdf_capture(s, p, nullptr, 0, nullptr, t);
+}
+
+int fluid_dist_sdf_trails_stats(fluid_sim_t* s, int64_t* particles, int64_t* instances)
+{
+    if (!s) return fail(FLUID_ERR_ARG, "null handle");
+    if (particles) *particles = s->sdf ? s->sdf->dist_trail_particles : 0;
+    if (instances) *instances = s->sdf ? s->sdf->dist_trail_instances : 0;
+    return FLUID_OK;
 }
 
 int fluid_dist_sdf_stats(fluid_sim_t* s, int64_t* leaves_in_grid, int64_t* leaves_listed, int64_t* bytes_to_host)

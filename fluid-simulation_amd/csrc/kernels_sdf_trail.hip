@@ -5,6 +5,9 @@
 //   expand   two passes over the live particles, each running tdef::next.  The first counts a particle's instances (icnt), adds
 //            them to a 64-bit total and reduces the base-cell box of the instances that lie in the grid (integer min / max, as
 //            k_sdf_bbox).  After the scan of icnt the second writes ix, iy, iz (double) and ir (float) at the particle's slots.
+//            LIVE (as in k_sdf_bbox): the arrays of a decomposed handle, where an entry with pid == PID_DEAD has a stale position
+//            and velocity: it has no instance (icnt 0, nothing to the box or the total, no slot written), and the first pass also
+//            counts the live entries.  The one-GPU form never reads pid.
 //   bin      k_sdf_count<false> (kernels_sdf.hip) on the instance arrays as it stands; the scatter here carries the radius.
 //   search   k_sdf_search_rad, in the place of k_sdf_search: same cell starts in LDS, same early exit of a leaf out of reach, same
 //            tv / tm / flags.
@@ -29,23 +32,33 @@ __device__ __forceinline__ bool trail_cell(double px, double py, double pz, int 
     return true;
 }
 
-// small[0..5] = the empty box, small[8..9] = the 64-bit total 0
+// small[0..5] = the empty box, small[8..9] = the 64-bit total 0, small[10..11] = the 64-bit count of live entries 0
 __global__ void k_trail_init(int* __restrict__ small)
 {
     if (threadIdx.x < 6) small[threadIdx.x] = threadIdx.x < 3 ? INT_MAX : INT_MIN;
-    if (threadIdx.x == 8 || threadIdx.x == 9) small[threadIdx.x] = 0;
+    if (threadIdx.x >= 8 && threadIdx.x < 12) small[threadIdx.x] = 0;
 }
 
-// icnt[i] = instances of particle i (1 .. max_instances), in or out of the grid; box and total as described above
+// icnt[i] = instances of particle i (1 .. max_instances), in or out of the grid; box and total as described above.  LIVE: icnt[i] = 0
+// for a dead entry, and *nlive += the live entries (pid and nlive are read by that form alone)
+template <bool LIVE>
 __global__ __launch_bounds__(256) void k_trail_count(long n, const double* __restrict__ px, const double* __restrict__ py,
                                                      const double* __restrict__ pz, const double* __restrict__ vx,
                                                      const double* __restrict__ vy, const double* __restrict__ vz, tdef::Consts tc, int lo,
                                                      int hi, int* __restrict__ icnt, int* __restrict__ box,
-                                                     unsigned long long* __restrict__ total)
+                                                     unsigned long long* __restrict__ total, const uint32_t* __restrict__ pid,
+                                                     unsigned long long* __restrict__ nlive)
 {
     int mn[3] = {INT_MAX, INT_MAX, INT_MAX}, mx[3] = {INT_MIN, INT_MIN, INT_MIN};
-    unsigned long long made = 0;
+    unsigned long long made = 0, alive = 0;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        if (LIVE) {
+            if (pid[i] == PID_DEAD) {
+                icnt[i] = 0;
+                continue;
+            }
+            ++alive;
+        }
         const double p0[3] = {px[i], py[i], pz[i]};
         tdef::Trail T = tdef::trail(tc, vx[i], vy[i], vz[i]);
         int k = 0;
@@ -73,8 +86,10 @@ __global__ __launch_bounds__(256) void k_trail_count(long n, const double* __res
         }
     }
     made = wave_sum(made);
+    if (LIVE) alive = wave_sum(alive);
     if ((threadIdx.x & 63) == 0) {
         if (made) atomicAdd(total, made);
+        if (LIVE && alive) atomicAdd(nlive, alive);
         if (mx[0] >= mn[0]) {
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
@@ -85,15 +100,18 @@ __global__ __launch_bounds__(256) void k_trail_count(long n, const double* __res
     }
 }
 
-// the same loop again: instance k of particle i goes to slot ioff[i] + k (k < icnt[i] by construction: the loop is the count's)
+// the same loop again: instance k of particle i goes to slot ioff[i] + k (k < icnt[i] by construction: the loop is the count's).
+// LIVE: a dead entry has no slot (its ioff is the next live particle's) and returns before the loop, which runs once before it tests
+template <bool LIVE>
 __global__ __launch_bounds__(256) void k_trail_expand(long n, const double* __restrict__ px, const double* __restrict__ py,
                                                       const double* __restrict__ pz, const double* __restrict__ vx,
                                                       const double* __restrict__ vy, const double* __restrict__ vz, tdef::Consts tc,
                                                       const int* __restrict__ ioff, long cap, double* __restrict__ ix, double* __restrict__ iy,
-                                                      double* __restrict__ iz, float* __restrict__ ir)
+                                                      double* __restrict__ iz, float* __restrict__ ir, const uint32_t* __restrict__ pid)
 {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
+    if (LIVE && pid[i] == PID_DEAD) return;
     const double p0[3] = {px[i], py[i], pz[i]};
     tdef::Trail T = tdef::trail(tc, vx[i], vy[i], vz[i]);
     const long d0 = ioff[i];
@@ -202,20 +220,24 @@ void launch_sdf_search_rad(hipStream_t st, const SdfGeom& g, const int* start, c
     hipLaunchKernelGGL(k_sdf_search_rad, dim3((unsigned)g.leaves()), dim3(512), 0, st, g, start, sx, sy, sz, sr, tv, (unsigned long long*)tm, flags);
 }
 
-void launch_trail_count(hipStream_t st, long n, Particles p, const tdef::Consts& tc, int lo, int hi, int* icnt, int* small)
+void launch_trail_count(hipStream_t st, long n, Particles p, const tdef::Consts& tc, int lo, int hi, int* icnt, int* small, bool live)
 {
     hipLaunchKernelGGL(k_trail_init, dim3(1), dim3(64), 0, st, small);
     if (n <= 0) return;
     const long nb = (n + 255) / 256;
-    hipLaunchKernelGGL(k_trail_count, dim3((unsigned)(nb < 2048 ? nb : 2048)), dim3(256), 0, st, n, p.px, p.py, p.pz, p.vx, p.vy, p.vz, tc, lo, hi,
-                       icnt, small, (unsigned long long*)(small + 8));
+    const dim3 grid((unsigned)(nb < 2048 ? nb : 2048));
+    unsigned long long *total = (unsigned long long*)(small + 8), *nlive = (unsigned long long*)(small + 10);
+    if (live) hipLaunchKernelGGL(k_trail_count<true>, grid, dim3(256), 0, st, n, p.px, p.py, p.pz, p.vx, p.vy, p.vz, tc, lo, hi, icnt, small, total, p.pid, nlive);
+    else hipLaunchKernelGGL(k_trail_count<false>, grid, dim3(256), 0, st, n, p.px, p.py, p.pz, p.vx, p.vy, p.vz, tc, lo, hi, icnt, small, total, p.pid, nlive);
 }
 
 void launch_trail_expand(hipStream_t st, long n, Particles p, const tdef::Consts& tc, const int* ioff, long cap, double* ix, double* iy,
-                         double* iz, float* ir)
+                         double* iz, float* ir, bool live)
 {
-    hipLaunchKernelGGL(k_trail_expand, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, p.px, p.py, p.pz, p.vx, p.vy, p.vz, tc, ioff, cap, ix,
-                       iy, iz, ir);
+    if (n <= 0) return;
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (live) hipLaunchKernelGGL(k_trail_expand<true>, grid, dim3(256), 0, st, n, p.px, p.py, p.pz, p.vx, p.vy, p.vz, tc, ioff, cap, ix, iy, iz, ir, p.pid);
+    else hipLaunchKernelGGL(k_trail_expand<false>, grid, dim3(256), 0, st, n, p.px, p.py, p.pz, p.vx, p.vy, p.vz, tc, ioff, cap, ix, iy, iz, ir, p.pid);
 }
 
 void launch_trail_scatter(hipStream_t st, long n, const double* ix, const double* iy, const double* iz, const float* ir, const SdfGeom& g,

@@ -328,11 +328,15 @@ struct SdfFront {
                           // tv / tm; set by the caller after an sdf_begin that was handed the surface
     bool trails;          // "liquid surface, velocity trails": the handle's fluid_sdf_set_trails setting is on, copied by sdf_begin (never
                           // with a surface handed in); sdf_front bins the particles' instances and refuses it together with attr
+    fluid_sdf_trails_t tr;   // trails: the setting's copy, or the trails handed in
+    bool trails_arg;      // "velocity trails (decomposed runs)": the trails were handed in (spheres, whatever the handle's settings say);
+                          // sdf_front passes over the dead entries of a decomposed handle and keeps the rank record's counters
 };
 // limits of the parameters (and of the filter, when one is given), the state, the constants of g.  sf: nullptr = the handle's
-// fluid_sdf_set_surface setting; otherwise the surface is this one (checked by the caller) and the setting is not read
+// fluid_sdf_set_surface setting; otherwise the surface is this one (checked by the caller) and the setting is not read.  tr: nullptr =
+// the handle's fluid_sdf_set_trails setting; otherwise spheres and these trails (limits checked by the caller), no setting is read
 int sdf_begin(fluid_sim* s, const fluid_sdf_params_t* p, SdfFront* f, const fluid_sdf_filter_t* filt = nullptr,
-              const fluid_sdf_surface_t* sf = nullptr);
+              const fluid_sdf_surface_t* sf = nullptr, const fluid_sdf_trails_t* tr = nullptr);
 int sdf_front(fluid_sim* s, SdfFront* f);   // bbox (waits for the stream) -> count, scan, scatter -> search -> the filter's passes and tracks
 
 // fluid_mesh.hip

@@ -451,6 +451,9 @@ class DistFluidSim(FluidSim):
         check(lib.fluid_dist_sdf_wait_avg(self._h, C.byref(a)))
         return _sdf_avg_part_copy(a)
 
+    # sdf_snapshot_trails / sdf_dist_trails_stats ("liquid surface, velocity trails (decomposed runs)") are FluidSim's: the entry points
+    # take either kind of handle, and the record is a plain one that sdf_wait() above takes
+
     def sdf_stats(self):
         v = [C.c_int64() for _ in range(3)]
         check(lib.fluid_dist_sdf_stats(self._h, *[C.byref(x) for x in v]))

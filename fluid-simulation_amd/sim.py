@@ -994,6 +994,22 @@ class FluidSim:
         check(lib.fluid_sdf_trails_stats(self._h, C.byref(a), C.byref(b)))
         return {"particles": a.value, "instances": b.value}
 
+    def sdf_snapshot_trails(self, radius, half_width, shutter, delta=1.0, radius_min=0.5, max_instances=16):
+        """Enqueue the level set of the velocity trails of the particles as they are now (of a DistFluidSim: this rank's live
+        particles, global origins, every leaf their instances reach), the trails given here and not by a setting: no setting of the
+        handle is read or changed (include/fluid_hip.h, "liquid surface, velocity trails (decomposed runs)").  A plain record in the
+        level set's two slots: sdf_wait() takes it and merge_sdf_grids joins the ranks' exactly."""
+        p = SdfParams(float(radius), float(half_width))
+        t = SdfTrails(float(shutter), float(delta), float(radius_min), int(max_instances), 0)
+        check(lib.fluid_dist_sdf_snapshot_trails(self._h, C.byref(p), C.byref(t)))
+
+    def sdf_dist_trails_stats(self):
+        """Of the last sdf_snapshot_trails: the live particles expanded and the instances made (before the in-grid test); zeros
+        before the first.  sdf_trails_stats keeps reporting the last snapshot under sdf_set_trails."""
+        a, b = C.c_int64(), C.c_int64()
+        check(lib.fluid_dist_sdf_trails_stats(self._h, C.byref(a), C.byref(b)))
+        return {"particles": a.value, "instances": b.value}
+
     def sdf_snapshot_avg(self, radius, half_width, influence):
         """Enqueue the rank record of the averaged-position surface of the particles as they are now: squared distances and
         weighted sums per voxel, the surface given here and not by a setting (include/fluid_hip.h, "liquid surface, averaged

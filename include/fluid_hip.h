@@ -1079,8 +1079,8 @@ int64_t fluid_sdf_avg_grids_merge(const fluid_sdf_avg_part_t* parts, int32_t n_p
  *   When every radius equals R this is "liquid surface" bit for bit: sqrtf, the subtraction of a constant and the product with
  *   dxf > 0 are monotone, so min d = d(min x2).
  * Limits: R + w <= 4 as before; since r <= R an instance within its own mx of a voxel has its base cell within Chebyshev distance 4.
- * Not built: trails on decomposed runs (the union splits exactly over ranks: an OR and a minimum; the rank record is the next step),
- * radii given per particle on the device (fluid_spheres_surface has them on the host), attributes, anisotropic kernels. */
+ * Decomposed runs: "liquid surface, velocity trails (decomposed runs)" below.
+ * Not built: radii given per particle on the device (fluid_spheres_surface has them on the host), attributes, anisotropic kernels. */
 typedef struct fluid_sdf_trails {
     double shutter, delta, radius_min;
     int32_t max_instances, reserved;
@@ -1094,8 +1094,8 @@ typedef struct fluid_sdf_trails {
  * entry point what it was.  FLUID_ERR_STATE: on a decomposed handle; while the handle's surface kind is AVERAGED (and
  * fluid_sdf_set_surface(AVERAGED) while trails are set).  Under trails the attribute entry points (fluid_sdf_snapshot_attr,
  * fluid_mesh_snapshot_attr, FLUID_MESH_VELOCITY) and fluid_dist_sdf_snapshot / fluid_dist_sdf_snapshot_attr (on a plain handle)
- * return FLUID_ERR_STATE, as under AVERAGED.  fluid_dist_sdf_snapshot_avg takes its surface as an argument: it neither reads nor is
- * changed by this setting. */
+ * return FLUID_ERR_STATE, as under AVERAGED.  fluid_dist_sdf_snapshot_avg takes its surface as an argument and
+ * fluid_dist_sdf_snapshot_trails its trails: they neither read nor are changed by this setting. */
 int fluid_sdf_set_trails(fluid_sim_t* s, const fluid_sdf_trails_t* t);
 /* Of the last snapshot taken under the setting (either pointer may be NULL): the live particles expanded and the instances made,
  * before the in-grid test. */
@@ -1113,6 +1113,47 @@ int64_t fluid_particles_trails(int64_t np, const double* pos, const double* vel,
  * available today, and what k_sdf_search_rad is pinned to bit for bit. */
 int fluid_spheres_surface(int32_t n, double dx, int64_t n_items, const double* pos, const float* radius, const fluid_sdf_params_t* p,
                           float* values, uint8_t* active);
+
+/* ---- liquid surface, velocity trails (decomposed runs): a rank record of the rank's own instances, merged exactly ---------------------
+ * The trails of "liquid surface, velocity trails" for a FLUID_BLOCKS run.  No new record and no new merge: a rank's record is the
+ * plain leaf list (FLUID_SDF_LEAF_BYTES per listed leaf) of the trail surface of the rank's LIVE particles, with their positions and
+ * velocities, and the ranks' lists merge through fluid_sdf_grids_merge as it is.
+ *
+ * The record is exactly what fluid_sdf_snapshot gives under fluid_sdf_set_trails(t) on a one-GPU handle of the same grid that holds
+ * the rank's live particles.  Origins are global.  Every leaf the instances reach is listed, whether the rank owns it or not.  An
+ * instance counts iff its own base cell lies in the GLOBAL [lo,hi]^3; the rank's block and window play no part in that test, so a
+ * trail that leaves the rank's block is whole, and a live particle outside the grid contributes its in-grid instances.  An entry of
+ * the rank's arrays that is dead (a served ghost, a particle a sink removed) has a stale position and velocity and no instance.
+ * fluid_sdf_grid_t.radius reports R.
+ *
+ * Why the merge is exact.  A trail voxel of a particle set is inactive -bg if any counted instance says inside; otherwise active
+ * with the minimum candidate d* if d* < bg; otherwise inactive +bg.  A rank's list holds, per voxel, that rule over the rank's own
+ * instances (a voxel of a leaf a rank does not list is inactive +bg there).  fluid_sdf_grids_merge takes, per voxel over the parts,
+ * inactive -bg if any part holds it, else the smallest active value, else inactive +bg.  The instances of the whole set are the
+ * disjoint union of the ranks' (every live particle is on exactly one rank, and its instances are a function of it alone), "any
+ * instance says inside" is the OR of the ranks' ORs, and where no instance says inside the minimum candidate below bg is the minimum
+ * of the ranks' minima below bg (a rank whose own voxel is inside cannot occur then; a rank with no candidate below bg holds +bg,
+ * which loses).  A voxel inside on one rank and active on another is -bg in the whole and in the merge.  So the merged list is, byte
+ * for byte, what fluid_sdf_snapshot gives under fluid_sdf_set_trails(t) on one handle that holds all ranks' live particles.
+ *
+ *   per step, every rank:    fluid_step(s, &st);  t.shutter = st.dt_out;  fluid_dist_sdf_snapshot_trails(s, &sp, &t);
+ *                            fluid_dist_sdf_wait(s, &part[rank]);
+ *   one place:               k = fluid_sdf_grids_merge(part, R, cap, origin, values, active);  filter / mesh / render / write.
+ * st.dt_out is the same double on every rank (the step all-reduces the maximum speed before it advects), so shutter = dt is one
+ * setting for the whole run.  The rank record is unfiltered and carries no attributes: a block run filters after the merge. */
+/* fluid_dist_sdf_snapshot in every respect (live particles only, global coordinates, no transport call, the surface's own two slots
+ * and their shared count of outstanding snapshots, survival of a re-balance, a plain record that fluid_dist_sdf_wait takes — and
+ * fluid_sdf_wait on a plain fluid_create handle, which is accepted — and fluid_dist_sdf_wait_avg refuses), but the level set is the
+ * trails' and they come with the call: t NULL or outside the limits of fluid_sdf_set_trails, or (float)t->radius_min > R:
+ * FLUID_ERR_ARG, and no snapshot is outstanding from a refused call.  The handle's surface kind (AVERAGED included) and its own
+ * trails setting are neither read nor changed: the surface is the spheres' with these trails.  fluid_dist_sdf_stats reports
+ * bytes_to_host = leaves_listed * FLUID_SDF_LEAF_BYTES + 4.  Beside the instances' box and total the live count is read back (8 more
+ * bytes); the scratch is that of fluid_sdf_set_trails, shared with it, allocated by the handle's first snapshot of either form. */
+int fluid_dist_sdf_snapshot_trails(fluid_sim_t* s, const fluid_sdf_params_t* p, const fluid_sdf_trails_t* t);
+/* Of the last fluid_dist_sdf_snapshot_trails (either pointer may be NULL; zeros before the first): the live particles expanded and
+ * the instances made, before the in-grid test.  Counters of their own: fluid_sdf_trails_stats keeps reporting the last snapshot
+ * under the setting. */
+int fluid_dist_sdf_trails_stats(fluid_sim_t* s, int64_t* particles, int64_t* instances);
 
 /* ---- liquid surface as a mesh: surface nets of the level set ----------------------------------------------------------------
  * Polygons for everyone who is no volume renderer.  The reference names tools/VolumeToMesh.h, whose output depends on the library's
